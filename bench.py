@@ -11,6 +11,12 @@ Launch: python bench.py --gpus N --steps K --warmup W           (any N: for N > 
                                                                  starts its own N ranks as child processes)
         python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N>1, under a launcher)
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the stage timers of the
+timed steps).  `--full` adds everything else: the other legs (configs[2], FASTQ text, host pinned memory, two handles in
+flight, the one-rank shard layer, the isolates comparison at N > 1), the streaming-read peak of the roofline, the
+closed-form check of the contig and the multi-threaded CPU baseline.  `--dump-outputs DIR` writes what the last timed
+step handed its caller (the assembly and the k-mer counts) as float arrays, DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -22,6 +28,56 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_MAX_BASES = 1 << 23       # --dump-outputs: contig bases written whole up to this many (float32: 32 MB) ...
+DUMP_SAMPLE_BASES = 1 << 22    # ... beyond it a fixed, seeded sample of this many, with its positions (16 + 32 MB)
+ASSEMBLY_TEXTS = ("outfasta", "outgfa", "outgfav2", "outdot")
+
+
+def dump_outputs(out_dir, asm_json, n_distinct, n_solid, prefix="", share=1):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as DIR/<prefix><name>.npy:
+      ncontigs              float64 [1]
+      kmer_counts           float64 [n_distinct, n_solid]
+      contig_lengths        float64 [ncontigs], in the order of the FASTA
+      contig_bases          float32, the contigs' bases concatenated, A C G T = 0 1 2 3 (anything else 4); when there are more
+                            than DUMP_MAX_BASES / share of them, contig_bases_sample (float32) at the positions
+                            contig_bases_sample_index (float64), a sorted sample drawn with a fixed seed
+      assembly_text_bytes   float64 [4], assembly_text_sha256 float64 [4, 32]: length and SHA-256 bytes of each text of the
+                            assembly (FASTA, GFA 1, GFA 2, DOT), so that every byte of it is compared
+    Under 64 MB in all (`share` divides the budget between the ranks that write)."""
+    import hashlib
+    import numpy as np
+    res = json.loads(asm_json)
+    contigs, cur = [], None
+    for ln in res["outfasta"].split("\n"):
+        if ln.startswith(">"):
+            if cur is not None:
+                contigs.append("".join(cur))
+            cur = []
+        elif ln and cur is not None:
+            cur.append(ln.strip())
+    if cur is not None:
+        contigs.append("".join(cur))
+    lut = np.full(256, 4, dtype=np.uint8)
+    for i, c in enumerate(b"ACGT"):
+        lut[c] = i
+    bases = lut[np.frombuffer("".join(contigs).encode(), dtype=np.uint8)]
+    texts = [res.get(f, "").encode() for f in ASSEMBLY_TEXTS]
+    arrays = {
+        "ncontigs": np.array([res["ncontigs"]], dtype=np.float64),
+        "kmer_counts": np.array([n_distinct, n_solid], dtype=np.float64),
+        "contig_lengths": np.array([len(c) for c in contigs], dtype=np.float64),
+        "assembly_text_bytes": np.array([len(t) for t in texts], dtype=np.float64),
+        "assembly_text_sha256": np.array([list(hashlib.sha256(t).digest()) for t in texts], dtype=np.float64),
+    }
+    if bases.size <= DUMP_MAX_BASES // share:
+        arrays["contig_bases"] = bases.astype(np.float32)
+    else:
+        idx = np.sort(np.random.default_rng(0x5EED).choice(bases.size, DUMP_SAMPLE_BASES // share, replace=False))
+        arrays["contig_bases_sample"] = bases[idx].astype(np.float32)
+        arrays["contig_bases_sample_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
 
 
 def make_reads_on_device(torch, dev, genome_len, coverage, read_len, seed, read_seed=None, n_reads=None):
@@ -250,6 +306,11 @@ def main():
     ap.add_argument("--err", type=float, default=0.0, help="substitution error rate of the reads (configs[2]: 0.01 with --k 51)")
     ap.add_argument("--mask-errors", action="store_true", help="erroneous bases carry a low quality and are masked "
                     "(min_qual): reads are cut into error-free segments before they reach the device entry point")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the other legs, the "
+                    "streaming-read peak, the closed-form check of the contig and the CPU baseline (the --no-* options "
+                    "below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed "
+                    "(assembly, k-mer counts) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-leg", action="store_true", help="skip the second timed leg (packed reads in host pinned memory)")
     ap.add_argument("--no-inflight-leg", action="store_true", help="skip the leg with two handles in flight")
@@ -269,6 +330,8 @@ def main():
                     help="sharded mode: 'lib' = RCCL inside the library (production); 'torch' = the same shk_shard_* "
                          "pieces driven by torch.distributed collectives (rehearsal with --backend gloo --one-gpu)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     # ---- N > 1 without a launcher: `python bench.py --gpus N` starts its own N ranks — as FRESH child processes of
     # torch.distributed.run, before this process has imported torch or touched the GPU (a process that has initialised
     # the GPU must never exec or be replaced) — hands their stdout through (rank 0's ONE JSON line) and exits with
@@ -358,7 +421,9 @@ def main():
 
     call_times = {} if os.environ.get("BENCH_CALL_TIMES") else None     # host time per C call, printed to stderr at the end
 
-    def one_step(keep=False):
+    def one_step(hold=False):
+        """one step; with `hold` the handle is returned instead of freed, so that the caller can read its assembly behind
+        the timed region (and then frees it)"""
         c0 = time.perf_counter()
         h = AssemblyHelper.new(args.k, False, args.min_count, 20, 0, False, False, False, False)
         c1 = time.perf_counter()
@@ -372,19 +437,21 @@ def main():
         h.assemble()
         c3 = time.perf_counter()
         # the JSON (contigs as FASTA/GFA/DOT) is on the host now; take the pointer without making
-        # a Python copy of ~15 MB inside the timed region (copied once, after timing, for checking)
+        # a Python copy of ~15 MB inside the timed region (the last timed step's is copied after timing)
         ptr = raw_get_assembly(h._h)
         assert ptr
-        out = ctypes.string_at(ptr) if keep else None
         t = h._L.shk_get_timings(h._h)                   # (the JSON text; parsed behind the timed region: json.loads is 15-20 us of host time per step)
         info = (h.n_solid, h.n_distinct)
         c4 = time.perf_counter()
-        h.free()
-        c5 = time.perf_counter()
         if call_times is not None:
-            for name, dt_ in (("new", c1 - c0), ("preprocess", c2 - c1), ("assemble", c3 - c2), ("get_assembly+timings", c4 - c3), ("free", c5 - c4)):
+            for name, dt_ in (("new", c1 - c0), ("preprocess", c2 - c1), ("assemble", c3 - c2), ("get_assembly+timings", c4 - c3)):
                 call_times.setdefault(name, []).append(dt_ * 1e3)
-        return out, t, info
+        if hold:
+            return h, t, info
+        h.free()
+        if call_times is not None:
+            call_times.setdefault("free", []).append((time.perf_counter() - c4) * 1e3)
+        return None, t, info
 
     def barrier():
         if world > 1:
@@ -430,11 +497,18 @@ def main():
     t0 = time.perf_counter()
     kern_ms, all_t = [], []
     raw_t = []
-    for _ in range(args.steps):
-        _, t, info = one_step()
+    for i in range(args.steps):
+        held, t, info = one_step(hold=(i == args.steps - 1))
         raw_t.append(t)
     barrier()
     dt = time.perf_counter() - t0
+    # the last step's handle was kept: its result is read here, behind the timed region, and the free it still owes is
+    # timed and counted with the steps
+    out = ctypes.string_at(raw_get_assembly(held._h))
+    tf = time.perf_counter()
+    held.free()
+    dt += time.perf_counter() - tf
+    del held
     for t in raw_t:
         t = json.loads(t.decode())
         kern_ms.append(t.get("count_kernel", 0.0))
@@ -443,11 +517,20 @@ def main():
         print("[bench] host ms per call (median of the timed steps):",
               {k_: round(sorted(v[args.warmup:args.warmup + args.steps])[len(v[args.warmup:args.warmup + args.steps]) // 2], 3) for k_, v in call_times.items()},
               file=sys.stderr, flush=True)
-    out, _, _ = one_step(keep=True)                      # untimed: fetch the result for checking
+    if world > 1:
+        tt = torch.tensor([dt], device=dev if args.backend == "nccl" else "cpu", dtype=torch.float64)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        dt = float(tt.item())
+    res = json.loads(out)
+    ncontigs = res["ncontigs"]
+    if args.dump_outputs and (rank == 0 or sharded):
+        # (sharded: every rank holds a share of the assembly and writes it; otherwise rank 0's isolate stands for all)
+        dump_outputs(args.dump_outputs, out, info[1], info[0], prefix=f"rank{rank}." if sharded and world > 1 else "",
+                     share=world if sharded else 1)
     # ---- comparison point (N > 1, sharded): the same ranks, every one assembling an isolate of its own — independent
     # objects, no data-path collective.  Timed the same way, reported beside `value`, never as it.
     iso_leg = None
-    if sharded and world > 1 and args.err == 0:
+    if args.full and sharded and world > 1 and args.err == 0:
         ib, iseg, inr, inb, _g = make_reads_on_device(torch, dev, args.genome, args.coverage, args.read_len, 0xEC02 + rank)
 
         def iso_step():
@@ -472,7 +555,7 @@ def main():
     # back and writes the FASTA / GFA text — each handle on its own host thread and stream (sparrowhawk_amd/batch.py does
     # the same).  Reported beside `value` (which stays one handle at a time: its kernel timings are undisturbed).
     inflight_leg = None
-    if world == 1 and not sharded and not args.no_inflight_leg:
+    if args.full and world == 1 and not sharded and not args.no_inflight_leg:
         import threading
         n_fl, todo_lock, todo = 2, threading.Lock(), [0]
 
@@ -497,12 +580,12 @@ def main():
     # ---- the other driver-timed legs (N = 1): BASELINE configs[2] (k = 51, 1 % errors: masked by quality, left in, and
     # left in with the Bloom pre-filter) and the drop-in entry point on FASTQ text in host memory
     legs = None
-    if world == 1 and not sharded and args.err == 0 and not args.no_legs and args.genome == 5_000_000:
+    if args.full and world == 1 and not sharded and args.err == 0 and not args.no_legs and args.genome == 5_000_000:
         legs = run_legs(torch, dev, args, raw_get_assembly)
     # ---- second leg (N = 1): the clock of SURVEY.md 8(d) — packed reads resident in host PINNED memory -> contig
     # strings on the host; the upload rides in front of pass 1 on the library's stream
     host_leg = None
-    if world == 1 and args.err == 0 and not args.no_host_leg and not sharded:
+    if args.full and world == 1 and args.err == 0 and not args.no_host_leg and not sharded:
         hw = torch.empty(d_bases.numel(), dtype=torch.int32).pin_memory()
         hs = torch.empty(d_seg.numel(), dtype=torch.int32).pin_memory()
         hw.copy_(d_bases); hs.copy_(d_seg)
@@ -550,7 +633,7 @@ def main():
     # ---- the shard layer with a one-rank communicator (N = 1): what the exchange machinery and the collective shk_assemble
     # cost when nothing has to leave the GPU — driver-timed beside the plain path
     sharded_one_rank = None
-    if world == 1 and not sharded and args.err == 0 and not args.no_legs:
+    if args.full and world == 1 and not sharded and args.err == 0 and not args.no_legs:
         try:
             from sparrowhawk_amd.dist import LibComm, sharded_preprocess_rccl
             comm1 = LibComm(0, 1)
@@ -579,17 +662,10 @@ def main():
             comm1.free()
         except Exception as e:
             sharded_one_rank = {"error": repr(e)}
-    if world > 1:
-        tt = torch.tensor([dt], device=dev if args.backend == "nccl" else "cpu", dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt = float(tt.item())
 
-    # sanity on the result of the last step: one contig that is a substring of the genome
-    res = json.loads(out)
-    ncontigs = res["ncontigs"]
     # closed-form check of the last result: error-free reads of a repeat-free isolate
     # give one contig that is a substring of the genome (up to strand), ends trimmed by the filter
-    if args.coverage >= 30 and ncontigs == 1 and not sharded and args.err == 0:
+    if args.full and args.coverage >= 30 and ncontigs == 1 and not sharded and args.err == 0:
         contig = res["outfasta"].split("\n")[1]
         gs = "".join("ACGT"[int(c)] for c in genome.cpu().tolist()) if args.genome <= 20_000_000 else None
         if gs is not None:
@@ -620,7 +696,7 @@ def main():
     achieved = alg_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
     # the second denominator SURVEY.md 8(d) asks for: what a pure streaming read of 2 GiB reaches on this box
     stream_gbs = None
-    if rank == 0:
+    if args.full and rank == 0:
         g = ctypes.c_double(0.0)
         if L.shk_measure_stream_read(2 << 30, 5, ctypes.byref(g)) == 0:
             stream_gbs = g.value
@@ -649,7 +725,7 @@ def main():
                    "ncontigs": ncontigs, "n_distinct_kmers": n_distinct, "n_solid_kmers": n_solid,
                    "peak_device_bytes": int(max(t.get("peak_device_bytes", 0) for t in all_t)),
                    "clock": "`value` starts with the packed reads resident in HBM (the bench contract); the SURVEY 8(d) clock — packed reads "
-                            "in host pinned memory -> contig strings on the host — is `host_pinned.value` / `value_host_pinned`"},
+                            "in host pinned memory -> contig strings on the host — is `host_pinned.value` / `value_host_pinned` (with --full)"},
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                      # what SURVEY.md 8(d) asks to report beside the algorithmic fraction: the kernel's MEASURED fabric
@@ -696,7 +772,7 @@ def main():
                                     "pieces on a copy stream, pass 1 of a piece under the upload of the next (shk_preprocess_packed_host)"
                                     % ((d_bases.numel() + d_seg.numel()) * 4 / 1e6))
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and args.k <= 63:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.k <= 63:
             line["cpu_baseline"] = cpu_baseline(args.k, args.min_count, d_bases.cpu().numpy().view("uint32"),
                                                 d_seg.cpu().numpy().view("uint32"), n_bases, res["outfasta"])
         sys.stdout.flush()

@@ -8,5 +8,5 @@ if [ "$TESTS" = tests ]; then
   timeout -k 10 900 python -m pytest tests -m gpu -x -q --durations=8 > "$OUT/pytest.log" 2>&1 || { tail -40 "$OUT/pytest.log"; exit 1; }
   tail -14 "$OUT/pytest.log"
 fi
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline "$@" > "$OUT/bench_line.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 300 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline "$@" > "$OUT/bench_line.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 python tools/bench_summary.py "$OUT/bench_line.json"

@@ -13,7 +13,7 @@ if [ "$TESTS" = tests ]; then
   timeout -k 10 900 python -m pytest tests -m gpu -x -q --durations=8 > "$OUT/pytest.log" 2>&1 || { tail -30 "$OUT/pytest.log"; exit 1; }
   tail -3 "$OUT/pytest.log"
 fi
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 > "$OUT/bench_line.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 300 python bench.py --steps 20 --warmup 3 --full > "$OUT/bench_line.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench_line.json"
 # per-kernel time
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_stats" -o s -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-host-leg --no-legs --no-inflight-leg > "$OUT/prof_stats.log" 2>&1

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:?}"
 OUT=$PWD/gpurun_out/r02_first; mkdir -p "$OUT"
 timeout -k 10 900 python -m pytest tests -m gpu -x -q --durations=10 > "$OUT/pytest.log" 2>&1 || { tail -60 "$OUT/pytest.log"; exit 1; }
 tail -16 "$OUT/pytest.log"
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/bench_line.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 300 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline > "$OUT/bench_line.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 python tools/bench_summary.py "$OUT/bench_line.json"
 echo "--- N=2 one GPU, RCCL inside the library"
 timeout -k 10 200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29811 bench.py --gpus 2 --steps 3 --warmup 1 --one-gpu --backend gloo > "$OUT/n2_lib.json" 2> "$OUT/n2_lib.err" || { echo "rc=$?"; tail -5 "$OUT/n2_lib.err"; }

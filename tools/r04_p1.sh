@@ -17,5 +17,5 @@ for win in 20 16; do
   echo "== SHK_PART_WIN=$win"; SHK_PART_WIN=$win timeout -k 10 200 python tools/pre_only.py 2>&1 | tail -2
 done
 echo "== K=51 masked"; K=51 ERR=0.01 MASK=1 timeout -k 10 200 python tools/pre_only.py 2>&1 | tail -1
-timeout -k 10 400 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-legs > "$OUT/bench_line.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
+timeout -k 10 400 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-legs > "$OUT/bench_line.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
 python tools/bench_summary.py "$OUT/bench_line.json" || true
