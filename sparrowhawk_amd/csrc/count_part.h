@@ -730,6 +730,24 @@ template <int W> __device__ __forceinline__ void table_reset(CountShared<W> &tb,
     kmer_table_reset<W>(tb, ctl);
 }
 
+// slots of a graph partition's mini table (graph_part.h): the power of two >= 2 x rows, at least 8 (no loop: this sits
+// 32 times in every thread of the one workgroup of k_gp_scan, where a shift loop cost 20 us)
+__device__ __forceinline__ uint32_t gp_table_size(uint32_t rows) {
+    const uint32_t want = 2u * rows;
+    return want <= 8u ? 8u : 1u << (32 - __clz((int)(want - 1u)));
+}
+// Where the rows of each group of k_count_weighted went: group g's rows are [start[g], start[g] + cnt[g]) when it is
+// emitted by ONE table round.  build_graph takes the groups as its graph partitions then (no regrouping kernels): the
+// mini table of group g gets its place here too — off[g] from a second cursor, reserved together with the rows, and
+// msk[g] = its size - 1.  A group counted member by member or handed to the k-mer-level repartition sets *broken.
+// The cursor counts the recorded ROWS too (high word; slots in the low word, which the host keeps below 2^32): the host
+// takes the ranges only when they hold every row, so a group whose rows left unrecorded is noticed without the flag.
+struct EmitRanges {
+    unsigned long long *tab_cursor = nullptr;   // nullptr: nothing recorded; else rows << 32 | slots
+    unsigned long long *off = nullptr;
+    uint32_t *msk = nullptr, *start = nullptr, *cnt = nullptr, *broken = nullptr;
+};
+
 // a finished round: histogram of the table's counts, rows with count > threshold appended to the output.
 // One scan of the table feeds the round-local histogram and lists the slots to emit in LDS (list: room
 // for S slot numbers); then one global atomic reserves the rows and they are written densely — one
@@ -740,7 +758,8 @@ __device__ __forceinline__ void table_emit(KmerTable<W> &tb, CountCtlCore &ctl, 
                                            uint32_t *__restrict__ out_cnt, unsigned long long out_cap,
                                            unsigned long long *__restrict__ out_cursor, LT *list, uint32_t dbg_arg = 0,
                                            uint32_t *hist_accum = nullptr /* LDS: the round's histogram is added here instead of to `histo` */,
-                                           uint32_t bias = 0 /* Bloom mode: the occurrence that only set the filter's bits */) {
+                                           uint32_t bias = 0 /* Bloom mode: the occurrence that only set the filter's bits */,
+                                           const EmitRanges &er = EmitRanges{}, uint32_t er_g = 0xFFFFFFFFu /* the group recorded in er */) {
     const uint32_t dbg = SHK_DBG(dbg_arg);
     constexpr uint32_t S = KmerTable<W>::S;
     const int lane = threadIdx.x & 63;
@@ -768,6 +787,11 @@ __device__ __forceinline__ void table_emit(KmerTable<W> &tb, CountCtlCore &ctl, 
     const uint32_t n_emit = ctl.n_emit;
     if (threadIdx.x == 0) {
         unsigned long long base = (n_emit && dbg != 5) ? atomicAdd(out_cursor, (unsigned long long)n_emit) : 0ull;
+        if (er.tab_cursor && er_g != 0xFFFFFFFFu) {         // (both reservations in flight together: one round trip)
+            const uint32_t sz = gp_table_size(n_emit);
+            const unsigned long long tab_base = atomicAdd(er.tab_cursor, ((unsigned long long)n_emit << 32) | sz);
+            er.off[er_g] = (uint32_t)tab_base; er.msk[er_g] = sz - 1u; er.start[er_g] = (uint32_t)base; er.cnt[er_g] = n_emit;
+        }
         ctl.emit_base_lo = (uint32_t)base; ctl.emit_base_hi = (uint32_t)(base >> 32);
     }
     if (hist_accum) {                                       // (thread b owns bin b: no atomics)
@@ -1429,7 +1453,8 @@ __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_count_weighte
     unsigned long long *__restrict__ n_inst, OvfRec *__restrict__ ovf, uint32_t *__restrict__ ovf_n,
     unsigned long long *__restrict__ work_and_tally /* low word: groups handed out, zero at launch; high word: this kernel's tally, tried |
                                                        overflowed << 16, which k_dedupe_partitions starts at its verdict — ONE atomic fetches both */,
-    uint32_t probe_groups, uint32_t defer_after, uint32_t dbg_arg /* timing experiments (ABLATE builds) */) {
+    uint32_t probe_groups, uint32_t defer_after, uint32_t dbg_arg /* timing experiments (ABLATE builds) */,
+    EmitRanges er /* where each group's rows went (build_graph's partitions); tab_cursor nullptr: not recorded */) {
     constexpr int RW = 2 * W;
     constexpr uint32_t S = KmerTable<W>::S;
     const uint32_t dbg = SHK_DBG(dbg_arg);
@@ -1522,11 +1547,13 @@ __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_count_weighte
         __syncthreads();
         return !(ctl.overflow != 0 || ctl.n_used > (S / 10) * 9);
     };
-    auto emit = [&]() {
+    // (er_g: the group whose rows this round emits whole, recorded in er; NIL: a member of a group counted member by member)
+    auto emit = [&](uint32_t er_g) {
         if (dbg == 32) return;                                           // timing experiment: no emit
-        if constexpr (W == 1) table_emit<W>(tb, ctl, mine, threshold, histo, out_keys, out_cnt, out_cap, out_cursor, elist, 0u, whist);
-        else table_emit<W>(tb, ctl, mine, threshold, histo, out_keys, out_cnt, out_cap, out_cursor, tb.state, 0u, whist);
+        if constexpr (W == 1) table_emit<W>(tb, ctl, mine, threshold, histo, out_keys, out_cnt, out_cap, out_cursor, elist, 0u, whist, 0u, er, er_g);
+        else table_emit<W>(tb, ctl, mine, threshold, histo, out_keys, out_cnt, out_cap, out_cursor, tb.state, 0u, whist, 0u, er, er_g);
     };
+    auto mark_broken = [&]() { if (threadIdx.x == 0 && er.broken) *er.broken = 1u; };
     // hand partition p to the k-mer-level repartition: exact instances, estimated distinct k-mers (of the attempt just made)
     uint32_t *const tally = reinterpret_cast<uint32_t *>(work_and_tally) + 1;
     bool in_sample = true;                               // (this workgroup's first group: see the loop below)
@@ -1534,6 +1561,7 @@ __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_count_weighte
         const uint32_t R = n_recs[p];
         const uint64_t *src = recs + base[p] * RW;
         const uint32_t *src_w = weights + base[p];
+        mark_broken();                                   // (its rows come out of the repartition, elsewhere)
         __syncthreads();
         if (threadIdx.x == 0) { ctl.tried = 0; ctl.part_inst = 0; }
         __syncthreads();
@@ -1584,15 +1612,16 @@ __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_count_weighte
             continue;
         }
         if (nm > 1 && count_range(pm, nm)) {
-            emit();
+            emit(g);
             if (threadIdx.x == 0 && defer_after && in_sample) atomicAdd(tally, nm);                        // tried, and they fitted
             continue;
         }
+        if (nm > 1) mark_broken();                       // (the group's rows leave in several rounds)
 #pragma unroll
         for (uint32_t j = 0; j < 4; j++) {
             if (j >= nm) continue;
             const uint32_t one[4] = {pm[j], 0, 0, 0};
-            if (count_range(one, 1u)) { emit(); if (threadIdx.x == 0 && defer_after && in_sample) atomicAdd(tally, 1u); }
+            if (count_range(one, 1u)) { emit(nm == 1 ? g : 0xFFFFFFFFu); if (threadIdx.x == 0 && defer_after && in_sample) atomicAdd(tally, 1u); }
             else defer(pm[j], true);
         }
     }

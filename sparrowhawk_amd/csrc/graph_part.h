@@ -7,7 +7,10 @@
 // a10: graph table over the solid set
 // ------------------------------------------------------------------------------------------
 // Graph partition of a k-mer = low bits of the smallest canonical ntHash (32-bit state) over its
-// gm-mers; strand-symmetric, so a k-mer and its reverse complement agree.
+// gm-mers; strand-symmetric, so a k-mer and its reverse complement agree.  gm is the counting pass's
+// minimiser length, so a counting group of k_count_weighted is a graph partition: when every group's rows
+// left pass 2 in one piece (EmitRanges), build_graph takes those ranges and the tables' places reserved
+// there, and k_gp_count / k_gp_scan / k_gp_rows / k_row_starts below do not run (the fallback otherwise).
 struct MinScan {
     Nt32State first, last;      // hash state of the first / last gm-mer
     uint32_t h_first, h_last;   // their canonical hashes
@@ -175,14 +178,8 @@ __global__ __launch_bounds__(256) void k_gp_count(KeyArr<W> keys, uint32_t n, in
     }
 }
 
-// table sizes (power of two >= 2 x rows, at least 8) and their exclusive prefix sum, plus the
+// table sizes (gp_table_size, count_part.h) and their exclusive prefix sum, plus the
 // exclusive prefix sum of the row counts (row list offsets); one workgroup
-// slots of a partition's mini table: the power of two >= 2 x rows, at least 8 (no loop: this sits 32 times in every thread of
-// the one workgroup of k_gp_scan, where a shift loop cost 20 us)
-__device__ __forceinline__ uint32_t gp_table_size(uint32_t rows) {
-    const uint32_t want = 2u * rows;
-    return want <= 8u ? 8u : 1u << (32 - __clz((int)(want - 1u)));
-}
 __global__ __launch_bounds__(1024) void k_gp_scan(uint32_t *__restrict__ gp_cnt /* read, then zeroed: k_gp_rows uses it as its cursors */, uint32_t GP,
                                                   unsigned long long *__restrict__ off, uint32_t *__restrict__ msk,
                                                   uint32_t *__restrict__ roff, unsigned long long *__restrict__ total) {
@@ -335,6 +332,21 @@ __device__ __forceinline__ uint32_t gt_lookup(const GraphTable &gt, const KeyArr
 // prepending drops the last and adds one in front.
 static constexpr uint32_t ADJ_LDS_SLOTS = 2048;        // 16 KB (8 workgroups per CU); larger (skewed) partitions work in global memory
 static constexpr uint32_t NB_MULTI = 0xFFFFFFFEu;
+// The graph partitions taken from the counting pass's groups (EmitRanges, count_part.h): ~1200 rows each on the bench
+// isolate (4096 groups), so tables of 4096 slots — 48 KB of LDS for one-word keys — and 512 threads, which keep up to
+// 2048 rows in registers (KEEP per thread).  Partitions beyond the table still work in global memory.
+static constexpr uint32_t ADJ_LDS_SLOTS_RANGES = 4096;
+static constexpr int ADJ_THREADS_RANGES = 512;
+
+// the rows of graph partition P
+struct GpRows {
+    const uint32_t *roff;       // cnt == nullptr: list entries roff[P] .. roff[P + 1); else rows roff[P] .. roff[P] + cnt[P]
+    const uint32_t *cnt;
+    const uint32_t *rows;       // the row lists; nullptr: the identity (a partition's rows are side by side)
+    __device__ __forceinline__ uint32_t begin(uint32_t P) const { return roff[P]; }
+    __device__ __forceinline__ uint32_t end(uint32_t P) const { return cnt ? roff[P] + cnt[P] : roff[P + 1]; }
+    __device__ __forceinline__ uint32_t row(uint32_t r) const { return rows ? rows[r] : r; }
+};
 
 // candidate j of node x: j < 4 successor by appended base j, else predecessor by prepended base j-4
 template <int W>
@@ -349,23 +361,27 @@ __device__ __forceinline__ Kmer<W> adj_candidate(const Kmer<W> &x, const Kmer<W>
     return c;
 }
 
-template <int W>
-__global__ __launch_bounds__(256) void k_graph_local(KeyArr<W> keys, int k, GraphTable gt,
-                                                     const uint32_t *__restrict__ roff, const uint32_t *__restrict__ rows,
-                                                     uint8_t *__restrict__ adj, uint32_t *__restrict__ nb,
-                                                     unsigned long long *__restrict__ queries, uint32_t *__restrict__ qcnt,
-                                                     uint32_t *__restrict__ overflow) {
+// Partitions from the counting groups (gr.cnt != nullptr) come with no scan kept and no k_row_starts: every row's scan is
+// made here, its partition checked against P (a mismatch is reported like an overflow: *overflow = 2), and the
+// alive flag and the collapse's row-start bit (lowmask: as k_row_starts) are written here.
+template <int W, uint32_t SLOTS, int NT>
+__global__ __launch_bounds__(NT) void k_graph_local(KeyArr<W> keys, int k, GraphTable gt, GpRows gr,
+                                                    uint8_t *__restrict__ adj, uint32_t *__restrict__ nb,
+                                                    unsigned long long *__restrict__ queries, uint32_t *__restrict__ qcnt,
+                                                    uint32_t *__restrict__ overflow, uint32_t lds_slots /* <= SLOTS */,
+                                                    uint8_t *__restrict__ alive, uint32_t *__restrict__ row_bits, uint32_t lowmask) {
     const unsigned gm = (unsigned)gt.gm;
     __shared__ uint2 lut[16];
     // LDS copy of the mini table.  One-word keys (k <= 31): the key itself plus the node id (12 B per slot),
     // so a local probe never leaves the CU; wider keys: fingerprint | id, verified against the key array.
-    __shared__ uint64_t tab[ADJ_LDS_SLOTS];                // W == 1: keys; else fingerprint << 32 | id
-    __shared__ uint32_t tabi[W == 1 ? ADJ_LDS_SLOTS : 1];  // W == 1: node ids
+    __shared__ uint64_t tab[SLOTS];                        // W == 1: keys; else fingerprint << 32 | id
+    __shared__ uint32_t tabi[W == 1 ? SLOTS : 1];          // W == 1: node ids
     __shared__ uint32_t q_fill;
     const uint32_t P = blockIdx.x;
-    const uint32_t r0 = roff[P], r1 = roff[P + 1];
+    const bool ranges = gr.cnt != nullptr;
+    const uint32_t r0 = gr.begin(P), r1 = gr.end(P);
     const uint32_t pmask = gt.msk[P];
-    const bool in_lds = pmask < ADJ_LDS_SLOTS;
+    const bool in_lds = pmask < lds_slots;
     uint64_t *gtab = gt.e + gt.off[P];
     nt32_fill_lut(lut, gm);
     const Nt32State all_a = nt32_all_a(gt.gm);
@@ -378,16 +394,17 @@ __global__ __launch_bounds__(256) void k_graph_local(KeyArr<W> keys, int k, Grap
         if (!in_lds || KEYS_IN_LDS) gtab[t] = EMPTY64;
     }
     __syncthreads();
-    // A thread's rows (every 256th of the partition's list) are used twice — inserted here, expanded below.  Up to four
-    // per thread (1024 rows: every partition whose table fits the LDS) stay in registers: their ids and then their keys
+    // A thread's rows (every NT-th of the partition's list) are used twice — inserted here, expanded below.  Up to four
+    // per thread (4 NT rows: every partition whose table fits the LDS) stay in registers: their ids and then their keys
     // are requested in two rounds of independent loads, instead of two dependent loads per row in either phase.
     constexpr int KEEP = 4;
-    const bool keep = W <= 2 && (r1 - r0) <= (uint32_t)KEEP * 256u;      // (uniform; wider keys: the registers cost more occupancy than the loads)
+    static_assert(SLOTS <= 2u * KEEP * NT, "a partition whose table fits the LDS keeps its rows in registers");
+    const bool keep = W <= 2 && (r1 - r0) <= (uint32_t)KEEP * NT;        // (uniform; wider keys: the registers cost more occupancy than the loads)
     // (four named registers each, chosen by compare-and-select: an indexed array would live in scratch memory)
     static_assert(KEEP == 4, "kept rows are four named registers");
     const uint32_t rt = r0 + threadIdx.x;
-    const uint32_t i0 = (keep && rt < r1) ? rows[rt] : NIL, i1 = (keep && rt + 256u < r1) ? rows[rt + 256u] : NIL;
-    const uint32_t i2 = (keep && rt + 512u < r1) ? rows[rt + 512u] : NIL, i3 = (keep && rt + 768u < r1) ? rows[rt + 768u] : NIL;
+    const uint32_t i0 = (keep && rt < r1) ? gr.row(rt) : NIL, i1 = (keep && rt + NT < r1) ? gr.row(rt + NT) : NIL;
+    const uint32_t i2 = (keep && rt + 2 * NT < r1) ? gr.row(rt + 2 * NT) : NIL, i3 = (keep && rt + 3 * NT < r1) ? gr.row(rt + 3 * NT) : NIL;
     const Kmer<W> k0 = i0 != NIL ? keys.load(i0) : km_zero<W>(), k1 = i1 != NIL ? keys.load(i1) : km_zero<W>();
     const Kmer<W> k2 = i2 != NIL ? keys.load(i2) : km_zero<W>(), k3 = i3 != NIL ? keys.load(i3) : km_zero<W>();
     auto kept_i = [=](uint32_t q) { return q == 0 ? i0 : (q == 1 ? i1 : (q == 2 ? i2 : i3)); };
@@ -398,7 +415,7 @@ __global__ __launch_bounds__(256) void k_graph_local(KeyArr<W> keys, int k, Grap
         return r;
     };
     for (uint32_t r = r0 + threadIdx.x, q = 0; r < r1; r += blockDim.x, q++) {
-        const uint32_t i = keep ? kept_i(q) : rows[r];
+        const uint32_t i = keep ? kept_i(q) : gr.row(r);
         const Kmer<W> key = keep ? kept_key(q) : keys.load(i);
         const uint64_t h = gt_hash<W>(key);
         const uint64_t entry = (h & 0xFFFFFFFF00000000ull) | (uint64_t)i;
@@ -418,6 +435,13 @@ __global__ __launch_bounds__(256) void k_graph_local(KeyArr<W> keys, int k, Grap
         if (!done) *overflow = 1;
     }
     __syncthreads();
+    // (partitions from the counting groups) a group of rows with other low minimiser bits than the row before starts here: the
+    // collapse's tile edges, as k_row_starts sets them (the bits were zeroed; a partition's rows all share its bits)
+    if (ranges && threadIdx.x == NT - 1 && r1 > r0) {
+        bool st = r0 == 0u;
+        if (!st) st = ((km_min_scan_lut<W>(keys.load(r0 - 1u), k, gt.gm, lut, all_a).min_all() ^ P) & lowmask) != 0u;
+        if (st) atomicOr(&row_bits[r0 >> 5], 1u << (r0 & 31u));
+    }
     if (in_lds && !KEYS_IN_LDS) for (uint32_t t = threadIdx.x; t <= pmask; t += blockDim.x) gtab[t] = tab[t];
     // which slots are taken, a bit each (tables are 8 slots at least and start at multiples of 8: whole bytes, no atomics)
     {
@@ -440,7 +464,7 @@ __global__ __launch_bounds__(256) void k_graph_local(KeyArr<W> keys, int k, Grap
     const uint32_t n_round = (n_rows + blockDim.x - 1) / blockDim.x * blockDim.x;
     for (uint32_t rr_ = threadIdx.x, q = 0; rr_ < n_round; rr_ += blockDim.x, q++) {
         const bool act = rr_ < n_rows;
-        const uint32_t i = act ? (keep ? kept_i(q) : rows[r0 + rr_]) : 0u;
+        const uint32_t i = act ? (keep ? kept_i(q) : gr.row(r0 + rr_)) : 0u;
         Kmer<W> x = km_zero<W>(), rx = km_zero<W>();
         MinScan ms{};
         uint32_t out_b = 0, last_b = 0;
@@ -453,6 +477,7 @@ __global__ __launch_bounds__(256) void k_graph_local(KeyArr<W> keys, int k, Grap
                 ms.h_first = min(a.x, a.y); ms.h_last = min(b.x, b.y);
             } else
             if (SHK_DBG(gt.dbg) != 2) ms = km_min_scan_lut<W>(x, k, gt.gm, lut, all_a);      // (2: timing experiment without the scan)
+            if (ranges && ((ms.min_all() & gt.gp_mask) != P)) *overflow = 2u;         // (the row is not of this group's minimiser)
             out_b = km_base<W>(x, k, k - (int)gm);                 // first base of the last gm-mer
             last_b = km_base<W>(x, k, (int)gm - 1);                // last base of the first gm-mer
         }
@@ -502,6 +527,7 @@ __global__ __launch_bounds__(256) void k_graph_local(KeyArr<W> keys, int k, Grap
         }
         if (act) {
             adj[i] = (uint8_t)a;
+            if (alive) alive[i] = 1;
             uint2 v;
             v.x = n_out == 0 ? NIL : (n_out == 1 ? u_out : NB_MULTI);
             v.y = n_in == 0 ? NIL : (n_in == 1 ? u_in : NB_MULTI);
@@ -518,13 +544,12 @@ __global__ __launch_bounds__(256) void k_graph_local(KeyArr<W> keys, int k, Grap
 // together, so that a round trip is waited for once per four queries (round 4; one at a time: 177 us for the 4 M queries
 // of the bench isolate).
 template <int W>
-__global__ __launch_bounds__(256) void k_graph_remote(KeyArr<W> keys, int k, GraphTable gt,
-                                                      const uint32_t *__restrict__ roff,
+__global__ __launch_bounds__(256) void k_graph_remote(KeyArr<W> keys, int k, GraphTable gt, GpRows gr,
                                                       const unsigned long long *__restrict__ queries,
                                                       const uint32_t *__restrict__ qcnt,
                                                       uint8_t *__restrict__ adj, uint32_t *__restrict__ nb) {
     const uint32_t P = blockIdx.x;
-    const unsigned long long *myq = queries + 8ull * roff[P];
+    const unsigned long long *myq = queries + 8ull * gr.begin(P);
     const uint32_t nq = qcnt[P];
     constexpr int U = W <= 2 ? 4 : (W <= 4 ? 2 : 1);       // (wide keys: the registers cost more than the round trips)
     for (uint32_t t0 = threadIdx.x; t0 < nq; t0 += blockDim.x * U) {

@@ -57,6 +57,8 @@ static constexpr uint32_t NIL = 0xFFFFFFFFu;
 // pass 1, 11-12 / 14 pass 2, 13 shard layer, 16-17 what the FIRST correction round removed (tips, bubbles: read back with
 // the collapse's first counters — the round costs no host round trip of its own)
 static constexpr int CTL_WORDS = 32;
+static constexpr int CTL_ER = 22;                  // ctl_[22]: table slots reserved by the counting groups (EmitRanges), [23]: a group broken up
+static constexpr uint32_t GP_MAX = 131072;         // graph partitions at most (17 bits of a queued neighbour query)
 static constexpr uint64_t EMPTY64 = ~0ull;
 static constexpr int MAX_PROBE = 4096;
 static constexpr int SPLIT_LOG_DEFAULT = 6;    // one sampled splitter every ~64 oriented nodes (the walk hops over LDS-built fragments: 5 -> 6 measured best)
@@ -947,12 +949,27 @@ public:
                 if (merge == 3) merge = 2;
                 while (merge > 1 && (n_parts % merge != 0 || (n_parts / merge) % 256u != 0 || n_parts / merge < 2u * per_cu * (uint32_t)n_cus_)) merge >>= 1;
                 const uint32_t n_groups = (n_parts + merge - 1) / merge;
+                // where every group's rows go: build_graph takes the groups as its graph partitions when each left in one piece
+                // (their number a power of two: a group's k-mers are those whose minimiser hash has its number in the low bits)
+                EmitRanges er{};
+                er_groups_ = 0;
+                // (cap >= rows: below 2^28 rows the tables' slots, <= 4 rows + 8 groups, stay in the cursor's low word)
+                if (n_parts % merge == 0 && (n_groups & (n_groups - 1u)) == 0 && n_groups <= GP_MAX && cap < (1ull << 28) &&
+                    env_u64("SHK_GRAPH_RANGES", 1) != 0) {
+                    if (int rc = er_off_.alloc(n_groups, err)) return rc;
+                    if (int rc = er_msk_.alloc(n_groups, err)) return rc;
+                    if (int rc = er_start_.alloc(n_groups, err)) return rc;
+                    if (int rc = er_cnt_.alloc(n_groups, err)) return rc;
+                    er.tab_cursor = ctl_.p + CTL_ER; er.broken = (uint32_t *)(ctl_.p + CTL_ER + 1);
+                    er.off = er_off_.p; er.msk = er_msk_.p; er.start = er_start_.p; er.cnt = er_cnt_.p;
+                    er_groups_ = n_groups;
+                }
                 hipLaunchKernelGGL(k_count_weighted<W>, dim3(std::min<uint32_t>(n_groups, per_cu * (uint32_t)n_cus_)), dim3(COUNT_THREADS), 0, stream_,
                                    dd_recs_.p, dd_w_.p, dd_base_.p, dd_n_.p, 0u, n_parts, merge, rv.k, threshold, dh.p, ok, cnt.p, (unsigned long long)cap,
                                    // (ctl_[14]: the groups handed out and, in its high word, this kernel's tally — it starts at the dedupe's verdict
                                    // and covers reads whose records repeat but whose k-mers do not fit)
                                    ctl_.p + 0, ctl_.p + 1, d_ovf.p, (uint32_t *)(ctl_.p + 3), ctl_.p + 14, 0u, defer_after,
-                                   env_dbg("SHK_DEBUG_P2"));
+                                   env_dbg("SHK_DEBUG_P2"), er);
             } else {
                 // (persistent workgroups, one per CU: the tables take the whole LDS)
                 auto kern = rv.weights ? k_count_partitions<W, true> : k_count_partitions<W, false>;
@@ -963,10 +980,11 @@ public:
             }
             HIPCHK(hipGetLastError());
             t.mark();
-            unsigned long long h[4];
+            unsigned long long h[4], her[2] = {0, 0};
             HIPCHK(hipMemcpyAsync(h, ctl_.p, sizeof h, hipMemcpyDeviceToHost, stream_));
             HIPCHK(hipMemcpyAsync(hist_out, dh.p, 500 * 8, hipMemcpyDeviceToHost, stream_));   // (final unless partitions overflowed)
-            WAIT_STREAM();          // one host round trip: counters, histogram and the timer
+            if (split && er_groups_) HIPCHK(hipMemcpyAsync(her, ctl_.p + CTL_ER, sizeof her, hipMemcpyDeviceToHost, stream_));
+            WAIT_STREAM();          // one host round trip: counters, histogram, the groups' ranges' verdict and the timer
             ms_out = t.elapsed();      // (sample + dedupe + count)
             const uint32_t n_ovf = (uint32_t)h[3];
             if (env_u64("SHK_VERBOSE_TALLY", 0)) fprintf(stderr, "[shk] pass 2: %u partitions, %u handed over, tally tried %u / over %u, split %d\n", n_parts, n_ovf,
@@ -1102,6 +1120,10 @@ public:
             }
             if ((uint32_t)h[2]) { err = "partition too large for the LDS table even after 4096-way residue splitting"; return -6; }
             n_rows = h[0]; inst_out = h[1];
+            // (every row lies in the recorded range of its group: no group broken up, none handed to the repartition, and the
+            // recorded ranges hold all the rows)
+            er_ok_ = split && er_groups_ && (uint32_t)her[1] == 0u && n_ovf == 0 && (her[0] >> 32) == h[0];
+            er_rows_ = n_rows;
             if (n_rows <= cap) {
                 return 0;
             }
@@ -1112,6 +1134,7 @@ public:
     }
 
     int histogram(uint64_t histo[500], uint32_t emit_threshold, std::string &err) override {
+        er_ok_ = false;
         if (!global_mode_) {
             memset(histo, 0, 500 * 8);
             n_distinct_ = 0; n_emitted_ = 0; emit_threshold_ = emit_threshold;
@@ -1222,6 +1245,7 @@ public:
             ecnt_.release();
         } else {
             if (threshold < emit_threshold_) { err = "filter threshold below the emit threshold"; return -6; }
+            er_ok_ = false;                                 // (the rows move)
             for (int j = 0; j < W; j++) if (int rc = skeys_[j].alloc(expect, err)) return rc;
             if (int rc = scnt_.alloc(expect, err)) return rc;
             HIPCHK(hipMemsetAsync(ctl_.p, 0, CTL_WORDS * sizeof(unsigned long long), stream_));
@@ -1434,7 +1458,7 @@ public:
         WAIT_STREAM();
         for (int j = 0; j < W; j++) skeys_[j].swap(nk[j]);
         scnt_.swap(nc);
-        n_solid_ = n; total_instances_ = total_instances; n_distinct_ = 0;
+        n_solid_ = n; total_instances_ = total_instances; n_distinct_ = 0; er_ok_ = false;
         for (int i = 0; i < 500; i++) { histo_[i] = histo[i]; n_distinct_ += histo[i]; }
         graph_ready_ = false;
         return 0;
@@ -1461,8 +1485,24 @@ public:
         for (int j = 0; j < W; j++) tkeys_[j].release();
         tcnt_.release(); tstate_.release(); tslots_ = 0;
         recs_.release(); fill_.release(); run_off_.release(); run_cnt_.release(); shard_recv_ = nullptr; batches_.clear();
-        // graph partitions: 320-640 rows each on average (mini tables of <= 2048 slots fit 16 KB of LDS); the minimiser length is the counting pass's, so rows that
-        // arrive grouped by counting partition are grouped by graph partition too
+        // Graph partitions from the counting pass (round 5): the rows of every counting group (EmitRanges, count_part.h) left
+        // k_count_weighted side by side, and a group is the set of k-mers whose minimiser hash — over gm-mers of the counting
+        // pass's length, as here — has the group's number in its low bits.  So the groups ARE graph partitions, their row
+        // ranges the row lists and their tables already placed: k_gp_count, k_gp_scan, k_gp_rows and k_row_starts drop out.
+        // Not when a group was broken up or handed to the repartition, nor for the sharded assembly (every rank must cut the
+        // same partitions, from the global node count), nor when SHK_GP_ROWS or SHK_REGROUP_ROWS=1 ask for the partitions below.
+        // Nor when the groups are too large for the LDS tables: pass 1 sizes them by INSTANCES (a 5 Mbp isolate at 50x: 2048
+        // groups of ~2440 rows), and a partition whose table does not fit sends every neighbour candidate to k_graph_remote —
+        // the partitions below (~610 rows) fit.  Up to 1536 rows on average (std / mean ~0.11): a rare group beyond 2048 rows
+        // works in global memory.
+        const uint64_t regroup_env = env_u64("SHK_REGROUP_ROWS", 2);        // 0 never, 1 always, 2 when the rows are scattered
+        const uint64_t range_rows = env_u64("SHK_GRAPH_RANGE_ROWS", ADJ_LDS_SLOTS_RANGES * 3 / 8);
+        const bool ranges = er_ok_ && er_rows_ == n && n && !sh_active_ && !rows_scattered_ && regroup_env != 1 &&
+                            n <= (uint64_t)er_groups_ * range_rows &&
+                            getenv("SHK_GP_ROWS") == nullptr && env_u64("SHK_GRAPH_RANGES", 1) != 0;
+        er_ok_ = false;                                 // (its tables' places are handed over below)
+        // otherwise: 320-640 rows per partition on average (mini tables of <= 2048 slots fit 16 KB of LDS); the minimiser length is
+        // the counting pass's, so rows that arrive grouped by counting partition are grouped by graph partition too
         gp_ = 64;
         // (measured, `profiles/r02_frag/graph_partition_rows.txt`: 610 rows per partition on average beat 305 — fewer workgroups, the
         // same fixed cost each — while 790 and 980 lose to 400 and 490: partitions above 1024 rows need a table beyond the LDS
@@ -1470,21 +1510,27 @@ public:
         const uint64_t gp_rows_target = env_u64("SHK_GP_ROWS", 640);
         // (sharded assembly: every rank must cut the k-mer space into the same graph partitions — from the global node count)
         const uint64_t n_for_gp = sh_active_ ? n_solid_global_ : n;
-        while (gp_ < 131072u && (uint64_t)gp_ * gp_rows_target < n_for_gp) gp_ <<= 1;
+        while (gp_ < GP_MAX && (uint64_t)gp_ * gp_rows_target < n_for_gp) gp_ <<= 1;
+        if (ranges) gp_ = er_groups_;
         gt_slots_ = 4 * n + 8ull * gp_;               // >= sum of max(8, pow2 >= 2 x rows)
         if (int rc = gt_.alloc(gt_slots_, err)) return rc;
         if (int rc = gt_occ_.alloc(gt_slots_ / 8 + 8, err)) return rc;
         // the nodes' minimiser scans, kept from k_gp_count for k_graph_local (24 B per node; not for graphs beyond 64 M nodes,
         // and dropped when the rows are regrouped in between: k_graph_local then repeats the scan as before)
         gt_scan_.release();
-        if (n && n <= (64ull << 20) && env_u64("SHK_KEEP_SCAN", 1)) if (int rc = gt_scan_.alloc(3 * n, err)) return rc;
-        if (int rc = gt_off_.alloc(gp_, err)) return rc;
-        if (int rc = gt_msk_.alloc(gp_, err)) return rc;
-        DevBuf<uint32_t> gp_of, gp_cnt, gp_roff, gp_rows;
-        if (int rc = gp_of.alloc(n, err)) return rc;
+        if (!ranges && n && n <= (64ull << 20) && env_u64("SHK_KEEP_SCAN", 1)) if (int rc = gt_scan_.alloc(3 * n, err)) return rc;
+        DevBuf<uint32_t> gp_of, gp_cnt, gp_roff, gp_rows, gp_n;   // (gp_n: rows per partition, from the counting groups)
+        if (ranges) {
+            gt_off_.swap(er_off_); gt_msk_.swap(er_msk_); gp_roff.swap(er_start_); gp_n.swap(er_cnt_);
+            er_off_.release(); er_msk_.release(); er_start_.release(); er_cnt_.release();
+        } else {
+            if (int rc = gt_off_.alloc(gp_, err)) return rc;
+            if (int rc = gt_msk_.alloc(gp_, err)) return rc;
+            if (int rc = gp_of.alloc(n, err)) return rc;
+            if (int rc = gp_roff.alloc(gp_ + 1, err)) return rc;
+            if (int rc = gp_rows.alloc(n, err)) return rc;
+        }
         if (int rc = gp_cnt.alloc(gp_, err)) return rc;
-        if (int rc = gp_roff.alloc(gp_ + 1, err)) return rc;
-        if (int rc = gp_rows.alloc(n, err)) return rc;
         DevBuf<unsigned long long> queries;              // 8 slots per row, grouped by partition; only a prefix is touched
         if (int rc = queries.alloc(8 * n + 8, err)) return rc;
         if (int rc = adj_.alloc((n + 8) & ~3ull, err)) return rc;
@@ -1493,53 +1539,75 @@ public:
         if (int rc = alive_.alloc(n, err)) return rc;
         if (int rc = row_starts_.alloc(((n + 63) / 64) * 2 + 2, err)) return rc;
         // (the mini tables are initialised by their builders; no fills for adj_ and alive_: k_graph_local writes the adjacency
-        // byte of every row before k_graph_remote ORs into it, k_row_starts sets the alive flags)
-        HIPCHK(fill2_async(gp_cnt.p, (size_t)gp_ * 4, 0u, ctl_.p, CTL_WORDS * sizeof(unsigned long long), 0u, stream_));
+        // byte of every row before k_graph_remote ORs into it, k_row_starts — or k_graph_local on partitions from the counting
+        // groups — sets the alive flags.  The row-start bits are zeroed for k_graph_local, which sets one per group that needs it)
+        if (ranges) HIPCHK(fill2_async(row_starts_.p, row_starts_.bytes, 0u, ctl_.p, CTL_WORDS * sizeof(unsigned long long), 0u, stream_));
+        else HIPCHK(fill2_async(gp_cnt.p, (size_t)gp_ * 4, 0u, ctl_.p, CTL_WORDS * sizeof(unsigned long long), 0u, stream_));
         // (sharded assembly: a rank that holds NO solid k-mer still owns partitions and is asked about neighbour candidates by
         // the others — its (empty) mini tables must exist: found by the 250-case campaign on 4 ranks, where such a rank answered
         // from tables nobody had built and took a memory fault)
         if (n || sh_active_) {
             Graph<W> g = graph_view();
-            EvTimer t(stream_, stage_timers_);
-            hipLaunchKernelGGL(k_gp_count<W>, dim3(grid_for(n)), dim3(256), 0, stream_, g.keys, (uint32_t)n, k_, g.gt,
-                               gp_of.p, gp_cnt.p);
-            hipLaunchKernelGGL(k_gp_scan, dim3(1), dim3(1024), 0, stream_, gp_cnt.p, gp_, gt_off_.p, gt_msk_.p, gp_roff.p,
-                               ctl_.p + 2);
-            // (gp_cnt is reused as the row-list cursors: k_gp_scan left it zeroed)
-            hipLaunchKernelGGL(k_gp_rows, dim3(grid_for(n)), dim3(256), 0, stream_, gp_of.p, (uint32_t)n, gp_roff.p, gp_cnt.p,
-                               gp_rows.p);
-            HIPCHK(hipGetLastError());
-            const uint64_t regroup_env = env_u64("SHK_REGROUP_ROWS", 2);        // 0 never, 1 always, 2 when the rows are scattered
-            if (n && (regroup_env == 1 || (regroup_env == 2 && rows_scattered_))) {
-                // The rows are not grouped by minimiser partition (they came out of the bucket path in key-hash order): move them
-                // into the order of the row lists once.  Every later pass finds a partition's rows side by side again — the key
-                // reads of k_graph_local coalesce, the LDS tiles of the collapse hold neighbours — and the lists become the identity.
-                DevBuf<uint64_t> nk[W]; DevBuf<uint32_t> nc, ngp;
-                for (int j = 0; j < W; j++) if (int rc = nk[j].alloc(n, err)) return rc;
-                if (int rc = nc.alloc(n, err)) return rc;
-                if (int rc = ngp.alloc(n, err)) return rc;
-                KeyArr<W> out_keys; for (int j = 0; j < W; j++) out_keys.w[j] = nk[j].p;
-                hipLaunchKernelGGL(k_regroup_rows<W>, dim3(grid_for(n)), dim3(256), 0, stream_, g.keys, scnt_.p, gp_of.p, gp_rows.p, (uint32_t)n,
-                                   out_keys, nc.p, ngp.p);
+            const uint32_t lowmask = std::min<uint32_t>(gp_, 256u) - 1u;        // (the collapse's tile edges: see k_row_starts)
+            if (ranges) {
+                // the groups' row ranges and table places are written; k_graph_local checks every row's group
+                EvTimer t(stream_, stage_timers_);
+                t.stop_later("graph_table_kernel", pending_timers_);
+                EvTimer t2(stream_, stage_timers_);
+                const GpRows gr{gp_roff.p, gp_n.p, nullptr};
+                const uint32_t lds_slots = (uint32_t)std::min<uint64_t>(env_u64("SHK_GRAPH_LDS_SLOTS", ADJ_LDS_SLOTS_RANGES), ADJ_LDS_SLOTS_RANGES);
+                hipLaunchKernelGGL((k_graph_local<W, ADJ_LDS_SLOTS_RANGES, ADJ_THREADS_RANGES>), dim3(gp_), dim3(ADJ_THREADS_RANGES), 0, stream_,
+                                   g.keys, k_, g.gt, gr, adj_.p, nb_.p, queries.p, gp_cnt.p, (uint32_t *)(ctl_.p + 1), lds_slots,
+                                   alive_.p, row_starts_.p, lowmask);
+                hipLaunchKernelGGL(k_graph_remote<W>, dim3(gp_), dim3(256), 0, stream_, g.keys, k_, g.gt, gr, queries.p,
+                                   gp_cnt.p, adj_.p, nb_.p);
                 HIPCHK(hipGetLastError());
-                WAIT_STREAM();                          // (the old arrays go back to the pool below)
-                for (int j = 0; j < W; j++) skeys_[j].swap(nk[j]);
-                scnt_.swap(nc); gp_of.swap(ngp);
-                gt_scan_.release();                     // (indexed by the old row numbers)
-                g = graph_view();
-                times_.add("graph_rows_regrouped_x1", 1.0);
+                t2.stop_later("adjacency_kernel", pending_timers_);
+                times_.add("graph_partitions_from_counting_x1", 1.0);
+            } else {
+                EvTimer t(stream_, stage_timers_);
+                hipLaunchKernelGGL(k_gp_count<W>, dim3(grid_for(n)), dim3(256), 0, stream_, g.keys, (uint32_t)n, k_, g.gt,
+                                   gp_of.p, gp_cnt.p);
+                hipLaunchKernelGGL(k_gp_scan, dim3(1), dim3(1024), 0, stream_, gp_cnt.p, gp_, gt_off_.p, gt_msk_.p, gp_roff.p,
+                                   ctl_.p + 2);
+                // (gp_cnt is reused as the row-list cursors: k_gp_scan left it zeroed)
+                hipLaunchKernelGGL(k_gp_rows, dim3(grid_for(n)), dim3(256), 0, stream_, gp_of.p, (uint32_t)n, gp_roff.p, gp_cnt.p,
+                                   gp_rows.p);
+                HIPCHK(hipGetLastError());
+                if (n && (regroup_env == 1 || (regroup_env == 2 && rows_scattered_))) {
+                    // The rows are not grouped by minimiser partition (they came out of the bucket path in key-hash order): move them
+                    // into the order of the row lists once.  Every later pass finds a partition's rows side by side again — the key
+                    // reads of k_graph_local coalesce, the LDS tiles of the collapse hold neighbours — and the lists become the identity.
+                    DevBuf<uint64_t> nk[W]; DevBuf<uint32_t> nc, ngp;
+                    for (int j = 0; j < W; j++) if (int rc = nk[j].alloc(n, err)) return rc;
+                    if (int rc = nc.alloc(n, err)) return rc;
+                    if (int rc = ngp.alloc(n, err)) return rc;
+                    KeyArr<W> out_keys; for (int j = 0; j < W; j++) out_keys.w[j] = nk[j].p;
+                    hipLaunchKernelGGL(k_regroup_rows<W>, dim3(grid_for(n)), dim3(256), 0, stream_, g.keys, scnt_.p, gp_of.p, gp_rows.p, (uint32_t)n,
+                                       out_keys, nc.p, ngp.p);
+                    HIPCHK(hipGetLastError());
+                    WAIT_STREAM();                          // (the old arrays go back to the pool below)
+                    for (int j = 0; j < W; j++) skeys_[j].swap(nk[j]);
+                    scnt_.swap(nc); gp_of.swap(ngp);
+                    gt_scan_.release();                     // (indexed by the old row numbers)
+                    g = graph_view();
+                    times_.add("graph_rows_regrouped_x1", 1.0);
+                }
+                // where a group of rows with the same low minimiser-hash bits starts: the tile edges of the collapse (collapse.h)
+                hipLaunchKernelGGL(k_row_starts, dim3(grid_for(n)), dim3(256), 0, stream_, gp_of.p, (uint32_t)n, lowmask,
+                                   row_starts_.p, alive_.p);
+                t.stop_later("graph_table_kernel", pending_timers_);
+                EvTimer t2(stream_, stage_timers_);
+                const GpRows gr{gp_roff.p, nullptr, gp_rows.p};
+                hipLaunchKernelGGL((k_graph_local<W, ADJ_LDS_SLOTS, 256>), dim3(gp_), dim3(256), 0, stream_, g.keys, k_, g.gt, gr,
+                                   adj_.p, nb_.p, queries.p, gp_cnt.p, (uint32_t *)(ctl_.p + 1), ADJ_LDS_SLOTS,
+                                   (uint8_t *)nullptr, (uint32_t *)nullptr, 0u);
+                hipLaunchKernelGGL(k_graph_remote<W>, dim3(gp_), dim3(256), 0, stream_, g.keys, k_, g.gt, gr, queries.p,
+                                   gp_cnt.p, adj_.p, nb_.p);
+                HIPCHK(hipGetLastError());
+                t2.stop_later("adjacency_kernel", pending_timers_);
+                times_.add("graph_partitions_cut_x1", 1.0);
             }
-            // where a group of rows with the same low minimiser-hash bits starts: the tile edges of the collapse (collapse.h)
-            hipLaunchKernelGGL(k_row_starts, dim3(grid_for(n)), dim3(256), 0, stream_, gp_of.p, (uint32_t)n, std::min<uint32_t>(gp_, 256u) - 1u,
-                               row_starts_.p, alive_.p);
-            t.stop_later("graph_table_kernel", pending_timers_);
-            EvTimer t2(stream_, stage_timers_);
-            hipLaunchKernelGGL(k_graph_local<W>, dim3(gp_), dim3(256), 0, stream_, g.keys, k_, g.gt, gp_roff.p, gp_rows.p,
-                               adj_.p, nb_.p, queries.p, gp_cnt.p, (uint32_t *)(ctl_.p + 1));
-            hipLaunchKernelGGL(k_graph_remote<W>, dim3(gp_), dim3(256), 0, stream_, g.keys, k_, g.gt, gp_roff.p, queries.p,
-                               gp_cnt.p, adj_.p, nb_.p);
-            HIPCHK(hipGetLastError());
-            t2.stop_later("adjacency_kernel", pending_timers_);
             if (sh_active_ && sh_world_ > 1) {
                 // the candidates that live on other ranks: staged compactly before `queries` goes (shard_cross_adjacency)
                 HIPCHK(fill2_async(ctl_.p + 13, 8, 0u, nullptr, 0, 0u, stream_));
@@ -1578,6 +1646,7 @@ public:
         if (!graph_check_pending_) return 0;
         graph_check_pending_ = false;
         const unsigned long long *h = mbox64() + MB_CTL;
+        if ((uint32_t)h[1] == 2u) { err = "graph partition: a row lies outside its counting group's minimiser range"; return -6; }
         if ((uint32_t)h[1] || h[2] > gt_slots_) { err = "graph table overflow"; return -6; }
         return 0;
     }
@@ -2649,6 +2718,9 @@ private:
     DevBuf<uint64_t> ekeys_[W]; DevBuf<uint32_t> ecnt_;
     uint64_t n_emitted_ = 0; uint32_t emit_threshold_ = 0;
     bool rows_scattered_ = false;                    // most rows came out of the k-mer-level repartition (run_count_partitions)
+    // the groups of k_count_weighted and where their rows went (EmitRanges): build_graph's partitions when er_ok_
+    DevBuf<unsigned long long> er_off_; DevBuf<uint32_t> er_msk_, er_start_, er_cnt_;
+    uint32_t er_groups_ = 0; uint64_t er_rows_ = 0; bool er_ok_ = false;
     // solid set / graph
     DevBuf<uint64_t> skeys_[W]; DevBuf<uint32_t> scnt_;
     DevBuf<uint64_t> gt_; DevBuf<uint8_t> gt_occ_; DevBuf<uint2> gt_scan_; uint64_t gt_slots_ = 0; uint32_t gp_ = 64;
