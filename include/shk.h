@@ -62,6 +62,10 @@ void shk_set_progress_cb(shk_handle *h, shk_progress_cb cb, void *user);
 
 /* AssemblyHelper::preprocess(file1, file2|null)                        Assembler.ts:35,100
  * fq1/fq2: whole FASTQ files in memory, plain or gzip (fastx_wasm.rs:9,53-70); fq2 may be NULL.
+ * gzip: a file of >= 4 MiB (SHK_GUNZIP_DEVICE_MIN) that is one plain member, or a BGZF (bgzip) chain of blocks from its
+ * first byte to its last, is inflated on the device (a BGZF file one wave per block), a plain member or a BGZF file in any
+ * combination within a pair; everything else (several plain members, a broken chain, damaged data) is read on the host,
+ * which owns the error messages.  SHK_GUNZIP_DEVICE=0: always on the host.
  * The buffers are not retained. */
 int shk_preprocess(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2);
 
@@ -221,10 +225,11 @@ void shk_host_free(void *p);
  * has handled in this process so far; *reader_seconds (optional): the time the reader itself took (without the copy into
  * *out).  SHK_GUNZIP_THREADS (environment): its thread count, 0 or 1 = zlib only. */
 int shk_host_gunzip(const uint8_t *gz, size_t n, uint8_t **out, size_t *out_n, uint64_t *mt_members, double *reader_seconds);
-/* the DEVICE inflater alone (csrc/inflate_gpu.hip; needs a GPU): shk_preprocess hands a plain gzip member of >= 4 MiB
- * (SHK_GUNZIP_DEVICE_MIN) to it first — the compressed bytes are what crosses PCIe — and reads on the host whatever it does
- * not take.  0: *out (malloc'd, shk_host_free) holds the member's bytes, equal to zlib's; 1: not taken, *why (optional) says
- * why; < 0: error.  *ms_total (optional): upload + kernels + checks. */
+/* the DEVICE inflater alone (csrc/inflate_gpu.hip; needs a GPU): shk_preprocess hands a plain gzip member or a BGZF
+ * (bgzip) file of >= 4 MiB (SHK_GUNZIP_DEVICE_MIN) to it first — the compressed bytes are what crosses PCIe; a BGZF file is
+ * decoded one wave per block — and reads on the host whatever it does not take.  0: *out (malloc'd, shk_host_free) holds
+ * the bytes of the member or of the whole BGZF file, equal to zlib's; 1: not taken, *why (optional) says why; < 0: error.
+ * *ms_total (optional): upload + kernels + checks. */
 int shk_device_gunzip(const uint8_t *gz, size_t n, uint8_t **out, size_t *out_n, const char **why, double *ms_total);
 /* SPEC S9 (tips, bubbles) and S10 (chains of simple links, the circular cut) on UNITIG records instead of k-mers — what the
  * sharded assembly runs on every rank's host once the k-mer-level contraction is done on the GPUs (csrc/unitig_graph.h:

@@ -435,7 +435,8 @@ static int preprocess_device_pieces(shk_handle *h, const uint8_t *t1, size_t l1,
     return finish_counting(h);
 }
 
-// Both files (or the one) are plain gzip members the device inflater takes: inflate -> device parser -> one batch.
+// Both files (or the one) are what the device inflater takes — a plain gzip member or a BGZF chain, in any combination
+// within a pair: inflate -> device parser -> one batch.
 // handled = false (nothing counted, nothing posted beyond what the host path posts again) when any file is not taken or
 // turns out not to be regular 4-line FASTQ: the caller's host reader then starts over.
 static int preprocess_device_gzip(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, size_t total, bool &handled) {
@@ -449,12 +450,14 @@ static int preprocess_device_gzip(shk_handle *h, const uint8_t *fq1, size_t n1, 
     GpuPacked packed[2];
     auto drop = [&]() { for (int f = 0; f < 2; f++) { gpu_text_free(text[f]); gpu_packed_free(packed[f]); } };
     double ms_h2d = 0, ms_search = 0, ms_decode = 0, ms_resolve = 0;
+    uint64_t bgzf_blocks = 0;
     for (int f = 0; f < nf; f++) {
         GpuInflateStats st;
         const int rc = gpu_inflate_member(gz[f], gn[f], h->pipe->device(), h->pipe->stream(), text[f], err, &st);
         if (rc == 1) { drop(); h->pipe->times().add("gunzip_device_not_taken_x1", 1.0); return SHK_OK; }
         if (rc) { drop(); return fail(h, rc == -4 ? SHK_E_OOM : SHK_E_DEVICE, err); }
         ms_h2d += st.h2d_ms; ms_search += st.search_ms; ms_decode += st.decode_ms; ms_resolve += st.resolve_ms;
+        bgzf_blocks += st.blocks;
     }
     const double t1 = now_ms();
     uint64_t text_total = 0;
@@ -484,6 +487,7 @@ static int preprocess_device_gzip(shk_handle *h, const uint8_t *fq1, size_t n1, 
     h->pipe->times().add("gunzip_device_decode", ms_decode);
     h->pipe->times().add("gunzip_device_windows_resolve_crc", ms_resolve);
     h->pipe->times().add("gunzip_device_members_x1", (double)nf);
+    if (bgzf_blocks) h->pipe->times().add("gunzip_device_bgzf_blocks_x1", (double)bgzf_blocks);      // non-empty BGZF blocks, one wave each
     h->pipe->times().add("fastq_device_parse_pack_host_clock", now_ms() - t1);
     h->n_reads = reads_done;
     std::vector<DevPiece> pcs;
@@ -513,9 +517,10 @@ static int preprocess_impl(shk_handle *h, const uint8_t *fq1, size_t n1, const u
     // packed by streaming kernels.  Irregular input and every malformed record go to the host parser
     // below, which owns the error messages.
     // gzip (plain members: one thread per file; BGZF: block-parallel) is inflated once, for either parser
-    // ---- .fastq.gz (the reference's real input: fastx_wasm.rs:53-70): a plain gzip member of some size is inflated ON THE
-    // DEVICE — the compressed bytes are what crosses PCIe — and its text goes straight to the device parser; whatever the
-    // device inflater does not take (several members, BGZF, binary data, a damaged stream) is read on the host below
+    // ---- .fastq.gz (the reference's real input: fastx_wasm.rs:53-70): a plain gzip member or a BGZF (bgzip) file of some
+    // size is inflated ON THE DEVICE — the compressed bytes are what crosses PCIe — and its text goes straight to the device
+    // parser; whatever the device inflater does not take (several plain members, a broken BGZF chain, binary data, a
+    // damaged stream) is read on the host below
     {
         const char *gd = getenv("SHK_GUNZIP_DEVICE");
         const char *fh = getenv("SHK_HOST_PARSER");
@@ -1341,8 +1346,8 @@ char *shk_host_assembly_json_arriving(const char *seqs, const uint64_t *offsets,
     } catch (...) { return nullptr; }
 }
 void shk_host_free(void *p) { free(p); }
-// the device inflater alone (csrc/inflate_gpu.hip): 0 = *out (malloc'd, shk_host_free) holds the member's bytes; 1 = the
-// member was not taken (*why says why: the product then reads it on the host); < 0 = error
+// the device inflater alone (csrc/inflate_gpu.hip): 0 = *out (malloc'd, shk_host_free) holds the bytes of the member or of
+// the BGZF file; 1 = the file was not taken (*why says why: the product then reads it on the host); < 0 = error
 int shk_device_gunzip(const uint8_t *gz, size_t n, uint8_t **out, size_t *out_n, const char **why, double *ms_total) {
     try {
         if (!gz || !out || !out_n) return SHK_E_PARAM;

@@ -140,7 +140,7 @@ static int inflate_all(const uint8_t *in, size_t n, ByteVec &out, std::string &e
 
 // ---- BGZF (bgzip) input: a gzip file made of independent blocks of <= 64 KiB, each announcing its
 // compressed size in a 'BC' extra subfield (SAM spec section 4.1).  The blocks are inflated in parallel.
-static bool bgzf_block(const uint8_t *b, size_t n, size_t &bsize) {
+bool bgzf_block(const uint8_t *b, size_t n, size_t &bsize) {
     if (n < 18 || b[0] != 0x1F || b[1] != 0x8B || b[2] != 8 || !(b[3] & 4)) return false;
     const size_t xlen = b[10] | ((size_t)b[11] << 8);
     if (12 + xlen > n) return false;
@@ -186,7 +186,8 @@ static int inflate_bgzf(const uint8_t *in, size_t n, ByteVec &out, std::string &
             memset(&zs, 0, sizeof zs);
             if (inflateInit2(&zs, -15) != Z_OK) { bad = 1; break; }
             zs.next_in = (Bytef *)(in + b.in_off + b.hdr); zs.avail_in = (uInt)(b.in_len - b.hdr - 8);
-            zs.next_out = out.data() + b.out_off; zs.avail_out = (uInt)b.out_len;
+            uint8_t none;                                    // (a file of empty blocks alone has no output buffer, and zlib wants a pointer)
+            zs.next_out = total ? out.data() + b.out_off : &none; zs.avail_out = (uInt)b.out_len;
             const int rc = inflate(&zs, Z_FINISH);
             const bool ok = (rc == Z_STREAM_END) && zs.avail_out == 0;
             inflateEnd(&zs);

@@ -37,6 +37,9 @@ int pack_fastq(const uint8_t *buf, size_t n, uint32_t k, uint32_t min_qual, Pack
                uint64_t flush_reads = 0, uint64_t flush_bases = 0, const FlushFn &flush = nullptr,
                uint64_t rec_base = 0 /* records of this file that came before buf: numbering of the error messages */);
 
+// b[0..n) starts with a whole BGZF block (SAM spec 4.1: a gzip member with a 'BC' extra subfield that holds its size - 1):
+// bsize = that size.  The one rule by which both the host reader and the device inflater (inflate_gpu.hip) walk a chain.
+bool bgzf_block(const uint8_t *b, size_t n, size_t &bsize);
 // gzip sniff (1F 8B) + multi-member inflate; plain input is passed through (p/n point at buf or at `storage`)
 int maybe_inflate(const uint8_t *buf, size_t n, ByteVec &storage, const uint8_t *&p, size_t &pn,
                   std::string &err);

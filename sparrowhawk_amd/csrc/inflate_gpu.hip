@@ -1,4 +1,5 @@
-// inflate_gpu.hip — see inflate_gpu.h.  One gzip member (one deflate stream) inflated on gfx950.
+// inflate_gpu.hip — see inflate_gpu.h.  One gzip member (one deflate stream), or a BGZF file (a chain of small ones),
+// inflated on gfx950.
 //
 // The reference's real input is a `.fastq.gz` pair read through flate2's MultiGzDecoder
 // (/root/reference/rust/orphos-bridge/src/fastx_wasm.rs:53-70; /root/reference/docs/src/assembly.md:25-28).  A deflate
@@ -13,10 +14,19 @@
 //                      of it: 16-bit symbols, a back-reference into the unknown window is a MARKER (256 + position in that
 //                      window).  The Huffman state is wave-uniform (every lane decodes the same symbol: tables in LDS,
 //                      broadcast reads), the copy of a match is done by the 64 lanes together out of an LDS ring that holds
-//                      the last 4096 symbols (older ones from HBM); output leaves in coalesced 1 KB flushes
-//   k_gz_windows       the 32 KiB windows in front of the chunks, front to back (the one serial step: one workgroup, the
-//                      window of chunk c from that of c - 1 through LDS)
+//                      the last 2048 symbols (RING; older ones from HBM); output leaves in coalesced 512-byte flushes
+//                      (FLUSH = 256 symbols)
+//   k_gz_win_init      the 32 KiB windows in front of the chunks: window c starts as the tail of chunk c - 1, and what is
+//   k_gz_win_round     not known there (a marker, a chunk shorter than a window) points into the window in front of c - 1;
+//                      round r replaces every pointer into the window 2^r chunks further front by what stands there after
+//                      round r - 1 — ceil(log2(chunks)) rounds over all windows at once, no serial step
 //   k_gz_resolve       markers -> bytes, 16 -> 8 bits, coalesced;  k_gz_crc  CRC-32 of 64 KiB slices (combined on the host)
+// A BGZF (bgzip) file needs none of the speculation: every block is a deflate stream of its own of at most 64 KiB of text,
+// with its compressed size in its header and CRC-32 and length of its text in its trailer (SAM specification 4.1):
+//   k_bgzf_decode      one wave per non-empty block, the same wave-uniform decoder with its window known: BYTES, through a
+//                      4 KiB ring in LDS, straight into the final text at the block's offset (the prefix sum of the lengths);
+//                      nothing is produced or stored beyond the block's length, whatever its stream says
+//   k_bgzf_crc         CRC-32 of every block's text against its trailer; one word comes back, not a checksum per block
 // Everything that does not look as expected makes gpu_inflate_member return 1 and the caller inflates on the host: the
 // bytes handed on are always the bytes zlib would produce (CRC-32 and ISIZE of the trailer are checked here too).
 #include <hip/hip_runtime.h>
@@ -32,6 +42,7 @@
 
 #include "inflate_gpu.h"
 #include "pipeline.h"
+#include "fastq.h"
 
 namespace shk {
 namespace {
@@ -560,6 +571,161 @@ __global__ __launch_bounds__(256) void k_gz_crc(const uint8_t *__restrict__ text
     crc_out[s] = crc ^ 0xFFFFFFFFu;
 }
 
+// ---- BGZF (bgzip): a chain of independent deflate streams of <= 64 KiB of text each --------------------------------------
+// Every block announces its compressed size in its header and carries CRC-32 and length (ISIZE) of its text in its trailer
+// (SAM specification 4.1), so nothing is searched for and nothing is unknown: no markers, no windows, no second pass.  One
+// wave per non-empty block decodes BYTES into an LDS ring and writes them straight into the final text at the block's
+// offset (the prefix sum of the ISIZE fields).  The blocks' texts lie back to back, so bounds hold by construction: nothing
+// is produced at or beyond ISIZE, and no store touches a byte outside [out_off, out_off + ISIZE).
+constexpr uint32_t BZ_RING = 4096, BZ_MASK = BZ_RING - 1, BZ_NEAR = BZ_RING - 512, BZ_GROUP = 256;
+enum : uint32_t { BZ_GOOD = 1, BZ_FINAL = 2, BZ_CORRUPT = 3, BZ_TOO_LONG = 4, BZ_TOO_SHORT = 5, BZ_NOT_AT_END = 6 };
+struct BgzfDesc { unsigned long long in_off; uint32_t in_len, out_off, isize, crc; };      // deflate bytes in the file / text
+struct BgzfLds {
+    HuffLds h;
+    alignas(4) uint8_t ring[BZ_RING];        // the block's last BZ_RING bytes, indexed by their address in the text (mod BZ_RING)
+};
+
+// bad[0]: the first block (atomicMin) that is not good; status[blk]: why
+__global__ __launch_bounds__(64) void k_bgzf_decode(const uint32_t *__restrict__ w, const BgzfDesc *__restrict__ desc, uint32_t n_blocks,
+                                                   uint8_t *text, uint32_t *__restrict__ status_out, uint32_t *__restrict__ bad) {
+    __shared__ BgzfLds L;
+    const uint32_t blk = blockIdx.x;
+    if (blk >= n_blocks) return;
+    const uint32_t lane = threadIdx.x;
+    const BgzfDesc d = desc[blk];
+    const uint32_t isize = d.isize, a32 = d.out_off;
+    const uint64_t in_end = d.in_off + d.in_len;
+    uint8_t *out = text + d.out_off;
+    UBits b; b.w = w; b.nbytes = in_end;                        // (overrun(): the reader has left THIS block's deflate data)
+    b.seek(d.in_off * 8ull);
+    uint32_t pos = 0, flushed = 0;                              // bytes produced / already in HBM
+    uint32_t status = 0;
+    // bytes [lo, hi) of the block, all inside one aligned group of BZ_GROUP bytes of the text, ring -> HBM.  A lane owns one
+    // aligned dword of the group: stored whole if it lies inside [lo, hi), byte by byte where the range starts or ends inside
+    // it (the neighbouring blocks' waves write the other bytes of such a dword)
+    auto store_range = [&](uint32_t lo, uint32_t hi) {
+        const uint32_t g = ((a32 + lo) & ~(BZ_GROUP - 1u)) + 4u * lane;      // this lane's dword: its address in the text ...
+        const int r = (int)(g - a32);                                      // ... and in the block (may lie in front of it)
+        if (r >= (int)lo && r + 4 <= (int)hi) *reinterpret_cast<uint32_t *>(out + r) = *reinterpret_cast<const uint32_t *>(&L.ring[g & BZ_MASK]);
+        else {
+#pragma unroll
+            for (int q = 0; q < 4; q++) if (r + q >= (int)lo && r + q < (int)hi) out[r + q] = L.ring[(g + (uint32_t)q) & BZ_MASK];
+        }
+    };
+    auto group_end = [&](uint32_t at) { return at + BZ_GROUP - ((a32 + at) & (BZ_GROUP - 1u)); };
+    // whenever BZ_GROUP bytes have piled up: out go the groups that are complete, and the reader is checked (the input is
+    // zero-padded far enough for what can be read in between)
+    auto flush_full = [&]() -> bool {
+        for (uint32_t e = group_end(flushed); e <= pos; e = group_end(flushed)) { store_range(flushed, e); flushed = e; }
+        // (bytes this far back are read from HBM again by far matches — by lanes of this same wave: the stores have to be complete)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        if (b.overrun()) { status = BZ_CORRUPT; return false; }
+        return true;
+    };
+    for (;;) {
+        const uint32_t bfinal = b.get(1), btype = b.get(2);
+        if (b.overrun() || btype == 3) { status = BZ_CORRUPT; break; }
+        if (btype == 0) {
+            b.drop(b.cnt & 7u);                                  // to the byte boundary
+            const uint32_t len = b.get(16), nlen = b.get(16);
+            if ((len ^ nlen) != 0xFFFFu || b.overrun()) { status = BZ_CORRUPT; break; }
+            uint64_t at = b.pos() >> 3;                          // the stored bytes: copied by the lanes, 256 at a time
+            if (at + len > in_end) { status = BZ_CORRUPT; break; }
+            if (len > isize - pos) { status = BZ_TOO_LONG; break; }
+            const uint8_t *in8 = reinterpret_cast<const uint8_t *>(w);
+            for (uint32_t left = len; left;) {
+                const uint32_t m = left < BZ_GROUP ? left : BZ_GROUP;
+                for (uint32_t i = lane; i < m; i += 64) L.ring[(a32 + pos + i) & BZ_MASK] = in8[at + i];
+                pos += m; at += m; left -= m;
+                if (pos - flushed >= BZ_GROUP) (void)flush_full();   // (the reader stands still: it cannot fail here)
+            }
+            b.seek(at * 8ull);
+        } else {
+            if (btype == 1) fixed_codes(L.h);
+            else if (!read_dynamic(b, L.h)) { status = BZ_CORRUPT; break; }
+            const uint32_t lit_max = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.h.lit_maxlen), dist_max = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.h.dist_maxlen);
+            bool bad_code = false;
+            for (;;) {
+                b.refill();
+                const int s = decode_sym(b, L.h.lit_tab, LIT_PB, L.h.lit_count, L.h.lit_sym, lit_max);
+                if (s < 0) { bad_code = true; break; }
+                if (s < 256) {
+                    if (pos >= isize) { status = BZ_TOO_LONG; break; }
+                    L.ring[(a32 + pos) & BZ_MASK] = (uint8_t)s;
+                    pos++;
+                    if (pos - flushed >= BZ_GROUP) { if (!flush_full()) break; }
+                    continue;
+                }
+                if (s == 256) break;
+                if (s > 285) { bad_code = true; break; }
+                uint32_t lb, le; len_code((uint32_t)s - 257u, lb, le);
+                const uint32_t len = lb + b.get(le);
+                b.refill();
+                const int ds = decode_sym(b, L.h.dist_tab, DIST_PB, L.h.dist_count, L.h.dist_sym, dist_max);
+                if (ds < 0 || ds > 29) { bad_code = true; break; }
+                uint32_t db, de; dist_code((uint32_t)ds, db, de);
+                const uint32_t dist = db + b.get(de);
+                if (dist > pos) { bad_code = true; break; }      // in front of the block's first byte: a block starts its own history
+                if (len > isize - pos) { status = BZ_TOO_LONG; break; }
+                // the copy, by all lanes: position pos + i takes what stands dist back — periodic when the match overlaps itself,
+                // so every source lies in front of pos and the lanes do not depend on one another
+                for (uint32_t i = lane; i < len; i += 64) {
+                    const uint32_t j = i < dist ? i : i % dist;
+                    const uint32_t src = pos - dist + j;
+                    const uint8_t v = pos - src <= BZ_NEAR ? L.ring[(a32 + src) & BZ_MASK] : out[src];
+                    L.ring[(a32 + pos + i) & BZ_MASK] = v;
+                }
+                pos += len;
+                if (pos - flushed >= BZ_GROUP) { if (!flush_full()) break; }
+            }
+            if (status) break;
+            if (bad_code) { status = BZ_CORRUPT; break; }
+        }
+        if (bfinal) { status = BZ_FINAL; break; }
+    }
+    // what is left in the ring (pos <= isize: inside the block's range)
+    while (flushed < pos) { const uint32_t e = min(group_end(flushed), pos); store_range(flushed, e); flushed = e; }
+    // good: the final block was reached, exactly ISIZE bytes came out, and the stream ends in the block's last deflate byte
+    if (status == BZ_FINAL) status = pos != isize ? BZ_TOO_SHORT : (b.pos() + 7ull) / 8ull != in_end ? BZ_NOT_AT_END : BZ_GOOD;
+    if (lane == 0) { status_out[blk] = status; if (status != BZ_GOOD) atomicMin(&bad[0], blk); }
+}
+
+// CRC-32 of every block's text against its trailer: one thread per block, four table look-ups per dword (slicing by 4).
+// bad[1]: the first block (atomicMin) whose checksum differs
+__global__ __launch_bounds__(64) void k_bgzf_crc(const uint8_t *__restrict__ text, const BgzfDesc *__restrict__ desc, uint32_t n_blocks, uint32_t *__restrict__ bad) {
+    __shared__ uint32_t tab[4][256];
+    for (uint32_t e = threadIdx.x; e < 256; e += 64) {
+        uint32_t cc = e;
+        for (int k = 0; k < 8; k++) cc = (cc & 1u) ? 0xEDB88320u ^ (cc >> 1) : cc >> 1;
+        tab[0][e] = cc;
+    }
+    __syncthreads();
+    for (uint32_t e = threadIdx.x; e < 256; e += 64) {
+        uint32_t cc = tab[0][e];
+        for (int t = 1; t < 4; t++) { cc = (cc >> 8) ^ tab[0][cc & 0xFFu]; tab[t][e] = cc; }
+    }
+    __syncthreads();
+    const uint32_t blk = blockIdx.x * 64u + threadIdx.x;
+    if (blk >= n_blocks) return;
+    const BgzfDesc d = desc[blk];
+    unsigned long long p = d.out_off;
+    const unsigned long long e = p + d.isize;
+    uint32_t crc = 0xFFFFFFFFu;
+    // a block starts at any byte: byte-wise up to the first 16-byte boundary of the text, then 16 bytes per load
+    for (; p < e && (p & 15u); p++) crc = tab[0][(crc ^ text[p]) & 0xFFu] ^ (crc >> 8);
+    for (; p + 16 <= e; p += 16) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(text + p);
+        const uint32_t ws[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const uint32_t x = crc ^ ws[q];
+            crc = tab[3][x & 0xFFu] ^ tab[2][(x >> 8) & 0xFFu] ^ tab[1][(x >> 16) & 0xFFu] ^ tab[0][x >> 24];
+        }
+    }
+    for (; p < e; p++) crc = tab[0][(crc ^ text[p]) & 0xFFu] ^ (crc >> 8);
+    if ((crc ^ 0xFFFFFFFFu) != d.crc) atomicMin(&bad[1], blk);
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 // CRC-32 of A || B from crc(A), crc(B): crc(A) advanced over len(B) zero bytes (a GF(2) matrix), XOR crc(B).  The slices
 // have one length, so the matrix is built once (zlib 1.2.11 has no crc32_combine_gen).
@@ -596,6 +762,116 @@ struct Blk {                                               // a device block of 
         if (_e != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(_e); (void)hipStreamSynchronize(st); return -5; } \
     } while (0)
 
+namespace {
+// The inflated text (d_text: `total` bytes and 64 more, `tail`: a copy of its last tail_n bytes) as gpu_upload_text hands a
+// text on: trailing blank lines cut off, 32 zero bytes behind it (fastq_gpu.hip: trimmed_len — "\n\n" and "\n\r\n" at the
+// end lose their last line end, repeatedly); raw: every byte stays.  0: out owns the block; 1: not taken (*why); -5.
+int hand_on_text(Blk &d_text, uint64_t total, const char *tail, size_t tail_n, bool raw, hipStream_t st, GpuText &out, const char *&why, std::string &err) {
+    size_t te = tail_n;
+    for (;;) {
+        if (te >= 2 && tail[te - 1] == '\n' && tail[te - 2] == '\n') { te -= 1; continue; }
+        if (te >= 3 && tail[te - 1] == '\n' && tail[te - 2] == '\r' && tail[te - 3] == '\n') { te -= 2; continue; }
+        break;
+    }
+    if (raw) te = tail_n;
+    if (te < 8 && total > tail_n) { why = "kilobytes of blank lines at the end"; return 1; }
+    const size_t e = (size_t)(total - tail_n) + te;
+    if (e == 0) { why = "empty text"; return 1; }
+    if (!raw) GZCHK(hipMemsetAsync((char *)d_text.p + e, 0, std::min<size_t>(32, (size_t)total + 64 - e), st));
+    GZCHK(hipStreamSynchronize(st));
+    out.pool_bytes = d_text.bytes; out.d = (uint8_t *)d_text.take();
+    out.e = e; out.unterminated = te == 0 || tail[te - 1] != '\n';
+    return 0;
+}
+
+// gz[0..n) starts with a BGZF block.  Taken only if every byte of the file belongs to the chain of blocks (what follows a
+// first BGZF block may be anything: the host reader owns "BGZF block chain broken" and its kin); same results as
+// gpu_inflate_member, except that running out of device memory is "not taken" too: the host reader reads these files.
+int gpu_inflate_bgzf(const uint8_t *gz, size_t n, int device, hipStream_t st, GpuText &out, std::string &err, GpuInflateStats &S, bool raw) {
+    auto not_taken = [&](const char *why) { S.why_not = why; return 1; };
+    const char *mv = getenv("SHK_GUNZIP_DEVICE_MIN");
+    const size_t min_bytes = (mv && *mv) ? (size_t)strtoull(mv, nullptr, 10) : ((size_t)4 << 20);
+    if (n < min_bytes) return not_taken("small file");
+    if (n >= ((size_t)1 << 34)) return not_taken("beyond 16 GiB");      // (UBits counts the input in 32-bit dwords)
+    // ---- the chain: one descriptor per non-empty block
+    std::vector<BgzfDesc> desc;
+    uint64_t total = 0;
+    for (size_t p = 0; p < n;) {
+        size_t bs = 0;
+        if (!bgzf_block(gz + p, n - p, bs)) return not_taken("BGZF block chain broken");
+        if (gz[p + 3] != 4) return not_taken("a BGZF block with more than the extra field");      // (FNAME, FCOMMENT, FHCRC: bgzip writes none)
+        const size_t hdr = 12 + (gz[p + 10] | ((size_t)gz[p + 11] << 8));
+        const uint8_t *t = gz + p + bs - 8;
+        const uint32_t crc = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+        const uint32_t isize = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+        if (isize > 65536) return not_taken("a BGZF block of more than 64 KiB");
+        if (isize) desc.push_back(BgzfDesc{(unsigned long long)(p + hdr), (uint32_t)(bs - hdr - 8), (uint32_t)total, isize, crc});
+        else {
+            // an empty block (the end-of-file marker, also in mid-file) gets no wave: a few bytes for zlib
+            uint8_t sink[8];
+            z_stream zs; memset(&zs, 0, sizeof zs);
+            if (inflateInit2(&zs, -15) != Z_OK) return not_taken("zlib init failed");
+            zs.next_in = (Bytef *)(gz + p + hdr); zs.avail_in = (uInt)(bs - hdr - 8);
+            zs.next_out = sink; zs.avail_out = sizeof sink;
+            const int rc = inflate(&zs, Z_FINISH);
+            const bool ok = rc == Z_STREAM_END && zs.avail_out == sizeof sink && zs.avail_in == 0;
+            inflateEnd(&zs);
+            if (!ok || crc != 0) return not_taken("a damaged empty BGZF block");
+        }
+        total += isize; p += bs;
+        if (total >= ((uint64_t)1 << 32)) return not_taken("empty or beyond 4 GiB");
+    }
+    if (total == 0) return not_taken("empty or beyond 4 GiB");
+    const uint32_t nb = (uint32_t)desc.size();
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); err = "hipSetDevice failed"; return -5; }
+    const double t_begin = now_ms();
+    // ---- upload: the file as it is (26 bytes of header and trailer per block are not worth a repack), zero padding behind
+    Blk d_in, d_desc, d_status, d_bad, d_text;
+    const size_t in_words = (n + 3) / 4 + 2048 + 256;        // (the same padding as for a plain member: see gpu_inflate_member)
+    if (!d_in.get(in_words * 4) || !d_desc.get((size_t)nb * sizeof(BgzfDesc)) || !d_status.get((size_t)nb * 4) || !d_bad.get(64) ||
+        !d_text.get((size_t)total + 64))
+        return not_taken("out of device memory");
+    GZCHK(hipMemsetAsync((char *)d_in.p + (n & ~(size_t)3), 0, in_words * 4 - (n & ~(size_t)3), st));
+    GZCHK(hipMemcpyAsync(d_in.p, gz, n, hipMemcpyHostToDevice, st));
+    GZCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nb * sizeof(BgzfDesc), hipMemcpyHostToDevice, st));
+    GZCHK(hipMemsetAsync(d_bad.p, 0xFF, 64, st));
+    GZCHK(hipMemsetAsync((char *)d_text.p + total, 0, 64, st));
+    GZCHK(hipStreamSynchronize(st));
+    S.h2d_ms = now_ms() - t_begin;
+    // ---- every block, then its checksum; one word each comes back
+    double t1 = now_ms();
+    hipLaunchKernelGGL(k_bgzf_decode, dim3(nb), dim3(64), 0, st, (const uint32_t *)d_in.p, (const BgzfDesc *)d_desc.p, nb, (uint8_t *)d_text.p,
+                       (uint32_t *)d_status.p, (uint32_t *)d_bad.p);
+    GZCHK(hipGetLastError());
+    if (getenv("SHK_GUNZIP_DEBUG")) { GZCHK(hipStreamSynchronize(st)); S.decode_ms = now_ms() - t1; }
+    hipLaunchKernelGGL(k_bgzf_crc, dim3((nb + 63) / 64), dim3(64), 0, st, (const uint8_t *)d_text.p, (const BgzfDesc *)d_desc.p, nb, (uint32_t *)d_bad.p);
+    GZCHK(hipGetLastError());
+    uint32_t h_bad[2] = {0, 0};
+    char tail[4096];
+    const size_t tail_n = (size_t)std::min<uint64_t>(total, sizeof tail);
+    GZCHK(hipMemcpyAsync(h_bad, d_bad.p, 8, hipMemcpyDeviceToHost, st));
+    GZCHK(hipMemcpyAsync(tail, (char *)d_text.p + (total - tail_n), tail_n, hipMemcpyDeviceToHost, st));
+    GZCHK(hipStreamSynchronize(st));
+    if (S.decode_ms == 0) S.decode_ms = now_ms() - t1; else S.resolve_ms = now_ms() - t1 - S.decode_ms;
+    if (h_bad[0] != 0xFFFFFFFFu) {                            // the first block that is not good: what it did
+        uint32_t status = 0;
+        GZCHK(hipMemcpyAsync(&status, (uint32_t *)d_status.p + h_bad[0], 4, hipMemcpyDeviceToHost, st));
+        GZCHK(hipStreamSynchronize(st));
+        return not_taken(status == BZ_TOO_LONG ? "a BGZF block inflates beyond its ISIZE" : status == BZ_TOO_SHORT ? "a BGZF block ends short of its ISIZE" :
+                         status == BZ_NOT_AT_END ? "a BGZF block's stream does not end where its data ends" : "a damaged BGZF block");
+    }
+    if (h_bad[1] != 0xFFFFFFFFu) return not_taken("CRC-32 mismatch");
+    const char *why = "";
+    if (const int rt = hand_on_text(d_text, total, tail, tail_n, raw, st, out, why, err)) return rt == 1 ? not_taken(why) : rt;
+    out.h2d_ms = S.h2d_ms;
+    S.blocks = nb; S.text_bytes = total; S.total_ms = now_ms() - t_begin;
+    if (getenv("SHK_GUNZIP_DEBUG"))
+        fprintf(stderr, "[inflate_gpu] BGZF, %u blocks: upload %.2f ms, decode %.2f, crc %.2f, total %.2f ms for %.3f GB of text\n",
+                nb, S.h2d_ms, S.decode_ms, S.resolve_ms, S.total_ms, (double)total / 1e9);
+    return 0;
+}
+}  // namespace
+
 int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, GpuText &out, std::string &err, GpuInflateStats *stats, bool raw) {
     GpuInflateStats local; GpuInflateStats &S = stats ? *stats : local;
     S = GpuInflateStats();
@@ -609,8 +885,10 @@ int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, Gp
     if (flg & 4) {
         if (p + 2 > n) return not_taken("truncated header");
         const size_t xlen = gz[p] | ((size_t)gz[p + 1] << 8);
-        // (BGZF: an extra field 'BC' — many small members: the host reader inflates them block-parallel)
-        if (xlen >= 6 && p + 2 + xlen <= n && gz[p + 2] == 'B' && gz[p + 3] == 'C') return not_taken("BGZF");
+        // (BGZF: a 'BC' subfield — many small members, one wave each)
+        size_t bs = 0;
+        if (bgzf_block(gz, n, bs)) return gpu_inflate_bgzf(gz, n, device, (hipStream_t)stream, out, err, S, raw);
+        if (xlen >= 6 && p + 2 + xlen <= n && gz[p + 2] == 'B' && gz[p + 3] == 'C') return not_taken("BGZF");      // (a first block cut short)
         p += 2 + xlen;
     }
     if (flg & 8) { while (p < n && gz[p]) p++; p++; }
@@ -740,23 +1018,9 @@ int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, Gp
         crc = (uint32_t)crc32_combine(crc, crcs[n_slices - 1], (z_off_t)last);
     }
     if (crc != want_crc) return not_taken("CRC-32 mismatch");
-    // ---- the text as gpu_upload_text hands it on: trailing blank lines cut off, 32 zero bytes behind it
-    // (fastq_gpu.hip: trimmed_len — "\n\n" and "\n\r\n" at the end lose their last line end, repeatedly)
-    size_t te = tail_n;
-    for (;;) {
-        if (te >= 2 && tail[te - 1] == '\n' && tail[te - 2] == '\n') { te -= 1; continue; }
-        if (te >= 3 && tail[te - 1] == '\n' && tail[te - 2] == '\r' && tail[te - 3] == '\n') { te -= 2; continue; }
-        break;
-    }
-    if (raw) te = tail_n;
-    if (te < 8 && total > tail_n) return not_taken("kilobytes of blank lines at the end");
-    size_t e = (size_t)(total - tail_n) + te;
-    const bool unterminated = te == 0 || tail[te - 1] != '\n';
-    if (e == 0) return not_taken("empty text");
-    if (!raw) GZCHK(hipMemsetAsync((char *)d_text.p + e, 0, std::min<size_t>(32, (size_t)total + 64 - e), st));
-    GZCHK(hipStreamSynchronize(st));
-    out.pool_bytes = d_text.bytes; out.d = (uint8_t *)d_text.take();
-    out.e = e; out.unterminated = unterminated; out.h2d_ms = S.h2d_ms;
+    const char *why = "";
+    if (const int rt = hand_on_text(d_text, total, tail, tail_n, raw, st, out, why, err)) return rt == 1 ? not_taken(why) : rt;
+    out.h2d_ms = S.h2d_ms;
     S.chunks = C; S.text_bytes = total; S.total_ms = now_ms() - t_begin;
     if (getenv("SHK_GUNZIP_DEBUG"))
         fprintf(stderr, "[inflate_gpu] %u chunks (%u cuts): upload %.2f ms, block starts %.2f, decode %.2f, windows (%.2f) + resolve + crc %.2f, total %.2f ms for %.3f GB of text\n",

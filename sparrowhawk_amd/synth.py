@@ -167,6 +167,29 @@ def to_fastq_fixed(codes, quals):
     return out.tobytes()
 
 
+def bgzf_compress(data, block=65280, level=6, eof=True):
+    """`data` as a BGZF (bgzip) file: a chain of gzip members of at most 64 KiB, each holding `block` bytes of `data` as a raw
+    deflate stream of its own and announcing its size in a 'BC' extra subfield (SAM specification 4.1; 65 280 bytes per
+    block is bgzip's own figure).  eof: the empty end-of-file block behind the last one."""
+    import struct
+    import zlib
+    if not 0 < block <= 65280:
+        raise ValueError("block: 1 .. 65280 bytes (a stored block of more does not fit BSIZE)")
+    data = bytes(data)
+
+    def one(chunk):
+        co = zlib.compressobj(level if chunk else 6, zlib.DEFLATED, -15)      # (no data: bgzip's 28-byte marker at every level)
+        body = co.compress(chunk) + co.flush()
+        bsize = 18 + len(body) + 8
+        assert bsize <= 65536
+        return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", bsize - 1) + body +
+                struct.pack("<II", zlib.crc32(chunk), len(chunk)))
+    out = [one(data[i:i + block]) for i in range(0, len(data), block)]
+    if eof:
+        out.append(one(b""))
+    return b"".join(out)
+
+
 # ---- configs[3] / configs[4] inputs: many genomes, generated on the device from one seed -------------------
 _M64 = (1 << 64) - 1
 

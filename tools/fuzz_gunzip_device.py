@@ -2,7 +2,11 @@
 tools/fuzz_gunzip.py: members of 70 kB ... 20 MB made with random levels, strategies, windows, flush points and member counts
 from FASTQ-like text, runs, binary data and mixtures, each also truncated and with single bits flipped.  The device inflater
 either hands back exactly zlib's bytes or declines (the product then reads the member on the host, which owns the error
-messages): it must NEVER return other bytes.  Needs a GPU.  Usage: python tools/fuzz_gunzip_device.py [cases] [seed]"""
+messages): it must NEVER return other bytes.  Needs a GPU.  Usage: python tools/fuzz_gunzip_device.py [cases] [seed] [bgzf]
+bgzf: BGZF (bgzip) files instead — blocks of random sizes (1 ... 65 280 bytes of text) and levels, empty blocks anywhere,
+with or without the end-of-file block.  Every intact file must be TAKEN with its text's bytes (this path has no speculative
+step); a damaged one (cut short, bits flipped, BSIZE / ISIZE / CRC-32 fields changed) is declined or comes back as the host
+reader (shk_host_gunzip) reads it."""
 import ctypes as C
 import os
 import sys
@@ -31,6 +35,69 @@ def device_gunzip(z):
         return 0, got, "", ms.value
     return rc, None, (why.value or b"").decode(), ms.value
 
+
+def bgzf_file(text):
+    """(file, [(offset, BSIZE)]): `text` in blocks of random sizes and levels, empty blocks strewn in"""
+    from sparrowhawk_amd import synth
+    small = rng.random() < 0.3                               # thousands of tiny blocks at times
+    parts, p = [], 0
+    while p < len(text):
+        n = int(rng.integers(1, 2000)) if small else int(rng.choice([65280, 65280, 30000, int(rng.integers(1, 65281))]))
+        parts.append(synth.bgzf_compress(text[p:p + n], block=65280, level=int(rng.integers(0, 10)), eof=False))
+        p += n
+        if rng.random() < 0.02:
+            parts.append(synth.bgzf_compress(b""))
+    if rng.random() < 0.7:
+        parts.append(synth.bgzf_compress(b""))
+    offs, o = [], 0
+    for b in parts:
+        offs.append((o, len(b))); o += len(b)
+    return b"".join(parts), offs
+
+
+def fuzz_bgzf():
+    import struct
+    os.environ["SHK_GUNZIP_DEVICE_MIN"] = "0"                # (every file, however small)
+    t0 = time.time()
+    reasons = Counter()
+    for case in range(n_cases):
+        text = fg.make_text(int(rng.choice([70000, 300_000, 3_000_000, 8_000_000])))
+        z, offs = bgzf_file(text)
+        desc = dict(case=case, size=len(text), zlen=len(z), blocks=len(offs))
+        try:
+            rc, got, why, _ = device_gunzip(z)
+            assert rc == 0, ("an intact BGZF file was not taken", rc, why)
+            assert got == text, ("intact file: OTHER BYTES", len(got), len(text))
+            bads = [z[:int(rng.integers(1, len(z)))], z[:-1], z + b"\0"]
+            for _ in range(3):
+                pos = int(rng.integers(0, len(z)))
+                bad = bytearray(z); bad[pos] ^= 1 << int(rng.integers(0, 8)); bads.append(bytes(bad))
+            for _ in range(3):                               # a header or trailer field of one block: BSIZE, CRC-32, ISIZE
+                o, bs = offs[int(rng.integers(0, len(offs)))]
+                at, fmt = [(o + 16, "<H"), (o + bs - 8, "<I"), (o + bs - 4, "<I")][int(rng.integers(0, 3))]
+                old = struct.unpack_from(fmt, z, at)[0]
+                new = max(0, old + int(rng.choice([-1, 1, 1000, 70000]))) & (0xFFFF if fmt == "<H" else 0xFFFFFFFF)
+                bad = bytearray(z); struct.pack_into(fmt, bad, at, new); bads.append(bytes(bad))
+            for bad in bads:
+                rc2, got2, why2, _ = device_gunzip(bad)
+                assert rc2 in (0, 1), ("error code", rc2, why2)
+                if rc2 == 0:
+                    rch, goth, _ = fg.gunzip(bad)
+                    assert rch == 0 and got2 == goth, ("damaged file: not the host reader's bytes", rch)
+                else:
+                    reasons[why2] += 1
+        except Exception as e:
+            print("FAIL", desc, repr(e), flush=True)
+            raise
+        if case % 10 == 0:
+            print("case", case, "ok  %.0f s" % (time.time() - t0), flush=True)
+    print("all", n_cases, "BGZF cases: every intact file taken with its bytes; damaged ones declined or as the host reads them; declined:", dict(reasons),
+          "; %.0f s" % (time.time() - t0))
+
+
+if "bgzf" in sys.argv[1:]:
+    fuzz_bgzf()
+    sys.exit(0)
 
 t0 = time.time()
 taken, reasons, rates = 0, Counter(), []

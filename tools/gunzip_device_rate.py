@@ -1,5 +1,8 @@
-"""The device inflater on the bench isolate's .fastq.gz (1.05 GB of text in one member): stage times.  Needs a GPU."""
-import ctypes as C, os, sys, time, zlib
+"""The device inflater on the bench isolate's .fastq.gz (1.05 GB of text in one member): stage times.  Needs a GPU.
+BGZF=1: the same text as a BGZF (bgzip) file as well (synth.bgzf_compress, 65 280-byte blocks; one wave per block);
+SHK_GUNZIP_DEBUG=1 makes the library print the stage times of either path."""
+import ctypes as C, os, struct, sys, time, zlib
+from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
@@ -16,10 +19,33 @@ for r0 in range(0, n_reads, 1 << 19):
     codes = genome[starts[:, None] + ar[None, :]]
     parts.append(synth.device_fastq_fixed(torch, codes).cpu())
 fq = torch.cat(parts).numpy().tobytes()
+
+
+def bgzf(text, level, threads=16):
+    """synth.bgzf_compress over `threads` pieces of whole blocks at once (zlib runs without the interpreter lock)"""
+    per = (len(text) // 65280 // threads + 1) * 65280
+    with ThreadPoolExecutor(threads) as ex:
+        parts = list(ex.map(lambda a: synth.bgzf_compress(text[a:a + per], level=level, eof=False), range(0, len(text), per)))
+    return b"".join(parts) + synth.bgzf_compress(b"")
+
+
+def n_blocks(z):
+    n = p = 0
+    while p < len(z):
+        bsize = struct.unpack_from("<H", z, p + 16)[0] + 1
+        n += struct.unpack_from("<I", z, p + bsize - 4)[0] > 0
+        p += bsize
+    return n
+
+
 for level in (int(x) for x in os.environ.get('LEVELS', '1,6').split(',')):
     co = zlib.compressobj(level, zlib.DEFLATED, 31)
     gz = co.compress(fq) + co.flush()
-    for chunk in (int(x) for x in os.environ.get('CHUNKS', '0,65536,131072').split(',')):
+    inputs = [(gz, chunk, "") for chunk in (int(x) for x in os.environ.get('CHUNKS', '0,65536,131072').split(','))]
+    if os.environ.get("BGZF") == "1":
+        bz = bgzf(fq, level)
+        inputs.append((bz, 0, ", BGZF: %d blocks" % n_blocks(bz)))
+    for gz, chunk, note in inputs:
         if chunk:
             os.environ["SHK_GUNZIP_DEVICE_CHUNK"] = str(chunk)
         else:
@@ -32,5 +58,5 @@ for level in (int(x) for x in os.environ.get('LEVELS', '1,6').split(',')):
             ok = rc == 0 and C.string_at(out.value, n.value) == fq
             if rc == 0:
                 L.shk_host_free(out)
-        print("level %d, %.3f GB -> %.3f GB, chunk %d: rc %d (%s) equal %s, inflate %.1f ms = %.1f GB/s of text (call incl. download %.0f ms)"
-              % (level, len(gz) / 1e9, len(fq) / 1e9, chunk, rc, (why.value or b"").decode(), ok, ms.value, len(fq) / 1e9 / (ms.value * 1e-3) if ms.value else 0, dt * 1e3), flush=True)
+        print("level %d, %.3f GB -> %.3f GB, chunk %d: rc %d (%s) equal %s, inflate %.1f ms = %.1f GB/s of text (call incl. download %.0f ms)%s"
+              % (level, len(gz) / 1e9, len(fq) / 1e9, chunk, rc, (why.value or b"").decode(), ok, ms.value, len(fq) / 1e9 / (ms.value * 1e-3) if ms.value else 0, dt * 1e3, note), flush=True)
