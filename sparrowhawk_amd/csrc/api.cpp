@@ -1,13 +1,11 @@
 // api.cpp — the C ABI of libshk_hip.so (include/shk.h): the stateful AssemblyHelper the
 // reference's worker drives (www/src/workers/Assembler.ts:15-39,73-143), its call-order state
 // machine, the progress strings (AssemblyPage.vue:458-609) and the JSON getters.
-#include "../../include/shk.h"
-
 #include <atomic>
-#include <chrono>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <mutex>
 #include <new>
 #include <set>
@@ -15,84 +13,19 @@
 #include <thread>
 #include <vector>
 
-#include "fastq.h"
 #include "fastq_gpu.h"
 #include "inflate_gpu.h"
 #include "inflate_mt.h"
-#include "outputs.h"
-#include "pipeline.h"
-#include "shard_comm.h"
+#include "preprocess.h"
 #include "unitig_graph.h"
 
-namespace shk {
-bool spectrum_fit(const uint64_t *histo500, uint32_t *out);
-}
+namespace shk { bool spectrum_fit(const uint64_t *histo500, uint32_t *out); }   // fit.cpp
 
 using namespace shk;
 
-namespace {
+static thread_local int g_new_err = 0;
+static thread_local std::string g_new_msg;
 
-thread_local int g_new_err = 0;
-thread_local std::string g_new_msg;
-
-enum class St { Fresh, Streaming, Sharding, Preprocessed, Assembled, Failed };
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-}  // namespace
-
-struct shk_handle {
-    uint32_t k = 31, min_count = 5, min_qual = 20;
-    uint64_t chunk_size = 0;
-    bool verbose = false, do_bloom = false, do_fit = false, no_bubble = false, no_deadend = false;
-    St st = St::Fresh;
-    IPipeline *pipe = nullptr;
-    shk_progress_cb cb = nullptr;
-    void *cb_user = nullptr;
-    std::string err, first_err, pre_json, timings_json;
-    ByteVec asm_json;                  // NUL-terminated
-    const char *asm_json_dev = nullptr; // a fragmented assembly's JSON, written on the device: pinned memory owned by the pipeline
-    uint64_t histo[SHK_HISTO_BINS] = {0};
-    uint32_t used_min_count = 0;
-    bool fit_ok = false;
-    PackedReads stream_reads;          // shk_push_reads accumulator
-    uint64_t n_reads = 0;
-    uint64_t batches_started = 0;      // batches handed to the pipeline (a failure after the first one poisons the handle)
-    ShardComm *shard_comm = nullptr;   // sharded assembly: the communicator shk_shard_preprocess ran on (shk_assemble is collective over it)
-    AssemblyText text;
-    std::shared_ptr<void> mem = mem_acct_new();   // device bytes this handle holds / held at most (pipeline.h: mem_acct_*)
-
-    const char *mode() const { return do_bloom ? "bloom" : (chunk_size > 0 ? "chunked" : "bulk"); }
-    void post(const std::string &s) { if (cb) cb(s.c_str(), cb_user); }
-    void post_mode(const char *suffix) { post(std::string("preprocess:") + mode() + ":" + suffix); }
-    // `loop:start` / `loop:end` exist for bulk and bloom only: the reference UI defines no such state for the
-    // chunked mode (AssemblyPage.vue:548-579 has :start, :fitting, :filtering and :loop:<n>[:<pct>])
-    void post_loop_edge(const char *suffix) { if (do_bloom || chunk_size == 0) post_mode(suffix); }
-    uint64_t progress_every() const { return (!do_bloom && chunk_size > 0) ? chunk_size : 100000; }
-};
-
-static int fail(shk_handle *h, int code, const std::string &msg) { h->err = msg; return code; }
-
-// Every entry point that touches the device runs with the HANDLE's device current (the HIP current device is
-// per thread and new threads start on device 0: an FFI consumer may call from any thread) and restores the
-// caller's device afterwards; no exception crosses the C ABI (shk.h: "never aborts").
-struct DevGuard {
-    int prev;
-    explicit DevGuard(int dev) : prev(set_device(dev)) {}
-    ~DevGuard() { (void)set_device(prev); }
-    DevGuard(const DevGuard &) = delete;
-    DevGuard &operator=(const DevGuard &) = delete;
-};
-// the calling thread allocates (and frees) device blocks on behalf of this handle while the guard lives
-struct MemGuard {
-    std::shared_ptr<void> prev;
-    explicit MemGuard(const std::shared_ptr<void> &a) : prev(mem_acct_set(a)) {}
-    ~MemGuard() { (void)mem_acct_set(prev); }
-    MemGuard(const MemGuard &) = delete;
-    MemGuard &operator=(const MemGuard &) = delete;
-};
 enum class Poison { Never, AfterFirstBatch, Always };
 template <typename F> static int guarded(shk_handle *h, Poison poison, F &&body) {
     if (!h) return SHK_E_PARAM;
@@ -127,7 +60,7 @@ void shk_release_cached_memory(void) { device_pool_trim(); big_trim(); }
 int shk_measure_stream_read(size_t bytes, int iters, double *gbs) {
     std::string err;
     const int rc = stream_read_gbs(bytes, iters, gbs, err);
-    return rc == 0 ? SHK_OK : rc == -1 ? SHK_E_PARAM : rc == -4 ? SHK_E_OOM : SHK_E_DEVICE;
+    return rc == 0 ? SHK_OK : code_of(Rc::Device, rc);
 }
 
 const char *shk_version(void) { return "sparrowhawk_amd 0.1 (gfx950)"; }
@@ -171,554 +104,18 @@ void shk_free(shk_handle *h) {
 const char *shk_last_error(shk_handle *h) { return h ? h->err.c_str() : "null handle"; }
 void shk_set_progress_cb(shk_handle *h, shk_progress_cb cb, void *user) { if (h) { h->cb = cb; h->cb_user = user; } }
 
-// common tail of every preprocess entry point: packed segments are in HBM
-// one batch of packed segments in HBM -> pass 1 (several batches per handle are allowed)
-static int count_one_batch(shk_handle *h, const uint32_t *d_bases, const uint32_t *d_seg_off, uint64_t n_seg,
-                           uint64_t n_bases) {
-    std::string err;
-    const double t0 = now_ms();
-    h->batches_started++;
-    int rc = h->pipe->count_batch(d_bases, d_seg_off, n_seg, n_bases, err);
-    h->pipe->times().add("preprocess_device_total_host_clock", now_ms() - t0);
-    if (rc) return fail(h, rc == -4 ? SHK_E_OOM : (rc == -1 ? SHK_E_PARAM : SHK_E_DEVICE), err);
-    return SHK_OK;
-}
-
-// common tail of every preprocess entry point: all batches are in -> histogram, fit, filter
-static int finish_counting(shk_handle *h) {
-    std::string err;
-    const double t0 = now_ms();
-    h->post_loop_edge("loop:end");
-    if (!h->do_bloom && h->chunk_size == 0) h->post("preprocess:bulk:sorting");
-    // the fit never returns less than 1 and falls back to min_count (SPEC S6)
-    const uint32_t emit_thr = h->do_fit ? (h->min_count < 1u ? h->min_count : 1u) : h->min_count;
-    int rc = h->pipe->histogram(h->histo, emit_thr, err);
-    if (rc) return fail(h, SHK_E_DEVICE, err);
-    h->used_min_count = h->min_count; h->fit_ok = false;
-    if (h->do_fit) {
-        h->post_mode("fitting");
-        uint32_t v = 0;
-        if (spectrum_fit(h->histo, &v)) { h->used_min_count = v; h->fit_ok = true; }
-    }
-    h->post_mode("filtering");
-    rc = h->pipe->filter(h->used_min_count, err);
-    if (rc) return fail(h, rc == -4 ? SHK_E_OOM : SHK_E_DEVICE, err);
-    h->post("preprocess:saving");
-    h->pre_json = preprocessing_json(h->pipe->n_solid(), h->histo, h->used_min_count);
-    h->pipe->times().add("preprocess_device_total_host_clock", now_ms() - t0);
-    h->st = St::Preprocessed;
-    h->post("preprocess:end");
-    return SHK_OK;
-}
-
-static int run_counting(shk_handle *h, const uint32_t *d_bases, const uint32_t *d_seg_off, uint64_t n_seg,
-                        uint64_t n_bases) {
-    // (one batch, and the caller's reads stay in place until this function returns: the two counting passes run back to back)
-    h->pipe->single_batch_resident(true);
-    int rc = count_one_batch(h, d_bases, d_seg_off, n_seg, n_bases);
-    if (!rc) rc = finish_counting(h);
-    h->pipe->single_batch_resident(false);
-    return rc;
-}
-
-// bases per batch of the host-parsed paths (a batch is limited to 2^32 packed bases by its 32-bit offsets)
-static uint64_t batch_bases() {
-    const char *v = getenv("SHK_BATCH_BASES");
-    const uint64_t b = (v && *v) ? strtoull(v, nullptr, 10) : (1ull << 31);
-    return b < 1024 ? 1024 : (b > (3ull << 30) ? (3ull << 30) : b);
-}
-
-// hand the packed stream on as one batch (upload + pass 1) and empty it; read counters are kept
-static int flush_host_batch(shk_handle *h, PackedReads &pr) {
-    if (pr.n_seg() == 0) { pr.reset_stream(); return SHK_OK; }
-    pr.finish();
-    std::string err;
-    void *d_bases = nullptr, *d_off = nullptr;
-    const double t0 = now_ms();
-    int rc = device_upload(pr.bases.data(), pr.bases.size() * 4, &d_bases, err);
-    if (!rc) rc = device_upload(pr.seg_off.data(), pr.seg_off.size() * 4, &d_off, err);
-    if (rc) { device_free(d_bases); device_free(d_off); return fail(h, SHK_E_OOM, err); }
-    h->pipe->times().add("h2d_upload_host_clock", now_ms() - t0);
-    rc = count_one_batch(h, (const uint32_t *)d_bases, (const uint32_t *)d_off, pr.n_seg(), pr.n_bases);
-    device_free(d_bases); device_free(d_off);
-    pr.reset_stream();
-    return rc;
-}
-
-// chunked mode hands a batch on every chunk_size reads (docs/src/assembly.md:17: "reads per batch")
-static uint64_t flush_every_reads(const shk_handle *h) { return (!h->do_bloom && h->chunk_size > 0) ? h->chunk_size : 0; }
-
-// start of the first FASTQ record at or after `from` (a line starting with '@' whose line after next starts
-// with '+': a quality line may start with '@' too, but then the line after next is a sequence); n = none,
-// SIZE_MAX = the text does not look like 4-line FASTQ here
-static size_t next_record_start(const uint8_t *t, size_t n, size_t from) {
-    size_t p = from;
-    if (p >= n) return n;
-    if (p > 0 && t[p - 1] != '\n') {
-        const void *nl = memchr(t + p, '\n', n - p);
-        if (!nl) return n;
-        p = (size_t)((const uint8_t *)nl - t) + 1;
-    }
-    for (int tries = 0; tries < 8 && p < n; tries++) {
-        const void *e0 = memchr(t + p, '\n', n - p);
-        if (!e0) return n;
-        const size_t b = (size_t)((const uint8_t *)e0 - t) + 1;
-        if (b >= n) return n;
-        const void *e1 = memchr(t + b, '\n', n - b);
-        if (!e1) return n;
-        const size_t c = (size_t)((const uint8_t *)e1 - t) + 1;
-        if (t[p] == '@' && c < n && t[c] == '+') return p;
-        p = b;
-    }
-    return SIZE_MAX;
-}
-
-// A text of more than one batch: pieces of ~2 * batch_bases() bytes, cut at record boundaries, go through
-// the device parser one after the other, each counted as its own batch (pass 1) before the next is parsed;
-// a helper thread uploads piece i+1 while piece i is parsed and counted (H2D is two thirds of the entry point).
-// handled = false (and nothing counted) when the very first piece is not regular 4-line FASTQ: the caller
-// then runs the host parser over everything.  A later piece that is not regular is parsed on the host from
-// there to the end of its file, with the record numbers and progress of the whole file.
-// one_batch: the text fits one batch.  It is still cut into a few pieces so that piece i+1 travels while piece i is
-// parsed, but the packed pieces are kept and counted together as ONE batch at the end (pass 1 runs over the pieces
-// into the same slices: the partitioning of a single batch, no batch packing, no merge).
-static int preprocess_device_pieces(shk_handle *h, const uint8_t *t1, size_t l1, const uint8_t *t2, size_t l2,
-                                    size_t n1, size_t total, bool &handled, bool one_batch = false) {
-    handled = false;
-    std::string err;
-    size_t piece_bytes = (size_t)(2 * batch_bases());
-    if (one_batch) {
-        const char *pv = getenv("SHK_FASTQ_PIECES");
-        const size_t C = (pv && *pv) ? (size_t)std::max<long long>(1, atoll(pv)) : 4;
-        // the last piece is parsed with nothing left to upload: it is the small one (a tenth of the text)
-        const size_t tot = l1 + (t2 ? l2 : 0);
-        piece_bytes = std::max<size_t>(C >= 3 ? tot / 10 * 9 / (C - 1) : tot / C, 1024);
-    }
-    std::vector<GpuPacked> kept;                          // one_batch: the parsed pieces, counted together
-    auto free_kept = [&]() { for (auto &g : kept) gpu_packed_free(g); kept.clear(); };
-    auto count_kept = [&]() -> int {
-        if (kept.empty()) return SHK_OK;
-        std::vector<DevPiece> pcs;
-        for (auto &g : kept) pcs.push_back(DevPiece{g.d_bases, g.d_seg_off, g.n_seg, g.n_bases});
-        std::string e2;
-        const double tc = now_ms();
-        h->batches_started++;
-        const int rc = h->pipe->count_batch_pieces(pcs.data(), pcs.size(), e2);
-        h->pipe->times().add("preprocess_device_total_host_clock", now_ms() - tc);
-        free_kept();
-        if (rc) return fail(h, rc == -4 ? SHK_E_OOM : (rc == -1 ? SHK_E_PARAM : SHK_E_DEVICE), e2);
-        return SHK_OK;
-    };
-    struct Piece { int file; size_t off, end; bool host_rest; };
-    std::vector<Piece> pieces;
-    for (int f = 0; f < 2; f++) {
-        const uint8_t *t = f ? t2 : t1;
-        const size_t len = f ? l2 : l1;
-        if (!t) continue;
-        size_t off = 0;
-        while (off < len) {
-            size_t end = len;
-            if (len - off > piece_bytes + piece_bytes / 8) {
-                end = next_record_start(t, len, off + piece_bytes);
-                if (end == SIZE_MAX || end <= off) { pieces.push_back(Piece{f, off, len, true}); break; }   // no record boundary: host from here
-            }
-            pieces.push_back(Piece{f, off, end, false});
-            off = end;
-        }
-    }
-    const int device = h->pipe->device();
-    uint64_t reads_done = 0, file_reads = 0;
-    bool counted_any = false;
-    const double t0 = now_ms();
-    GpuText cur, nxt;
-    bool have_cur = false;
-    struct Joining { std::thread t; ~Joining() { if (t.joinable()) t.join(); } } upl;   // joined on every way out, exceptions included
-    std::thread &uploader = upl.t;
-    int up_rc = 0; std::string up_err;
-    auto join_upload = [&]() { if (uploader.joinable()) uploader.join(); };
-    auto drop_all = [&]() { join_upload(); gpu_text_free(cur); gpu_text_free(nxt); free_kept(); };
-    // the rest of a file through the host parser (a piece that is not regular 4-line FASTQ, or no boundary found)
-    auto host_rest = [&](const Piece &pc) -> int {
-        const uint8_t *t = pc.file ? t2 : t1;
-        const size_t len = pc.file ? l2 : l1, done_before = pc.file ? n1 : 0;
-        PackedReads pr;
-        pr.n_reads = reads_done;
-        auto prog = [&](uint64_t reads, uint64_t bytes, uint64_t) {
-            const uint64_t pct = total ? (100 * (done_before + pc.off + bytes)) / total : 100;
-            h->post_mode(("loop:" + std::to_string(reads) + ":" + std::to_string(pct)).c_str());
-        };
-        int flush_rc = SHK_OK;
-        auto flush = [&](PackedReads &p) -> int { flush_rc = flush_host_batch(h, p); return flush_rc ? -7 : 0; };
-        if (int rck = count_kept()) return rck;           // (one_batch: what the device parsed so far is a batch of its own now)
-        if (!counted_any) h->pipe->expect_more_batches();
-        int rc2 = pack_fastq(t + pc.off, len - pc.off, h->k, h->min_qual, pr, err, h->progress_every(), prog, 0, batch_bases(), flush, file_reads);
-        if (rc2 == -7) return flush_rc;
-        if (rc2) return fail(h, rc2 == -3 ? SHK_E_PARSE : (rc2 == -4 ? SHK_E_OOM : SHK_E_PARAM), err);
-        if (int rc3 = flush_host_batch(h, pr)) return rc3;
-        reads_done = pr.n_reads;
-        counted_any = true;
-        return SHK_OK;
-    };
-    for (size_t i = 0; i < pieces.size(); i++) {
-        const Piece pc = pieces[i];
-        if (i == 0 || pieces[i - 1].file != pc.file) file_reads = 0;
-        if (pc.host_rest) {
-            if (!counted_any && i == 0) { drop_all(); return SHK_OK; }          // handled stays false: the caller's host path
-            if (int rc = host_rest(pc)) { drop_all(); return rc; }
-            continue;
-        }
-        const uint8_t *t = pc.file ? t2 : t1;
-        if (!have_cur) {
-            if (int rc = gpu_upload_text(t + pc.off, pc.end - pc.off, device, cur, err)) return fail(h, rc == -4 ? SHK_E_OOM : SHK_E_DEVICE, err);
-            have_cur = true;
-        }
-        // the next piece travels while this one is parsed and counted
-        const bool prefetch = i + 1 < pieces.size() && !pieces[i + 1].host_rest;
-        if (prefetch) {
-            const Piece nx = pieces[i + 1];
-            const uint8_t *tn = nx.file ? t2 : t1;
-            uploader = std::thread([&, nx, tn]() {
-                MemGuard mg(h->mem);                       // (the text block this thread allocates belongs to the handle)
-                try { up_rc = gpu_upload_text(tn + nx.off, nx.end - nx.off, device, nxt, up_err); }
-                catch (...) { up_rc = -4; up_err = "out of host memory (uploader)"; }
-            });
-        }
-        GpuPacked gp;
-        const double tp0 = now_ms();
-        int rc = gpu_pack_fastq(nullptr, 0, nullptr, 0, h->k, h->min_qual, h->progress_every(), h->pipe->stream(), gp, err, reads_done, &cur);
-        h->pipe->times().add("fastq_piece_parse_host_clock", now_ms() - tp0);
-        if (rc < 0) { gpu_packed_free(gp); drop_all(); return fail(h, rc == -4 ? SHK_E_OOM : (rc == -1 ? SHK_E_PARAM : SHK_E_DEVICE), err); }
-        if (rc == 1) {
-            gpu_packed_free(gp);
-            join_upload(); gpu_text_free(cur); gpu_text_free(nxt); have_cur = false;
-            if (!counted_any) { free_kept(); return SHK_OK; }             // handled stays false
-            Piece rest = pc; rest.end = pc.file ? l2 : l1; rest.host_rest = true;
-            if (int rc2 = host_rest(rest)) return rc2;
-            while (i + 1 < pieces.size() && pieces[i + 1].file == pc.file) i++;      // the rest of this file is done
-            continue;
-        }
-        if (!counted_any && !one_batch) h->pipe->expect_more_batches();
-        h->pipe->times().add("fastq_h2d_text", gp.h2d_ms);
-        h->pipe->times().add("fastq_device_kernels", gp.kernels_ms);
-        h->pipe->times().add("fastq_device_pieces_x1", 1.0);
-        const uint64_t every = h->progress_every();
-        const size_t done_before = pc.file ? n1 : 0;
-        for (size_t j = 0; j < gp.progress_bytes.size(); j++) {
-            const uint64_t bytes = gp.progress_bytes[j] & ~(1ull << 63);
-            const uint64_t pct = total ? (100 * (done_before + pc.off + bytes)) / total : 100;
-            h->post_mode(("loop:" + std::to_string(every * (gp.first_mark + j + 1)) + ":" + std::to_string(pct)).c_str());
-        }
-        int rc2 = SHK_OK;
-        reads_done += gp.n_reads; file_reads += gp.n_reads;
-        if (one_batch) { kept.push_back(gp); gp = GpuPacked(); }       // (counted with the other pieces at the end)
-        else {
-            rc2 = gp.n_seg ? count_one_batch(h, gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases) : SHK_OK;
-            gpu_packed_free(gp);
-        }
-        if (rc2) { drop_all(); return rc2; }
-        counted_any = true;
-        // hand over to the uploaded next piece
-        const double tj0 = now_ms();
-        join_upload();
-        h->pipe->times().add("fastq_piece_wait_for_upload_host_clock", now_ms() - tj0);
-        gpu_text_free(cur); have_cur = false;
-        if (prefetch) {
-            if (up_rc) { gpu_text_free(nxt); return fail(h, up_rc == -4 ? SHK_E_OOM : SHK_E_DEVICE, up_err); }
-            cur = nxt; nxt = GpuText(); have_cur = true;
-        }
-    }
-    join_upload(); gpu_text_free(cur); gpu_text_free(nxt);
-    h->pipe->times().add("fastq_device_parse_pack_host_clock", now_ms() - t0);
-    if (int rck = count_kept()) return rck;
-    handled = true;
-    h->n_reads = reads_done;
-    return finish_counting(h);
-}
-
-// Both files (or the one) are what the device inflater takes — a plain gzip member or a BGZF chain, in any combination
-// within a pair: inflate -> device parser -> one batch.
-// handled = false (nothing counted, nothing posted beyond what the host path posts again) when any file is not taken or
-// turns out not to be regular 4-line FASTQ: the caller's host reader then starts over.
-static int preprocess_device_gzip(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, size_t total, bool &handled) {
-    handled = false;
-    const uint8_t *gz[2] = {fq1, fq2}; const size_t gn[2] = {n1, fq2 ? n2 : 0};
-    const int nf = fq2 ? 2 : 1;
-    for (int f = 0; f < nf; f++) if (gn[f] < 18 || gz[f][0] != 0x1F || gz[f][1] != 0x8B) return SHK_OK;
-    std::string err;
-    const double t0 = now_ms();
-    GpuText text[2];
-    GpuPacked packed[2];
-    auto drop = [&]() { for (int f = 0; f < 2; f++) { gpu_text_free(text[f]); gpu_packed_free(packed[f]); } };
-    double ms_h2d = 0, ms_search = 0, ms_decode = 0, ms_resolve = 0;
-    uint64_t bgzf_blocks = 0;
-    for (int f = 0; f < nf; f++) {
-        GpuInflateStats st;
-        const int rc = gpu_inflate_member(gz[f], gn[f], h->pipe->device(), h->pipe->stream(), text[f], err, &st);
-        if (rc == 1) { drop(); h->pipe->times().add("gunzip_device_not_taken_x1", 1.0); return SHK_OK; }
-        if (rc) { drop(); return fail(h, rc == -4 ? SHK_E_OOM : SHK_E_DEVICE, err); }
-        ms_h2d += st.h2d_ms; ms_search += st.search_ms; ms_decode += st.decode_ms; ms_resolve += st.resolve_ms;
-        bgzf_blocks += st.blocks;
-    }
-    const double t1 = now_ms();
-    uint64_t text_total = 0;
-    for (int f = 0; f < nf; f++) text_total += text[f].e;
-    if (text_total / 2 > batch_bases()) { drop(); return SHK_OK; }             // (several batches: the host reader's piece-wise path)
-    uint64_t reads_done = 0, text_before = 0;
-    for (int f = 0; f < nf; f++) {
-        const int rc = gpu_pack_fastq(nullptr, 0, nullptr, 0, h->k, h->min_qual, h->progress_every(), h->pipe->stream(), packed[f], err, reads_done, &text[f]);
-        if (rc < 0) { drop(); return fail(h, rc == -4 ? SHK_E_OOM : (rc == -1 ? SHK_E_PARAM : SHK_E_DEVICE), err); }
-        if (rc == 1) { drop(); h->pipe->times().add("gunzip_device_not_taken_x1", 1.0); return SHK_OK; }      // not regular FASTQ: the host parser owns the messages
-        // progress as the text path posts it: every `every` reads, with the share of the (inflated) text consumed so far
-        const uint64_t every = h->progress_every();
-        for (size_t j = 0; j < packed[f].progress_bytes.size(); j++) {
-            const uint64_t bytes = packed[f].progress_bytes[j] & ~(1ull << 63);
-            const uint64_t pct = text_total ? (100 * (text_before + bytes)) / text_total : 100;
-            h->post_mode(("loop:" + std::to_string(every * (packed[f].first_mark + j + 1)) + ":" + std::to_string(pct)).c_str());
-        }
-        reads_done += packed[f].n_reads;
-        text_before += text[f].e;
-        h->pipe->times().add("fastq_device_kernels", packed[f].kernels_ms);
-        gpu_text_free(text[f]);
-    }
-    (void)total;
-    h->pipe->times().add("gunzip_device_host_clock", t1 - t0);
-    h->pipe->times().add("gunzip_device_h2d", ms_h2d);
-    h->pipe->times().add("gunzip_device_search", ms_search);
-    h->pipe->times().add("gunzip_device_decode", ms_decode);
-    h->pipe->times().add("gunzip_device_windows_resolve_crc", ms_resolve);
-    h->pipe->times().add("gunzip_device_members_x1", (double)nf);
-    if (bgzf_blocks) h->pipe->times().add("gunzip_device_bgzf_blocks_x1", (double)bgzf_blocks);      // non-empty BGZF blocks, one wave each
-    h->pipe->times().add("fastq_device_parse_pack_host_clock", now_ms() - t1);
-    h->n_reads = reads_done;
-    std::vector<DevPiece> pcs;
-    for (int f = 0; f < nf; f++) if (packed[f].n_seg) pcs.push_back(DevPiece{packed[f].d_bases, packed[f].d_seg_off, packed[f].n_seg, packed[f].n_bases});
-    const double tc = now_ms();
-    h->batches_started++;
-    const int rc = h->pipe->count_batch_pieces(pcs.data(), pcs.size(), err);
-    h->pipe->times().add("preprocess_device_total_host_clock", now_ms() - tc);
-    if (rc) { drop(); return fail(h, rc == -4 ? SHK_E_OOM : (rc == -1 ? SHK_E_PARAM : SHK_E_DEVICE), err); }
-    handled = true;
-    const int rf = finish_counting(h);
-    drop();
-    return rf;
-}
-
-static int preprocess_impl(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2) {
-    if (!h) return SHK_E_PARAM;
-    if (h->st != St::Fresh) return fail(h, SHK_E_STATE, "preprocess: handle already used (Assembler.ts:92: one preprocess per handle)");
-    if (!fq1) return fail(h, SHK_E_PARAM, "preprocess: file1 is required");
-    h->post("preprocess:start");
-    h->post_mode("start");
-    h->post_loop_edge("loop:start");
-    std::string err;
-    const double t0 = now_ms();
-    const size_t total = n1 + (fq2 ? n2 : 0);
-    // ---- device-side parsing (fastq_gpu.hip): regular 4-line FASTQ is parsed, masked, segmented and
-    // packed by streaming kernels.  Irregular input and every malformed record go to the host parser
-    // below, which owns the error messages.
-    // gzip (plain members: one thread per file; BGZF: block-parallel) is inflated once, for either parser
-    // ---- .fastq.gz (the reference's real input: fastx_wasm.rs:53-70): a plain gzip member or a BGZF (bgzip) file of some
-    // size is inflated ON THE DEVICE — the compressed bytes are what crosses PCIe — and its text goes straight to the device
-    // parser; whatever the device inflater does not take (several plain members, a broken BGZF chain, binary data, a
-    // damaged stream) is read on the host below
-    {
-        const char *gd = getenv("SHK_GUNZIP_DEVICE");
-        const char *fh = getenv("SHK_HOST_PARSER");
-        if (!(gd && *gd == '0') && !(fh && *fh == '1')) {
-            bool handled = false;
-            const int rc = preprocess_device_gzip(h, fq1, n1, fq2, n2, total, handled);
-            if (rc || handled) return rc;
-        }
-    }
-    ByteVec st1, st2;
-    const uint8_t *t1 = nullptr, *t2 = nullptr; size_t l1 = 0, l2 = 0;
-    {
-        const uint64_t mt0 = inflate_mt_members();
-        int rc = maybe_inflate_pair(fq1, n1, fq2, n2, st1, st2, t1, l1, t2, l2, err);
-        if (rc) return fail(h, rc == -3 ? SHK_E_PARSE : SHK_E_OOM, err);
-        h->pipe->times().add("gunzip_host_clock", now_ms() - t0);
-        h->pipe->times().add("gunzip_mt_members_x1", (double)(inflate_mt_members() - mt0));     // members the multi-threaded inflater took
-    }
-    const size_t text_total = l1 + (fq2 ? l2 : 0);
-    const char *force_host = getenv("SHK_HOST_PARSER");
-    // a single-batch text of some size: cut into pieces, piece i+1 uploaded while piece i is parsed (H2D is two thirds
-    // of this entry point), all counted as one batch
-    {
-        const char *mv = getenv("SHK_FASTQ_PIPELINE_MIN");
-        const size_t pipe_min = (mv && *mv) ? (size_t)strtoull(mv, nullptr, 10) : ((size_t)64 << 20);
-        if (!(force_host && *force_host == '1') && text_total / 2 <= batch_bases() && text_total >= pipe_min) {
-            bool handled = false;
-            int rc = preprocess_device_pieces(h, t1, l1, fq2 ? t2 : nullptr, l2, n1, total, handled, true);
-            if (rc || handled) return rc;
-            // (not regular 4-line FASTQ from the first piece on: the host parser below; the single-shot device path
-            // would find the same)
-            force_host = "1";
-        }
-    }
-    if (!(force_host && *force_host == '1') && text_total / 2 <= batch_bases()) {
-        const double t1c = now_ms();
-        GpuPacked gp;
-        int rc = gpu_pack_fastq(t1, l1, fq2 ? t2 : nullptr, l2, h->k, h->min_qual, h->progress_every(), h->pipe->stream(), gp, err);
-        if (rc < 0) { gpu_packed_free(gp); return fail(h, rc == -4 ? SHK_E_OOM : (rc == -1 ? SHK_E_PARAM : SHK_E_DEVICE), err); }
-        if (rc == 0) {
-            h->pipe->times().add("fastq_device_parse_pack_host_clock", now_ms() - t1c);
-            h->pipe->times().add("fastq_h2d_text", gp.h2d_ms);
-            h->pipe->times().add("fastq_device_kernels", gp.kernels_ms);
-            const uint64_t every = h->progress_every();
-            for (size_t j = 0; j < gp.progress_bytes.size(); j++) {
-                const bool second = (gp.progress_bytes[j] >> 63) != 0;
-                const uint64_t bytes = gp.progress_bytes[j] & ~(1ull << 63);
-                const uint64_t pct = total ? (100 * ((second ? n1 : 0) + bytes)) / total : 100;
-                h->post_mode(("loop:" + std::to_string(every * (j + 1)) + ":" + std::to_string(pct)).c_str());
-            }
-            h->n_reads = gp.n_reads;
-            rc = run_counting(h, gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases);
-            gpu_packed_free(gp);
-            return rc;
-        }
-        gpu_packed_free(gp);                            // rc == 1: not regular -> host parser
-    }
-    // ---- texts of several batches: pieces cut at record boundaries, each through the device parser
-    if (!(force_host && *force_host == '1') && text_total / 2 > batch_bases()) {
-        bool handled = false;
-        int rc = preprocess_device_pieces(h, t1, l1, fq2 ? t2 : nullptr, l2, n1, total, handled);
-        if (rc || handled) return rc;
-    }
-    // ---- host parser (irregular framing, malformed records, inputs of several batches)
-    PackedReads pr;
-    size_t done_before = 0;
-    auto prog = [&](uint64_t reads, uint64_t bytes, uint64_t) {
-        const uint64_t pct = total ? (100 * (done_before + bytes)) / total : 100;
-        h->post_mode(("loop:" + std::to_string(reads) + ":" + std::to_string(pct)).c_str());
-    };
-    int flush_rc = SHK_OK;
-    auto flush = [&](PackedReads &p) -> int { flush_rc = flush_host_batch(h, p); return flush_rc ? -7 : 0; };
-    if (flush_every_reads(h) || text_total / 2 > batch_bases()) h->pipe->expect_more_batches();
-    int rc = pack_fastq(t1, l1, h->k, h->min_qual, pr, err, h->progress_every(), prog, flush_every_reads(h), batch_bases(), flush);
-    if (!rc && fq2) {
-        done_before = n1;
-        rc = pack_fastq(t2, l2, h->k, h->min_qual, pr, err, h->progress_every(), prog, flush_every_reads(h), batch_bases(), flush);
-    }
-    if (rc == -7) return flush_rc;                       // the batch hand-over failed: its error is set
-    if (rc) return fail(h, rc == -3 ? SHK_E_PARSE : (rc == -4 ? SHK_E_OOM : SHK_E_PARAM), err);
-    h->n_reads = pr.n_reads;
-    h->pipe->times().add("fastq_parse_pack_host_clock", now_ms() - t0);
-    if (int rc2 = flush_host_batch(h, pr)) return rc2;
-    return finish_counting(h);
-}
-
-static int push_reads_impl(shk_handle *h, const uint8_t *chunk, size_t n) {
-    if (!h) return SHK_E_PARAM;
-    if (h->st != St::Fresh && h->st != St::Streaming) return fail(h, SHK_E_STATE, "push_reads: handle already preprocessed");
-    if (h->st == St::Fresh) {
-        h->post("preprocess:start"); h->post_mode("start"); h->post_loop_edge("loop:start");
-        h->st = St::Streaming;
-    }
-    std::string err;
-    auto prog = [&](uint64_t reads, uint64_t, uint64_t) { h->post_mode(("loop:" + std::to_string(reads)).c_str()); };
-    int flush_rc = SHK_OK;
-    auto flush = [&](PackedReads &p) -> int { flush_rc = flush_host_batch(h, p); return flush_rc ? -7 : 0; };
-    h->pipe->expect_more_batches();                      // the total is unknown while chunks keep coming
-    // a large chunk (whole records, like every chunk) is parsed on the device and counted as a batch of its
-    // own; small chunks — and any chunk the device parser finds irregular — are packed on the host below
-    {
-        const char *force_host = getenv("SHK_HOST_PARSER");
-        const char *mv = getenv("SHK_STREAM_DEVICE_MIN");
-        const size_t dev_min = (mv && *mv) ? (size_t)strtoull(mv, nullptr, 10) : ((size_t)8 << 20);
-        if (!(force_host && *force_host == '1') && n >= dev_min) {
-            ByteVec st;
-            const uint8_t *t = nullptr; size_t l = 0;
-            int rc = maybe_inflate(chunk, n, st, t, l, err);
-            if (rc) return fail(h, rc == -3 ? SHK_E_PARSE : SHK_E_OOM, err);
-            if (l / 2 <= batch_bases()) {
-                GpuPacked gp;
-                rc = gpu_pack_fastq(t, l, nullptr, 0, h->k, h->min_qual, h->progress_every(), h->pipe->stream(), gp, err, h->stream_reads.n_reads);
-                if (rc < 0) { gpu_packed_free(gp); return fail(h, rc == -4 ? SHK_E_OOM : (rc == -1 ? SHK_E_PARAM : SHK_E_DEVICE), err); }
-                if (rc == 0) {
-                    const uint64_t every = h->progress_every();
-                    for (size_t j = 0; j < gp.progress_bytes.size(); j++) prog(every * (gp.first_mark + j + 1), 0, 0);
-                    h->pipe->times().add("fastq_device_chunks_x1", 1.0);
-                    const int rc2 = gp.n_seg ? count_one_batch(h, gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases) : SHK_OK;
-                    h->stream_reads.n_reads += gp.n_reads; h->stream_reads.n_input_bases += gp.n_input_bases;
-                    gpu_packed_free(gp);
-                    return rc2;
-                }
-                gpu_packed_free(gp);                    // not regular 4-line FASTQ: the host parser decides
-            }
-        }
-    }
-    int rc = pack_fastq(chunk, n, h->k, h->min_qual, h->stream_reads, err, h->progress_every(), prog,
-                        flush_every_reads(h), batch_bases(), flush);
-    if (rc == -7) return flush_rc;
-    if (rc) return fail(h, rc == -3 ? SHK_E_PARSE : (rc == -4 ? SHK_E_OOM : SHK_E_PARAM), err);
-    return SHK_OK;
-}
-
-static int finish_reads_impl(shk_handle *h) {
-    if (!h) return SHK_E_PARAM;
-    if (h->st != St::Streaming) return fail(h, SHK_E_STATE, "finish_reads: no reads pushed");
-    h->n_reads = h->stream_reads.n_reads;
-    int rc = flush_host_batch(h, h->stream_reads);
-    h->stream_reads.clear();
-    if (rc) return rc;
-    return finish_counting(h);
-}
-
-static int preprocess_packed_device_impl(shk_handle *h, const void *d_bases, const void *d_seg_off, uint64_t n_seg,
-                                 uint64_t n_bases, uint64_t n_reads) {
-    if (!h) return SHK_E_PARAM;
-    if (h->st != St::Fresh) return fail(h, SHK_E_STATE, "preprocess: handle already used");
-    if (!d_bases || !d_seg_off) return fail(h, SHK_E_PARAM, "null device pointer");
-    h->post("preprocess:start"); h->post_mode("start"); h->post_loop_edge("loop:start");
-    h->n_reads = n_reads;
-    h->post_mode(("loop:" + std::to_string(n_reads) + ":100").c_str());
-    return run_counting(h, (const uint32_t *)d_bases, (const uint32_t *)d_seg_off, n_seg, n_bases);
-}
-
-static int preprocess_packed_host_impl(shk_handle *h, const uint32_t *bases, const uint32_t *seg_off, uint64_t n_seg,
-                                       uint64_t n_bases, uint64_t n_reads) {
-    if (h->st != St::Fresh) return fail(h, SHK_E_STATE, "preprocess: handle already used");
-    if (!bases || !seg_off) return fail(h, SHK_E_PARAM, "null host pointer");
-    if (n_bases >= 0xFFFFFFFFull || n_seg >= 0xFFFFFFFFull) return fail(h, SHK_E_PARAM, "batch too large (>= 2^32 bases)");
-    std::string err;
-    struct Block { void *p = nullptr; size_t bytes = 0; ~Block() { if (p) device_pool_release(p, bytes); } } db, ds;
-    db.bytes = (size_t)((n_bases + 15) / 16 + 1) * 4; ds.bytes = (size_t)(n_seg + 1) * 4;
-    const size_t want_b = db.bytes, want_s = ds.bytes;
-    db.p = device_pool_alloc(db.bytes); ds.p = device_pool_alloc(ds.bytes);
-    if (!db.p || !ds.p) return fail(h, SHK_E_OOM, "preprocess: device memory for the packed reads");
-    const double t0 = now_ms();
-    void *st = h->pipe->stream();
-    h->post("preprocess:start"); h->post_mode("start"); h->post_loop_edge("loop:start");
-    h->n_reads = n_reads;
-    h->post_mode(("loop:" + std::to_string(n_reads) + ":100").c_str());
-    // upload and pass 1 overlap piece by piece (Pipeline::count_batch_host), then histogram / fit / filter as usual
-    h->batches_started++;
-    h->pipe->single_batch_resident(true);
-    int rc = h->pipe->count_batch_host((uint32_t *)db.p, (uint32_t *)ds.p, bases, seg_off, n_seg, n_bases, err);
-    if (rc) rc = fail(h, rc == -4 ? SHK_E_OOM : (rc == -1 ? SHK_E_PARAM : SHK_E_DEVICE), err);
-    else rc = finish_counting(h);
-    h->pipe->single_batch_resident(false);
-    { std::string e2; (void)device_stream_sync(st, e2); }      // the blocks go back to the pool idle, also after a failure
-    h->pipe->times().add("h2d_packed_reads_MB", (double)(want_b + want_s) / 1e6);
-    h->pipe->times().add("preprocess_from_host_total_host_clock", now_ms() - t0);
-    return rc;
-}
-
 // ---- shard layer: the single-GPU preprocess cut at its two exchange points ----------------------
-static uint32_t emit_threshold_of(const shk_handle *h) {
-    return h->do_fit ? (h->min_count < 1u ? h->min_count : 1u) : h->min_count;
-}
 
 static int shard_partition_impl(shk_handle *h, const void *d_bases, const void *d_seg_off, uint64_t n_seg, uint64_t n_bases,
                         uint64_t n_reads, uint32_t n_partitions, uint64_t *part_records) {
     if (!h || !part_records) return SHK_E_PARAM;
     if (h->st != St::Fresh) return fail(h, SHK_E_STATE, "shard_partition: handle already used");
-    h->post("preprocess:start"); h->post_mode("start"); h->post_loop_edge("loop:start");
+    h->post_start();
     h->n_reads = n_reads;
     std::vector<uint64_t> pr;
     std::string err;
     int rc = h->pipe->shard_partition((const uint32_t *)d_bases, (const uint32_t *)d_seg_off, n_seg, n_bases, n_partitions, pr, err);
-    if (rc) return fail(h, rc == -4 ? SHK_E_OOM : (rc == -1 ? SHK_E_PARAM : SHK_E_DEVICE), err);
+    if (rc) return fail_rc(h, Rc::Device, rc, err);
     memcpy(part_records, pr.data(), (size_t)n_partitions * 8);
     h->post_mode(("loop:" + std::to_string(n_reads) + ":100").c_str());
     h->post_loop_edge("loop:end");
@@ -733,7 +130,7 @@ static int shard_pack_impl(shk_handle *h, void *d_send, const uint64_t *base_rec
     if (h->st != St::Sharding) return fail(h, SHK_E_STATE, "shard_pack: call shard_partition first");
     std::string err;
     int rc = h->pipe->shard_pack(d_send, base_records, n_partitions, err);
-    return rc ? fail(h, rc == -4 ? SHK_E_OOM : (rc == -1 ? SHK_E_PARAM : SHK_E_DEVICE), err) : SHK_OK;
+    return rc ? fail_rc(h, Rc::Device, rc, err) : SHK_OK;
 }
 
 static int shard_count_impl(shk_handle *h, const void *d_recv, const uint64_t *run_off, const uint32_t *run_cnt,
@@ -744,7 +141,7 @@ static int shard_count_impl(shk_handle *h, const void *d_recv, const uint64_t *r
     std::string err;
     if (!h->do_bloom && h->chunk_size == 0) h->post("preprocess:bulk:sorting");
     int rc = h->pipe->shard_count(d_recv, d_recv_w, run_off, run_cnt, n_owned, n_sources, emit_threshold_of(h), histo500_local, err);
-    if (rc) return fail(h, rc == -4 ? SHK_E_OOM : (rc == -1 ? SHK_E_PARAM : SHK_E_DEVICE), err);
+    if (rc) return fail_rc(h, Rc::Device, rc, err);
     if (n_instances_local) *n_instances_local = h->pipe->total_instances();
     return SHK_OK;
 }
@@ -763,7 +160,7 @@ static int shard_rows_impl(shk_handle *h, const uint64_t *histo500_global, const
     h->post_mode("filtering");
     std::string err;
     int rc = h->pipe->shard_rows(h->used_min_count, d_keys, d_cnt, n_rows, err);
-    if (rc) return fail(h, rc == -4 ? SHK_E_OOM : SHK_E_DEVICE, err);
+    if (rc) return fail_rc(h, Rc::DeviceNoParam, rc, err);
     if (used_min_count) *used_min_count = h->used_min_count;
     return SHK_OK;
 }
@@ -774,7 +171,7 @@ static int shard_set_solid_impl(shk_handle *h, const void *const *d_keys, const 
     if (h->st != St::Sharding) return fail(h, SHK_E_STATE, "shard_set_solid: call shard_rows first");
     std::string err;
     int rc = h->pipe->shard_set_solid(d_keys, d_cnt, n_rows, h->histo, n_instances_global, err);
-    if (rc) return fail(h, rc == -4 ? SHK_E_OOM : (rc == -1 ? SHK_E_PARAM : SHK_E_DEVICE), err);
+    if (rc) return fail_rc(h, Rc::Device, rc, err);
     h->post("preprocess:saving");
     h->pre_json = preprocessing_json(h->pipe->n_solid(), h->histo, h->used_min_count);
     h->st = St::Preprocessed;
@@ -803,7 +200,7 @@ static int assemble_impl(shk_handle *h) {
         if (h->pipe->n_solid_global() >= (1u << 20)) writer_prewarm(3000);
         int rc = h->pipe->shard_assemble(h->shard_comm, !h->no_deadend, !h->no_bubble, contigs, err);
         // (a failure the other ranks cannot know of has aborted the communicator already: Pipeline::shard_assemble)
-        if (rc) return fail(h, rc == -4 ? SHK_E_OOM : SHK_E_DEVICE, err);
+        if (rc) return fail_rc(h, Rc::DeviceNoParam, rc, err);
         h->post("assembly:correct_graph");
         h->post("assembly:collapse_graph");
         h->pipe->times().add("assemble_device_total_host_clock", now_ms() - t0);
@@ -819,17 +216,17 @@ static int assemble_impl(shk_handle *h) {
     }
     h->post("assembly:create_graph");
     int rc = h->pipe->build_graph(err);
-    if (rc) return fail(h, rc == -4 ? SHK_E_OOM : SHK_E_DEVICE, err);
+    if (rc) return fail_rc(h, Rc::DeviceNoParam, rc, err);
     h->post("assembly:correct_graph");
     rc = h->pipe->correct(!h->no_deadend, !h->no_bubble, err);
-    if (rc) return fail(h, rc == -4 ? SHK_E_OOM : SHK_E_DEVICE, err);
+    if (rc) return fail_rc(h, Rc::DeviceNoParam, rc, err);
     h->post("assembly:collapse_graph");
     if (h->pipe->n_solid() >= (1u << 20)) writer_prewarm(3000);     // megabases of output in about a millisecond
     std::vector<RawContig> contigs;
     const char *dev_json = nullptr; size_t dev_json_len = 0; uint64_t dev_nc = 0;
     TextArrival *arrival = nullptr;                    // megabases of contigs: their text is still crossing PCIe when the writer starts
     rc = h->pipe->collapse(contigs, err, &dev_json, &dev_json_len, &dev_nc, &arrival);
-    if (rc) return fail(h, rc == -4 ? SHK_E_OOM : SHK_E_DEVICE, err);
+    if (rc) return fail_rc(h, Rc::DeviceNoParam, rc, err);
     h->pipe->times().add("assemble_device_total_host_clock", now_ms() - t0);
     h->post("assembly:saving");
     if (dev_json) {                                    // a fragmented assembly: its text was written on the device (csrc/writer_gpu.h)
@@ -842,7 +239,7 @@ static int assemble_impl(shk_handle *h) {
     const double t1 = now_ms();
     struct ArrivalDone { TextArrival *a; ~ArrivalDone() { if (a) { std::string e; (void)a->finish(e); } } } arrival_done{arrival};   // (also when the writer throws)
     build_assembly_text(contigs, h->k, h->text, arrival);
-    if (arrival) { arrival_done.a = nullptr; if (int rc2 = arrival->finish(err)) return fail(h, rc2 == -4 ? SHK_E_OOM : SHK_E_DEVICE, err); }
+    if (arrival) { arrival_done.a = nullptr; if (int rc2 = arrival->finish(err)) return fail_rc(h, Rc::DeviceNoParam, rc2, err); }
     h->asm_json.swap(h->text.json);
     h->pipe->times().add("outputs_host_clock", now_ms() - t1);
     if (arrival) h->pipe->times().add("outputs_with_arrival_x1", 1.0);
@@ -865,7 +262,7 @@ int shk_pack_fastq(const uint8_t *fq, size_t n, uint32_t k, uint32_t min_qual, s
     if (!out) return SHK_E_PARAM;
     PackedReads pr;
     int rc = pack_fastq(fq, n, k, min_qual, pr, msg);
-    if (rc) { if (errp) *errp = msg.c_str(); return rc == -3 ? SHK_E_PARSE : (rc == -4 ? SHK_E_OOM : SHK_E_PARAM); }
+    if (rc) { if (errp) *errp = msg.c_str(); return code_of(Rc::Parser, rc); }
     pr.finish();
     out->n_seg = pr.n_seg(); out->n_bases = pr.n_bases; out->n_reads = pr.n_reads; out->n_input_bases = pr.n_input_bases;
     out->bases = (uint32_t *)malloc(pr.bases.size() * 4);
@@ -946,7 +343,6 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
     const uint32_t W = (2 * h->k + 63) / 64;
     void *st = h->pipe->stream();
     std::string err;
-    auto cfail = [&](int rc) { return fail(h, rc == -4 ? SHK_E_OOM : (rc == -1 ? SHK_E_PARAM : SHK_E_DEVICE), err); };
     const double t0 = now_ms();
     // SHK_STAGE_LOG=1: after every step the stream is drained and the step's name goes to stderr (which step a fault belongs to)
     const bool stage_log = getenv("SHK_STAGE_LOG") != nullptr;
@@ -972,14 +368,14 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
     auto agree = [&](int local_rc, const char *stage) -> int {
         uint64_t f = local_rc ? 1u : 0u;
         std::string e2;
-        if (int rc = comm_allreduce_host_u64(c, &f, 1, st, e2)) { if (local_rc) return local_rc; err = e2; return cfail(rc); }
+        if (int rc = comm_allreduce_host_u64(c, &f, 1, st, e2)) { if (local_rc) return local_rc; err = e2; return fail_rc(h, Rc::Device, rc, err); }
         if (local_rc) return local_rc;
         return f ? peer_failed(stage) : SHK_OK;
     };
     // ---- the partition count must be the same everywhere: from the global instance count
     if (n_partitions == 0) {
         uint64_t inst = n_bases > n_seg * (uint64_t)(h->k - 1) ? n_bases - n_seg * (uint64_t)(h->k - 1) : 0;
-        if (int rc = comm_allreduce_host_u64(c, &inst, 1, st, err)) return cfail(rc);
+        if (int rc = comm_allreduce_host_u64(c, &inst, 1, st, err)) return fail_rc(h, Rc::Device, rc, err);
         n_partitions = choose_partitions(inst, world, W == 1 ? 100000 : 40000);
     }
     if (n_partitions < world) return fail(h, SHK_E_PARAM, "shard_preprocess: fewer partitions than ranks");
@@ -999,7 +395,7 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
         if (mode) {
             std::vector<uint64_t> pr(part.begin(), part.begin() + P);
             std::string e2;
-            if (int r2 = h->pipe->shard_dedupe(pr, e2)) rc_p1 = fail(h, r2 == -4 ? SHK_E_OOM : SHK_E_DEVICE, e2);
+            if (int r2 = h->pipe->shard_dedupe(pr, e2)) rc_p1 = fail_rc(h, Rc::DeviceNoParam, r2, e2);
             else memcpy(&part[0], pr.data(), (size_t)P * 8);
         }
         part[2 * (size_t)P + 1] = mode;
@@ -1009,7 +405,7 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
     // ---- the size exchange: every rank learns what every rank holds per partition
     const size_t ROW = 2 * (size_t)P + 2;
     std::vector<uint64_t> all_raw((size_t)world * ROW), all((size_t)world * P), raw_counts((size_t)world * P);
-    if (int rc = comm_allgather_host_u64(c, part.data(), ROW, all_raw.data(), st, err)) { if (rc_p1) return rc_p1; return cfail(rc); }
+    if (int rc = comm_allgather_host_u64(c, part.data(), ROW, all_raw.data(), st, err)) { if (rc_p1) return rc_p1; return fail_rc(h, Rc::Device, rc, err); }
     if (rc_p1) return rc_p1;
     bool weighted = true, forced = false;
     uint64_t sum_dd = 0, sum_raw = 0;
@@ -1035,7 +431,7 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
     struct DrainOnExit { ShardComm *c; void *st; ~DrainOnExit() { std::string e; (void)comm_stream_wait(c, st, e); } } drain{c, st};
     {
         int rc_pack = SHK_OK;
-        if (int rc = plan_exchange(all.data(), world, P, rank, plan, err)) rc_pack = cfail(rc);
+        if (int rc = plan_exchange(all.data(), world, P, rank, plan, err)) rc_pack = fail_rc(h, Rc::Device, rc, err);
         if (!rc_pack && weighted) {
             // (a partition's record index — and a record's multiplicity — are 32 bits wide in pass 2: the limit is on the RAW records)
             for (uint32_t p = rank; p < P && !rc_pack; p += world) {
@@ -1056,7 +452,7 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
         }
         if (!rc_pack && weighted) {
             std::string e2;
-            if (int r2 = h->pipe->shard_pack_dedup(send.p, send_w.p, plan.base.data(), P, e2)) rc_pack = fail(h, r2 == -4 ? SHK_E_OOM : (r2 == -1 ? SHK_E_PARAM : SHK_E_DEVICE), e2);
+            if (int r2 = h->pipe->shard_pack_dedup(send.p, send_w.p, plan.base.data(), P, e2)) rc_pack = fail_rc(h, Rc::Device, r2, e2);
         } else if (!rc_pack) rc_pack = shard_pack_impl(h, send.p, plan.base.data(), P);
         if (!rc_pack) rc_pack = injected("pack");
         stage("pack");
@@ -1070,13 +466,13 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
             ro[r] = b; rb[r] = plan.recv_counts[r] * rec_bytes; b += rb[r];
         }
         const double tx = now_ms();
-        if (int rc = comm_alltoallv(c, send.p, so.data(), sb.data(), recv.p, ro.data(), rb.data(), st, err)) return cfail(rc);
+        if (int rc = comm_alltoallv(c, send.p, so.data(), sb.data(), recv.p, ro.data(), rb.data(), st, err)) return fail_rc(h, Rc::Device, rc, err);
         if (weighted) {
             // the weights: same element offsets as the records, 4 bytes each
             for (uint32_t r = 0; r < world; r++) { so[r] = so[r] / rec_bytes * 4; sb[r] = plan.send_counts[r] * 4; ro[r] = ro[r] / rec_bytes * 4; rb[r] = plan.recv_counts[r] * 4; }
-            if (int rc = comm_alltoallv(c, send_w.p, so.data(), sb.data(), recv_w.p, ro.data(), rb.data(), st, err, 4)) return cfail(rc);
+            if (int rc = comm_alltoallv(c, send_w.p, so.data(), sb.data(), recv_w.p, ro.data(), rb.data(), st, err, 4)) return fail_rc(h, Rc::Device, rc, err);
         }
-        if (int rc = comm_stream_wait(c, st, err)) { comm_mark_broken(c); return cfail(rc); }
+        if (int rc = comm_stream_wait(c, st, err)) { comm_mark_broken(c); return fail_rc(h, Rc::Device, rc, err); }
         h->pipe->times().add("shard_exchange_host_clock", now_ms() - tx);
         h->pipe->times().add("shard_exchange_sent_MB", (double)(n_send * (rec_bytes + (weighted ? 4 : 0))) / 1e6);
     }
@@ -1095,7 +491,7 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
     if (rc_cnt) memset(red, 0, sizeof red);
     red[SHK_HISTO_BINS + 1] = rc_cnt ? 1u : 0u;
     red[SHK_HISTO_BINS + 2] = inst_in_reads;
-    if (int rc = comm_allreduce_host_u64(c, red, SHK_HISTO_BINS + 3, st, err)) { if (rc_cnt) return rc_cnt; return cfail(rc); }
+    if (int rc = comm_allreduce_host_u64(c, red, SHK_HISTO_BINS + 3, st, err)) { if (rc_cnt) return rc_cnt; return fail_rc(h, Rc::Device, rc, err); }
     if (rc_cnt) return rc_cnt;
     if (red[SHK_HISTO_BINS + 1]) return peer_failed("pass 2");
     if (red[SHK_HISTO_BINS] != red[SHK_HISTO_BINS + 2])
@@ -1127,7 +523,7 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
     // ---- all-gather of the solid rows
     std::vector<uint64_t> counts2((size_t)world * 2), counts(world);
     const uint64_t mine2[2] = {rc_rows ? 0u : n_local, rc_rows ? 1u : 0u};
-    if (int rc = comm_allgather_host_u64(c, mine2, 2, counts2.data(), st, err)) { if (rc_rows) return rc_rows; return cfail(rc); }
+    if (int rc = comm_allgather_host_u64(c, mine2, 2, counts2.data(), st, err)) { if (rc_rows) return rc_rows; return fail_rc(h, Rc::Device, rc, err); }
     if (rc_rows) return rc_rows;
     for (uint32_t r = 0; r < world; r++) { if (counts2[2 * r + 1]) return peer_failed("the filter"); counts[r] = counts2[2 * r]; }
     // ---- the graph stays sharded (default): every rank keeps its own rows and shk_assemble() runs collectively over this
@@ -1166,9 +562,9 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
         if (int rc = agree(rc_alloc, "the allocation of the solid set")) return rc;
     }
     for (uint32_t j = 0; j < W; j++)
-        if (int rc = comm_allgatherv(c, keys[j], gk[j].p, off8.data(), len8.data(), st, err)) return cfail(rc);
-    if (int rc = comm_allgatherv(c, cnt, gc.p, off4.data(), len4.data(), st, err)) return cfail(rc);
-    if (int rc = comm_stream_wait(c, st, err)) { comm_mark_broken(c); return cfail(rc); }
+        if (int rc = comm_allgatherv(c, keys[j], gk[j].p, off8.data(), len8.data(), st, err)) return fail_rc(h, Rc::Device, rc, err);
+    if (int rc = comm_allgatherv(c, cnt, gc.p, off4.data(), len4.data(), st, err)) return fail_rc(h, Rc::Device, rc, err);
+    if (int rc = comm_stream_wait(c, st, err)) { comm_mark_broken(c); return fail_rc(h, Rc::Device, rc, err); }
     const void *kp[8] = {gk[0].p, gk[1].p, gk[2].p, gk[3].p, gk[4].p, gk[5].p, gk[6].p, gk[7].p};
     if (int rc = shard_set_solid_impl(h, kp, gc.p, n_total, red[SHK_HISTO_BINS])) return rc;
     h->pipe->times().add("shard_preprocess_host_clock", now_ms() - t0);
@@ -1359,7 +755,7 @@ int shk_device_gunzip(const uint8_t *gz, size_t n, uint8_t **out, size_t *out_n,
         if (why) { msg = rc == 1 ? st.why_not : err; *why = msg.c_str(); }
         if (ms_total) *ms_total = st.total_ms;
         if (rc == 1) return 1;
-        if (rc) return rc == -4 ? SHK_E_OOM : SHK_E_DEVICE;
+        if (rc) return code_of(Rc::DeviceNoParam, rc);
         const size_t bytes = text.e;
         uint8_t *o = (uint8_t *)malloc(bytes ? bytes : 1);
         if (!o) { gpu_text_free(text); return SHK_E_OOM; }
@@ -1377,7 +773,7 @@ int shk_host_gunzip(const uint8_t *gz, size_t n, uint8_t **out, size_t *out_n, u
         const double t0 = now_ms();
         const int rc = maybe_inflate(gz, n, st, p, pn, err);
         if (reader_seconds) *reader_seconds = (now_ms() - t0) * 1e-3;
-        if (rc) return rc == -3 ? SHK_E_PARSE : SHK_E_OOM;
+        if (rc) return code_of(Rc::Inflater, rc);
         *out = (uint8_t *)malloc(pn ? pn : 1);
         if (!*out) return SHK_E_OOM;
         if (pn) memcpy(*out, p, pn);

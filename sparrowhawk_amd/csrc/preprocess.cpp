@@ -1,0 +1,508 @@
+// preprocess.cpp — how reads reach the counting passes.  shk_preprocess tries these routes in this order; a route fails
+// (error set, SHK_E_*), handles the input, or declines having counted nothing, and the next one is tried:
+//   1 route_device_gzip          every file starts with the gzip magic, SHK_GUNZIP_DEVICE != 0, SHK_HOST_PARSER != 1: device
+//                                inflater (a plain member or a BGZF file) -> device parser -> one batch.  Declines when the
+//                                inflater or the parser declines or the text exceeds one batch.
+//     (what is gzip is inflated on the host here, once, for the routes below)
+//   2 route_device_pieces(one)   the text fits one batch and is >= SHK_FASTQ_PIPELINE_MIN (64 MiB): cut into a few pieces,
+//                                piece i+1 uploaded while piece i is parsed, counted as ONE batch
+//   3 route_device_single        the text fits one batch (and route 2 has not found it irregular): one upload, one parse
+//   4 route_device_pieces        the text exceeds one batch: one batch per piece
+//   5 route_host                 SHK_HOST_PARSER=1, or every route above declined.  Never declines.
+//   6 push_reads_impl            the streaming entry point: the device parser for a chunk of >= SHK_STREAM_DEVICE_MIN bytes
+//                                that is regular 4-line FASTQ, else the host parser
+// The device parser (fastq_gpu.hip) takes regular 4-line FASTQ only; irregular framing and every malformed record go to
+// the host parser (fastq.cpp), which owns the error messages.
+#include "preprocess.h"
+
+#include <stdlib.h>
+#include <string.h>
+#include <algorithm>
+#include <thread>
+#include <utility>
+#include <vector>
+
+#include "fastq_gpu.h"
+#include "inflate_gpu.h"
+#include "inflate_mt.h"
+
+namespace shk { bool spectrum_fit(const uint64_t *histo500, uint32_t *out); }   // fit.cpp
+
+using namespace shk;
+
+uint32_t emit_threshold_of(const shk_handle *h) {
+    // the fit never returns less than 1 and falls back to min_count (SPEC S6)
+    return h->do_fit ? (h->min_count < 1u ? h->min_count : 1u) : h->min_count;
+}
+
+namespace {
+
+const int DECLINED = 1;                 // what a route returns when the next one is to be tried (SHK_E_* are <= 0)
+
+// the environment's switches, read once per call (the tests change them between handles of one process)
+struct Knobs {
+    static bool is(const char *v, char c) { return v && *v == c; }
+    static uint64_t num(const char *v, uint64_t dflt) { return (v && *v) ? strtoull(v, nullptr, 10) : dflt; }
+    const bool host_parser = is(getenv("SHK_HOST_PARSER"), '1'), gunzip_device = !is(getenv("SHK_GUNZIP_DEVICE"), '0');
+    const size_t pipeline_min = num(getenv("SHK_FASTQ_PIPELINE_MIN"), 64ull << 20), stream_device_min = num(getenv("SHK_STREAM_DEVICE_MIN"), 8ull << 20);
+    const size_t pieces = (size_t)std::max<long long>(1, (long long)num(getenv("SHK_FASTQ_PIECES"), 4));
+    // bases per batch of the host-parsed paths (a batch is limited to 2^32 packed bases by its 32-bit offsets)
+    const uint64_t batch_bases = std::min<uint64_t>(std::max<uint64_t>(num(getenv("SHK_BATCH_BASES"), 1ull << 31), 1024), 3ull << 30);
+};
+
+// a device block of the parser that goes back to the pool when its owner goes out of scope (every error and
+// "declined" exit), or at reset() where the success path lets go of it earlier
+template <typename T, void (*Free)(T &)> struct Owned : T {
+    Owned() = default;
+    Owned(Owned &&o) noexcept : T(std::move(static_cast<T &>(o))) { static_cast<T &>(o) = T(); }
+    Owned &operator=(Owned &&o) noexcept { if (this != &o) { reset(); T::operator=(std::move(o)); static_cast<T &>(o) = T(); } return *this; }
+    ~Owned() { reset(); }
+    void reset() { Free(*this); }
+};
+using Text = Owned<GpuText, gpu_text_free>;
+using Packed = Owned<GpuPacked, gpu_packed_free>;
+
+// where a text lies in the whole input: the percentage of a `loop:<n>:<pct>` string (the streaming entry point posts none)
+struct Span { uint64_t base = 0, total = 0; bool pct = true; };
+void post_loop(shk_handle *h, uint64_t reads, const Span &sp, uint64_t bytes) {
+    std::string s = "loop:" + std::to_string(reads);
+    if (sp.pct) s += ":" + std::to_string(sp.total ? (100 * (sp.base + bytes)) / sp.total : 100);
+    h->post_mode(s.c_str());
+}
+// the marks of a device-parsed batch: one every `every` reads, with the bytes consumed inside the file the mark lies in
+// (bit 63: the second file of a single-shot pair, which starts n1 bytes into the input)
+void post_device_progress(shk_handle *h, const GpuPacked &gp, const Span &sp, uint64_t n1 = 0) {
+    const uint64_t every = h->progress_every();
+    for (size_t j = 0; j < gp.progress_bytes.size(); j++) {
+        const bool second = (gp.progress_bytes[j] >> 63) != 0;
+        post_loop(h, every * (gp.first_mark + j + 1), sp, (second ? n1 : 0) + (gp.progress_bytes[j] & ~(1ull << 63)));
+    }
+}
+
+// one batch of packed segments in HBM -> pass 1 (several batches per handle are allowed)
+int count_one_batch(shk_handle *h, const uint32_t *d_bases, const uint32_t *d_seg_off, uint64_t n_seg, uint64_t n_bases) {
+    std::string err;
+    const double t0 = now_ms();
+    h->batches_started++;
+    int rc = h->pipe->count_batch(d_bases, d_seg_off, n_seg, n_bases, err);
+    h->pipe->times().add("preprocess_device_total_host_clock", now_ms() - t0);
+    return rc ? fail_rc(h, Rc::Device, rc, err) : SHK_OK;
+}
+// the packed pieces of ONE batch -> pass 1 (the pieces with no segment are left out by the caller)
+int count_pieces(shk_handle *h, const std::vector<DevPiece> &pcs) {
+    std::string err;
+    const double t0 = now_ms();
+    h->batches_started++;
+    const int rc = h->pipe->count_batch_pieces(pcs.data(), pcs.size(), err);
+    h->pipe->times().add("preprocess_device_total_host_clock", now_ms() - t0);
+    return rc ? fail_rc(h, Rc::Device, rc, err) : SHK_OK;
+}
+
+// common tail of every preprocess entry point: all batches are in -> histogram, fit, filter
+int finish_counting(shk_handle *h) {
+    std::string err;
+    const double t0 = now_ms();
+    h->post_loop_edge("loop:end");
+    if (!h->do_bloom && h->chunk_size == 0) h->post("preprocess:bulk:sorting");
+    int rc = h->pipe->histogram(h->histo, emit_threshold_of(h), err);
+    if (rc) return fail(h, SHK_E_DEVICE, err);
+    h->used_min_count = h->min_count; h->fit_ok = false;
+    if (h->do_fit) {
+        h->post_mode("fitting");
+        uint32_t v = 0;
+        if (spectrum_fit(h->histo, &v)) { h->used_min_count = v; h->fit_ok = true; }
+    }
+    h->post_mode("filtering");
+    rc = h->pipe->filter(h->used_min_count, err);
+    if (rc) return fail_rc(h, Rc::DeviceNoParam, rc, err);
+    h->post("preprocess:saving");
+    h->pre_json = preprocessing_json(h->pipe->n_solid(), h->histo, h->used_min_count);
+    h->pipe->times().add("preprocess_device_total_host_clock", now_ms() - t0);
+    h->st = St::Preprocessed;
+    h->post("preprocess:end");
+    return SHK_OK;
+}
+
+// one batch, and the caller's reads stay in place until this function returns: the two counting passes run back to back
+int run_counting(shk_handle *h, const uint32_t *d_bases, const uint32_t *d_seg_off, uint64_t n_seg, uint64_t n_bases) {
+    h->pipe->single_batch_resident(true);
+    int rc = count_one_batch(h, d_bases, d_seg_off, n_seg, n_bases);
+    if (!rc) rc = finish_counting(h);
+    h->pipe->single_batch_resident(false);
+    return rc;
+}
+
+// hand the packed stream on as one batch (upload + pass 1) and empty it; read counters are kept
+int flush_host_batch(shk_handle *h, PackedReads &pr) {
+    if (pr.n_seg() == 0) { pr.reset_stream(); return SHK_OK; }
+    pr.finish();
+    std::string err;
+    void *d_bases = nullptr, *d_off = nullptr;
+    const double t0 = now_ms();
+    int rc = device_upload(pr.bases.data(), pr.bases.size() * 4, &d_bases, err);
+    if (!rc) rc = device_upload(pr.seg_off.data(), pr.seg_off.size() * 4, &d_off, err);
+    if (rc) { device_free(d_bases); device_free(d_off); return fail(h, SHK_E_OOM, err); }
+    h->pipe->times().add("h2d_upload_host_clock", now_ms() - t0);
+    rc = count_one_batch(h, (const uint32_t *)d_bases, (const uint32_t *)d_off, pr.n_seg(), pr.n_bases);
+    device_free(d_bases); device_free(d_off);
+    pr.reset_stream();
+    return rc;
+}
+
+// chunked mode hands a batch on every chunk_size reads (docs/src/assembly.md:17: "reads per batch")
+uint64_t flush_every_reads(const shk_handle *h) { return (!h->do_bloom && h->chunk_size > 0) ? h->chunk_size : 0; }
+
+// The host parser over one text, appended to `pr`: progress is posted as it goes, and a batch is handed on every
+// flush_reads reads (0 = never) or batch_bases bases.  What is left in `pr` at the end is the caller's to flush.
+// rec_base: records of this file that came before the text (numbering of the error messages).
+int host_parse(shk_handle *h, const Knobs &kn, const uint8_t *t, size_t n, PackedReads &pr, const Span &sp, uint64_t flush_reads, uint64_t rec_base = 0) {
+    std::string err;
+    auto prog = [&](uint64_t reads, uint64_t bytes, uint64_t) { post_loop(h, reads, sp, bytes); };
+    int flush_rc = SHK_OK;
+    auto flush = [&](PackedReads &p) -> int { flush_rc = flush_host_batch(h, p); return flush_rc ? -7 : 0; };
+    const int rc = pack_fastq(t, n, h->k, h->min_qual, pr, err, h->progress_every(), prog, flush_reads, kn.batch_bases, flush, rec_base);
+    if (rc == -7) return flush_rc;                       // the batch hand-over failed: its error is set
+    return rc ? fail_rc(h, Rc::Parser, rc, err) : SHK_OK;
+}
+
+// start of the first FASTQ record at or after `from` (a line starting with '@' whose line after next starts
+// with '+': a quality line may start with '@' too, but then the line after next is a sequence); n = none,
+// SIZE_MAX = the text does not look like 4-line FASTQ here
+size_t next_record_start(const uint8_t *t, size_t n, size_t from) {
+    size_t p = from;
+    if (p >= n) return n;
+    if (p > 0 && t[p - 1] != '\n') {
+        const void *nl = memchr(t + p, '\n', n - p);
+        if (!nl) return n;
+        p = (size_t)((const uint8_t *)nl - t) + 1;
+    }
+    for (int tries = 0; tries < 8 && p < n; tries++) {
+        const void *e0 = memchr(t + p, '\n', n - p);
+        if (!e0) return n;
+        const size_t b = (size_t)((const uint8_t *)e0 - t) + 1;
+        if (b >= n) return n;
+        const void *e1 = memchr(t + b, '\n', n - b);
+        if (!e1) return n;
+        const size_t c = (size_t)((const uint8_t *)e1 - t) + 1;
+        if (t[p] == '@' && c < n && t[c] == '+') return p;
+        p = b;
+    }
+    return SIZE_MAX;
+}
+
+// what shk_preprocess was given, and (from route 2 on) its text
+struct Input {
+    const uint8_t *fq1, *fq2; size_t n1, n2, total;     // fq2 null: one file; total: the bytes given, the denominator of the progress percentages
+    double t0;                                           // when the entry point started
+    ByteVec st1, st2;
+    const uint8_t *t1 = nullptr, *t2 = nullptr; size_t l1 = 0, l2 = 0;      // the plain text (t2 null, l2 0: one file)
+    size_t text_total() const { return l1 + l2; }
+};
+
+// Route 1.  Both files (or the one) are what the device inflater takes — a plain gzip member or a BGZF chain, in any
+// combination within a pair.  Declines (nothing counted) when any file is not taken or turns out not to be regular
+// 4-line FASTQ: the host reader then starts over.  (The progress of file 1 is posted before file 2 is parsed, so a
+// decline over file 2 leaves marks behind that the later route posts again.)
+int route_device_gzip(shk_handle *h, const Knobs &kn, const Input &in) {
+    const uint8_t *gz[2] = {in.fq1, in.fq2}; const size_t gn[2] = {in.n1, in.fq2 ? in.n2 : 0};
+    const int nf = in.fq2 ? 2 : 1;
+    for (int f = 0; f < nf; f++) if (gn[f] < 18 || gz[f][0] != 0x1F || gz[f][1] != 0x8B) return DECLINED;
+    std::string err;
+    const double t0 = now_ms();
+    Text text[2]; Packed packed[2];
+    double ms_h2d = 0, ms_search = 0, ms_decode = 0, ms_resolve = 0;
+    uint64_t bgzf_blocks = 0;
+    for (int f = 0; f < nf; f++) {
+        GpuInflateStats st;
+        const int rc = gpu_inflate_member(gz[f], gn[f], h->pipe->device(), h->pipe->stream(), text[f], err, &st);
+        if (rc == 1) { h->pipe->times().add("gunzip_device_not_taken_x1", 1.0); return DECLINED; }
+        if (rc) return fail_rc(h, Rc::DeviceNoParam, rc, err);
+        ms_h2d += st.h2d_ms; ms_search += st.search_ms; ms_decode += st.decode_ms; ms_resolve += st.resolve_ms;
+        bgzf_blocks += st.blocks;
+    }
+    const double t1 = now_ms();
+    Span sp;                                             // progress as the text path posts it, with the share of the (inflated) text consumed so far
+    for (int f = 0; f < nf; f++) sp.total += text[f].e;
+    if (sp.total / 2 > kn.batch_bases) return DECLINED;  // (several batches: the host reader's piece-wise path)
+    uint64_t reads_done = 0;
+    for (int f = 0; f < nf; f++) {
+        const int rc = gpu_pack_fastq(nullptr, 0, nullptr, 0, h->k, h->min_qual, h->progress_every(), h->pipe->stream(), packed[f], err, reads_done, &text[f]);
+        if (rc < 0) return fail_rc(h, Rc::Device, rc, err);
+        if (rc == 1) { h->pipe->times().add("gunzip_device_not_taken_x1", 1.0); return DECLINED; }      // not regular FASTQ: the host parser owns the messages
+        post_device_progress(h, packed[f], sp);
+        reads_done += packed[f].n_reads;
+        sp.base += text[f].e;
+        h->pipe->times().add("fastq_device_kernels", packed[f].kernels_ms);
+        text[f].reset();
+    }
+    h->pipe->times().add("gunzip_device_host_clock", t1 - t0);
+    h->pipe->times().add("gunzip_device_h2d", ms_h2d);
+    h->pipe->times().add("gunzip_device_search", ms_search);
+    h->pipe->times().add("gunzip_device_decode", ms_decode);
+    h->pipe->times().add("gunzip_device_windows_resolve_crc", ms_resolve);
+    h->pipe->times().add("gunzip_device_members_x1", (double)nf);
+    if (bgzf_blocks) h->pipe->times().add("gunzip_device_bgzf_blocks_x1", (double)bgzf_blocks);      // non-empty BGZF blocks, one wave each
+    h->pipe->times().add("fastq_device_parse_pack_host_clock", now_ms() - t1);
+    h->n_reads = reads_done;
+    std::vector<DevPiece> pcs;
+    for (int f = 0; f < nf; f++) if (packed[f].n_seg) pcs.push_back(DevPiece{packed[f].d_bases, packed[f].d_seg_off, packed[f].n_seg, packed[f].n_bases});
+    const int rc = count_pieces(h, pcs);
+    return rc ? rc : finish_counting(h);
+}
+
+// Routes 2 and 4.  The text is cut at record boundaries into pieces that go through the device parser one after the
+// other; a helper thread uploads piece i+1 while piece i is parsed and counted (H2D is two thirds of the entry point).
+// Route 4 (a text of more than one batch): pieces of ~2 * batch_bases bytes, each counted as its own batch (pass 1)
+// before the next is parsed.  Route 2 (one_batch: the text fits one batch): SHK_FASTQ_PIECES pieces, kept and counted
+// together as ONE batch at the end (pass 1 runs over the pieces into the same slices: the partitioning of a single
+// batch, no batch packing, no merge).
+// Declines (nothing counted) when the very first piece is not regular 4-line FASTQ.  A later piece that is not
+// regular is parsed on the host from there to the end of its file, with the record numbers and progress of the
+// whole file.
+int route_device_pieces(shk_handle *h, const Knobs &kn, const Input &in, bool one_batch) {
+    std::string err;
+    const uint8_t *const text[2] = {in.t1, in.t2}; const size_t len[2] = {in.l1, in.l2};
+    size_t piece_bytes = (size_t)(2 * kn.batch_bases);
+    if (one_batch) {
+        // the last piece is parsed with nothing left to upload: it is the small one (a tenth of the text)
+        const size_t C = kn.pieces, tot = in.text_total();
+        piece_bytes = std::max<size_t>(C >= 3 ? tot / 10 * 9 / (C - 1) : tot / C, 1024);
+    }
+    struct Piece { int file; size_t off, end; bool host_rest; };
+    std::vector<Piece> pieces;
+    for (int f = 0; f < 2; f++)
+        for (size_t off = 0, end; text[f] && off < len[f]; off = end) {
+            end = len[f];
+            if (len[f] - off > piece_bytes + piece_bytes / 8) {
+                end = next_record_start(text[f], len[f], off + piece_bytes);
+                if (end == SIZE_MAX || end <= off) { pieces.push_back(Piece{f, off, len[f], true}); break; }   // no record boundary: host from here
+            }
+            pieces.push_back(Piece{f, off, end, false});
+        }
+    std::vector<Packed> kept;                             // one_batch: the parsed pieces, counted together
+    auto count_kept = [&]() -> int {
+        if (kept.empty()) return SHK_OK;
+        std::vector<DevPiece> pcs;
+        for (auto &g : kept) pcs.push_back(DevPiece{g.d_bases, g.d_seg_off, g.n_seg, g.n_bases});
+        const int rc = count_pieces(h, pcs);
+        kept.clear();
+        return rc;
+    };
+    const int device = h->pipe->device();
+    uint64_t reads_done = 0, file_reads = 0;
+    bool counted_any = false;
+    const double t0 = now_ms();
+    Text cur, nxt;
+    // (declared after the texts: joined before they are released, on every way out, exceptions included)
+    struct Uploader { int rc = 0; std::string err; std::thread t; void join() { if (t.joinable()) t.join(); } ~Uploader() { join(); } } upl;
+    // the rest of a file through the host parser (a piece that is not regular 4-line FASTQ, or no boundary found)
+    auto host_rest = [&](const Piece &pc) -> int {
+        PackedReads pr;
+        pr.n_reads = reads_done;
+        if (int rc = count_kept()) return rc;             // (one_batch: what the device parsed so far is a batch of its own now)
+        if (!counted_any) h->pipe->expect_more_batches();
+        if (int rc = host_parse(h, kn, text[pc.file] + pc.off, len[pc.file] - pc.off, pr, Span{(pc.file ? in.n1 : 0) + pc.off, in.total}, 0, file_reads)) return rc;
+        if (int rc = flush_host_batch(h, pr)) return rc;
+        reads_done = pr.n_reads;
+        counted_any = true;
+        return SHK_OK;
+    };
+    for (size_t i = 0; i < pieces.size(); i++) {
+        const Piece pc = pieces[i];
+        if (i == 0 || pieces[i - 1].file != pc.file) file_reads = 0;
+        if (pc.host_rest) {
+            if (!counted_any && i == 0) return DECLINED;
+            if (int rc = host_rest(pc)) return rc;
+            continue;
+        }
+        if (!cur.d)
+            if (int rc = gpu_upload_text(text[pc.file] + pc.off, pc.end - pc.off, device, cur, err)) return fail_rc(h, Rc::DeviceNoParam, rc, err);
+        // the next piece travels while this one is parsed and counted
+        const bool prefetch = i + 1 < pieces.size() && !pieces[i + 1].host_rest;
+        if (prefetch)
+            upl.t = std::thread([&, nx = pieces[i + 1]]() {
+                MemGuard mg(h->mem);                       // (the text block this thread allocates belongs to the handle)
+                try { upl.rc = gpu_upload_text(text[nx.file] + nx.off, nx.end - nx.off, device, nxt, upl.err); }
+                catch (...) { upl.rc = -4; upl.err = "out of host memory (uploader)"; }
+            });
+        Packed gp;
+        const double tp0 = now_ms();
+        int rc = gpu_pack_fastq(nullptr, 0, nullptr, 0, h->k, h->min_qual, h->progress_every(), h->pipe->stream(), gp, err, reads_done, &cur);
+        h->pipe->times().add("fastq_piece_parse_host_clock", now_ms() - tp0);
+        if (rc < 0) return fail_rc(h, Rc::Device, rc, err);
+        if (rc == 1) {
+            gp.reset();
+            upl.join(); cur.reset(); nxt.reset();
+            if (!counted_any) return DECLINED;
+            if (int rc2 = host_rest(Piece{pc.file, pc.off, len[pc.file], true})) return rc2;
+            while (i + 1 < pieces.size() && pieces[i + 1].file == pc.file) i++;      // the rest of this file is done
+            continue;
+        }
+        if (!counted_any && !one_batch) h->pipe->expect_more_batches();
+        h->pipe->times().add("fastq_h2d_text", gp.h2d_ms);
+        h->pipe->times().add("fastq_device_kernels", gp.kernels_ms);
+        h->pipe->times().add("fastq_device_pieces_x1", 1.0);
+        post_device_progress(h, gp, Span{(pc.file ? in.n1 : 0) + pc.off, in.total});
+        reads_done += gp.n_reads; file_reads += gp.n_reads;
+        if (one_batch) kept.push_back(std::move(gp));     // (counted with the other pieces at the end)
+        else {
+            const int rc2 = gp.n_seg ? count_one_batch(h, gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases) : SHK_OK;
+            gp.reset();
+            if (rc2) return rc2;
+        }
+        counted_any = true;
+        // hand over to the uploaded next piece
+        const double tj0 = now_ms();
+        upl.join();
+        h->pipe->times().add("fastq_piece_wait_for_upload_host_clock", now_ms() - tj0);
+        cur.reset();
+        if (prefetch && upl.rc) return fail_rc(h, Rc::DeviceNoParam, upl.rc, upl.err);
+        if (prefetch) cur = std::move(nxt);
+    }
+    h->pipe->times().add("fastq_device_parse_pack_host_clock", now_ms() - t0);
+    if (int rc = count_kept()) return rc;
+    h->n_reads = reads_done;
+    return finish_counting(h);
+}
+
+// Route 3.  The whole text (both files) in one upload and one parse.  Declines when it is not regular 4-line FASTQ.
+int route_device_single(shk_handle *h, const Knobs &, const Input &in) {
+    std::string err;
+    const double t0 = now_ms();
+    Packed gp;
+    const int rc = gpu_pack_fastq(in.t1, in.l1, in.t2, in.l2, h->k, h->min_qual, h->progress_every(), h->pipe->stream(), gp, err);
+    if (rc < 0) return fail_rc(h, Rc::Device, rc, err);
+    if (rc == 1) return DECLINED;
+    h->pipe->times().add("fastq_device_parse_pack_host_clock", now_ms() - t0);
+    h->pipe->times().add("fastq_h2d_text", gp.h2d_ms);
+    h->pipe->times().add("fastq_device_kernels", gp.kernels_ms);
+    post_device_progress(h, gp, Span{0, in.total}, in.n1);
+    h->n_reads = gp.n_reads;
+    return run_counting(h, gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases);
+}
+
+// Route 5.  The host parser (irregular framing, malformed records, SHK_HOST_PARSER=1), batch by batch.
+int route_host(shk_handle *h, const Knobs &kn, const Input &in) {
+    PackedReads pr;
+    if (flush_every_reads(h) || in.text_total() / 2 > kn.batch_bases) h->pipe->expect_more_batches();
+    if (int rc = host_parse(h, kn, in.t1, in.l1, pr, Span{0, in.total}, flush_every_reads(h))) return rc;
+    if (in.fq2) if (int rc = host_parse(h, kn, in.t2, in.l2, pr, Span{in.n1, in.total}, flush_every_reads(h))) return rc;
+    h->n_reads = pr.n_reads;
+    h->pipe->times().add("fastq_parse_pack_host_clock", now_ms() - in.t0);
+    const int rc = flush_host_batch(h, pr);
+    return rc ? rc : finish_counting(h);
+}
+
+}  // namespace
+
+int preprocess_impl(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2) {
+    if (!h) return SHK_E_PARAM;
+    if (h->st != St::Fresh) return fail(h, SHK_E_STATE, "preprocess: handle already used (Assembler.ts:92: one preprocess per handle)");
+    if (!fq1) return fail(h, SHK_E_PARAM, "preprocess: file1 is required");
+    h->post_start();
+    const Knobs kn;
+    Input in{fq1, fq2, n1, n2, n1 + (fq2 ? n2 : 0), now_ms()};
+    const bool device = !kn.host_parser;
+    // .fastq.gz (the reference's real input: fastx_wasm.rs:53-70) of some size is inflated ON THE DEVICE — the compressed
+    // bytes are what crosses PCIe — and its text goes straight to the device parser
+    int rc = device && kn.gunzip_device ? route_device_gzip(h, kn, in) : DECLINED;
+    if (rc != DECLINED) return rc;
+    // whatever the device inflater does not take (several plain members, a broken BGZF chain, binary data, a damaged
+    // stream) is inflated on the host (plain members: one thread per file; BGZF: block-parallel), for either parser
+    std::string err;
+    const uint64_t mt0 = inflate_mt_members();
+    if (int ri = maybe_inflate_pair(fq1, n1, fq2, n2, in.st1, in.st2, in.t1, in.l1, in.t2, in.l2, err)) return fail_rc(h, Rc::Inflater, ri, err);
+    h->pipe->times().add("gunzip_host_clock", now_ms() - in.t0);
+    h->pipe->times().add("gunzip_mt_members_x1", (double)(inflate_mt_members() - mt0));     // members the multi-threaded inflater took
+    const bool one_batch = in.text_total() / 2 <= kn.batch_bases;
+    const bool pipelined = device && one_batch && in.text_total() >= kn.pipeline_min;
+    if (pipelined) rc = route_device_pieces(h, kn, in, true);
+    // (route 2 declines a text that is irregular from the first piece on: route 3 would find the same, so it is skipped)
+    if (rc == DECLINED && device && one_batch && !pipelined) rc = route_device_single(h, kn, in);
+    if (rc == DECLINED && device && !one_batch) rc = route_device_pieces(h, kn, in, false);
+    return rc == DECLINED ? route_host(h, kn, in) : rc;
+}
+
+int push_reads_impl(shk_handle *h, const uint8_t *chunk, size_t n) {
+    if (!h) return SHK_E_PARAM;
+    if (h->st != St::Fresh && h->st != St::Streaming) return fail(h, SHK_E_STATE, "push_reads: handle already preprocessed");
+    if (h->st == St::Fresh) {
+        h->post_start();
+        h->st = St::Streaming;
+    }
+    const Knobs kn;
+    const Span no_pct{0, 0, false};
+    h->pipe->expect_more_batches();                      // the total is unknown while chunks keep coming
+    // a large chunk (whole records, like every chunk) is parsed on the device and counted as a batch of its
+    // own; small chunks — and any chunk the device parser finds irregular — are packed on the host below
+    if (!kn.host_parser && n >= kn.stream_device_min) {
+        std::string err;
+        ByteVec st;
+        const uint8_t *t = nullptr; size_t l = 0;
+        int rc = maybe_inflate(chunk, n, st, t, l, err);
+        if (rc) return fail_rc(h, Rc::Inflater, rc, err);
+        if (l / 2 <= kn.batch_bases) {
+            Packed gp;
+            rc = gpu_pack_fastq(t, l, nullptr, 0, h->k, h->min_qual, h->progress_every(), h->pipe->stream(), gp, err, h->stream_reads.n_reads);
+            if (rc < 0) return fail_rc(h, Rc::Device, rc, err);
+            if (rc == 0) {
+                post_device_progress(h, gp, no_pct);
+                h->pipe->times().add("fastq_device_chunks_x1", 1.0);
+                const int rc2 = gp.n_seg ? count_one_batch(h, gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases) : SHK_OK;
+                h->stream_reads.n_reads += gp.n_reads; h->stream_reads.n_input_bases += gp.n_input_bases;
+                return rc2;
+            }
+            // (rc == 1, not regular 4-line FASTQ: the host parser decides)
+        }
+    }
+    return host_parse(h, kn, chunk, n, h->stream_reads, no_pct, flush_every_reads(h));
+}
+
+int finish_reads_impl(shk_handle *h) {
+    if (!h) return SHK_E_PARAM;
+    if (h->st != St::Streaming) return fail(h, SHK_E_STATE, "finish_reads: no reads pushed");
+    h->n_reads = h->stream_reads.n_reads;
+    int rc = flush_host_batch(h, h->stream_reads);
+    h->stream_reads.clear();
+    return rc ? rc : finish_counting(h);
+}
+
+int preprocess_packed_device_impl(shk_handle *h, const void *d_bases, const void *d_seg_off, uint64_t n_seg,
+                                  uint64_t n_bases, uint64_t n_reads) {
+    if (!h) return SHK_E_PARAM;
+    if (h->st != St::Fresh) return fail(h, SHK_E_STATE, "preprocess: handle already used");
+    if (!d_bases || !d_seg_off) return fail(h, SHK_E_PARAM, "null device pointer");
+    h->post_start();
+    h->n_reads = n_reads;
+    h->post_mode(("loop:" + std::to_string(n_reads) + ":100").c_str());
+    return run_counting(h, (const uint32_t *)d_bases, (const uint32_t *)d_seg_off, n_seg, n_bases);
+}
+
+int preprocess_packed_host_impl(shk_handle *h, const uint32_t *bases, const uint32_t *seg_off, uint64_t n_seg,
+                                uint64_t n_bases, uint64_t n_reads) {
+    if (h->st != St::Fresh) return fail(h, SHK_E_STATE, "preprocess: handle already used");
+    if (!bases || !seg_off) return fail(h, SHK_E_PARAM, "null host pointer");
+    if (n_bases >= 0xFFFFFFFFull || n_seg >= 0xFFFFFFFFull) return fail(h, SHK_E_PARAM, "batch too large (>= 2^32 bases)");
+    std::string err;
+    struct Block { void *p = nullptr; size_t bytes = 0; ~Block() { if (p) device_pool_release(p, bytes); } } db, ds;
+    db.bytes = (size_t)((n_bases + 15) / 16 + 1) * 4; ds.bytes = (size_t)(n_seg + 1) * 4;
+    const size_t want_b = db.bytes, want_s = ds.bytes;
+    db.p = device_pool_alloc(db.bytes); ds.p = device_pool_alloc(ds.bytes);
+    if (!db.p || !ds.p) return fail(h, SHK_E_OOM, "preprocess: device memory for the packed reads");
+    const double t0 = now_ms();
+    void *st = h->pipe->stream();
+    h->post_start();
+    h->n_reads = n_reads;
+    h->post_mode(("loop:" + std::to_string(n_reads) + ":100").c_str());
+    // upload and pass 1 overlap piece by piece (Pipeline::count_batch_host), then histogram / fit / filter as usual
+    h->batches_started++;
+    h->pipe->single_batch_resident(true);
+    int rc = h->pipe->count_batch_host((uint32_t *)db.p, (uint32_t *)ds.p, bases, seg_off, n_seg, n_bases, err);
+    if (rc) rc = fail_rc(h, Rc::Device, rc, err);
+    else rc = finish_counting(h);
+    h->pipe->single_batch_resident(false);
+    { std::string e2; (void)device_stream_sync(st, e2); }      // the blocks go back to the pool idle, also after a failure
+    h->pipe->times().add("h2d_packed_reads_MB", (double)(want_b + want_s) / 1e6);
+    h->pipe->times().add("preprocess_from_host_total_host_clock", now_ms() - t0);
+    return rc;
+}
