@@ -66,6 +66,10 @@ void shk_set_progress_cb(shk_handle *h, shk_progress_cb cb, void *user);
  * first byte to its last, is inflated on the device (a BGZF file one wave per block), a plain member or a BGZF file in any
  * combination within a pair; everything else (several plain members, a broken chain, damaged data) is read on the host,
  * which owns the error messages.  SHK_GUNZIP_DEVICE=0: always on the host.
+ * BGZF input of more text than one batch holds, or of 4 GiB and more a file, is inflated, parsed and counted on the device
+ * window by window: runs of blocks of at most SHK_GUNZIP_DEVICE_WINDOW bytes of text (default 1 GiB, a value not yet chosen from a measured sweep: DESIGN.md §5; where it is set, a
+ * file beyond it goes this way whatever its size), planned from the blocks' trailers before anything is uploaded.  A window
+ * that is damaged or not regular 4-line FASTQ sends the rest of its file to the host reader.
  * The buffers are not retained. */
 int shk_preprocess(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2);
 
@@ -169,6 +173,18 @@ int shk_plan_exchange(const uint64_t *part_records_all, uint32_t world, uint32_t
                       uint64_t *base, uint64_t *send_counts, uint64_t *recv_counts, uint64_t *run_off,
                       uint32_t *run_cnt);
 uint32_t shk_choose_partitions(uint64_t total_instances_ub, uint32_t world, uint32_t key_words);
+/* host-only: the windows shk_preprocess cuts a BGZF chain into that is too large to be inflated at once (exposed for
+ * the CPU tests).  isize[n_blocks]: the blocks' ISIZE fields (0 ... 65536, empty blocks anywhere); budget: bytes of text
+ * per window.  Window w is the blocks first_block[w] ... first_block[w + 1] - 1, the last one ends at n_blocks; every
+ * window holds at most `budget` bytes of text and, unless the file has none, some.  Returns the number of windows (of
+ * which the first `cap` are written), or SHK_E_PARAM when a block alone exceeds the budget. */
+int64_t shk_plan_bgzf_windows(const uint32_t *isize, uint64_t n_blocks, uint64_t budget, uint64_t *first_block, uint64_t cap);
+/* host-only: where such a window is cut — the start of the last FASTQ record of text[0..n) that is known to be one: a
+ * line that begins with '@' and whose line after next begins with '+' (a quality line may begin with '@' too); a line
+ * whose line after next has not begun inside the text is undecided and passed over.  UINT64_MAX: none.
+ * shk_device_last_record_start (needs a GPU): the device kernel that finds the same on the uploaded window. */
+uint64_t shk_host_last_record_start(const uint8_t *text, size_t n);
+int shk_device_last_record_start(const uint8_t *text, size_t n, uint64_t *at);
 
 /* ---- host-side packer (the parser the preprocess entry points use), exposed so a caller can
  * stage packed reads in HBM itself (bench.py, the multi-GPU shard layer). */
@@ -229,7 +245,9 @@ int shk_host_gunzip(const uint8_t *gz, size_t n, uint8_t **out, size_t *out_n, u
  * (bgzip) file of >= 4 MiB (SHK_GUNZIP_DEVICE_MIN) to it first — the compressed bytes are what crosses PCIe; a BGZF file is
  * decoded one wave per block — and reads on the host whatever it does not take.  0: *out (malloc'd, shk_host_free) holds
  * the bytes of the member or of the whole BGZF file, equal to zlib's; 1: not taken, *why (optional) says why; < 0: error.
- * *ms_total (optional): upload + kernels + checks. */
+ * *ms_total (optional): upload + kernels + checks.
+ * Where SHK_GUNZIP_DEVICE_WINDOW is set, or the text of a BGZF file reaches 4 GiB, the file goes through the windows of
+ * shk_preprocess (cut at record starts, the rest carried into the next window) and all its bytes come back. */
 int shk_device_gunzip(const uint8_t *gz, size_t n, uint8_t **out, size_t *out_n, const char **why, double *ms_total);
 /* SPEC S9 (tips, bubbles) and S10 (chains of simple links, the circular cut) on UNITIG records instead of k-mers — what the
  * sharded assembly runs on every rank's host once the k-mer-level contraction is done on the GPUs (csrc/unitig_graph.h:

@@ -50,6 +50,9 @@ SIGNATURES = {
     "shk_shard_preprocess": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u64, _u32]),
     "shk_plan_exchange": (_int, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "shk_choose_partitions": (_u32, [_u64, _u32, _u32]),
+    "shk_plan_bgzf_windows": (C.c_int64, [_vp, _u64, _u64, _vp, _u64]),
+    "shk_host_last_record_start": (_u64, [_cp, _sz]),
+    "shk_device_last_record_start": (_int, [_cp, _sz, C.POINTER(_u64)]),
     "shk_pack_fastq": (_int, [_cp, _sz, _u32, _u32, C.POINTER(ShkPacked), C.POINTER(_cp)]),
     "shk_packed_free": (None, [C.POINTER(ShkPacked)]),
     "shk_key_words": (_u32, [_vp]),

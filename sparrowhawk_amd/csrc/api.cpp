@@ -620,6 +620,24 @@ int shk_plan_exchange(const uint64_t *part_records_all, uint32_t world, uint32_t
         return SHK_OK;
     } catch (...) { return SHK_E_OOM; }
 }
+int64_t shk_plan_bgzf_windows(const uint32_t *isize, uint64_t n_blocks, uint64_t budget, uint64_t *first_block, uint64_t cap) {
+    try {
+        if ((!isize && n_blocks) || (!first_block && cap)) return SHK_E_PARAM;
+        std::vector<uint64_t> first;
+        if (plan_bgzf_windows(isize, (size_t)n_blocks, budget, first)) return SHK_E_PARAM;
+        for (size_t i = 0; i < first.size() && i < cap; i++) first_block[i] = first[i];
+        return (int64_t)first.size();
+    } catch (...) { return SHK_E_OOM; }
+}
+uint64_t shk_host_last_record_start(const uint8_t *text, size_t n) { return (text || !n) ? last_record_start(text, n) : UINT64_MAX; }
+int shk_device_last_record_start(const uint8_t *text, size_t n, uint64_t *at) {
+    try {
+        if ((!text && n) || !at) return SHK_E_PARAM;
+        std::string err;
+        const int rc = gpu_last_record_start(text, n, current_device(), *at, err);
+        return rc ? code_of(Rc::DeviceNoParam, rc) : SHK_OK;
+    } catch (...) { return SHK_E_OOM; }
+}
 uint32_t shk_choose_partitions(uint64_t total_instances_ub, uint32_t world, uint32_t key_words) {
     return choose_partitions(total_instances_ub, world ? world : 1, key_words <= 1 ? 100000 : 40000);
 }
@@ -750,6 +768,50 @@ int shk_device_gunzip(const uint8_t *gz, size_t n, uint8_t **out, size_t *out_n,
         *out = nullptr; *out_n = 0;
         static thread_local std::string msg;
         std::string err;
+        // a BGZF file through the windows of shk_preprocess's route 2: where SHK_GUNZIP_DEVICE_WINDOW is set, or the text
+        // reaches 4 GiB.  Every window is cut at its last record start and its rest carried into the next, as the route does
+        // (text without one, or a carry beyond the room for it: the window is handed on whole); the bytes are all returned.
+        {
+            const char *wv = getenv("SHK_GUNZIP_DEVICE_WINDOW");
+            size_t bs = 0;
+            BgzfChain chain; const char *why_not = "";
+            if (n >= 18 && bgzf_block(gz, n, bs) && bgzf_walk(gz, n, chain, why_not) == 0 && chain.text && ((wv && *wv) || chain.text >= (1ull << 32))) {
+                const uint64_t W = std::max<uint64_t>(std::min<uint64_t>((wv && *wv) ? strtoull(wv, nullptr, 10) : (1ull << 30), 3ull << 30), 65536);
+                auto say = [&](const std::string &m) { if (why) { msg = m; *why = msg.c_str(); } };
+                if (bgzf_cut_windows(chain, W)) return SHK_E_INTERNAL;
+                const double t0 = now_ms();
+                uint8_t *o = (uint8_t *)malloc((size_t)chain.text);
+                if (!o) return SHK_E_OOM;
+                struct Free { uint8_t *&p; ~Free() { free(p); } } guard{o};
+                BgzfWindows bw;
+                int rc = bw.open(gz, &chain, current_device(), nullptr, err);
+                if (rc == 1) { say("out of device memory"); return 1; }
+                if (rc) { say(err); return code_of(Rc::DeviceNoParam, rc); }
+                uint64_t carry = 0, done = 0;
+                for (size_t w = 0; w < chain.windows.size(); w++) {
+                    const char *wn = "";
+                    if ((rc = bw.upload(w, err))) { say(err); return code_of(Rc::DeviceNoParam, rc); }
+                    rc = bw.inflate(w, carry, wn, err);
+                    if (rc == 1) { say(wn); return 1; }
+                    if (rc) { say(err); return code_of(Rc::DeviceNoParam, rc); }
+                    const uint64_t nn = carry + chain.windows[w].text;
+                    uint64_t cut = nn;
+                    if (w + 1 < chain.windows.size()) {
+                        if ((rc = bw.last_start(w, nn, cut, err))) { say(err); return code_of(Rc::DeviceNoParam, rc); }
+                        if (cut == UINT64_MAX || nn - cut > BgzfWindows::CARRY_MAX) cut = nn;
+                    }
+                    // (down first: carry_over puts the parser's zero bytes behind the cut)
+                    if (cut) if (device_download(o + done, bw.text(w), (size_t)cut, err)) { say(err); return SHK_E_DEVICE; }
+                    if (w + 1 < chain.windows.size()) if ((rc = bw.carry_over(w, cut, nn, err))) { say(err); return code_of(Rc::DeviceNoParam, rc); }
+                    done += cut; carry = nn - cut;
+                }
+                if (done != chain.text) { say("the windows do not add up"); return SHK_E_INTERNAL; }
+                if (ms_total) *ms_total = now_ms() - t0;
+                if (why) { msg.clear(); *why = msg.c_str(); }
+                *out = o; *out_n = (size_t)done; o = nullptr;
+                return SHK_OK;
+            }
+        }
         GpuText text; GpuInflateStats st;
         const int rc = gpu_inflate_member(gz, n, current_device(), nullptr, text, err, &st, true);
         if (why) { msg = rc == 1 ? st.why_not : err; *why = msg.c_str(); }

@@ -155,6 +155,32 @@ bool bgzf_block(const uint8_t *b, size_t n, size_t &bsize) {
     return false;
 }
 
+int plan_bgzf_windows(const uint32_t *isize, size_t n_blocks, uint64_t budget, std::vector<uint64_t> &first) {
+    first.clear();
+    uint64_t sum = 0;
+    for (size_t i = 0; i < n_blocks; i++) {
+        if (isize[i] > budget) return -1;
+        if (first.empty() || sum + isize[i] > budget) { first.push_back(i); sum = 0; }      // (an empty block never opens a window but the first)
+        sum += isize[i];
+    }
+    return 0;
+}
+
+uint64_t last_record_start(const uint8_t *t, size_t n) {
+    // line starts from the back; s1 / s2: the starts of the next line and of the line after next (n: not inside t)
+    size_t s1 = n, s2 = n;
+    for (size_t q = n; ; ) {
+        const void *nl = q ? memrchr(t, '\n', q) : nullptr;
+        const size_t p = nl ? (size_t)((const uint8_t *)nl - t) + 1 : 0;
+        if (p < n) {
+            if (s2 < n && t[p] == '@' && t[s2] == '+') return p;
+            s2 = s1; s1 = p;
+        }
+        if (!nl) return UINT64_MAX;
+        q = p - 1;
+    }
+}
+
 static int inflate_bgzf(const uint8_t *in, size_t n, ByteVec &out, std::string &err, bool &is_bgzf) {
     struct Blk { size_t in_off, in_len, out_off, out_len, hdr; };
     std::vector<Blk> blocks;

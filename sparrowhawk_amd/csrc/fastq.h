@@ -40,6 +40,17 @@ int pack_fastq(const uint8_t *buf, size_t n, uint32_t k, uint32_t min_qual, Pack
 // b[0..n) starts with a whole BGZF block (SAM spec 4.1: a gzip member with a 'BC' extra subfield that holds its size - 1):
 // bsize = that size.  The one rule by which both the host reader and the device inflater (inflate_gpu.hip) walk a chain.
 bool bgzf_block(const uint8_t *b, size_t n, size_t &bsize);
+// The windows of a BGZF chain (preprocess.cpp, route 2): runs of consecutive blocks whose text (the sum of their ISIZE
+// fields) is at most `budget` bytes.  first[w] = the first block of window w; window w ends where window w + 1 begins, the
+// last one at n_blocks.  Every block lies in exactly one window and no window is without text, unless the file has none
+// (then there is one window, or none for a file of no blocks).  Empty blocks ride with the window in front of them.
+// Returns 0, or -1 when a block alone exceeds the budget.
+int plan_bgzf_windows(const uint32_t *isize, size_t n_blocks, uint64_t budget, std::vector<uint64_t> &first);
+// Where the last FASTQ record of t[0..n) starts that is known to be one: a line that begins with '@' and whose line after
+// next begins with '+' (the rule of next_record_start in preprocess.cpp; a quality line may begin with '@', but its line
+// after next is a sequence).  A line whose line after next has not begun inside t is undecided and is passed over.  Byte 0
+// begins a line.  UINT64_MAX: no such line.  The device states the same rule in k_last_record_start (inflate_gpu.hip).
+uint64_t last_record_start(const uint8_t *t, size_t n);
 // gzip sniff (1F 8B) + multi-member inflate; plain input is passed through (p/n point at buf or at `storage`)
 int maybe_inflate(const uint8_t *buf, size_t n, ByteVec &storage, const uint8_t *&p, size_t &pn,
                   std::string &err);

@@ -2,10 +2,13 @@
 // are what crosses PCIe, the FASTQ text is born in HBM and goes straight to the device parser (fastq_gpu.h).  A plain
 // member: the same two-pass scheme as the host reader (inflate_mt.cpp, after pugz / rapidgzip) with thousands of chunks
 // instead of one per host thread.  A BGZF file: one wave per block, no speculation (every block is a stream of its own).
+// A BGZF file of more text than is inflated at once goes window by window (BgzfWindows below): the same two kernels on a run
+// of blocks at a time, and k_last_record_start to cut the window's text where its last whole record ends.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 #include <string>
+#include <vector>
 #include "fastq_gpu.h"
 
 namespace shk {
@@ -29,7 +32,65 @@ struct GpuInflateStats {
 //  <0  -4 out of device memory (a plain member), -5 HIP error.
 // raw: every byte of the member stays as it is (out.e = the member's size; the tests compare with zlib) — otherwise the text
 // is made ready for the parser (trailing blank lines cut, see above).
+struct BgzfChain;
+// walked: the file's chain as bgzf_walk (below) has walked it already, or null
 int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, GpuText &out, std::string &err,
-                       GpuInflateStats *stats = nullptr, bool raw = false);
+                       GpuInflateStats *stats = nullptr, bool raw = false, const BgzfChain *walked = nullptr);
+
+// ---- a BGZF file of any size, window by window ------------------------------------------------------------------------
+// The chain is walked on the host before a byte crosses PCIe (every block's ISIZE stands in its trailer), cut into windows
+// of consecutive blocks whose text fits a budget (fastq.h: plan_bgzf_windows), and each window is uploaded, inflated by
+// k_bgzf_decode / k_bgzf_crc with window-relative descriptors, and cut at its last record start on the device.
+struct BgzfChain {
+    struct Block { uint64_t in_off; uint32_t bsize, hdr, isize, crc; };      // in_off: of the block's header in the file
+    struct Window { size_t b0, b1; uint64_t in_off, in_end, text, text_before; uint32_t nonempty; };
+    std::vector<Block> blocks;
+    std::vector<Window> windows;
+    uint64_t text = 0, nonempty = 0;      // bytes of text / non-empty blocks of the whole file
+};
+// Walks gz[0..n) as gpu_inflate_member walks a BGZF file (bgzf_block, FLG == 4, ISIZE <= 65536, empty blocks checked by zlib).
+// 0: out.blocks, out.text, out.nonempty are set; 1: not a complete chain of such blocks, or smaller than SHK_GUNZIP_DEVICE_MIN
+// (*why).  Host only.
+int bgzf_walk(const uint8_t *gz, size_t n, BgzfChain &out, const char *&why);
+// out.windows from out.blocks; -1: a block exceeds the budget
+int bgzf_cut_windows(BgzfChain &c, uint64_t budget);
+
+// The device side of one file's windows: two input buffers (window i + 1 is uploaded, from a helper thread, while window i
+// is worked on) and two text buffers (window i's text starts with the carry: the partial record left over from window i - 1).
+class BgzfWindows {
+  public:
+    static const uint64_t CARRY_MAX = 16ull << 20;        // a partial record of more than this goes to the host reader
+    BgzfWindows();
+    ~BgzfWindows();
+    BgzfWindows(const BgzfWindows &) = delete;
+    BgzfWindows &operator=(const BgzfWindows &) = delete;
+    // 0; 1 out of device memory (nothing is held); -5
+    int open(const uint8_t *gz, const BgzfChain *chain, int device, void *stream, std::string &err);
+    void close();
+    // window w's compressed bytes -> its input buffer; blocking, on a stream of its own (callable from a helper thread)
+    int upload(size_t w, std::string &err);
+    // window w (uploaded) -> text(w)[carry, carry + windows[w].text).  0; 1 a damaged block (*why); -5
+    int inflate(size_t w, uint64_t carry, const char *&why, std::string &err);
+    // last_record_start (fastq.h) of text(w)[0..n), on the device; UINT64_MAX: none in the last CARRY_MAX bytes and a step (a
+    // start further front leaves more to carry than there is room for: the caller gives the window to the host either way)
+    int last_start(size_t w, uint64_t n, uint64_t &at, std::string &err);
+    // the end of a file's text, text(w)[0..n): e = n without trailing blank lines (the rule of gpu_upload_text).  0; 1: more
+    // blank lines than are looked at
+    int trim_end(size_t w, uint64_t n, uint64_t &e, bool &unterminated, std::string &err);
+    // text(w)[cut, n) -> the front of text(w + 1); only then the 32 zero bytes the parser wants behind text(w)[0..cut)
+    int carry_over(size_t w, uint64_t cut, uint64_t n, std::string &err);
+    uint8_t *text(size_t w) const { return d_text_[w & 1]; }
+    double h2d_ms = 0, decode_ms = 0;                      // summed over the windows
+  private:
+    const uint8_t *gz_ = nullptr; const BgzfChain *chain_ = nullptr;
+    int device_ = 0; void *st_ = nullptr;
+    uint8_t *d_in_[2] = {nullptr, nullptr}, *d_text_[2] = {nullptr, nullptr};
+    void *d_desc_ = nullptr, *d_status_ = nullptr, *d_bad_ = nullptr;
+    size_t in_bytes_[2] = {0, 0}, text_bytes_[2] = {0, 0}, desc_bytes_ = 0, status_bytes_ = 0, bad_bytes_ = 0;      // as the pool handed them out, block by block
+    double up_ms_[2] = {0, 0};
+};
+
+// k_last_record_start alone on n bytes of host text (the tests compare it with last_record_start)
+int gpu_last_record_start(const uint8_t *t, size_t n, int device, uint64_t &at, std::string &err);
 
 }  // namespace shk

@@ -27,6 +27,8 @@
 //                      4 KiB ring in LDS, straight into the final text at the block's offset (the prefix sum of the lengths);
 //                      nothing is produced or stored beyond the block's length, whatever its stream says
 //   k_bgzf_crc         CRC-32 of every block's text against its trailer; one word comes back, not a checksum per block
+//   k_last_record_start  a BGZF file window by window (BgzfWindows): where the last whole FASTQ record of a window's text ends —
+//                      one wave walks the text's tail from the back, a ballot over the newlines of 64 bytes per step
 // Everything that does not look as expected makes gpu_inflate_member return 1 and the caller inflates on the host: the
 // bytes handed on are always the bytes zlib would produce (CRC-32 and ISIZE of the trailer are checked here too).
 #include <hip/hip_runtime.h>
@@ -37,6 +39,7 @@
 #include <string.h>
 #include <algorithm>
 #include <chrono>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -726,6 +729,36 @@ __global__ __launch_bounds__(64) void k_bgzf_crc(const uint8_t *__restrict__ tex
     if ((crc ^ 0xFFFFFFFFu) != d.crc) atomicMin(&bad[1], blk);
 }
 
+// Where the last record of text[0..n) starts that is known to be one — the rule of last_record_start (fastq.cpp), which this
+// kernel must agree with byte for byte: a line that begins with '@' and whose line after next begins with '+'; a line whose
+// line after next has not begun inside the text is undecided.  One wave walks the tail [from, n) from the back, 64 bytes a
+// step: a ballot over the newlines of the step, its bits taken from the top (all of it wave-uniform).  `from` begins a line
+// only where it is 0.  out[0] = the start, or ~0 (the host then widens the tail).
+__global__ __launch_bounds__(64) void k_last_record_start(const uint8_t *__restrict__ text, unsigned long long n, unsigned long long from,
+                                                         unsigned long long *__restrict__ out) {
+    const uint32_t lane = threadIdx.x;
+    unsigned long long s1 = n, s2 = n, found = ~0ull;      // the starts of the next line and of the line after next (n: none)
+    auto line = [&](unsigned long long p) -> bool {        // a line starts at p < n
+        if (s2 < n && text[p] == '@' && text[s2] == '+') { found = p; return true; }
+        s2 = s1; s1 = p;
+        return false;
+    };
+    for (unsigned long long hi = n; hi > from && found == ~0ull;) {
+        const unsigned long long lo = hi - from > 64ull ? hi - 64ull : from;
+        const unsigned long long at = lo + lane;
+        unsigned long long m = __ballot(at < hi && text[at] == '\n');
+        while (m) {
+            const int b = 63 - __clzll((long long)m);
+            m &= ~(1ull << b);
+            const unsigned long long p = lo + (unsigned)b + 1ull;
+            if (p < n && line(p)) break;
+        }
+        hi = lo;
+    }
+    if (found == ~0ull && from == 0 && n > 0) (void)line(0);
+    if (lane == 0) out[0] = found;
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 // CRC-32 of A || B from crc(A), crc(B): crc(A) advanced over len(B) zero bytes (a GF(2) matrix), XOR crc(B).  The slices
 // have one length, so the matrix is built once (zlib 1.2.11 has no crc32_combine_gen).
@@ -787,39 +820,24 @@ int hand_on_text(Blk &d_text, uint64_t total, const char *tail, size_t tail_n, b
 // gz[0..n) starts with a BGZF block.  Taken only if every byte of the file belongs to the chain of blocks (what follows a
 // first BGZF block may be anything: the host reader owns "BGZF block chain broken" and its kin); same results as
 // gpu_inflate_member, except that running out of device memory is "not taken" too: the host reader reads these files.
-int gpu_inflate_bgzf(const uint8_t *gz, size_t n, int device, hipStream_t st, GpuText &out, std::string &err, GpuInflateStats &S, bool raw) {
+int gpu_inflate_bgzf(const uint8_t *gz, size_t n, int device, hipStream_t st, GpuText &out, std::string &err, GpuInflateStats &S, bool raw, const BgzfChain *walked) {
     auto not_taken = [&](const char *why) { S.why_not = why; return 1; };
-    const char *mv = getenv("SHK_GUNZIP_DEVICE_MIN");
-    const size_t min_bytes = (mv && *mv) ? (size_t)strtoull(mv, nullptr, 10) : ((size_t)4 << 20);
-    if (n < min_bytes) return not_taken("small file");
     if (n >= ((size_t)1 << 34)) return not_taken("beyond 16 GiB");      // (UBits counts the input in 32-bit dwords)
     // ---- the chain: one descriptor per non-empty block
+    BgzfChain own;
+    const char *why_chain = "";
+    if (!walked && bgzf_walk(gz, n, own, why_chain)) return not_taken(why_chain);
+    const BgzfChain &chain = walked ? *walked : own;
+    const uint64_t total = chain.text;
+    if (total >= ((uint64_t)1 << 32)) return not_taken("empty or beyond 4 GiB");
     std::vector<BgzfDesc> desc;
-    uint64_t total = 0;
-    for (size_t p = 0; p < n;) {
-        size_t bs = 0;
-        if (!bgzf_block(gz + p, n - p, bs)) return not_taken("BGZF block chain broken");
-        if (gz[p + 3] != 4) return not_taken("a BGZF block with more than the extra field");      // (FNAME, FCOMMENT, FHCRC: bgzip writes none)
-        const size_t hdr = 12 + (gz[p + 10] | ((size_t)gz[p + 11] << 8));
-        const uint8_t *t = gz + p + bs - 8;
-        const uint32_t crc = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-        const uint32_t isize = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
-        if (isize > 65536) return not_taken("a BGZF block of more than 64 KiB");
-        if (isize) desc.push_back(BgzfDesc{(unsigned long long)(p + hdr), (uint32_t)(bs - hdr - 8), (uint32_t)total, isize, crc});
-        else {
-            // an empty block (the end-of-file marker, also in mid-file) gets no wave: a few bytes for zlib
-            uint8_t sink[8];
-            z_stream zs; memset(&zs, 0, sizeof zs);
-            if (inflateInit2(&zs, -15) != Z_OK) return not_taken("zlib init failed");
-            zs.next_in = (Bytef *)(gz + p + hdr); zs.avail_in = (uInt)(bs - hdr - 8);
-            zs.next_out = sink; zs.avail_out = sizeof sink;
-            const int rc = inflate(&zs, Z_FINISH);
-            const bool ok = rc == Z_STREAM_END && zs.avail_out == sizeof sink && zs.avail_in == 0;
-            inflateEnd(&zs);
-            if (!ok || crc != 0) return not_taken("a damaged empty BGZF block");
+    desc.reserve((size_t)chain.nonempty);
+    {
+        uint64_t at = 0;
+        for (const BgzfChain::Block &b : chain.blocks) {
+            if (b.isize) desc.push_back(BgzfDesc{(unsigned long long)(b.in_off + b.hdr), b.bsize - b.hdr - 8, (uint32_t)at, b.isize, b.crc});
+            at += b.isize;
         }
-        total += isize; p += bs;
-        if (total >= ((uint64_t)1 << 32)) return not_taken("empty or beyond 4 GiB");
     }
     if (total == 0) return not_taken("empty or beyond 4 GiB");
     const uint32_t nb = (uint32_t)desc.size();
@@ -872,7 +890,7 @@ int gpu_inflate_bgzf(const uint8_t *gz, size_t n, int device, hipStream_t st, Gp
 }
 }  // namespace
 
-int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, GpuText &out, std::string &err, GpuInflateStats *stats, bool raw) {
+int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, GpuText &out, std::string &err, GpuInflateStats *stats, bool raw, const BgzfChain *walked) {
     GpuInflateStats local; GpuInflateStats &S = stats ? *stats : local;
     S = GpuInflateStats();
     out = GpuText();
@@ -887,7 +905,7 @@ int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, Gp
         const size_t xlen = gz[p] | ((size_t)gz[p + 1] << 8);
         // (BGZF: a 'BC' subfield — many small members, one wave each)
         size_t bs = 0;
-        if (bgzf_block(gz, n, bs)) return gpu_inflate_bgzf(gz, n, device, (hipStream_t)stream, out, err, S, raw);
+        if (bgzf_block(gz, n, bs)) return gpu_inflate_bgzf(gz, n, device, (hipStream_t)stream, out, err, S, raw, walked);
         if (xlen >= 6 && p + 2 + xlen <= n && gz[p + 2] == 'B' && gz[p + 3] == 'C') return not_taken("BGZF");      // (a first block cut short)
         p += 2 + xlen;
     }
@@ -1026,6 +1044,220 @@ int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, Gp
         fprintf(stderr, "[inflate_gpu] %u chunks (%u cuts): upload %.2f ms, block starts %.2f, decode %.2f, windows (%.2f) + resolve + crc %.2f, total %.2f ms for %.3f GB of text\n",
                 C, C0, S.h2d_ms, S.search_ms, S.decode_ms, S.windows_ms, S.resolve_ms, S.total_ms, (double)total / 1e9);
     return 0;
+}
+
+// ---- a BGZF file window by window (inflate_gpu.h) -----------------------------------------------------------------------
+int bgzf_walk(const uint8_t *gz, size_t n, BgzfChain &out, const char *&why) {
+    out = BgzfChain();
+    const char *mv = getenv("SHK_GUNZIP_DEVICE_MIN");
+    const size_t min_bytes = (mv && *mv) ? (size_t)strtoull(mv, nullptr, 10) : ((size_t)4 << 20);
+    if (n < min_bytes) { why = "small file"; return 1; }
+    for (size_t p = 0; p < n;) {
+        size_t bs = 0;
+        if (!bgzf_block(gz + p, n - p, bs)) { why = "BGZF block chain broken"; return 1; }
+        if (gz[p + 3] != 4) { why = "a BGZF block with more than the extra field"; return 1; }      // (FNAME, FCOMMENT, FHCRC: bgzip writes none)
+        const size_t hdr = 12 + (gz[p + 10] | ((size_t)gz[p + 11] << 8));
+        const uint8_t *t = gz + p + bs - 8;
+        const uint32_t crc = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+        const uint32_t isize = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+        if (isize > 65536) { why = "a BGZF block of more than 64 KiB"; return 1; }
+        if (!isize) {
+            // an empty block (the end-of-file marker, also in mid-file) gets no wave: a few bytes for zlib
+            uint8_t sink[8];
+            z_stream zs; memset(&zs, 0, sizeof zs);
+            if (inflateInit2(&zs, -15) != Z_OK) { why = "zlib init failed"; return 1; }
+            zs.next_in = (Bytef *)(gz + p + hdr); zs.avail_in = (uInt)(bs - hdr - 8);
+            zs.next_out = sink; zs.avail_out = sizeof sink;
+            const int rc = inflate(&zs, Z_FINISH);
+            const bool ok = rc == Z_STREAM_END && zs.avail_out == sizeof sink && zs.avail_in == 0;
+            inflateEnd(&zs);
+            if (!ok || crc != 0) { why = "a damaged empty BGZF block"; return 1; }
+        } else out.nonempty++;
+        out.blocks.push_back(BgzfChain::Block{(uint64_t)p, (uint32_t)bs, (uint32_t)hdr, isize, crc});
+        out.text += isize; p += bs;
+    }
+    return 0;
+}
+
+int bgzf_cut_windows(BgzfChain &c, uint64_t budget) {
+    std::vector<uint32_t> isize(c.blocks.size());
+    for (size_t i = 0; i < c.blocks.size(); i++) isize[i] = c.blocks[i].isize;
+    std::vector<uint64_t> first;
+    c.windows.clear();
+    if (plan_bgzf_windows(isize.data(), isize.size(), budget, first)) return -1;
+    uint64_t before = 0;
+    for (size_t w = 0; w < first.size(); w++) {
+        BgzfChain::Window win{(size_t)first[w], w + 1 < first.size() ? (size_t)first[w + 1] : c.blocks.size(), 0, 0, 0, before, 0};
+        win.in_off = c.blocks[win.b0].in_off;
+        win.in_end = c.blocks[win.b1 - 1].in_off + c.blocks[win.b1 - 1].bsize;
+        for (size_t b = win.b0; b < win.b1; b++) { win.text += c.blocks[b].isize; win.nonempty += c.blocks[b].isize != 0; }
+        before += win.text;
+        c.windows.push_back(win);
+    }
+    return 0;
+}
+
+namespace {
+// one upload stream per device for the windows' compressed bytes, kept for the process (as gpu_upload_text keeps its own)
+hipError_t window_upload_stream(int device, hipStream_t &s) {
+    static std::mutex mu;
+    static hipStream_t streams[64] = {};
+    std::lock_guard<std::mutex> lk(mu);
+    const int di = device >= 0 && device < 64 ? device : 0;
+    hipError_t e = hipSuccess;
+    if (!streams[di]) e = hipStreamCreateWithFlags(&streams[di], hipStreamNonBlocking);
+    s = streams[di];
+    return e;
+}
+const size_t WIN_IN_PAD = (2048 + 256) * 4 + 8;           // zero bytes behind a window's input (see gpu_inflate_member)
+
+// the last record start of d_text[0..n): the tail of 1 MiB first, a wider one while nothing is found — up to max_tail bytes
+// (one wave walks it: the windows' caller has no use for a start further front than it can carry)
+int device_last_start(const uint8_t *d_text, uint64_t n, unsigned long long *d_out, hipStream_t st, uint64_t &at, std::string &err, uint64_t max_tail = UINT64_MAX) {
+    at = UINT64_MAX;
+    for (uint64_t tail = std::min<uint64_t>(1ull << 20, max_tail);; tail = tail > max_tail / 16 ? max_tail : tail * 16) {
+        const uint64_t from = n > tail ? n - tail : 0;
+        hipLaunchKernelGGL(k_last_record_start, dim3(1), dim3(64), 0, st, d_text, (unsigned long long)n, (unsigned long long)from, d_out);
+        GZCHK(hipGetLastError());
+        unsigned long long got = 0;
+        GZCHK(hipMemcpyAsync(&got, d_out, 8, hipMemcpyDeviceToHost, st));
+        GZCHK(hipStreamSynchronize(st));
+        if (got != ~0ull) { at = got; return 0; }
+        if (from == 0 || tail >= max_tail) return 0;
+    }
+}
+}  // namespace
+
+BgzfWindows::BgzfWindows() {}
+BgzfWindows::~BgzfWindows() { close(); }
+void BgzfWindows::close() {
+    if (st_ || d_in_[0]) (void)hipStreamSynchronize((hipStream_t)st_);      // the blocks go back to the pool idle
+    for (int i = 0; i < 2; i++) {
+        if (d_in_[i]) device_pool_release(d_in_[i], in_bytes_[i]);
+        if (d_text_[i]) device_pool_release(d_text_[i], text_bytes_[i]);
+        d_in_[i] = d_text_[i] = nullptr;
+    }
+    if (d_desc_) device_pool_release(d_desc_, desc_bytes_);
+    if (d_status_) device_pool_release(d_status_, status_bytes_);
+    if (d_bad_) device_pool_release(d_bad_, bad_bytes_);
+    d_desc_ = d_status_ = d_bad_ = nullptr;
+}
+
+int BgzfWindows::open(const uint8_t *gz, const BgzfChain *chain, int device, void *stream, std::string &err) {
+    close();
+    gz_ = gz; chain_ = chain; device_ = device; st_ = stream;
+    h2d_ms = decode_ms = 0;
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); err = "hipSetDevice failed"; return -5; }
+    uint64_t max_in = 0, max_text = 0; uint32_t max_nb = 1;
+    for (const BgzfChain::Window &w : chain->windows) {
+        max_in = std::max(max_in, w.in_end - w.in_off); max_text = std::max(max_text, w.text); max_nb = std::max(max_nb, w.nonempty);
+    }
+    const size_t in_bytes = (size_t)((max_in + 3) & ~3ull) + WIN_IN_PAD, text_bytes = (size_t)(CARRY_MAX + max_text + 64);
+    desc_bytes_ = (size_t)max_nb * sizeof(BgzfDesc); status_bytes_ = (size_t)max_nb * 4; bad_bytes_ = 64;
+    const bool two = chain->windows.size() > 1;
+    bool ok = true;
+    // (the pool rounds a size up, or hands out a cached block that is larger: every block keeps the size it came with)
+    for (int i = 0; i < (two ? 2 : 1) && ok; i++) {
+        in_bytes_[i] = in_bytes; d_in_[i] = (uint8_t *)device_pool_alloc(in_bytes_[i]);
+        text_bytes_[i] = text_bytes; d_text_[i] = (uint8_t *)device_pool_alloc(text_bytes_[i]);
+        ok = d_in_[i] && d_text_[i];
+    }
+    if (ok) { d_desc_ = device_pool_alloc(desc_bytes_); d_status_ = device_pool_alloc(status_bytes_); d_bad_ = device_pool_alloc(bad_bytes_); }
+    if (!ok || !d_desc_ || !d_status_ || !d_bad_) { close(); return 1; }
+    return 0;
+}
+
+int BgzfWindows::upload(size_t w, std::string &err) {
+    if (hipSetDevice(device_) != hipSuccess) { (void)hipGetLastError(); err = "hipSetDevice failed"; return -5; }
+    const BgzfChain::Window &win = chain_->windows[w];
+    const size_t n = (size_t)(win.in_end - win.in_off);
+    uint8_t *d = d_in_[w & 1];
+    hipStream_t s = nullptr;
+    const double t0 = now_ms();
+    hipError_t e = window_upload_stream(device_, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d + (n & ~(size_t)3), 0, ((n + 3) & ~(size_t)3) - (n & ~(size_t)3) + WIN_IN_PAD, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, gz_ + win.in_off, n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    up_ms_[w & 1] = now_ms() - t0;
+    if (e != hipSuccess) { err = std::string("upload of a BGZF window: ") + hipGetErrorString(e); return -5; }
+    return 0;
+}
+
+int BgzfWindows::inflate(size_t w, uint64_t carry, const char *&why, std::string &err) {
+    hipStream_t st = (hipStream_t)st_;
+    const BgzfChain::Window &win = chain_->windows[w];
+    h2d_ms += up_ms_[w & 1]; up_ms_[w & 1] = 0;
+    if (!win.nonempty) return 0;
+    if (carry > CARRY_MAX) { why = "a partial record beyond the room for it"; return 1; }
+    // descriptors relative to the window: the input from its first byte, the text from the buffer's (the carry lies in front)
+    std::vector<BgzfDesc> desc;
+    desc.reserve(win.nonempty);
+    uint64_t at = carry;
+    for (size_t b = win.b0; b < win.b1; b++) {
+        const BgzfChain::Block &k = chain_->blocks[b];
+        if (k.isize) desc.push_back(BgzfDesc{(unsigned long long)(k.in_off - win.in_off + k.hdr), k.bsize - k.hdr - 8, (uint32_t)at, k.isize, k.crc});
+        at += k.isize;
+    }
+    const uint32_t nb = (uint32_t)desc.size();
+    uint8_t *d_text = d_text_[w & 1];
+    const double t1 = now_ms();
+    GZCHK(hipMemcpyAsync(d_desc_, desc.data(), (size_t)nb * sizeof(BgzfDesc), hipMemcpyHostToDevice, st));
+    GZCHK(hipMemsetAsync(d_bad_, 0xFF, 64, st));
+    hipLaunchKernelGGL(k_bgzf_decode, dim3(nb), dim3(64), 0, st, (const uint32_t *)d_in_[w & 1], (const BgzfDesc *)d_desc_, nb, d_text,
+                       (uint32_t *)d_status_, (uint32_t *)d_bad_);
+    GZCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_bgzf_crc, dim3((nb + 63) / 64), dim3(64), 0, st, (const uint8_t *)d_text, (const BgzfDesc *)d_desc_, nb, (uint32_t *)d_bad_);
+    GZCHK(hipGetLastError());
+    uint32_t h_bad[2] = {0, 0};
+    GZCHK(hipMemcpyAsync(h_bad, d_bad_, 8, hipMemcpyDeviceToHost, st));
+    GZCHK(hipStreamSynchronize(st));                        // (desc is read by the copy until here)
+    decode_ms += now_ms() - t1;
+    if (h_bad[0] != 0xFFFFFFFFu) { why = "a damaged BGZF block"; return 1; }
+    if (h_bad[1] != 0xFFFFFFFFu) { why = "CRC-32 mismatch"; return 1; }
+    return 0;
+}
+
+int BgzfWindows::last_start(size_t w, uint64_t n, uint64_t &at, std::string &err) {
+    return device_last_start(d_text_[w & 1], n, (unsigned long long *)d_bad_ + 4, (hipStream_t)st_, at, err, CARRY_MAX + 64);
+}
+
+int BgzfWindows::trim_end(size_t w, uint64_t n, uint64_t &e, bool &unterminated, std::string &err) {
+    hipStream_t st = (hipStream_t)st_;
+    char tail[4096];
+    const size_t tail_n = (size_t)std::min<uint64_t>(n, sizeof tail);
+    if (tail_n) GZCHK(hipMemcpyAsync(tail, d_text_[w & 1] + (n - tail_n), tail_n, hipMemcpyDeviceToHost, st));
+    GZCHK(hipStreamSynchronize(st));
+    size_t te = tail_n;                                     // (hand_on_text's rule)
+    for (;;) {
+        if (te >= 2 && tail[te - 1] == '\n' && tail[te - 2] == '\n') { te -= 1; continue; }
+        if (te >= 3 && tail[te - 1] == '\n' && tail[te - 2] == '\r' && tail[te - 3] == '\n') { te -= 2; continue; }
+        break;
+    }
+    if (te < 8 && n > tail_n) return 1;
+    e = (n - tail_n) + te;
+    unterminated = te == 0 || tail[te - 1] != '\n';
+    GZCHK(hipMemsetAsync(d_text_[w & 1] + e, 0, 32, st));
+    GZCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int BgzfWindows::carry_over(size_t w, uint64_t cut, uint64_t n, std::string &err) {
+    hipStream_t st = (hipStream_t)st_;
+    if (n > cut) GZCHK(hipMemcpyAsync(d_text_[(w + 1) & 1], d_text_[w & 1] + cut, (size_t)(n - cut), hipMemcpyDeviceToDevice, st));
+    GZCHK(hipMemsetAsync(d_text_[w & 1] + cut, 0, 32, st));
+    GZCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int gpu_last_record_start(const uint8_t *t, size_t n, int device, uint64_t &at, std::string &err) {
+    hipStream_t st = nullptr;
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); err = "hipSetDevice failed"; return -5; }
+    Blk d_text, d_out;
+    if (!d_text.get(n + 64) || !d_out.get(64)) { err = "out of device memory"; return -4; }
+    if (n) GZCHK(hipMemcpyAsync(d_text.p, t, n, hipMemcpyHostToDevice, st));
+    const int rc = device_last_start((const uint8_t *)d_text.p, n, (unsigned long long *)d_out.p, st, at, err);
+    (void)hipStreamSynchronize(st);
+    return rc;
 }
 
 }  // namespace shk

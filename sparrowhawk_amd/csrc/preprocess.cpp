@@ -3,13 +3,19 @@
 //   1 route_device_gzip          every file starts with the gzip magic, SHK_GUNZIP_DEVICE != 0, SHK_HOST_PARSER != 1: device
 //                                inflater (a plain member or a BGZF file) -> device parser -> one batch.  Declines when the
 //                                inflater or the parser declines or the text exceeds one batch.
+//   2 route_device_bgzf_windows  the same switches; every file is a BGZF chain from its first byte to its last whose text (the
+//                                sum of the blocks' ISIZE fields, known before anything is uploaded) is more than route 1
+//                                takes: beyond one batch, a file of 4 GiB or more, or beyond SHK_GUNZIP_DEVICE_WINDOW where
+//                                that is set.  Window by window: upload, inflate, cut at the last record start, parse, one
+//                                batch each.  The size is looked at FIRST, so such a file never enters route 1; a decline
+//                                (window 0 damaged or not regular) goes on below.
 //     (what is gzip is inflated on the host here, once, for the routes below)
-//   2 route_device_pieces(one)   the text fits one batch and is >= SHK_FASTQ_PIPELINE_MIN (64 MiB): cut into a few pieces,
+//   3 route_device_pieces(one)   the text fits one batch and is >= SHK_FASTQ_PIPELINE_MIN (64 MiB): cut into a few pieces,
 //                                piece i+1 uploaded while piece i is parsed, counted as ONE batch
-//   3 route_device_single        the text fits one batch (and route 2 has not found it irregular): one upload, one parse
-//   4 route_device_pieces        the text exceeds one batch: one batch per piece
-//   5 route_host                 SHK_HOST_PARSER=1, or every route above declined.  Never declines.
-//   6 push_reads_impl            the streaming entry point: the device parser for a chunk of >= SHK_STREAM_DEVICE_MIN bytes
+//   4 route_device_single        the text fits one batch (and route 3 has not found it irregular): one upload, one parse
+//   5 route_device_pieces        the text exceeds one batch: one batch per piece
+//   6 route_host                 SHK_HOST_PARSER=1, or every route above declined.  Never declines.
+//   7 push_reads_impl            the streaming entry point: the device parser for a chunk of >= SHK_STREAM_DEVICE_MIN bytes
 //                                that is regular 4-line FASTQ, else the host parser
 // The device parser (fastq_gpu.hip) takes regular 4-line FASTQ only; irregular framing and every malformed record go to
 // the host parser (fastq.cpp), which owns the error messages.
@@ -48,6 +54,10 @@ struct Knobs {
     const size_t pieces = (size_t)std::max<long long>(1, (long long)num(getenv("SHK_FASTQ_PIECES"), 4));
     // bases per batch of the host-parsed paths (a batch is limited to 2^32 packed bases by its 32-bit offsets)
     const uint64_t batch_bases = std::min<uint64_t>(std::max<uint64_t>(num(getenv("SHK_BATCH_BASES"), 1ull << 31), 1024), 3ull << 30);
+    // text per window of route 2 (bytes; default 1 GiB — unmeasured so far): a window and its carry fit one batch and 32-bit offsets, and a
+    // window takes at least one block of 64 KiB.  Set: a BGZF file beyond it takes route 2 even where it fits one batch.
+    const bool window_set = getenv("SHK_GUNZIP_DEVICE_WINDOW") && *getenv("SHK_GUNZIP_DEVICE_WINDOW");
+    const uint64_t window = std::max<uint64_t>(std::min<uint64_t>({num(getenv("SHK_GUNZIP_DEVICE_WINDOW"), 1ull << 30), 2 * batch_bases, 3ull << 30}), 65536);
 };
 
 // a device block of the parser that goes back to the pool when its owner goes out of scope (every error and
@@ -190,13 +200,14 @@ size_t next_record_start(const uint8_t *t, size_t n, size_t from) {
     return SIZE_MAX;
 }
 
-// what shk_preprocess was given, and (from route 2 on) its text
+// what shk_preprocess was given, (routes 1 and 2) its BGZF chains as walked, and (from route 3 on) its text
 struct Input {
     const uint8_t *fq1, *fq2; size_t n1, n2, total;     // fq2 null: one file; total: the bytes given, the denominator of the progress percentages
     double t0;                                           // when the entry point started
     ByteVec st1, st2;
     const uint8_t *t1 = nullptr, *t2 = nullptr; size_t l1 = 0, l2 = 0;      // the plain text (t2 null, l2 0: one file)
     size_t text_total() const { return l1 + l2; }
+    BgzfChain chain[2]; bool walked[2] = {false, false};      // route 2's walk of a file that is a complete BGZF chain: route 1 does not repeat it
 };
 
 // Route 1.  Both files (or the one) are what the device inflater takes — a plain gzip member or a BGZF chain, in any
@@ -214,7 +225,7 @@ int route_device_gzip(shk_handle *h, const Knobs &kn, const Input &in) {
     uint64_t bgzf_blocks = 0;
     for (int f = 0; f < nf; f++) {
         GpuInflateStats st;
-        const int rc = gpu_inflate_member(gz[f], gn[f], h->pipe->device(), h->pipe->stream(), text[f], err, &st);
+        const int rc = gpu_inflate_member(gz[f], gn[f], h->pipe->device(), h->pipe->stream(), text[f], err, &st, false, in.walked[f] ? &in.chain[f] : nullptr);
         if (rc == 1) { h->pipe->times().add("gunzip_device_not_taken_x1", 1.0); return DECLINED; }
         if (rc) return fail_rc(h, Rc::DeviceNoParam, rc, err);
         ms_h2d += st.h2d_ms; ms_search += st.search_ms; ms_decode += st.decode_ms; ms_resolve += st.resolve_ms;
@@ -250,10 +261,152 @@ int route_device_gzip(shk_handle *h, const Knobs &kn, const Input &in) {
     return rc ? rc : finish_counting(h);
 }
 
-// Routes 2 and 4.  The text is cut at record boundaries into pieces that go through the device parser one after the
+// Route 2.  Every file is a complete BGZF chain (inflate_gpu.h: bgzf_walk) whose text is more than route 1 takes.  A window
+// is a run of consecutive blocks of at most kn.window bytes of text: its compressed bytes are uploaded by a helper thread
+// while the window before it is worked on, it is inflated behind the carry (the partial record the window before it ended
+// in), cut at its last record start on the device, parsed there and counted as a batch of its own.
+// *tried: the sizes called for this route (route 1 is then not tried: it would inflate everything to decline).
+// Declines while nothing is counted: a file that is no such chain, window 0 damaged or not regular 4-line FASTQ, no device
+// memory.  Later, whatever goes wrong with a window sends the rest of its file, from that window's first block on and with
+// the carry in front, through the host reader and the host parser, which own the messages (host_rest, as in
+// route_device_pieces); a carry never crosses from file 1 to file 2.
+int route_device_bgzf_windows(shk_handle *h, const Knobs &kn, Input &in, bool *tried) {
+    const uint8_t *gz[2] = {in.fq1, in.fq2}; const size_t gn[2] = {in.n1, in.fq2 ? in.n2 : 0};
+    const int nf = in.fq2 ? 2 : 1;
+    *tried = false;
+    for (int f = 0; f < nf; f++) if (gn[f] < 18 || gz[f][0] != 0x1F || gz[f][1] != 0x8B) return DECLINED;
+    // ---- the plan, before any upload
+    BgzfChain (&chain)[2] = in.chain;
+    uint64_t total = 0; bool wants = false;
+    for (int f = 0; f < nf; f++) {
+        const char *why = "";
+        size_t bs = 0;
+        if (!bgzf_block(gz[f], gn[f], bs) || bgzf_walk(gz[f], gn[f], chain[f], why)) return DECLINED;
+        in.walked[f] = true;
+        total += chain[f].text;
+        wants = wants || chain[f].text >= (1ull << 32) || (kn.window_set && chain[f].text > kn.window);
+    }
+    if (total == 0 || !(wants || total / 2 > kn.batch_bases)) return DECLINED;
+    for (int f = 0; f < nf; f++) if (bgzf_cut_windows(chain[f], kn.window)) return DECLINED;
+    *tried = true;
+    std::string err;
+    struct Book {                                         // the timings, on every way out
+        shk_handle *h; double h2d = 0, decode = 0, kernels = 0; uint64_t windows = 0, blocks = 0; int nf = 1;
+        ~Book() {
+            if (!windows) return;
+            auto &t = h->pipe->times();
+            t.add("gunzip_device_windows_x1", (double)windows); t.add("gunzip_device_bgzf_blocks_x1", (double)blocks);
+            t.add("gunzip_device_members_x1", (double)nf);
+            t.add("gunzip_device_h2d", h2d); t.add("gunzip_device_decode", decode); t.add("fastq_device_kernels", kernels);
+        }
+    } book{h}; book.nf = nf;
+    uint64_t reads_done = 0, file_reads = 0, text_before_file = 0;
+    bool counted_any = false;
+    // the rest of file f from window w on, `carry` in front: host reader, host parser, whole-file record numbers
+    auto host_rest = [&](int f, size_t w, const std::vector<uint8_t> &carry) -> int {
+        const BgzfChain::Window &win = chain[f].windows[w];
+        ByteVec st; const uint8_t *p = nullptr; size_t pn = 0;
+        const double th = now_ms();
+        if (int ri = maybe_inflate(gz[f] + win.in_off, gn[f] - (size_t)win.in_off, st, p, pn, err)) return fail_rc(h, Rc::Inflater, ri, err);
+        h->pipe->times().add("gunzip_host_clock", now_ms() - th);
+        ByteVec joined;
+        if (!carry.empty()) {
+            joined.resize(carry.size() + pn);
+            memcpy(joined.data(), carry.data(), carry.size()); memcpy(joined.data() + carry.size(), p, pn);
+            p = joined.data(); pn = joined.size();
+        }
+        PackedReads pr;
+        pr.n_reads = reads_done;
+        if (int rc = host_parse(h, kn, p, pn, pr, Span{text_before_file + win.text_before - carry.size(), total}, 0, file_reads)) return rc;
+        if (int rc = flush_host_batch(h, pr)) return rc;
+        reads_done = pr.n_reads;
+        return SHK_OK;
+    };
+    for (int f = 0; f < nf; f++) {
+        const std::vector<BgzfChain::Window> &wins = chain[f].windows;
+        file_reads = 0;
+        std::vector<uint8_t> carry_host;                  // the carry in front of the current window, for host_rest
+        BgzfWindows bw;
+        // (declared after the buffers: joined before they are released, on every way out)
+        struct Uploader { int rc = 0; std::string err; std::thread t; void join() { if (t.joinable()) t.join(); } ~Uploader() { join(); } } upl;
+        // (this file's share of the two sums, on every way out of the file)
+        struct Sum { Book &b; BgzfWindows &w; ~Sum() { b.h2d += w.h2d_ms; b.decode += w.decode_ms; } } sum{book, bw};
+        // what the device does not do with window w: nothing is counted yet -> decline; else the host takes the file from here
+        auto give_up = [&](size_t w) -> int {
+            upl.join(); bw.close();
+            if (!counted_any) return DECLINED;
+            return host_rest(f, w, carry_host);
+        };
+        int rc = bw.open(gz[f], &chain[f], h->pipe->device(), h->pipe->stream(), err);
+        if (rc < 0) return fail_rc(h, Rc::DeviceNoParam, rc, err);
+        if (rc == 1) { if (int r = give_up(0)) return r; text_before_file += chain[f].text; continue; }
+        if ((rc = bw.upload(0, err))) return fail_rc(h, Rc::DeviceNoParam, rc, err);
+        uint64_t carry = 0;
+        for (size_t w = 0; w < wins.size(); w++) {
+            const bool last = w + 1 == wins.size();
+            if (!last)
+                upl.t = std::thread([&, w]() {
+                    try { upl.rc = bw.upload(w + 1, upl.err); }
+                    catch (...) { upl.rc = -4; upl.err = "out of host memory (uploader)"; }
+                });
+            const char *why = "";                         // (for a debugger: the host reader words the message)
+            rc = bw.inflate(w, carry, why, err);
+            if (rc < 0) return fail_rc(h, Rc::DeviceNoParam, rc, err);
+            bool to_host = rc == 1;
+            const uint64_t n = carry + wins[w].text;
+            uint64_t cut = n; bool unterminated = false;
+            if (!to_host && last) {
+                rc = bw.trim_end(w, n, cut, unterminated, err);
+                if (rc < 0) return fail_rc(h, Rc::DeviceNoParam, rc, err);
+                to_host = rc == 1;
+            } else if (!to_host) {
+                if ((rc = bw.last_start(w, n, cut, err))) return fail_rc(h, Rc::DeviceNoParam, rc, err);
+                if (cut == UINT64_MAX) cut = 0;           // (one record's middle: all of it is carried on, if there is room)
+                to_host = n - cut > BgzfWindows::CARRY_MAX;
+                // the carry goes to the next window's buffer first: the parser wants 32 zero bytes behind the cut
+                if (!to_host) if ((rc = bw.carry_over(w, cut, n, err))) return fail_rc(h, Rc::DeviceNoParam, rc, err);
+            }
+            Packed gp;
+            if (!to_host && cut) {
+                GpuText text; text.d = bw.text(w); text.e = (size_t)cut; text.unterminated = unterminated;      // (the buffer stays bw's)
+                rc = gpu_pack_fastq(nullptr, 0, nullptr, 0, h->k, h->min_qual, h->progress_every(), h->pipe->stream(), gp, err, reads_done, &text);
+                if (rc < 0) return fail_rc(h, Rc::Device, rc, err);
+                to_host = rc == 1;                        // not regular FASTQ: the host parser owns the messages
+            }
+            if (to_host) {
+                gp.reset();
+                if (int r = give_up(w)) return r;
+                break;                                    // the rest of this file is done
+            }
+            book.windows++; book.blocks += wins[w].nonempty;
+            if (cut) {
+                if (!counted_any) h->pipe->expect_more_batches();
+                counted_any = true;
+                book.kernels += gp.kernels_ms;
+                post_device_progress(h, gp, Span{text_before_file + wins[w].text_before - carry, total});
+                reads_done += gp.n_reads; file_reads += gp.n_reads;
+                const int rc2 = gp.n_seg ? count_one_batch(h, gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases) : SHK_OK;
+                gp.reset();
+                if (rc2) return rc2;
+            }
+            carry = n - cut;
+            if (last) break;
+            // the carry as the host would need it, and the next window's bytes
+            carry_host.resize((size_t)carry);
+            if (carry && device_download(carry_host.data(), bw.text(w + 1), (size_t)carry, err)) return fail(h, SHK_E_DEVICE, err);
+            upl.join();
+            if (upl.rc) return fail_rc(h, Rc::DeviceNoParam, upl.rc, upl.err);
+        }
+        text_before_file += chain[f].text;
+    }
+    h->n_reads = reads_done;
+    return finish_counting(h);
+}
+
+// Routes 3 and 5.  The text is cut at record boundaries into pieces that go through the device parser one after the
 // other; a helper thread uploads piece i+1 while piece i is parsed and counted (H2D is two thirds of the entry point).
-// Route 4 (a text of more than one batch): pieces of ~2 * batch_bases bytes, each counted as its own batch (pass 1)
-// before the next is parsed.  Route 2 (one_batch: the text fits one batch): SHK_FASTQ_PIECES pieces, kept and counted
+// Route 5 (a text of more than one batch): pieces of ~2 * batch_bases bytes, each counted as its own batch (pass 1)
+// before the next is parsed.  Route 3 (one_batch: the text fits one batch): SHK_FASTQ_PIECES pieces, kept and counted
 // together as ONE batch at the end (pass 1 runs over the pieces into the same slices: the partitioning of a single
 // batch, no batch packing, no merge).
 // Declines (nothing counted) when the very first piece is not regular 4-line FASTQ.  A later piece that is not
@@ -365,7 +518,7 @@ int route_device_pieces(shk_handle *h, const Knobs &kn, const Input &in, bool on
     return finish_counting(h);
 }
 
-// Route 3.  The whole text (both files) in one upload and one parse.  Declines when it is not regular 4-line FASTQ.
+// Route 4.  The whole text (both files) in one upload and one parse.  Declines when it is not regular 4-line FASTQ.
 int route_device_single(shk_handle *h, const Knobs &, const Input &in) {
     std::string err;
     const double t0 = now_ms();
@@ -381,7 +534,7 @@ int route_device_single(shk_handle *h, const Knobs &, const Input &in) {
     return run_counting(h, gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases);
 }
 
-// Route 5.  The host parser (irregular framing, malformed records, SHK_HOST_PARSER=1), batch by batch.
+// Route 6.  The host parser (irregular framing, malformed records, SHK_HOST_PARSER=1), batch by batch.
 int route_host(shk_handle *h, const Knobs &kn, const Input &in) {
     PackedReads pr;
     if (flush_every_reads(h) || in.text_total() / 2 > kn.batch_bases) h->pipe->expect_more_batches();
@@ -405,7 +558,13 @@ int preprocess_impl(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t 
     const bool device = !kn.host_parser;
     // .fastq.gz (the reference's real input: fastx_wasm.rs:53-70) of some size is inflated ON THE DEVICE — the compressed
     // bytes are what crosses PCIe — and its text goes straight to the device parser
-    int rc = device && kn.gunzip_device ? route_device_gzip(h, kn, in) : DECLINED;
+    // ... unless it is a BGZF file beyond what fits at once: that is seen in the blocks' trailers before anything is uploaded
+    int rc = DECLINED;
+    if (device && kn.gunzip_device) {
+        bool windows_tried = false;
+        rc = route_device_bgzf_windows(h, kn, in, &windows_tried);
+        if (rc == DECLINED && !windows_tried) rc = route_device_gzip(h, kn, in);
+    }
     if (rc != DECLINED) return rc;
     // whatever the device inflater does not take (several plain members, a broken BGZF chain, binary data, a damaged
     // stream) is inflated on the host (plain members: one thread per file; BGZF: block-parallel), for either parser
@@ -417,7 +576,7 @@ int preprocess_impl(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t 
     const bool one_batch = in.text_total() / 2 <= kn.batch_bases;
     const bool pipelined = device && one_batch && in.text_total() >= kn.pipeline_min;
     if (pipelined) rc = route_device_pieces(h, kn, in, true);
-    // (route 2 declines a text that is irregular from the first piece on: route 3 would find the same, so it is skipped)
+    // (route 3 declines a text that is irregular from the first piece on: route 4 would find the same, so it is skipped)
     if (rc == DECLINED && device && one_batch && !pipelined) rc = route_device_single(h, kn, in);
     if (rc == DECLINED && device && !one_batch) rc = route_device_pieces(h, kn, in, false);
     return rc == DECLINED ? route_host(h, kn, in) : rc;

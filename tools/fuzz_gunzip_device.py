@@ -63,7 +63,11 @@ def fuzz_bgzf():
     for case in range(n_cases):
         text = fg.make_text(int(rng.choice([70000, 300_000, 3_000_000, 8_000_000])))
         z, offs = bgzf_file(text)
-        desc = dict(case=case, size=len(text), zlen=len(z), blocks=len(offs))
+        # at times through the windows of the large-file route: text per window from one block's worth up (csrc/preprocess.cpp, route 2)
+        os.environ.pop("SHK_GUNZIP_DEVICE_WINDOW", None)
+        if rng.random() < 0.5:
+            os.environ["SHK_GUNZIP_DEVICE_WINDOW"] = str(int(rng.choice([65536, 100000, 1 << 20, 5 << 20])))
+        desc = dict(case=case, size=len(text), zlen=len(z), blocks=len(offs), window=os.environ.get("SHK_GUNZIP_DEVICE_WINDOW"))
         try:
             rc, got, why, _ = device_gunzip(z)
             assert rc == 0, ("an intact BGZF file was not taken", rc, why)

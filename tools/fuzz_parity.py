@@ -87,6 +87,7 @@ for case in range(n_cases):
     if rng.random() < 0.4: env["SHK_PART_G"] = str(int(rng.choice([1, 2, 5])))   # round 4: few workgroups -> every wave of pass 1 walks many tiles (prefetch of the next round)
     if rng.random() < 0.3: env["SHK_PART_WIN"] = str(int(rng.choice([16, 18, 20])))   # round 4: minimiser window of pass 1 for k >= 31 (one block of 16, two of 9, two of 10)
     if rng.random() < 0.3: env["SHK_GUNZIP_DEVICE_MIN"] = "2048"   # round 4: gzip members go to the device inflater first (it declines most of these tiny ones)
+    if rng.random() < 0.2: env["SHK_GUNZIP_DEVICE_WINDOW"] = str(int(rng.choice([65536, 100000, 1 << 20])))   # BGZF input beyond it is inflated, parsed and counted window by window
     old = {e: os.environ.get(e) for e in env}
     os.environ.update(env)
     desc = dict(case=case, k=k, glen=glen, rl=rl, cov=cov, err=err, circ=circular, mc=min_count, mq=min_qual, fit=do_fit,
