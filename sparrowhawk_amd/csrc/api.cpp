@@ -772,13 +772,12 @@ int shk_device_gunzip(const uint8_t *gz, size_t n, uint8_t **out, size_t *out_n,
         // reaches 4 GiB.  Every window is cut at its last record start and its rest carried into the next, as the route does
         // (text without one, or a carry beyond the room for it: the window is handed on whole); the bytes are all returned.
         {
-            const char *wv = getenv("SHK_GUNZIP_DEVICE_WINDOW");
+            const BgzfWindowKnob window = bgzf_window_knob(UINT64_MAX);      // (no batch here to fit a window into)
             size_t bs = 0;
             BgzfChain chain; const char *why_not = "";
-            if (n >= 18 && bgzf_block(gz, n, bs) && bgzf_walk(gz, n, chain, why_not) == 0 && chain.text && ((wv && *wv) || chain.text >= (1ull << 32))) {
-                const uint64_t W = std::max<uint64_t>(std::min<uint64_t>((wv && *wv) ? strtoull(wv, nullptr, 10) : (1ull << 30), 3ull << 30), 65536);
+            if (n >= 18 && bgzf_block(gz, n, bs) && bgzf_walk(gz, n, chain, why_not) == 0 && chain.text && (window.set || chain.text >= (1ull << 32))) {
                 auto say = [&](const std::string &m) { if (why) { msg = m; *why = msg.c_str(); } };
-                if (bgzf_cut_windows(chain, W)) return SHK_E_INTERNAL;
+                if (bgzf_cut_windows(chain, window.bytes)) return SHK_E_INTERNAL;
                 const double t0 = now_ms();
                 uint8_t *o = (uint8_t *)malloc((size_t)chain.text);
                 if (!o) return SHK_E_OOM;
@@ -790,20 +789,12 @@ int shk_device_gunzip(const uint8_t *gz, size_t n, uint8_t **out, size_t *out_n,
                 uint64_t carry = 0, done = 0;
                 for (size_t w = 0; w < chain.windows.size(); w++) {
                     const char *wn = "";
-                    if ((rc = bw.upload(w, err))) { say(err); return code_of(Rc::DeviceNoParam, rc); }
-                    rc = bw.inflate(w, carry, wn, err);
+                    uint64_t cut = 0; bool unterminated = false;
+                    rc = bw.step(w, true, carry, cut, unterminated, wn, err);
                     if (rc == 1) { say(wn); return 1; }
                     if (rc) { say(err); return code_of(Rc::DeviceNoParam, rc); }
-                    const uint64_t nn = carry + chain.windows[w].text;
-                    uint64_t cut = nn;
-                    if (w + 1 < chain.windows.size()) {
-                        if ((rc = bw.last_start(w, nn, cut, err))) { say(err); return code_of(Rc::DeviceNoParam, rc); }
-                        if (cut == UINT64_MAX || nn - cut > BgzfWindows::CARRY_MAX) cut = nn;
-                    }
-                    // (down first: carry_over puts the parser's zero bytes behind the cut)
                     if (cut) if (device_download(o + done, bw.text(w), (size_t)cut, err)) { say(err); return SHK_E_DEVICE; }
-                    if (w + 1 < chain.windows.size()) if ((rc = bw.carry_over(w, cut, nn, err))) { say(err); return code_of(Rc::DeviceNoParam, rc); }
-                    done += cut; carry = nn - cut;
+                    done += cut;
                 }
                 if (done != chain.text) { say("the windows do not add up"); return SHK_E_INTERNAL; }
                 if (ms_total) *ms_total = now_ms() - t0;

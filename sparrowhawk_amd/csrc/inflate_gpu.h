@@ -2,14 +2,17 @@
 // are what crosses PCIe, the FASTQ text is born in HBM and goes straight to the device parser (fastq_gpu.h).  A plain
 // member: the same two-pass scheme as the host reader (inflate_mt.cpp, after pugz / rapidgzip) with thousands of chunks
 // instead of one per host thread.  A BGZF file: one wave per block, no speculation (every block is a stream of its own).
-// A BGZF file of more text than is inflated at once goes window by window (BgzfWindows below): the same two kernels on a run
-// of blocks at a time, and k_last_record_start to cut the window's text where its last whole record ends.
+// A BGZF file of more text than is inflated at once goes window by window (BgzfWindows below): the same inflater on a run of
+// blocks at a time (inflate_gpu.hip: inflate_block_run, the one launch of the two kernels), k_last_record_start to cut the
+// window's text where its last whole record ends, and the one end-of-text rule (trim_text_end) for the last window.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 #include <string>
+#include <thread>
 #include <vector>
 #include "fastq_gpu.h"
+#include "pipeline.h"
 
 namespace shk {
 
@@ -39,8 +42,8 @@ int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, Gp
 
 // ---- a BGZF file of any size, window by window ------------------------------------------------------------------------
 // The chain is walked on the host before a byte crosses PCIe (every block's ISIZE stands in its trailer), cut into windows
-// of consecutive blocks whose text fits a budget (fastq.h: plan_bgzf_windows), and each window is uploaded, inflated by
-// k_bgzf_decode / k_bgzf_crc with window-relative descriptors, and cut at its last record start on the device.
+// of consecutive blocks whose text fits a budget (fastq.h: plan_bgzf_windows, the budget: bgzf_window_knob), and each window
+// is uploaded, inflated with window-relative descriptors, and cut at its last record start on the device (BgzfWindows::step).
 struct BgzfChain {
     struct Block { uint64_t in_off; uint32_t bsize, hdr, isize, crc; };      // in_off: of the block's header in the file
     struct Window { size_t b0, b1; uint64_t in_off, in_end, text, text_before; uint32_t nonempty; };
@@ -55,39 +58,54 @@ int bgzf_walk(const uint8_t *gz, size_t n, BgzfChain &out, const char *&why);
 // out.windows from out.blocks; -1: a block exceeds the budget
 int bgzf_cut_windows(BgzfChain &c, uint64_t budget);
 
-// The device side of one file's windows: two input buffers (window i + 1 is uploaded, from a helper thread, while window i
-// is worked on) and two text buffers (window i's text starts with the carry: the partial record left over from window i - 1).
+// SHK_GUNZIP_DEVICE_WINDOW, bytes of text per window: 1 GiB by default, at most max_bytes (a window and its carry fit one
+// batch) and 3 GiB (32-bit offsets), at least one block of 64 KiB
+struct BgzfWindowKnob { bool set; uint64_t bytes; };
+BgzfWindowKnob bgzf_window_knob(uint64_t max_bytes);
+
+struct Blk {                                               // a device block of the process-wide pool
+    void *p = nullptr; size_t bytes = 0;
+    Blk() = default;
+    Blk(const Blk &) = delete;
+    Blk &operator=(const Blk &) = delete;
+    ~Blk() { put(); }
+    bool get(size_t b) { bytes = b ? b : 8; p = device_pool_alloc(bytes); return p != nullptr; }      // (the pool may hand out more: bytes says what)
+    void put() { if (p) device_pool_release(p, bytes); p = nullptr; }
+    void *take() { void *q = p; p = nullptr; return q; }
+};
+
+// The device side of one file's windows: two input buffers (window w + 1 is uploaded, from a helper thread, while window w
+// is worked on) and two text buffers (window w's text starts with the carry: the partial record left over from window w - 1).
+//     if (bw.open(gz, &chain, device, stream, err)) ...
+//     for (size_t w = 0; w < chain.windows.size(); w++) { if (bw.step(w, raw, carry, cut, unterminated, why, err)) ...; use text(w)[0..cut) }
 class BgzfWindows {
   public:
     static const uint64_t CARRY_MAX = 16ull << 20;        // a partial record of more than this goes to the host reader
-    BgzfWindows();
-    ~BgzfWindows();
+    BgzfWindows() = default;
+    ~BgzfWindows() { close(); }
     BgzfWindows(const BgzfWindows &) = delete;
     BgzfWindows &operator=(const BgzfWindows &) = delete;
     // 0; 1 out of device memory (nothing is held); -5
     int open(const uint8_t *gz, const BgzfChain *chain, int device, void *stream, std::string &err);
-    void close();
-    // window w's compressed bytes -> its input buffer; blocking, on a stream of its own (callable from a helper thread)
-    int upload(size_t w, std::string &err);
-    // window w (uploaded) -> text(w)[carry, carry + windows[w].text).  0; 1 a damaged block (*why); -5
-    int inflate(size_t w, uint64_t carry, const char *&why, std::string &err);
-    // last_record_start (fastq.h) of text(w)[0..n), on the device; UINT64_MAX: none in the last CARRY_MAX bytes and a step (a
-    // start further front leaves more to carry than there is room for: the caller gives the window to the host either way)
-    int last_start(size_t w, uint64_t n, uint64_t &at, std::string &err);
-    // the end of a file's text, text(w)[0..n): e = n without trailing blank lines (the rule of gpu_upload_text).  0; 1: more
-    // blank lines than are looked at
-    int trim_end(size_t w, uint64_t n, uint64_t &e, bool &unterminated, std::string &err);
-    // text(w)[cut, n) -> the front of text(w + 1); only then the 32 zero bytes the parser wants behind text(w)[0..cut)
-    int carry_over(size_t w, uint64_t cut, uint64_t n, std::string &err);
-    uint8_t *text(size_t w) const { return d_text_[w & 1]; }
+    void close();                                         // the helper thread is joined, then the blocks go back
+    // Windows in order, w = 0, 1, ...: window w is inflated behind `carry` bytes at the front of text(w) while window w + 1
+    // is uploaded.  Not the last window: cut = its last record start (k_last_record_start), text(w)[cut..) goes to the front
+    // of text(w + 1) and is the new carry, 32 zero bytes follow text(w)[0..cut) as the parser wants them.  The last window:
+    // cut = its end without trailing blank lines (the rule of gpu_upload_text), zero bytes as before, the new carry is 0.
+    // raw: the bytes stay as they are — the last window is not trimmed, and a window without a usable record start is handed
+    // on whole (cut = its end).
+    // 0; 1: this window is the host reader's (*why: a damaged block, more to carry than CARRY_MAX, kilobytes of blank lines
+    // at the end), carry is as it was; -5
+    int step(size_t w, bool raw, uint64_t &carry, uint64_t &cut, bool &unterminated, const char *&why, std::string &err);
+    uint8_t *text(size_t w) const { return (uint8_t *)d_text_[w & 1].p; }
     double h2d_ms = 0, decode_ms = 0;                      // summed over the windows
   private:
+    void upload(size_t w);                                // blocking, on a stream of its own: -> up_[w & 1]
     const uint8_t *gz_ = nullptr; const BgzfChain *chain_ = nullptr;
     int device_ = 0; void *st_ = nullptr;
-    uint8_t *d_in_[2] = {nullptr, nullptr}, *d_text_[2] = {nullptr, nullptr};
-    void *d_desc_ = nullptr, *d_status_ = nullptr, *d_bad_ = nullptr;
-    size_t in_bytes_[2] = {0, 0}, text_bytes_[2] = {0, 0}, desc_bytes_ = 0, status_bytes_ = 0, bad_bytes_ = 0;      // as the pool handed them out, block by block
-    double up_ms_[2] = {0, 0};
+    Blk d_in_[2], d_text_[2], d_desc_, d_status_, d_bad_;
+    struct Upload { int rc = 0; std::string err; double ms = 0; } up_[2];
+    std::thread prefetch_;                                // uploads window w + 1 during step(w); joined by step(w + 1) and close()
 };
 
 // k_last_record_start alone on n bytes of host text (the tests compare it with last_record_start)

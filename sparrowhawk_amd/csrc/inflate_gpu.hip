@@ -780,13 +780,6 @@ Gf2 crc_shift_matrix(uint64_t len_bytes) {              // operator "append len_
 
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-struct Blk {                                               // a device block of the process-wide pool
-    void *p = nullptr; size_t bytes = 0;
-    ~Blk() { if (p) device_pool_release(p, bytes); }
-    bool get(size_t b) { bytes = b ? b : 8; p = device_pool_alloc(bytes); return p != nullptr; }
-    void *take() { void *q = p; p = nullptr; return q; }
-};
-
 }  // namespace
 
 #define GZCHK(call)                                                                         \
@@ -796,24 +789,85 @@ struct Blk {                                               // a device block of 
     } while (0)
 
 namespace {
-// The inflated text (d_text: `total` bytes and 64 more, `tail`: a copy of its last tail_n bytes) as gpu_upload_text hands a
-// text on: trailing blank lines cut off, 32 zero bytes behind it (fastq_gpu.hip: trimmed_len — "\n\n" and "\n\r\n" at the
-// end lose their last line end, repeatedly); raw: every byte stays.  0: out owns the block; 1: not taken (*why); -5.
-int hand_on_text(Blk &d_text, uint64_t total, const char *tail, size_t tail_n, bool raw, hipStream_t st, GpuText &out, const char *&why, std::string &err) {
+// the last bytes of a text on the device, for trim_text_end: fetch_tail enqueues the copy, the caller waits (with whatever
+// else it waits for)
+struct Tail { char b[4096]; size_t n = 0; };
+hipError_t fetch_tail(const uint8_t *d_text, uint64_t n, Tail &t, hipStream_t st) {
+    t.n = (size_t)std::min<uint64_t>(n, sizeof t.b);
+    return t.n ? hipMemcpyAsync(t.b, d_text + (n - t.n), t.n, hipMemcpyDeviceToHost, st) : hipSuccess;
+}
+
+// The end of the text d_text[0..n) (t: its tail, arrived) as gpu_upload_text hands a text on (fastq_gpu.hip: trimmed_len):
+// "\n\n" and "\n\r\n" at the end lose their last line end, repeatedly, and 32 zero bytes follow what is left (d_text has
+// room for them); raw: every byte stays as it is.  0: e bytes of text; 1: more blank lines than are looked at (*why); -5.
+int trim_text_end(uint8_t *d_text, uint64_t n, const Tail &t, bool raw, hipStream_t st, uint64_t &e, bool &unterminated, const char *&why, std::string &err) {
+    const char *tail = t.b; const size_t tail_n = t.n;
     size_t te = tail_n;
-    for (;;) {
+    while (!raw) {
         if (te >= 2 && tail[te - 1] == '\n' && tail[te - 2] == '\n') { te -= 1; continue; }
         if (te >= 3 && tail[te - 1] == '\n' && tail[te - 2] == '\r' && tail[te - 3] == '\n') { te -= 2; continue; }
         break;
     }
-    if (raw) te = tail_n;
-    if (te < 8 && total > tail_n) { why = "kilobytes of blank lines at the end"; return 1; }
-    const size_t e = (size_t)(total - tail_n) + te;
-    if (e == 0) { why = "empty text"; return 1; }
-    if (!raw) GZCHK(hipMemsetAsync((char *)d_text.p + e, 0, std::min<size_t>(32, (size_t)total + 64 - e), st));
+    if (te < 8 && n > tail_n) { why = "kilobytes of blank lines at the end"; return 1; }
+    e = (n - tail_n) + te;
+    unterminated = te == 0 || tail[te - 1] != '\n';
+    if (!raw) GZCHK(hipMemsetAsync(d_text + e, 0, 32, st));
     GZCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// The inflated text (d_text: `total` bytes and 64 more, tail: its last bytes, arrived) becomes out's, made ready for the
+// parser unless raw (trim_text_end).  0: out owns the block; 1: not taken (*why); -5.
+int hand_on_text(Blk &d_text, uint64_t total, const Tail &tail, bool raw, hipStream_t st, GpuText &out, const char *&why, std::string &err) {
+    uint64_t e = 0; bool unterminated = false;
+    if (const int rc = trim_text_end((uint8_t *)d_text.p, total, tail, raw, st, e, unterminated, why, err)) return rc;
+    if (e == 0) { why = "empty text"; return 1; }
     out.pool_bytes = d_text.bytes; out.d = (uint8_t *)d_text.take();
-    out.e = e; out.unterminated = te == 0 || tail[te - 1] != '\n';
+    out.e = (size_t)e; out.unterminated = unterminated;
+    return 0;
+}
+
+// Blocks [b0, b1) of a walked chain: one wave per non-empty block, then the blocks' checksums.  d_in holds the file from
+// byte in_base on (zero padding behind it), the first block's text goes to d_text + text_at; d_desc and d_status have room
+// for the run's non-empty blocks, d_bad is 64 bytes.  ms: from the first copy to the verdict; crc_ms, where asked for
+// and SHK_GUNZIP_DEBUG is set: the share of it behind the decoder (one more wait); tail, where asked for: the last bytes of
+// the run's text, which come back in the verdict's wait.
+// 0; 1: a block is not what its trailer says (*why); -5.
+int inflate_block_run(const BgzfChain &chain, size_t b0, size_t b1, const void *d_in, uint64_t in_base, uint8_t *d_text, uint64_t text_at,
+                      Blk &d_desc, Blk &d_status, Blk &d_bad, hipStream_t st, double &ms, double *crc_ms, Tail *tail, const char *&why, std::string &err) {
+    std::vector<BgzfDesc> desc;
+    for (size_t b = b0; b < b1; b++) {
+        const BgzfChain::Block &k = chain.blocks[b];
+        if (k.isize) desc.push_back(BgzfDesc{(unsigned long long)(k.in_off - in_base + k.hdr), k.bsize - k.hdr - 8, (uint32_t)text_at, k.isize, k.crc});
+        text_at += k.isize;
+    }
+    const uint32_t nb = (uint32_t)desc.size();
+    if (!nb) return 0;
+    const double t1 = now_ms();
+    GZCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nb * sizeof(BgzfDesc), hipMemcpyHostToDevice, st));
+    GZCHK(hipMemsetAsync(d_bad.p, 0xFF, 64, st));
+    hipLaunchKernelGGL(k_bgzf_decode, dim3(nb), dim3(64), 0, st, (const uint32_t *)d_in, (const BgzfDesc *)d_desc.p, nb, d_text,
+                       (uint32_t *)d_status.p, (uint32_t *)d_bad.p);
+    GZCHK(hipGetLastError());
+    double t2 = 0;
+    if (crc_ms && getenv("SHK_GUNZIP_DEBUG")) { GZCHK(hipStreamSynchronize(st)); t2 = now_ms(); }
+    hipLaunchKernelGGL(k_bgzf_crc, dim3((nb + 63) / 64), dim3(64), 0, st, (const uint8_t *)d_text, (const BgzfDesc *)d_desc.p, nb, (uint32_t *)d_bad.p);
+    GZCHK(hipGetLastError());
+    uint32_t h_bad[2] = {0, 0};
+    GZCHK(hipMemcpyAsync(h_bad, d_bad.p, 8, hipMemcpyDeviceToHost, st));
+    if (tail) GZCHK(fetch_tail(d_text, text_at, *tail, st));
+    GZCHK(hipStreamSynchronize(st));                        // (desc is read by the copy until here)
+    ms = now_ms() - t1;
+    if (t2 != 0) *crc_ms = now_ms() - t2;
+    if (h_bad[0] != 0xFFFFFFFFu) {                            // the first block that is not good: what it did
+        uint32_t status = 0;
+        GZCHK(hipMemcpyAsync(&status, (uint32_t *)d_status.p + h_bad[0], 4, hipMemcpyDeviceToHost, st));
+        GZCHK(hipStreamSynchronize(st));
+        why = status == BZ_TOO_LONG ? "a BGZF block inflates beyond its ISIZE" : status == BZ_TOO_SHORT ? "a BGZF block ends short of its ISIZE" :
+              status == BZ_NOT_AT_END ? "a BGZF block's stream does not end where its data ends" : "a damaged BGZF block";
+        return 1;
+    }
+    if (h_bad[1] != 0xFFFFFFFFu) { why = "CRC-32 mismatch"; return 1; }
     return 0;
 }
 
@@ -823,24 +877,13 @@ int hand_on_text(Blk &d_text, uint64_t total, const char *tail, size_t tail_n, b
 int gpu_inflate_bgzf(const uint8_t *gz, size_t n, int device, hipStream_t st, GpuText &out, std::string &err, GpuInflateStats &S, bool raw, const BgzfChain *walked) {
     auto not_taken = [&](const char *why) { S.why_not = why; return 1; };
     if (n >= ((size_t)1 << 34)) return not_taken("beyond 16 GiB");      // (UBits counts the input in 32-bit dwords)
-    // ---- the chain: one descriptor per non-empty block
     BgzfChain own;
-    const char *why_chain = "";
-    if (!walked && bgzf_walk(gz, n, own, why_chain)) return not_taken(why_chain);
+    const char *why = "";
+    if (!walked && bgzf_walk(gz, n, own, why)) return not_taken(why);
     const BgzfChain &chain = walked ? *walked : own;
     const uint64_t total = chain.text;
-    if (total >= ((uint64_t)1 << 32)) return not_taken("empty or beyond 4 GiB");
-    std::vector<BgzfDesc> desc;
-    desc.reserve((size_t)chain.nonempty);
-    {
-        uint64_t at = 0;
-        for (const BgzfChain::Block &b : chain.blocks) {
-            if (b.isize) desc.push_back(BgzfDesc{(unsigned long long)(b.in_off + b.hdr), b.bsize - b.hdr - 8, (uint32_t)at, b.isize, b.crc});
-            at += b.isize;
-        }
-    }
-    if (total == 0) return not_taken("empty or beyond 4 GiB");
-    const uint32_t nb = (uint32_t)desc.size();
+    if (total == 0 || total >= ((uint64_t)1 << 32)) return not_taken("empty or beyond 4 GiB");
+    const uint32_t nb = (uint32_t)chain.nonempty;
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); err = "hipSetDevice failed"; return -5; }
     const double t_begin = now_ms();
     // ---- upload: the file as it is (26 bytes of header and trailer per block are not worth a repack), zero padding behind
@@ -851,36 +894,16 @@ int gpu_inflate_bgzf(const uint8_t *gz, size_t n, int device, hipStream_t st, Gp
         return not_taken("out of device memory");
     GZCHK(hipMemsetAsync((char *)d_in.p + (n & ~(size_t)3), 0, in_words * 4 - (n & ~(size_t)3), st));
     GZCHK(hipMemcpyAsync(d_in.p, gz, n, hipMemcpyHostToDevice, st));
-    GZCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nb * sizeof(BgzfDesc), hipMemcpyHostToDevice, st));
-    GZCHK(hipMemsetAsync(d_bad.p, 0xFF, 64, st));
     GZCHK(hipMemsetAsync((char *)d_text.p + total, 0, 64, st));
     GZCHK(hipStreamSynchronize(st));
     S.h2d_ms = now_ms() - t_begin;
     // ---- every block, then its checksum; one word each comes back
-    double t1 = now_ms();
-    hipLaunchKernelGGL(k_bgzf_decode, dim3(nb), dim3(64), 0, st, (const uint32_t *)d_in.p, (const BgzfDesc *)d_desc.p, nb, (uint8_t *)d_text.p,
-                       (uint32_t *)d_status.p, (uint32_t *)d_bad.p);
-    GZCHK(hipGetLastError());
-    if (getenv("SHK_GUNZIP_DEBUG")) { GZCHK(hipStreamSynchronize(st)); S.decode_ms = now_ms() - t1; }
-    hipLaunchKernelGGL(k_bgzf_crc, dim3((nb + 63) / 64), dim3(64), 0, st, (const uint8_t *)d_text.p, (const BgzfDesc *)d_desc.p, nb, (uint32_t *)d_bad.p);
-    GZCHK(hipGetLastError());
-    uint32_t h_bad[2] = {0, 0};
-    char tail[4096];
-    const size_t tail_n = (size_t)std::min<uint64_t>(total, sizeof tail);
-    GZCHK(hipMemcpyAsync(h_bad, d_bad.p, 8, hipMemcpyDeviceToHost, st));
-    GZCHK(hipMemcpyAsync(tail, (char *)d_text.p + (total - tail_n), tail_n, hipMemcpyDeviceToHost, st));
-    GZCHK(hipStreamSynchronize(st));
-    if (S.decode_ms == 0) S.decode_ms = now_ms() - t1; else S.resolve_ms = now_ms() - t1 - S.decode_ms;
-    if (h_bad[0] != 0xFFFFFFFFu) {                            // the first block that is not good: what it did
-        uint32_t status = 0;
-        GZCHK(hipMemcpyAsync(&status, (uint32_t *)d_status.p + h_bad[0], 4, hipMemcpyDeviceToHost, st));
-        GZCHK(hipStreamSynchronize(st));
-        return not_taken(status == BZ_TOO_LONG ? "a BGZF block inflates beyond its ISIZE" : status == BZ_TOO_SHORT ? "a BGZF block ends short of its ISIZE" :
-                         status == BZ_NOT_AT_END ? "a BGZF block's stream does not end where its data ends" : "a damaged BGZF block");
-    }
-    if (h_bad[1] != 0xFFFFFFFFu) return not_taken("CRC-32 mismatch");
-    const char *why = "";
-    if (const int rt = hand_on_text(d_text, total, tail, tail_n, raw, st, out, why, err)) return rt == 1 ? not_taken(why) : rt;
+    double ms = 0, crc_ms = 0;
+    Tail tail;
+    int rc = inflate_block_run(chain, 0, chain.blocks.size(), d_in.p, 0, (uint8_t *)d_text.p, 0, d_desc, d_status, d_bad, st, ms, &crc_ms, &tail, why, err);
+    S.decode_ms = ms - crc_ms; S.resolve_ms = crc_ms;
+    if (!rc) rc = hand_on_text(d_text, total, tail, raw, st, out, why, err);
+    if (rc) return rc == 1 ? not_taken(why) : rc;
     out.h2d_ms = S.h2d_ms;
     S.blocks = nb; S.text_bytes = total; S.total_ms = now_ms() - t_begin;
     if (getenv("SHK_GUNZIP_DEBUG"))
@@ -1019,11 +1042,10 @@ int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, Gp
     GZCHK(hipGetLastError());
     std::vector<uint32_t> crcs(n_slices);
     uint32_t h_bad[2] = {0, 0};
-    char tail[4096];
-    const size_t tail_n = (size_t)std::min<uint64_t>(total, sizeof tail);
+    Tail tail;
     GZCHK(hipMemcpyAsync(crcs.data(), d_crc.p, (size_t)n_slices * 4, hipMemcpyDeviceToHost, st));
     GZCHK(hipMemcpyAsync(h_bad, d_bad.p, 8, hipMemcpyDeviceToHost, st));
-    GZCHK(hipMemcpyAsync(tail, (char *)d_text.p + (total - tail_n), tail_n, hipMemcpyDeviceToHost, st));
+    GZCHK(fetch_tail((const uint8_t *)d_text.p, total, tail, st));
     GZCHK(hipStreamSynchronize(st));
     S.resolve_ms = now_ms() - t1;
     if (h_bad[0]) return not_taken("a back-reference in front of the stream");
@@ -1037,7 +1059,7 @@ int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, Gp
     }
     if (crc != want_crc) return not_taken("CRC-32 mismatch");
     const char *why = "";
-    if (const int rt = hand_on_text(d_text, total, tail, tail_n, raw, st, out, why, err)) return rt == 1 ? not_taken(why) : rt;
+    if (const int rt = hand_on_text(d_text, total, tail, raw, st, out, why, err)) return rt == 1 ? not_taken(why) : rt;
     out.h2d_ms = S.h2d_ms;
     S.chunks = C; S.text_bytes = total; S.total_ms = now_ms() - t_begin;
     if (getenv("SHK_GUNZIP_DEBUG"))
@@ -1128,124 +1150,97 @@ int device_last_start(const uint8_t *d_text, uint64_t n, unsigned long long *d_o
 }
 }  // namespace
 
-BgzfWindows::BgzfWindows() {}
-BgzfWindows::~BgzfWindows() { close(); }
+BgzfWindowKnob bgzf_window_knob(uint64_t max_bytes) {
+    const char *v = getenv("SHK_GUNZIP_DEVICE_WINDOW");
+    const bool set = v && *v;
+    return BgzfWindowKnob{set, std::max<uint64_t>(std::min<uint64_t>({set ? strtoull(v, nullptr, 10) : 1ull << 30, max_bytes, 3ull << 30}), 65536)};
+}
+
 void BgzfWindows::close() {
-    if (st_ || d_in_[0]) (void)hipStreamSynchronize((hipStream_t)st_);      // the blocks go back to the pool idle
-    for (int i = 0; i < 2; i++) {
-        if (d_in_[i]) device_pool_release(d_in_[i], in_bytes_[i]);
-        if (d_text_[i]) device_pool_release(d_text_[i], text_bytes_[i]);
-        d_in_[i] = d_text_[i] = nullptr;
-    }
-    if (d_desc_) device_pool_release(d_desc_, desc_bytes_);
-    if (d_status_) device_pool_release(d_status_, status_bytes_);
-    if (d_bad_) device_pool_release(d_bad_, bad_bytes_);
-    d_desc_ = d_status_ = d_bad_ = nullptr;
+    if (prefetch_.joinable()) prefetch_.join();
+    if (st_ || d_in_[0].p) (void)hipStreamSynchronize((hipStream_t)st_);      // the blocks go back to the pool idle
+    for (Blk *b : {&d_in_[0], &d_in_[1], &d_text_[0], &d_text_[1], &d_desc_, &d_status_, &d_bad_}) b->put();
 }
 
 int BgzfWindows::open(const uint8_t *gz, const BgzfChain *chain, int device, void *stream, std::string &err) {
     close();
     gz_ = gz; chain_ = chain; device_ = device; st_ = stream;
     h2d_ms = decode_ms = 0;
+    up_[0] = up_[1] = Upload();
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); err = "hipSetDevice failed"; return -5; }
     uint64_t max_in = 0, max_text = 0; uint32_t max_nb = 1;
     for (const BgzfChain::Window &w : chain->windows) {
         max_in = std::max(max_in, w.in_end - w.in_off); max_text = std::max(max_text, w.text); max_nb = std::max(max_nb, w.nonempty);
     }
-    const size_t in_bytes = (size_t)((max_in + 3) & ~3ull) + WIN_IN_PAD, text_bytes = (size_t)(CARRY_MAX + max_text + 64);
-    desc_bytes_ = (size_t)max_nb * sizeof(BgzfDesc); status_bytes_ = (size_t)max_nb * 4; bad_bytes_ = 64;
-    const bool two = chain->windows.size() > 1;
+    // (the pool rounds a size up, or hands out a cached block that is larger: every Blk keeps the size it came with)
     bool ok = true;
-    // (the pool rounds a size up, or hands out a cached block that is larger: every block keeps the size it came with)
-    for (int i = 0; i < (two ? 2 : 1) && ok; i++) {
-        in_bytes_[i] = in_bytes; d_in_[i] = (uint8_t *)device_pool_alloc(in_bytes_[i]);
-        text_bytes_[i] = text_bytes; d_text_[i] = (uint8_t *)device_pool_alloc(text_bytes_[i]);
-        ok = d_in_[i] && d_text_[i];
-    }
-    if (ok) { d_desc_ = device_pool_alloc(desc_bytes_); d_status_ = device_pool_alloc(status_bytes_); d_bad_ = device_pool_alloc(bad_bytes_); }
-    if (!ok || !d_desc_ || !d_status_ || !d_bad_) { close(); return 1; }
+    for (int i = 0; i < (chain->windows.size() > 1 ? 2 : 1) && ok; i++)
+        ok = d_in_[i].get((size_t)((max_in + 3) & ~3ull) + WIN_IN_PAD) && d_text_[i].get((size_t)(CARRY_MAX + max_text + 64));
+    ok = ok && d_desc_.get((size_t)max_nb * sizeof(BgzfDesc)) && d_status_.get((size_t)max_nb * 4) && d_bad_.get(64);
+    if (!ok) { close(); return 1; }
     return 0;
 }
 
-int BgzfWindows::upload(size_t w, std::string &err) {
-    if (hipSetDevice(device_) != hipSuccess) { (void)hipGetLastError(); err = "hipSetDevice failed"; return -5; }
+void BgzfWindows::upload(size_t w) {
+    Upload &up = up_[w & 1];
+    up = Upload();
+    if (hipSetDevice(device_) != hipSuccess) { (void)hipGetLastError(); up.err = "hipSetDevice failed"; up.rc = -5; return; }
     const BgzfChain::Window &win = chain_->windows[w];
     const size_t n = (size_t)(win.in_end - win.in_off);
-    uint8_t *d = d_in_[w & 1];
+    uint8_t *d = (uint8_t *)d_in_[w & 1].p;
     hipStream_t s = nullptr;
     const double t0 = now_ms();
     hipError_t e = window_upload_stream(device_, s);
     if (e == hipSuccess) e = hipMemsetAsync(d + (n & ~(size_t)3), 0, ((n + 3) & ~(size_t)3) - (n & ~(size_t)3) + WIN_IN_PAD, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d, gz_ + win.in_off, n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    up_ms_[w & 1] = now_ms() - t0;
-    if (e != hipSuccess) { err = std::string("upload of a BGZF window: ") + hipGetErrorString(e); return -5; }
-    return 0;
+    up.ms = now_ms() - t0;
+    if (e != hipSuccess) { up.err = std::string("upload of a BGZF window: ") + hipGetErrorString(e); up.rc = -5; }
 }
 
-int BgzfWindows::inflate(size_t w, uint64_t carry, const char *&why, std::string &err) {
+int BgzfWindows::step(size_t w, bool raw, uint64_t &carry, uint64_t &cut, bool &unterminated, const char *&why, std::string &err) {
     hipStream_t st = (hipStream_t)st_;
     const BgzfChain::Window &win = chain_->windows[w];
-    h2d_ms += up_ms_[w & 1]; up_ms_[w & 1] = 0;
-    if (!win.nonempty) return 0;
+    const bool last = w + 1 == chain_->windows.size();
+    // this window's compressed bytes have arrived (window 0: they travel now); the next window's travel while this one is worked on
+    if (w == 0) upload(0);
+    else if (prefetch_.joinable()) prefetch_.join();
+    if (up_[w & 1].rc) { err = up_[w & 1].err; return up_[w & 1].rc; }
+    h2d_ms += up_[w & 1].ms;
+    if (!last)
+        prefetch_ = std::thread([this, w]() {
+            try { upload(w + 1); }
+            catch (...) { up_[(w + 1) & 1].rc = -4; up_[(w + 1) & 1].err = "out of host memory (uploader)"; }
+        });
     if (carry > CARRY_MAX) { why = "a partial record beyond the room for it"; return 1; }
-    // descriptors relative to the window: the input from its first byte, the text from the buffer's (the carry lies in front)
-    std::vector<BgzfDesc> desc;
-    desc.reserve(win.nonempty);
-    uint64_t at = carry;
-    for (size_t b = win.b0; b < win.b1; b++) {
-        const BgzfChain::Block &k = chain_->blocks[b];
-        if (k.isize) desc.push_back(BgzfDesc{(unsigned long long)(k.in_off - win.in_off + k.hdr), k.bsize - k.hdr - 8, (uint32_t)at, k.isize, k.crc});
-        at += k.isize;
+    double ms = 0;
+    int rc = inflate_block_run(*chain_, win.b0, win.b1, d_in_[w & 1].p, win.in_off, text(w), carry, d_desc_, d_status_, d_bad_, st, ms, nullptr, nullptr, why, err);
+    decode_ms += ms;
+    if (rc) return rc;
+    const uint64_t n = carry + win.text;
+    cut = n; unterminated = false;
+    if (last) {
+        if (!raw) {
+            Tail tail;
+            GZCHK(fetch_tail(text(w), n, tail, st));
+            GZCHK(hipStreamSynchronize(st));
+            if ((rc = trim_text_end(text(w), n, tail, false, st, cut, unterminated, why, err))) return rc;
+        }
+        carry = 0;
+        return 0;
     }
-    const uint32_t nb = (uint32_t)desc.size();
-    uint8_t *d_text = d_text_[w & 1];
-    const double t1 = now_ms();
-    GZCHK(hipMemcpyAsync(d_desc_, desc.data(), (size_t)nb * sizeof(BgzfDesc), hipMemcpyHostToDevice, st));
-    GZCHK(hipMemsetAsync(d_bad_, 0xFF, 64, st));
-    hipLaunchKernelGGL(k_bgzf_decode, dim3(nb), dim3(64), 0, st, (const uint32_t *)d_in_[w & 1], (const BgzfDesc *)d_desc_, nb, d_text,
-                       (uint32_t *)d_status_, (uint32_t *)d_bad_);
-    GZCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_bgzf_crc, dim3((nb + 63) / 64), dim3(64), 0, st, (const uint8_t *)d_text, (const BgzfDesc *)d_desc_, nb, (uint32_t *)d_bad_);
-    GZCHK(hipGetLastError());
-    uint32_t h_bad[2] = {0, 0};
-    GZCHK(hipMemcpyAsync(h_bad, d_bad_, 8, hipMemcpyDeviceToHost, st));
-    GZCHK(hipStreamSynchronize(st));                        // (desc is read by the copy until here)
-    decode_ms += now_ms() - t1;
-    if (h_bad[0] != 0xFFFFFFFFu) { why = "a damaged BGZF block"; return 1; }
-    if (h_bad[1] != 0xFFFFFFFFu) { why = "CRC-32 mismatch"; return 1; }
-    return 0;
-}
-
-int BgzfWindows::last_start(size_t w, uint64_t n, uint64_t &at, std::string &err) {
-    return device_last_start(d_text_[w & 1], n, (unsigned long long *)d_bad_ + 4, (hipStream_t)st_, at, err, CARRY_MAX + 64);
-}
-
-int BgzfWindows::trim_end(size_t w, uint64_t n, uint64_t &e, bool &unterminated, std::string &err) {
-    hipStream_t st = (hipStream_t)st_;
-    char tail[4096];
-    const size_t tail_n = (size_t)std::min<uint64_t>(n, sizeof tail);
-    if (tail_n) GZCHK(hipMemcpyAsync(tail, d_text_[w & 1] + (n - tail_n), tail_n, hipMemcpyDeviceToHost, st));
-    GZCHK(hipStreamSynchronize(st));
-    size_t te = tail_n;                                     // (hand_on_text's rule)
-    for (;;) {
-        if (te >= 2 && tail[te - 1] == '\n' && tail[te - 2] == '\n') { te -= 1; continue; }
-        if (te >= 3 && tail[te - 1] == '\n' && tail[te - 2] == '\r' && tail[te - 3] == '\n') { te -= 2; continue; }
-        break;
+    // the last record start in reach: a start further front leaves more to carry than there is room for
+    if ((rc = device_last_start(text(w), n, (unsigned long long *)d_bad_.p + 4, st, cut, err, CARRY_MAX + 64))) return rc;
+    if (cut == UINT64_MAX) cut = raw ? n : 0;             // (none.  One record's middle: all of it is carried on, if there is room)
+    if (n - cut > CARRY_MAX) {
+        if (!raw) { why = "a partial record beyond the room for it"; return 1; }
+        cut = n;
     }
-    if (te < 8 && n > tail_n) return 1;
-    e = (n - tail_n) + te;
-    unterminated = te == 0 || tail[te - 1] != '\n';
-    GZCHK(hipMemsetAsync(d_text_[w & 1] + e, 0, 32, st));
+    // the carry goes to the next window's buffer first: the parser wants 32 zero bytes behind the cut
+    if (n > cut) GZCHK(hipMemcpyAsync(text(w + 1), text(w) + cut, (size_t)(n - cut), hipMemcpyDeviceToDevice, st));
+    GZCHK(hipMemsetAsync(text(w) + cut, 0, 32, st));
     GZCHK(hipStreamSynchronize(st));
-    return 0;
-}
-
-int BgzfWindows::carry_over(size_t w, uint64_t cut, uint64_t n, std::string &err) {
-    hipStream_t st = (hipStream_t)st_;
-    if (n > cut) GZCHK(hipMemcpyAsync(d_text_[(w + 1) & 1], d_text_[w & 1] + cut, (size_t)(n - cut), hipMemcpyDeviceToDevice, st));
-    GZCHK(hipMemsetAsync(d_text_[w & 1] + cut, 0, 32, st));
-    GZCHK(hipStreamSynchronize(st));
+    carry = n - cut;
     return 0;
 }
 

@@ -1,14 +1,15 @@
 // preprocess.cpp — how reads reach the counting passes.  shk_preprocess tries these routes in this order; a route fails
 // (error set, SHK_E_*), handles the input, or declines having counted nothing, and the next one is tried:
-//   1 route_device_gzip          every file starts with the gzip magic, SHK_GUNZIP_DEVICE != 0, SHK_HOST_PARSER != 1: device
-//                                inflater (a plain member or a BGZF file) -> device parser -> one batch.  Declines when the
+//     (plan_device_gunzip, where every file starts with the gzip magic, SHK_GUNZIP_DEVICE != 0 and SHK_HOST_PARSER != 1,
+//      picks ONE of the first two before anything is uploaded; its decline goes on to route 3)
+//   1 route_device_gzip          device inflater (a plain member or a BGZF file) -> device parser -> one batch.  Declines when the
 //                                inflater or the parser declines or the text exceeds one batch.
-//   2 route_device_bgzf_windows  the same switches; every file is a BGZF chain from its first byte to its last whose text (the
-//                                sum of the blocks' ISIZE fields, known before anything is uploaded) is more than route 1
-//                                takes: beyond one batch, a file of 4 GiB or more, or beyond SHK_GUNZIP_DEVICE_WINDOW where
-//                                that is set.  Window by window: upload, inflate, cut at the last record start, parse, one
-//                                batch each.  The size is looked at FIRST, so such a file never enters route 1; a decline
-//                                (window 0 damaged or not regular) goes on below.
+//   2 route_device_bgzf_windows  every file is a BGZF chain from its first byte to its last whose text (the sum of the blocks'
+//                                ISIZE fields) is more than route 1 takes: beyond one batch, a file of 4 GiB or more, or beyond
+//                                SHK_GUNZIP_DEVICE_WINDOW where that is set.  Window by window (inflate_gpu.h: BgzfWindows —
+//                                upload, inflate, cut at the last record start), parse, one batch each.  The size is looked at
+//                                FIRST, so such a file never enters route 1; a decline (window 0 damaged or not regular) goes
+//                                on below.
 //     (what is gzip is inflated on the host here, once, for the routes below)
 //   3 route_device_pieces(one)   the text fits one batch and is >= SHK_FASTQ_PIPELINE_MIN (64 MiB): cut into a few pieces,
 //                                piece i+1 uploaded while piece i is parsed, counted as ONE batch
@@ -54,10 +55,9 @@ struct Knobs {
     const size_t pieces = (size_t)std::max<long long>(1, (long long)num(getenv("SHK_FASTQ_PIECES"), 4));
     // bases per batch of the host-parsed paths (a batch is limited to 2^32 packed bases by its 32-bit offsets)
     const uint64_t batch_bases = std::min<uint64_t>(std::max<uint64_t>(num(getenv("SHK_BATCH_BASES"), 1ull << 31), 1024), 3ull << 30);
-    // text per window of route 2 (bytes; default 1 GiB — unmeasured so far): a window and its carry fit one batch and 32-bit offsets, and a
-    // window takes at least one block of 64 KiB.  Set: a BGZF file beyond it takes route 2 even where it fits one batch.
-    const bool window_set = getenv("SHK_GUNZIP_DEVICE_WINDOW") && *getenv("SHK_GUNZIP_DEVICE_WINDOW");
-    const uint64_t window = std::max<uint64_t>(std::min<uint64_t>({num(getenv("SHK_GUNZIP_DEVICE_WINDOW"), 1ull << 30), 2 * batch_bases, 3ull << 30}), 65536);
+    // text per window of route 2 (bytes; default 1 GiB — unmeasured so far): a window and its carry fit one batch.  Set: a BGZF
+    // file beyond it takes route 2 even where it fits one batch.
+    const BgzfWindowKnob window = bgzf_window_knob(2 * batch_bases);
 };
 
 // a device block of the parser that goes back to the pool when its owner goes out of scope (every error and
@@ -175,6 +175,31 @@ int host_parse(shk_handle *h, const Knobs &kn, const uint8_t *t, size_t n, Packe
     return rc ? fail_rc(h, Rc::Parser, rc, err) : SHK_OK;
 }
 
+// The rest of a file through the host parser, as a batch of its own: t[0..n) with the record numbers of the whole file
+// (file_reads came before it); reads_done goes in and comes out.
+int host_rest(shk_handle *h, const Knobs &kn, const uint8_t *t, size_t n, const Span &sp, uint64_t file_reads, uint64_t &reads_done) {
+    PackedReads pr;
+    pr.n_reads = reads_done;
+    if (int rc = host_parse(h, kn, t, n, pr, sp, 0, file_reads)) return rc;
+    if (int rc = flush_host_batch(h, pr)) return rc;
+    reads_done = pr.n_reads;
+    return SHK_OK;
+}
+
+// the device parser on a text that lies on the device already (0, 1 not regular 4-line FASTQ, < 0: as gpu_pack_fastq)
+int parse_device_text(shk_handle *h, const GpuText &text, uint64_t reads_done, GpuPacked &gp, std::string &err) {
+    return gpu_pack_fastq(nullptr, 0, nullptr, 0, h->k, h->min_qual, h->progress_every(), h->pipe->stream(), gp, err, reads_done, &text);
+}
+// a device-parsed batch is in: its progress marks, its reads, pass 1 (nothing to count without a segment), its blocks go back
+int device_batch_in(shk_handle *h, Packed &gp, const Span &sp, uint64_t &reads_done, uint64_t *file_reads = nullptr /* of the file the batch lies in */) {
+    post_device_progress(h, gp, sp);
+    reads_done += gp.n_reads;
+    if (file_reads) *file_reads += gp.n_reads;
+    const int rc = gp.n_seg ? count_one_batch(h, gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases) : SHK_OK;
+    gp.reset();
+    return rc;
+}
+
 // start of the first FASTQ record at or after `from` (a line starting with '@' whose line after next starts
 // with '+': a quality line may start with '@' too, but then the line after next is a sequence); n = none,
 // SIZE_MAX = the text does not look like 4-line FASTQ here
@@ -200,15 +225,36 @@ size_t next_record_start(const uint8_t *t, size_t n, size_t from) {
     return SIZE_MAX;
 }
 
-// what shk_preprocess was given, (routes 1 and 2) its BGZF chains as walked, and (from route 3 on) its text
+// what shk_preprocess was given, (routes 1 and 2) its BGZF chains as plan_device_gunzip walked them, and (from route 3 on) its text
 struct Input {
     const uint8_t *fq1, *fq2; size_t n1, n2, total;     // fq2 null: one file; total: the bytes given, the denominator of the progress percentages
     double t0;                                           // when the entry point started
     ByteVec st1, st2;
     const uint8_t *t1 = nullptr, *t2 = nullptr; size_t l1 = 0, l2 = 0;      // the plain text (t2 null, l2 0: one file)
     size_t text_total() const { return l1 + l2; }
-    BgzfChain chain[2]; bool walked[2] = {false, false};      // route 2's walk of a file that is a complete BGZF chain: route 1 does not repeat it
+    BgzfChain chain[2]; bool walked[2] = {false, false};      // a file that is a complete BGZF chain: the inflaters do not walk it again
 };
+
+// Before routes 1 and 2, and before anything is uploaded: 0 some file lacks the gzip magic (neither route), 2 every file is
+// a complete BGZF chain (inflate_gpu.h: bgzf_walk; the chains stay in `in`) whose text — the sum of the blocks' ISIZE
+// fields — is more than route 1 takes and can be cut into windows, 1 otherwise.
+int plan_device_gunzip(const Knobs &kn, Input &in) {
+    const uint8_t *gz[2] = {in.fq1, in.fq2}; const size_t gn[2] = {in.n1, in.fq2 ? in.n2 : 0};
+    const int nf = in.fq2 ? 2 : 1;
+    for (int f = 0; f < nf; f++) if (gn[f] < 18 || gz[f][0] != 0x1F || gz[f][1] != 0x8B) return 0;
+    uint64_t total = 0; bool chains = true, wants = false;
+    for (int f = 0; f < nf; f++) {
+        const char *why = "";
+        size_t bs = 0;
+        in.walked[f] = bgzf_block(gz[f], gn[f], bs) && bgzf_walk(gz[f], gn[f], in.chain[f], why) == 0;
+        chains = chains && in.walked[f];
+        total += in.chain[f].text;
+        wants = wants || in.chain[f].text >= (1ull << 32) || (kn.window.set && in.chain[f].text > kn.window.bytes);
+    }
+    if (!chains || total == 0 || !(wants || total / 2 > kn.batch_bases)) return 1;
+    for (int f = 0; f < nf; f++) if (bgzf_cut_windows(in.chain[f], kn.window.bytes)) return 1;
+    return 2;
+}
 
 // Route 1.  Both files (or the one) are what the device inflater takes — a plain gzip member or a BGZF chain, in any
 // combination within a pair.  Declines (nothing counted) when any file is not taken or turns out not to be regular
@@ -217,7 +263,6 @@ struct Input {
 int route_device_gzip(shk_handle *h, const Knobs &kn, const Input &in) {
     const uint8_t *gz[2] = {in.fq1, in.fq2}; const size_t gn[2] = {in.n1, in.fq2 ? in.n2 : 0};
     const int nf = in.fq2 ? 2 : 1;
-    for (int f = 0; f < nf; f++) if (gn[f] < 18 || gz[f][0] != 0x1F || gz[f][1] != 0x8B) return DECLINED;
     std::string err;
     const double t0 = now_ms();
     Text text[2]; Packed packed[2];
@@ -237,7 +282,7 @@ int route_device_gzip(shk_handle *h, const Knobs &kn, const Input &in) {
     if (sp.total / 2 > kn.batch_bases) return DECLINED;  // (several batches: the host reader's piece-wise path)
     uint64_t reads_done = 0;
     for (int f = 0; f < nf; f++) {
-        const int rc = gpu_pack_fastq(nullptr, 0, nullptr, 0, h->k, h->min_qual, h->progress_every(), h->pipe->stream(), packed[f], err, reads_done, &text[f]);
+        const int rc = parse_device_text(h, text[f], reads_done, packed[f], err);
         if (rc < 0) return fail_rc(h, Rc::Device, rc, err);
         if (rc == 1) { h->pipe->times().add("gunzip_device_not_taken_x1", 1.0); return DECLINED; }      // not regular FASTQ: the host parser owns the messages
         post_device_progress(h, packed[f], sp);
@@ -261,34 +306,18 @@ int route_device_gzip(shk_handle *h, const Knobs &kn, const Input &in) {
     return rc ? rc : finish_counting(h);
 }
 
-// Route 2.  Every file is a complete BGZF chain (inflate_gpu.h: bgzf_walk) whose text is more than route 1 takes.  A window
-// is a run of consecutive blocks of at most kn.window bytes of text: its compressed bytes are uploaded by a helper thread
-// while the window before it is worked on, it is inflated behind the carry (the partial record the window before it ended
-// in), cut at its last record start on the device, parsed there and counted as a batch of its own.
-// *tried: the sizes called for this route (route 1 is then not tried: it would inflate everything to decline).
-// Declines while nothing is counted: a file that is no such chain, window 0 damaged or not regular 4-line FASTQ, no device
-// memory.  Later, whatever goes wrong with a window sends the rest of its file, from that window's first block on and with
-// the carry in front, through the host reader and the host parser, which own the messages (host_rest, as in
-// route_device_pieces); a carry never crosses from file 1 to file 2.
-int route_device_bgzf_windows(shk_handle *h, const Knobs &kn, Input &in, bool *tried) {
+// Route 2.  Every file is a complete BGZF chain whose text is more than route 1 takes (plan_device_gunzip).  A window is a
+// run of consecutive blocks of at most kn.window bytes of text: BgzfWindows::step uploads its compressed bytes while the
+// window before it is worked on, inflates it behind the carry (the partial record the window before it ended in) and cuts
+// it at its last record start on the device; here it is parsed and counted as a batch of its own.
+// Declines while nothing is counted: window 0 damaged or not regular 4-line FASTQ, no device memory.  Later, whatever goes
+// wrong with a window sends the rest of its file, from that window's first block on and with the carry in front, through
+// the host reader and the host parser, which own the messages (host_rest); a carry never crosses from file 1 to file 2.
+int route_device_bgzf_windows(shk_handle *h, const Knobs &kn, const Input &in) {
     const uint8_t *gz[2] = {in.fq1, in.fq2}; const size_t gn[2] = {in.n1, in.fq2 ? in.n2 : 0};
     const int nf = in.fq2 ? 2 : 1;
-    *tried = false;
-    for (int f = 0; f < nf; f++) if (gn[f] < 18 || gz[f][0] != 0x1F || gz[f][1] != 0x8B) return DECLINED;
-    // ---- the plan, before any upload
-    BgzfChain (&chain)[2] = in.chain;
-    uint64_t total = 0; bool wants = false;
-    for (int f = 0; f < nf; f++) {
-        const char *why = "";
-        size_t bs = 0;
-        if (!bgzf_block(gz[f], gn[f], bs) || bgzf_walk(gz[f], gn[f], chain[f], why)) return DECLINED;
-        in.walked[f] = true;
-        total += chain[f].text;
-        wants = wants || chain[f].text >= (1ull << 32) || (kn.window_set && chain[f].text > kn.window);
-    }
-    if (total == 0 || !(wants || total / 2 > kn.batch_bases)) return DECLINED;
-    for (int f = 0; f < nf; f++) if (bgzf_cut_windows(chain[f], kn.window)) return DECLINED;
-    *tried = true;
+    const BgzfChain (&chain)[2] = in.chain;
+    const uint64_t total = chain[0].text + (nf == 2 ? chain[1].text : 0);
     std::string err;
     struct Book {                                         // the timings, on every way out
         shk_handle *h; double h2d = 0, decode = 0, kernels = 0; uint64_t windows = 0, blocks = 0; int nf = 1;
@@ -300,103 +329,64 @@ int route_device_bgzf_windows(shk_handle *h, const Knobs &kn, Input &in, bool *t
             t.add("gunzip_device_h2d", h2d); t.add("gunzip_device_decode", decode); t.add("fastq_device_kernels", kernels);
         }
     } book{h}; book.nf = nf;
-    uint64_t reads_done = 0, file_reads = 0, text_before_file = 0;
+    uint64_t reads_done = 0, text_before_file = 0;
     bool counted_any = false;
-    // the rest of file f from window w on, `carry` in front: host reader, host parser, whole-file record numbers
-    auto host_rest = [&](int f, size_t w, const std::vector<uint8_t> &carry) -> int {
-        const BgzfChain::Window &win = chain[f].windows[w];
-        ByteVec st; const uint8_t *p = nullptr; size_t pn = 0;
-        const double th = now_ms();
-        if (int ri = maybe_inflate(gz[f] + win.in_off, gn[f] - (size_t)win.in_off, st, p, pn, err)) return fail_rc(h, Rc::Inflater, ri, err);
-        h->pipe->times().add("gunzip_host_clock", now_ms() - th);
-        ByteVec joined;
-        if (!carry.empty()) {
-            joined.resize(carry.size() + pn);
-            memcpy(joined.data(), carry.data(), carry.size()); memcpy(joined.data() + carry.size(), p, pn);
-            p = joined.data(); pn = joined.size();
-        }
-        PackedReads pr;
-        pr.n_reads = reads_done;
-        if (int rc = host_parse(h, kn, p, pn, pr, Span{text_before_file + win.text_before - carry.size(), total}, 0, file_reads)) return rc;
-        if (int rc = flush_host_batch(h, pr)) return rc;
-        reads_done = pr.n_reads;
-        return SHK_OK;
-    };
     for (int f = 0; f < nf; f++) {
         const std::vector<BgzfChain::Window> &wins = chain[f].windows;
-        file_reads = 0;
-        std::vector<uint8_t> carry_host;                  // the carry in front of the current window, for host_rest
+        uint64_t file_reads = 0, carry = 0;
+        std::vector<uint8_t> carry_host;                  // the carry in front of the current window, for the host reader
         BgzfWindows bw;
-        // (declared after the buffers: joined before they are released, on every way out)
-        struct Uploader { int rc = 0; std::string err; std::thread t; void join() { if (t.joinable()) t.join(); } ~Uploader() { join(); } } upl;
         // (this file's share of the two sums, on every way out of the file)
         struct Sum { Book &b; BgzfWindows &w; ~Sum() { b.h2d += w.h2d_ms; b.decode += w.decode_ms; } } sum{book, bw};
-        // what the device does not do with window w: nothing is counted yet -> decline; else the host takes the file from here
+        // what the device does not do with window w: nothing is counted yet -> decline; else the host reader takes the file
+        // from that window's first block on, the carry in front
         auto give_up = [&](size_t w) -> int {
-            upl.join(); bw.close();
+            bw.close();
             if (!counted_any) return DECLINED;
-            return host_rest(f, w, carry_host);
+            const BgzfChain::Window &win = wins[w];
+            ByteVec st; const uint8_t *p = nullptr; size_t pn = 0;
+            const double th = now_ms();
+            if (int ri = maybe_inflate(gz[f] + win.in_off, gn[f] - (size_t)win.in_off, st, p, pn, err)) return fail_rc(h, Rc::Inflater, ri, err);
+            h->pipe->times().add("gunzip_host_clock", now_ms() - th);
+            ByteVec joined;
+            if (!carry_host.empty()) {
+                joined.resize(carry_host.size() + pn);
+                memcpy(joined.data(), carry_host.data(), carry_host.size()); memcpy(joined.data() + carry_host.size(), p, pn);
+                p = joined.data(); pn = joined.size();
+            }
+            return host_rest(h, kn, p, pn, Span{text_before_file + win.text_before - carry_host.size(), total}, file_reads, reads_done);
         };
         int rc = bw.open(gz[f], &chain[f], h->pipe->device(), h->pipe->stream(), err);
         if (rc < 0) return fail_rc(h, Rc::DeviceNoParam, rc, err);
-        if (rc == 1) { if (int r = give_up(0)) return r; text_before_file += chain[f].text; continue; }
-        if ((rc = bw.upload(0, err))) return fail_rc(h, Rc::DeviceNoParam, rc, err);
-        uint64_t carry = 0;
-        for (size_t w = 0; w < wins.size(); w++) {
-            const bool last = w + 1 == wins.size();
-            if (!last)
-                upl.t = std::thread([&, w]() {
-                    try { upl.rc = bw.upload(w + 1, upl.err); }
-                    catch (...) { upl.rc = -4; upl.err = "out of host memory (uploader)"; }
-                });
+        bool to_host = rc == 1;
+        size_t w = 0;
+        for (; !to_host && w < wins.size(); w++) {
+            const Span sp{text_before_file + wins[w].text_before - carry, total};
             const char *why = "";                         // (for a debugger: the host reader words the message)
-            rc = bw.inflate(w, carry, why, err);
+            GpuText text;                                 // (the buffer stays bw's)
+            uint64_t cut = 0;
+            rc = bw.step(w, false, carry, cut, text.unterminated, why, err);
             if (rc < 0) return fail_rc(h, Rc::DeviceNoParam, rc, err);
-            bool to_host = rc == 1;
-            const uint64_t n = carry + wins[w].text;
-            uint64_t cut = n; bool unterminated = false;
-            if (!to_host && last) {
-                rc = bw.trim_end(w, n, cut, unterminated, err);
-                if (rc < 0) return fail_rc(h, Rc::DeviceNoParam, rc, err);
-                to_host = rc == 1;
-            } else if (!to_host) {
-                if ((rc = bw.last_start(w, n, cut, err))) return fail_rc(h, Rc::DeviceNoParam, rc, err);
-                if (cut == UINT64_MAX) cut = 0;           // (one record's middle: all of it is carried on, if there is room)
-                to_host = n - cut > BgzfWindows::CARRY_MAX;
-                // the carry goes to the next window's buffer first: the parser wants 32 zero bytes behind the cut
-                if (!to_host) if ((rc = bw.carry_over(w, cut, n, err))) return fail_rc(h, Rc::DeviceNoParam, rc, err);
-            }
+            if ((to_host = rc == 1)) break;
             Packed gp;
-            if (!to_host && cut) {
-                GpuText text; text.d = bw.text(w); text.e = (size_t)cut; text.unterminated = unterminated;      // (the buffer stays bw's)
-                rc = gpu_pack_fastq(nullptr, 0, nullptr, 0, h->k, h->min_qual, h->progress_every(), h->pipe->stream(), gp, err, reads_done, &text);
+            if (cut) {
+                text.d = bw.text(w); text.e = (size_t)cut;
+                rc = parse_device_text(h, text, reads_done, gp, err);
                 if (rc < 0) return fail_rc(h, Rc::Device, rc, err);
-                to_host = rc == 1;                        // not regular FASTQ: the host parser owns the messages
-            }
-            if (to_host) {
-                gp.reset();
-                if (int r = give_up(w)) return r;
-                break;                                    // the rest of this file is done
+                if ((to_host = rc == 1)) break;           // not regular FASTQ: the host parser owns the messages
             }
             book.windows++; book.blocks += wins[w].nonempty;
             if (cut) {
                 if (!counted_any) h->pipe->expect_more_batches();
                 counted_any = true;
                 book.kernels += gp.kernels_ms;
-                post_device_progress(h, gp, Span{text_before_file + wins[w].text_before - carry, total});
-                reads_done += gp.n_reads; file_reads += gp.n_reads;
-                const int rc2 = gp.n_seg ? count_one_batch(h, gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases) : SHK_OK;
-                gp.reset();
-                if (rc2) return rc2;
+                if (int rc2 = device_batch_in(h, gp, sp, reads_done, &file_reads)) return rc2;
             }
-            carry = n - cut;
-            if (last) break;
-            // the carry as the host would need it, and the next window's bytes
+            // the carry as the host would need it
             carry_host.resize((size_t)carry);
             if (carry && device_download(carry_host.data(), bw.text(w + 1), (size_t)carry, err)) return fail(h, SHK_E_DEVICE, err);
-            upl.join();
-            if (upl.rc) return fail_rc(h, Rc::DeviceNoParam, upl.rc, upl.err);
         }
+        if (to_host) if (int r = give_up(w)) return r;  // (0: the rest of this file is done)
         text_before_file += chain[f].text;
     }
     h->n_reads = reads_done;
@@ -449,23 +439,18 @@ int route_device_pieces(shk_handle *h, const Knobs &kn, const Input &in, bool on
     // (declared after the texts: joined before they are released, on every way out, exceptions included)
     struct Uploader { int rc = 0; std::string err; std::thread t; void join() { if (t.joinable()) t.join(); } ~Uploader() { join(); } } upl;
     // the rest of a file through the host parser (a piece that is not regular 4-line FASTQ, or no boundary found)
-    auto host_rest = [&](const Piece &pc) -> int {
-        PackedReads pr;
-        pr.n_reads = reads_done;
+    auto rest_on_host = [&](const Piece &pc) -> int {
         if (int rc = count_kept()) return rc;             // (one_batch: what the device parsed so far is a batch of its own now)
         if (!counted_any) h->pipe->expect_more_batches();
-        if (int rc = host_parse(h, kn, text[pc.file] + pc.off, len[pc.file] - pc.off, pr, Span{(pc.file ? in.n1 : 0) + pc.off, in.total}, 0, file_reads)) return rc;
-        if (int rc = flush_host_batch(h, pr)) return rc;
-        reads_done = pr.n_reads;
         counted_any = true;
-        return SHK_OK;
+        return host_rest(h, kn, text[pc.file] + pc.off, len[pc.file] - pc.off, Span{(pc.file ? in.n1 : 0) + pc.off, in.total}, file_reads, reads_done);
     };
     for (size_t i = 0; i < pieces.size(); i++) {
         const Piece pc = pieces[i];
         if (i == 0 || pieces[i - 1].file != pc.file) file_reads = 0;
         if (pc.host_rest) {
             if (!counted_any && i == 0) return DECLINED;
-            if (int rc = host_rest(pc)) return rc;
+            if (int rc = rest_on_host(pc)) return rc;
             continue;
         }
         if (!cur.d)
@@ -480,14 +465,14 @@ int route_device_pieces(shk_handle *h, const Knobs &kn, const Input &in, bool on
             });
         Packed gp;
         const double tp0 = now_ms();
-        int rc = gpu_pack_fastq(nullptr, 0, nullptr, 0, h->k, h->min_qual, h->progress_every(), h->pipe->stream(), gp, err, reads_done, &cur);
+        int rc = parse_device_text(h, cur, reads_done, gp, err);
         h->pipe->times().add("fastq_piece_parse_host_clock", now_ms() - tp0);
         if (rc < 0) return fail_rc(h, Rc::Device, rc, err);
         if (rc == 1) {
             gp.reset();
             upl.join(); cur.reset(); nxt.reset();
             if (!counted_any) return DECLINED;
-            if (int rc2 = host_rest(Piece{pc.file, pc.off, len[pc.file], true})) return rc2;
+            if (int rc2 = rest_on_host(Piece{pc.file, pc.off, len[pc.file], true})) return rc2;
             while (i + 1 < pieces.size() && pieces[i + 1].file == pc.file) i++;      // the rest of this file is done
             continue;
         }
@@ -495,14 +480,12 @@ int route_device_pieces(shk_handle *h, const Knobs &kn, const Input &in, bool on
         h->pipe->times().add("fastq_h2d_text", gp.h2d_ms);
         h->pipe->times().add("fastq_device_kernels", gp.kernels_ms);
         h->pipe->times().add("fastq_device_pieces_x1", 1.0);
-        post_device_progress(h, gp, Span{(pc.file ? in.n1 : 0) + pc.off, in.total});
-        reads_done += gp.n_reads; file_reads += gp.n_reads;
-        if (one_batch) kept.push_back(std::move(gp));     // (counted with the other pieces at the end)
-        else {
-            const int rc2 = gp.n_seg ? count_one_batch(h, gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases) : SHK_OK;
-            gp.reset();
-            if (rc2) return rc2;
-        }
+        const Span sp{(pc.file ? in.n1 : 0) + pc.off, in.total};
+        if (one_batch) {                                  // (counted with the other pieces at the end)
+            post_device_progress(h, gp, sp);
+            reads_done += gp.n_reads; file_reads += gp.n_reads;
+            kept.push_back(std::move(gp));
+        } else if (int rc2 = device_batch_in(h, gp, sp, reads_done, &file_reads)) return rc2;
         counted_any = true;
         // hand over to the uploaded next piece
         const double tj0 = now_ms();
@@ -561,9 +544,9 @@ int preprocess_impl(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t 
     // ... unless it is a BGZF file beyond what fits at once: that is seen in the blocks' trailers before anything is uploaded
     int rc = DECLINED;
     if (device && kn.gunzip_device) {
-        bool windows_tried = false;
-        rc = route_device_bgzf_windows(h, kn, in, &windows_tried);
-        if (rc == DECLINED && !windows_tried) rc = route_device_gzip(h, kn, in);
+        const int plan = plan_device_gunzip(kn, in);
+        if (plan == 2) rc = route_device_bgzf_windows(h, kn, in);      // (a decline goes on below: route 1 would inflate everything to decline)
+        else if (plan == 1) rc = route_device_gzip(h, kn, in);
     }
     if (rc != DECLINED) return rc;
     // whatever the device inflater does not take (several plain members, a broken BGZF chain, binary data, a damaged
@@ -605,11 +588,9 @@ int push_reads_impl(shk_handle *h, const uint8_t *chunk, size_t n) {
             rc = gpu_pack_fastq(t, l, nullptr, 0, h->k, h->min_qual, h->progress_every(), h->pipe->stream(), gp, err, h->stream_reads.n_reads);
             if (rc < 0) return fail_rc(h, Rc::Device, rc, err);
             if (rc == 0) {
-                post_device_progress(h, gp, no_pct);
                 h->pipe->times().add("fastq_device_chunks_x1", 1.0);
-                const int rc2 = gp.n_seg ? count_one_batch(h, gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases) : SHK_OK;
-                h->stream_reads.n_reads += gp.n_reads; h->stream_reads.n_input_bases += gp.n_input_bases;
-                return rc2;
+                h->stream_reads.n_input_bases += gp.n_input_bases;
+                return device_batch_in(h, gp, no_pct, h->stream_reads.n_reads);
             }
             // (rc == 1, not regular 4-line FASTQ: the host parser decides)
         }

@@ -84,6 +84,42 @@ def test_windowed_gunzip_gives_zlibs_bytes(lib, monkeypatch):
             assert got == want, (window, name, len(got), len(want))
 
 
+def test_windowed_gunzip_names_the_reason(lib, monkeypatch):
+    """A damaged block is declined for the same reason through the windows as in one shot (one inflater serves both): block 9
+    of 16 with ISIZE one less, one bit of its CRC-32 flipped, one bit in the middle of its deflate data flipped — windows of
+    100 000 bytes hold one block each, so that block is decoded in mid-buffer, behind a carry.  Both ways return 1 with
+    the same words; the intact file gives zlib's bytes both ways."""
+    text = fastq_text()[:1_000_000]
+    z = synth.bgzf_compress(text)
+    bl = blocks_of(z)
+    assert len(bl) == 17 and z.endswith(EOF_BLOCK)            # 16 blocks of text and the end-of-file block
+    assert gzip.decompress(z) == text
+    at, bsize = bl[9]
+    trailer = at + bsize - 8
+
+    def damaged(where, mask):
+        b = bytearray(z)
+        b[where] ^= mask
+        return bytes(b)
+    isize = struct.unpack_from("<I", z, trailer + 4)[0]
+    less = bytearray(z)
+    struct.pack_into("<I", less, trailer + 4, isize - 1)
+    cases = [("ISIZE minus one", bytes(less)), ("a bit of the CRC-32", damaged(trailer + 2, 0x01)), ("a bit of the deflate data", damaged(at + bsize // 2, 0x04))]
+
+    def both_ways(f):
+        _with_env(monkeypatch, GUNZIP_DEVICE_MIN=32768)
+        one_shot = device_gunzip(lib, f)
+        _with_env(monkeypatch, GUNZIP_DEVICE_MIN=32768, GUNZIP_DEVICE_WINDOW=100000)
+        return one_shot, device_gunzip(lib, f)
+    for got in both_ways(z):
+        assert got[0] == 0 and got[1] == text, got[0::2]
+    for name, bad in cases:
+        one_shot, windowed = both_ways(bad)
+        print(name, one_shot[0::2], windowed[0::2])
+        assert one_shot[0] == 1 and windowed[0] == 1, (name, one_shot[0::2], windowed[0::2])
+        assert one_shot[2] and one_shot[2] == windowed[2], (name, one_shot[2], windowed[2])
+
+
 def window_buffers(lib, z, text, budget):
     """the text buffers of the route's windows: the carry of the window before, then the window's text"""
     isize = np.array([struct.unpack_from("<I", z, o + b - 4)[0] for o, b in blocks_of(z)], dtype=np.uint32)
