@@ -25,14 +25,6 @@
 #include <type_traits>
 #include "kmer.h"
 
-// Timing experiments (parts of a kernel switched off: wrong results) exist only in `make ABLATE=1` builds,
-// which produce libshk_hip_ablate.so; in the shipped library every SHK_DBG(...) is the constant 0 and the
-// branches behind it are compiled out (they also cost registers in kernels that run one workgroup per CU).
-#ifndef SHK_ABLATE
-#define SHK_ABLATE 0
-#endif
-#define SHK_DBG(x) (SHK_ABLATE ? (uint32_t)(x) : 0u)
-
 namespace shk {
 
 static constexpr int PART_THREADS = 1024;            // pass 1: 4 waves per SIMD
@@ -43,9 +35,6 @@ struct PartParams {
     uint32_t P, G, slice_cap;
     int k, m;
     uint32_t max_n;
-    uint32_t dbg_nostore;        // timing experiments only (SHK_DEBUG_NOSTORE): 1 = every record to slot 0 of its slice, 2 = no flush
-    uint32_t dbg_flush_at;       // timing experiments only (SHK_DEBUG_P1FLUSH, ABLATE builds): descriptors a lane may hold before its wave flushes
-    unsigned long long *dbg_clk; // timing experiments only (SHK_DEBUG_P1CLK, ABLATE builds): wave-cycles per phase of k_partition, summed over the waves
 };
 
 template <int RW> struct Rec { uint64_t w[RW]; };
@@ -203,9 +192,7 @@ __device__ __forceinline__ void part_store_record(const uint64_t (&out)[RW], uin
 // was spilled around EVERY load, a wait for memory each.)
 template <int RW>
 __device__ __forceinline__ uint32_t wave_flush(SHK_LDS PartSharedT<RW> *sh_l, uint32_t wave, uint32_t cnt, uint32_t fpos,
-                                            int k, uint32_t G, uint32_t slice_cap, uint32_t g, SHK_GLOBAL uint64_t *recs_g,
-                                            uint32_t dbg_arg = 0) {
-    const uint32_t dbg = SHK_DBG(dbg_arg);
+                                            int k, uint32_t G, uint32_t slice_cap, uint32_t g, SHK_GLOBAL uint64_t *recs_g) {
     PartSharedT<RW> *sh = (PartSharedT<RW> *)sh_l;       // address space is inferred from the cast
     uint64_t *recs = (uint64_t *)recs_g;
     const uint32_t lane = threadIdx.x & 63u;
@@ -222,27 +209,15 @@ __device__ __forceinline__ uint32_t wave_flush(SHK_LDS PartSharedT<RW> *sh_l, ui
             const uint32_t p = ds & 0x3FFFu, n1 = ds >> 14;
             const uint32_t off = fpos;
             fpos += n1 + 1u;
-            if (dbg != 2) {                                      // (2: timing experiment, the walk alone)
-                // LDS cursor of slice [p][g].  No branch on the room: a record behind the end of its slice goes to the slice's last
-                // slot (the cursor keeps counting, the host sees the overflow and repeats both passes with the exact room, so what
-                // pass 2 read from that slot meanwhile is thrown away) — with a branch the compiler sinks the loads of the bases
-                // behind the wait for the cursor, one more LDS round trip per record
-                // (timing experiments 3 .. 6: no cursor atomic / no bases and mask / no store / no mask)
-                const uint32_t idx = dbg == 3 ? (fpos & 15u) : min(atomicAdd(&sh->cursor[p], 1u), slice_cap - 1u);
-                uint64_t r[RW];
-                if (dbg == 4) {
-#pragma unroll
-                    for (int o = 0; o < RW; o++) r[o] = ((uint64_t)off << 20) | n1;
-                } else part_build_record<RW>(sh->stage + wave * WSTAGE, dbg == 6 ? sh->rmask : sh->rmask + n1 * (2 * RW), off, n1, k, r);
-                const uint32_t slice = p * G + g;                            // (P * G <= 2^22)
-                if (dbg == 7) {                                              // (timing experiment: every record twice, side by side — twice the requests, the same lines)
-                    const uint32_t i2 = min(2u * idx, slice_cap - 2u);
-                    part_store_record<RW>(r, recs + ((uint64_t)slice * slice_cap + i2) * RW);
-                    part_store_record<RW>(r, recs + ((uint64_t)slice * slice_cap + i2 + 1u) * RW);
-                } else
-                if (dbg != 5) part_store_record<RW>(r, recs + ((uint64_t)slice * slice_cap + (dbg == 1 ? 0u : idx)) * RW);
-                else if (r[0] == 0x1234567ull) recs[0] = r[1];               // (keeps the record alive)
-            }
+            // LDS cursor of slice [p][g].  No branch on the room: a record behind the end of its slice goes to the slice's last
+            // slot (the cursor keeps counting, the host sees the overflow and repeats both passes with the exact room, so what
+            // pass 2 read from that slot meanwhile is thrown away) — with a branch the compiler sinks the loads of the bases
+            // behind the wait for the cursor, one more LDS round trip per record
+            const uint32_t idx = min(atomicAdd(&sh->cursor[p], 1u), slice_cap - 1u);
+            uint64_t r[RW];
+            part_build_record<RW>(sh->stage + wave * WSTAGE, sh->rmask + n1 * (2 * RW), off, n1, k, r);
+            const uint32_t slice = p * G + g;                            // (P * G <= 2^22)
+            part_store_record<RW>(r, recs + ((uint64_t)slice * slice_cap + idx) * RW);
         }
         ds = ds_next;
     }
@@ -305,12 +280,6 @@ __global__ __launch_bounds__(PART_THREADS) void k_partition(const uint32_t *__re
     SHK_LDS uint32_t *const stage_l = (SHK_LDS uint32_t *)&sh.stage[wave * WSTAGE];
     const uint32_t *const stage = (const uint32_t *)stage_l;
     SHK_LDS uint32_t *const dbase = (SHK_LDS uint32_t *)&sh.desc[wave][0][lane];
-#if SHK_ABLATE
-    unsigned long long clk_pre = 0, clk_walk = 0, clk_flush = 0, clk_tail = 0, clk_t0 = 0;
-#define SHK_CLK(x) x
-#else
-#define SHK_CLK(x)
-#endif
     auto load_seg = [&](uint32_t T, uint32_t &s0, uint32_t &s1) {      // lanes behind the last segment get an empty one
         const uint32_t i = min(64u * T + (uint32_t)lane, n_seg);
         s0 = seg_off[i]; s1 = seg_off[min(i + 1u, n_seg)];
@@ -340,7 +309,6 @@ __global__ __launch_bounds__(PART_THREADS) void k_partition(const uint32_t *__re
         const uint32_t n_here = min(64u, n_seg - 64u * T);
         bool first_tile = true;
         while (start < n_here) {
-            SHK_CLK(clk_t0 = __builtin_amdgcn_s_memtime();)
             // ---- the tile: which lanes walk what
             const Plan pl = (first_tile && prefetched) ? pl_pf : plan(s0c, s1c, start);
             uint32_t L = 0, rel = 0, w0 = pl.w0, nwords = pl.nwords;
@@ -432,14 +400,11 @@ __global__ __launch_bounds__(PART_THREADS) void k_partition(const uint32_t *__re
             uint32_t fpos = rel;                             // where this lane's first unflushed run starts
             // the waves of one SIMD flush at different fill levels: a flush is a chain of LDS round trips,
             // it overlaps with the VALU-bound walk of the others only if they do not all flush together
-            SHK_LDS uint32_t *const flush_at = dbase + 64u * (SHK_DBG(pp.dbg_flush_at) ? min(SHK_DBG(pp.dbg_flush_at), LDESC_CAP - DESC_CHECK) - min(wave >> 2, SHK_DBG(pp.dbg_flush_at) - 1u)
-                                                                                          : LDESC_CAP - DESC_CHECK - (wave >> 2));
+            SHK_LDS uint32_t *const flush_at = dbase + 64u * (LDESC_CAP - DESC_CHECK - (wave >> 2));
             auto flush = [&]() {
-                SHK_CLK(const unsigned long long f0 = __builtin_amdgcn_s_memtime();)
                 fpos = wave_flush<RW>((SHK_LDS PartSharedT<RW> *)&sh, wave, ((uint32_t)(uintptr_t)dptr - (uint32_t)(uintptr_t)dbase) >> 8, fpos, k, pp.G, pp.slice_cap, g,
-                                      (SHK_GLOBAL uint64_t *)recs, SHK_DBG(pp.dbg_nostore));
+                                      (SHK_GLOBAL uint64_t *)recs);
                 dptr = dbase;
-                SHK_CLK(clk_flush += __builtin_amdgcn_s_memtime() - f0;)
             };
             const uint32_t n_mmers_max = maxL >= (uint32_t)m ? maxL - (uint32_t)m + 1u : 0u;
             const uint32_t n_blocks = (n_mmers_max + WBLK - 1) / WBLK;
@@ -494,7 +459,6 @@ __global__ __launch_bounds__(PART_THREADS) void k_partition(const uint32_t *__re
 #pragma unroll
                 for (int t = WBLK - 2; t >= 0; t--) srs[t] = min(hreg[t], srs[t + 1]);
             };
-            SHK_CLK({ const unsigned long long t1 = __builtin_amdgcn_s_memtime(); clk_pre += t1 - clk_t0; clk_t0 = t1; })
             for (uint32_t bq = 0; bq < n_blocks; bq++) {
                 // The next tile's words (requested before the walk) are waited for HERE, a few blocks in and before this tile's
                 // first record leaves: loads and stores share one in-order counter, and a wait placed where the words are used —
@@ -514,17 +478,14 @@ __global__ __launch_bounds__(PART_THREADS) void k_partition(const uint32_t *__re
                     }
                 }
             }
-            SHK_CLK({ const unsigned long long t1 = __builtin_amdgcn_s_memtime(); clk_walk += t1 - clk_t0; clk_t0 = t1; })
             // close the last run of every segment (it ends with the segment's last k-mer)
             if (__ballot(dptr >= dbase + 64u * LDESC_CAP)) flush();
             if (run_p != NO_RUN) emit((L - (uint32_t)k + max_n) << 14);
             if (__ballot(dptr != dbase)) flush();
             start = next_start; round = next_round;
-            SHK_CLK(clk_tail += __builtin_amdgcn_s_memtime() - clk_t0;)
         }
         s0c = s0n; s1c = s1n; s0n = s0nn; s1n = s1nn;
     }
-    SHK_CLK(if (pp.dbg_clk && lane == 0) { atomicAdd(pp.dbg_clk + 0, clk_pre); atomicAdd(pp.dbg_clk + 1, clk_walk); atomicAdd(pp.dbg_clk + 2, clk_flush); atomicAdd(pp.dbg_clk + 3, clk_tail); atomicAdd(pp.dbg_clk + 4, 1ull); })
     __syncthreads();
     // publish this workgroup's slice fills (may exceed slice_cap: the host then retries bigger) and
     // their maximum (one global atomic per workgroup)
@@ -756,14 +717,12 @@ template <int W, typename LT>
 __device__ __forceinline__ void table_emit(KmerTable<W> &tb, CountCtlCore &ctl, unsigned long long mine, uint32_t threshold,
                                            unsigned long long *__restrict__ histo, KeyArr<W> out_keys,
                                            uint32_t *__restrict__ out_cnt, unsigned long long out_cap,
-                                           unsigned long long *__restrict__ out_cursor, LT *list, uint32_t dbg_arg = 0,
+                                           unsigned long long *__restrict__ out_cursor, LT *list,
                                            uint32_t *hist_accum = nullptr /* LDS: the round's histogram is added here instead of to `histo` */,
                                            uint32_t bias = 0 /* Bloom mode: the occurrence that only set the filter's bits */,
                                            const EmitRanges &er = EmitRanges{}, uint32_t er_g = 0xFFFFFFFFu /* the group recorded in er */) {
-    const uint32_t dbg = SHK_DBG(dbg_arg);
     constexpr uint32_t S = KmerTable<W>::S;
     const int lane = threadIdx.x & 63;
-    if (dbg == 10) return;                                  // (timing experiments 10, 11, 4: stop after successive stages)
     for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
     if (lane == 0 && mine) atomicAdd(&ctl.n_inst, mine);
     for (uint32_t s = threadIdx.x; s < S; s += COUNT_THREADS) {
@@ -782,11 +741,10 @@ __device__ __forceinline__ void table_emit(KmerTable<W> &tb, CountCtlCore &ctl, 
         wb = __shfl(wb, 0);
         if (e) list[wb + (uint32_t)__popcll(em & ((1ull << lane) - 1ull))] = (LT)s;
     }
-    if (dbg == 11) return;
     __syncthreads();
     const uint32_t n_emit = ctl.n_emit;
     if (threadIdx.x == 0) {
-        unsigned long long base = (n_emit && dbg != 5) ? atomicAdd(out_cursor, (unsigned long long)n_emit) : 0ull;
+        unsigned long long base = n_emit ? atomicAdd(out_cursor, (unsigned long long)n_emit) : 0ull;
         if (er.tab_cursor && er_g != 0xFFFFFFFFu) {         // (both reservations in flight together: one round trip)
             const uint32_t sz = gp_table_size(n_emit);
             const unsigned long long tab_base = atomicAdd(er.tab_cursor, ((unsigned long long)n_emit << 32) | sz);
@@ -796,11 +754,11 @@ __device__ __forceinline__ void table_emit(KmerTable<W> &tb, CountCtlCore &ctl, 
     }
     if (hist_accum) {                                       // (thread b owns bin b: no atomics)
         for (uint32_t b = threadIdx.x; b < 500; b += COUNT_THREADS) hist_accum[b] += ctl.histo[b];
-    } else if (dbg != 1) {                                  // (dbg 1: timing experiment, no global histogram flush)
+    } else {
         for (uint32_t b = threadIdx.x; b < 500; b += COUNT_THREADS)
             if (ctl.histo[b]) atomicAdd(&histo[b], (unsigned long long)ctl.histo[b]);
     }
-    if (!n_emit || dbg == 4) return;                        // (uniform)
+    if (!n_emit) return;                                    // (uniform)
     __syncthreads();
     const unsigned long long gbase = ((unsigned long long)ctl.emit_base_hi << 32) | ctl.emit_base_lo;
     for (uint32_t i = threadIdx.x; i < n_emit; i += COUNT_THREADS) {
@@ -834,7 +792,6 @@ struct RunView {
     const uint32_t *run_cnt;
     uint32_t S;            // runs per partition (<= 256)
     int k;
-    uint32_t dbg;          // timing experiments only (SHK_DEBUG_P2)
     // sharded counting with records deduplicated by their source rank (k_dedupe_partitions): the record at address
     // 16 * (rec_base16 + i * W) stands for weights[i] identical records.  nullptr: every record counts once.
     const uint32_t *weights = nullptr;
@@ -1018,7 +975,6 @@ __global__ __launch_bounds__(COUNT_THREADS) void k_count_partitions(
     const uint32_t R = ctl.pre[S_runs];
     // a k-mer count can only reach 2^32 (SPEC S4: saturating) in a partition of >= 2^32 instances = R x (<= 64 per record)
     const bool sat = R >= (1u << 26) || WEIGHTED;
-    if (SHK_DBG(rvw.dbg) == 5) return;                            // timing experiment: launch + run prefix only
 
     // hand the whole partition to the k-mer-level repartition (k_ovf_scatter / k_count_buckets): report the
     // estimated number of distinct k-mers (distinct / instance ratio of what was inserted before the table
@@ -1129,23 +1085,20 @@ __global__ __launch_bounds__(COUNT_THREADS) void k_count_partitions(
         uint32_t have_nxt = fetch(w_begin + (uint32_t)lane, nxt, w_nxt);
         uint32_t have_nxt2 = fetch(w_begin + 64u + (uint32_t)lane, nxt2, w_nxt2);
         if (threadIdx.x == 0) ctl.prog_den = R ? R : 1u;
-        for (uint32_t r0 = w_begin; r0 < (SHK_DBG(rvw.dbg) == 6 ? w_begin : w_end); r0 += 64) {
+        for (uint32_t r0 = w_begin; r0 < w_end; r0 += 64) {
             // the table filled up: stop early (every insert into a full table walks a long probe chain);
             // how far this round got (all waves advance alike) sizes the split
             if (ctl.overflow || ctl.n_used > (S / 10) * 9) { atomicMax(&ctl.prog_num, min(R, (r0 - w_begin) * (COUNT_THREADS / 64) + 1u)); break; }
             Rec<RW> rec = nxt;
             const uint32_t n = have_nxt ? (uint32_t)(rec.w[RW - 1] >> 58) + 1u : 0u;
             // one spelling per locus (pass 1 is bound by its instruction issue, this pass by latencies: done here)
-            if (n && SHK_DBG(rvw.dbg) != 11) rec_canonicalise<RW>(rec.w, n, k);
+            if (n) rec_canonicalise<RW>(rec.w, n, k);
             const uint32_t wgt = w_nxt;
             nxt = nxt2; have_nxt = have_nxt2; w_nxt = w_nxt2;
             have_nxt2 = fetch(r0 + 128u + (uint32_t)lane, nxt2, w_nxt2);
             // phase A: identical records (the same genomic run seen in many reads) are counted
             // once here and expanded once, with their multiplicity, in phase B
-            if (SHK_DBG(rvw.dbg) == 4) { if (n && rec.w[0] == 0x123456789ull) ctl.overflow = 1; }   // timing experiment: fetch only
-            else if (SHK_DBG(rvw.dbg) == 2) { if (n) expand(rec, n, wgt); }
-            else if (SHK_DBG(rvw.dbg) == 7) { if (n) (void)rec_insert<W>(tb.rt, ctl, rec, wgt); }      // timing experiment: dedupe only
-            else if (n && !rec_insert<W>(tb.rt, ctl, rec, wgt)) {
+            if (n && !rec_insert<W>(tb.rt, ctl, rec, wgt)) {
                 // the record table is saturated.  If that happens in the first half of the records, most of
                 // them are unique (error-rich reads): their k-mers cannot fit the k-mer table either, so the
                 // round is given up at once when the k-mer-level repartition can take over (always correct)
@@ -1153,7 +1106,6 @@ __global__ __launch_bounds__(COUNT_THREADS) void k_count_partitions(
                 else expand(rec, n, wgt);
             }
         }
-        if (SHK_DBG(rvw.dbg) == 10) return;                          // timing experiment: phase A only, no phase B
         {
             // phase B: every distinct record once, weighted.  The occupied slots are first listed in
             // order of record length (counting sort in LDS) so that the 64 records a wave expands
@@ -1162,7 +1114,6 @@ __global__ __launch_bounds__(COUNT_THREADS) void k_count_partitions(
             auto &rt = tb.rt;
             if (threadIdx.x < 64) rt.nhist[threadIdx.x] = 0;
             __syncthreads();
-            if (SHK_DBG(rvw.dbg) != 3)
             for (uint32_t s = threadIdx.x; s < SRc; s += COUNT_THREADS)
                 if (rt.rst[s] >= 3u) atomicAdd(&rt.nhist[(uint32_t)(rt.w[s][RW - 1] >> 58)], 1u);
             __syncthreads();
@@ -1174,30 +1125,25 @@ __global__ __launch_bounds__(COUNT_THREADS) void k_count_partitions(
                 if (threadIdx.x == 63) ctl.n_recs = incl;
             }
             __syncthreads();
-            if (SHK_DBG(rvw.dbg) != 3)
             for (uint32_t s = threadIdx.x; s < SRc; s += COUNT_THREADS)
                 if (rt.rst[s] >= 3u) rt.order[atomicAdd(&rt.nbase[(uint32_t)(rt.w[s][RW - 1] >> 58)], 1u)] = (uint16_t)s;
             __syncthreads();
-            uint32_t n_recs = ctl.n_recs;
-            if (SHK_DBG(rvw.dbg) == 3) n_recs = SRc;                 // timing experiment: slot order instead of length order
+            const uint32_t n_recs = ctl.n_recs;
             // (a table that filled up in phase A keeps its progress mark; phase B then stops at once)
             if (threadIdx.x == 0 && ctl.prog_num == 0) ctl.prog_den = n_recs ? n_recs : 1u;
             __syncthreads();
             for (uint32_t i = threadIdx.x; i < n_recs; i += COUNT_THREADS) {
                 if (ctl.overflow || ctl.n_used > (S / 10) * 9) { atomicMax(&ctl.prog_num, i - threadIdx.x + 1u); break; }
-                const uint32_t s = SHK_DBG(rvw.dbg) == 3 ? i : rt.order[i];
-                if (SHK_DBG(rvw.dbg) == 3 && rt.rst[s] < 3u) continue;
+                const uint32_t s = rt.order[i];
                 Rec<RW> rec;
 #pragma unroll
                 for (int o = 0; o < RW; o++) rec.w[o] = rt.w[s][o];
-                if (SHK_DBG(rvw.dbg) != 1) expand(rec, (uint32_t)(rec.w[RW - 1] >> 58) + 1u, rt.rst[s] - 2u);
+                expand(rec, (uint32_t)(rec.w[RW - 1] >> 58) + 1u, rt.rst[s] - 2u);
             }
         }
         __syncthreads();
         const bool over = ctl.overflow != 0 || ctl.n_used > (S / 10) * 9;
-        if (SHK_DBG(rvw.dbg) == 8) return;                           // timing experiment: no defer / emit work at all
         if (over && ovf && mod == 1) {
-            if (SHK_DBG(rvw.dbg) == 9) return;                       // timing experiment: overflow detected, nothing reported
             defer(mine, true);
             return;
         }
@@ -1218,7 +1164,7 @@ __global__ __launch_bounds__(COUNT_THREADS) void k_count_partitions(
         }
         // (phase B is over: the record table's multiplicity words are free to hold the emit list)
         static_assert(2u * decltype(tb.rt)::SR >= S, "emit list");
-        table_emit<W>(tb, ctl, mine, threshold, histo, out_keys, out_cnt, out_cap, out_cursor, reinterpret_cast<uint16_t *>(tb.rt.rst), 0u, whist);
+        table_emit<W>(tb, ctl, mine, threshold, histo, out_keys, out_cnt, out_cap, out_cursor, reinterpret_cast<uint16_t *>(tb.rt.rst), whist);
     }
     if (threadIdx.x == 0 && ovf && defer_after) atomicAdd(&ovf_n[1], 1u);                          // tried, and it fitted
    }();
@@ -1373,10 +1319,9 @@ __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_dedupe_partit
         for (uint32_t r0 = w_begin; r0 < w_end; r0 += 64) {
             Rec<RW> rec = nxt;
             const uint32_t n = have_nxt ? (uint32_t)(rec.w[RW - 1] >> 58) + 1u : 0u;
-            if (n && SHK_DBG(rvw.dbg) != 21) rec_canonicalise<RW>(rec.w, n, k);
+            if (n) rec_canonicalise<RW>(rec.w, n, k);
             nxt = nxt2; have_nxt = have_nxt2;
             have_nxt2 = fetch(r0 + 128u + (uint32_t)lane, nxt2);
-            if (SHK_DBG(rvw.dbg) == 21 || SHK_DBG(rvw.dbg) == 22) { if (n && rec.w[0] == 0x123456789ull) ctl.n_emit = 1; continue; }   // timing experiments: fetch (+ canonical spelling) only
             // (the table is saturated and holds no copy within a few probes: passed through, once)
             const bool pass = n && !rec_insert<W>(tb.rt, ctl, rec);
             const unsigned long long m = __ballot(pass);
@@ -1421,7 +1366,7 @@ __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_dedupe_partit
             }
         }
         if (hand) { hand_over(); continue; }
-        for (uint32_t s = threadIdx.x; s < (SHK_DBG(rvw.dbg) == 23 ? 0u : SR); s += COUNT_THREADS) {     // (23: timing experiment, nothing written)
+        for (uint32_t s = threadIdx.x; s < SR; s += COUNT_THREADS) {
             const uint32_t st = rt.rst[s];
             if (st < 3u) continue;
             const uint32_t at = atomicAdd(&rt.nbase[(uint32_t)(rt.w[s][RW - 1] >> 58)], 1u);
@@ -1453,11 +1398,10 @@ __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_count_weighte
     unsigned long long *__restrict__ n_inst, OvfRec *__restrict__ ovf, uint32_t *__restrict__ ovf_n,
     unsigned long long *__restrict__ work_and_tally /* low word: groups handed out, zero at launch; high word: this kernel's tally, tried |
                                                        overflowed << 16, which k_dedupe_partitions starts at its verdict — ONE atomic fetches both */,
-    uint32_t probe_groups, uint32_t defer_after, uint32_t dbg_arg /* timing experiments (ABLATE builds) */,
+    uint32_t probe_groups, uint32_t defer_after,
     EmitRanges er /* where each group's rows went (build_graph's partitions); tab_cursor nullptr: not recorded */) {
     constexpr int RW = 2 * W;
     constexpr uint32_t S = KmerTable<W>::S;
-    const uint32_t dbg = SHK_DBG(dbg_arg);
     __shared__ KmerTable<W> tb;
     __shared__ CountCtlCore ctl;
     constexpr uint32_t ELIST = W == 1 ? S : 64;         // emit list: W >= 2 reuses the state words
@@ -1512,7 +1456,6 @@ __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_count_weighte
         }
         kmer_table_reset<W>(tb, ctl);                                    // (ends with a barrier)
         mine = 0;
-        if (dbg != 31)
         for (uint32_t r0 = 0; r0 < Rt; r0 += COUNT_THREADS) {
             if (ctl.overflow || ctl.n_used > (S / 10) * 9) break;
             Rec<RW> rec = nxt; const uint32_t weight = w_nxt;
@@ -1539,8 +1482,7 @@ __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_count_weighte
 #pragma unroll
                 for (int j = 0; j < W; j++) c.w[j] = use_r ? rv.w[j] : f.w[j];
                 const uint32_t h = km_mix32<W>(c);
-                if (dbg == 33) { if (h == 0x12345u && c.w[0] == 77ull) ctl.overflow = 1; }       // timing experiment: roll + hash, no insert
-                else if (!lds_insert<W>(tb, ctl, c, h ^ __builtin_amdgcn_alignbit(h, h, 19), weight, true)) ctl.overflow = 1;
+                if (!lds_insert<W>(tb, ctl, c, h ^ __builtin_amdgcn_alignbit(h, h, 19), weight, true)) ctl.overflow = 1;
                 mine += weight;
             }
         }
@@ -1549,9 +1491,8 @@ __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_count_weighte
     };
     // (er_g: the group whose rows this round emits whole, recorded in er; NIL: a member of a group counted member by member)
     auto emit = [&](uint32_t er_g) {
-        if (dbg == 32) return;                                           // timing experiment: no emit
-        if constexpr (W == 1) table_emit<W>(tb, ctl, mine, threshold, histo, out_keys, out_cnt, out_cap, out_cursor, elist, 0u, whist, 0u, er, er_g);
-        else table_emit<W>(tb, ctl, mine, threshold, histo, out_keys, out_cnt, out_cap, out_cursor, tb.state, 0u, whist, 0u, er, er_g);
+        if constexpr (W == 1) table_emit<W>(tb, ctl, mine, threshold, histo, out_keys, out_cnt, out_cap, out_cursor, elist, whist, 0u, er, er_g);
+        else table_emit<W>(tb, ctl, mine, threshold, histo, out_keys, out_cnt, out_cap, out_cursor, tb.state, whist, 0u, er, er_g);
     };
     auto mark_broken = [&]() { if (threadIdx.x == 0 && er.broken) *er.broken = 1u; };
     // hand partition p to the k-mer-level repartition: exact instances, estimated distinct k-mers (of the attempt just made)
@@ -1790,9 +1731,8 @@ __global__ __launch_bounds__(COUNT_THREADS, 8) void k_count_buckets(   // 8 wave
     const BucketRef *__restrict__ list, uint32_t n_list, const uint64_t *__restrict__ kmers,
     uint32_t threshold, unsigned long long *__restrict__ histo, KeyArr<W> out_keys, uint32_t *__restrict__ out_cnt,
     unsigned long long out_cap, unsigned long long *__restrict__ out_cursor,
-    unsigned long long *__restrict__ n_inst, uint32_t *__restrict__ flags, uint32_t dbg_arg /* timing experiments (ABLATE builds) */,
+    unsigned long long *__restrict__ n_inst, uint32_t *__restrict__ flags,
     uint32_t bias /* Bloom mode: 1 */, unsigned long long *__restrict__ n_keys /* Bloom mode: distinct k-mers that reached a table */) {
-    const uint32_t dbg = SHK_DBG(dbg_arg);
     constexpr uint32_t S = KmerTable<W>::S;
     // k-mers per thread that travel in registers: covers the bucket size the host aims for (<= 1.1 S, binomial
     // spread of a few per cent); the rare longer bucket is read from memory by the residue path below
@@ -1827,8 +1767,8 @@ __global__ __launch_bounds__(COUNT_THREADS, 8) void k_count_buckets(   // 8 wave
     unsigned long long my_keys = 0;                      // (thread 0: table keys over all buckets of this workgroup)
     auto emit = [&](unsigned long long mine) {
         if (bias && threadIdx.x == 0) my_keys += ctl.n_used;
-        if constexpr (W == 1) table_emit<W>(tb, ctl, mine, threshold, histo, out_keys, out_cnt, out_cap, out_cursor, elist, dbg, whist, bias);
-        else table_emit<W>(tb, ctl, mine, threshold, histo, out_keys, out_cnt, out_cap, out_cursor, tb.state, dbg, whist, bias);   // (the state words are not read after counting)
+        if constexpr (W == 1) table_emit<W>(tb, ctl, mine, threshold, histo, out_keys, out_cnt, out_cap, out_cursor, elist, whist, bias);
+        else table_emit<W>(tb, ctl, mine, threshold, histo, out_keys, out_cnt, out_cap, out_cursor, tb.state, whist, bias);   // (the state words are not read after counting)
     };
     uint32_t e = blockIdx.x;
     BucketRef ref = load_ref(e), ref_n = load_ref(e + gridDim.x);
@@ -1855,14 +1795,13 @@ __global__ __launch_bounds__(COUNT_THREADS, 8) void k_count_buckets(   // 8 wave
                 if ((uint32_t)u * COUNT_THREADS < nb && !(ctl.overflow || ctl.n_used > (S / 10) * 9)) {   // (whole waves: uniform enough for the ballot)
                     const uint32_t i = (uint32_t)u * COUNT_THREADS + threadIdx.x;
                     bool fresh = false;
-                    if (i < nb && dbg != 3) {
+                    if (i < nb) {
                         const uint32_t h = km_mix32<W>(kv[u]);
                         const int r = lds_insert<W, false>(tb, ctl, kv[u], h ^ __builtin_amdgcn_alignbit(h, h, 19), 1u);
                         if (!r) ctl.overflow = 1;
                         fresh = r == 2;
                         mine++;
                     }
-                    if (dbg == 3 && i < nb && kv[u].w[0] == 0x123456789ull) ctl.overflow = 1;
                     // most k-mers of an error-rich bucket are new keys: one LDS atomic per wave for the fill level
                     const unsigned long long fm = __ballot(fresh);
                     if (lane == 0 && fm) atomicAdd(&ctl.n_used, (uint32_t)__popcll(fm));
@@ -1872,7 +1811,6 @@ __global__ __launch_bounds__(COUNT_THREADS, 8) void k_count_buckets(   // 8 wave
             // the registers are free again: the next bucket's k-mers travel while this one is scanned,
             // its rows reserved and written
             if (ref.nb && ref.nb <= PF_MAX) fetch_all(ref, kv);
-            if (dbg == 2 || dbg == 3) continue;                          // timing experiments: no emit
             __syncthreads();
             if (!(ctl.overflow != 0 || ctl.n_used > (S / 10) * 9)) { emit(mine); done = true; }
         } else if (ref.nb && ref.nb <= PF_MAX) fetch_all(ref, kv);
@@ -1941,10 +1879,9 @@ __global__ __launch_bounds__(COUNT_THREADS, 8) void k_count_buckets(   // 8 wave
         }
     }
     __syncthreads();
-    if (dbg != 1)
     for (uint32_t b = threadIdx.x; b < 500; b += COUNT_THREADS)
         if (whist[b]) atomicAdd(&histo[b], (unsigned long long)whist[b]);
-    if (threadIdx.x == 0 && ctl.n_inst && dbg != 8) atomicAdd(n_inst, ctl.n_inst);
+    if (threadIdx.x == 0 && ctl.n_inst) atomicAdd(n_inst, ctl.n_inst);
     if (threadIdx.x == 0 && bias && my_keys) atomicAdd(n_keys, my_keys);
 }
 

@@ -456,7 +456,6 @@ __global__ __launch_bounds__(NT) void k_graph_local(KeyArr<W> keys, int k, Graph
             occ[t8] = (uint8_t)bits;
         }
     }
-    if (SHK_DBG(gt.dbg) == 1) { if (threadIdx.x == 0) qcnt[P] = 0; return; }     // timing experiment: table build only
     // ---- neighbours
     unsigned long long *myq = queries + 8ull * r0;
     const int lane = threadIdx.x & 63;
@@ -475,8 +474,7 @@ __global__ __launch_bounds__(NT) void k_graph_local(KeyArr<W> keys, int k, Graph
                 const uint2 a = gt.scan[i], b = gt.scan[(size_t)gt.scan_n + i], c = gt.scan[2 * (size_t)gt.scan_n + i];
                 ms.first.fh = a.x; ms.first.rh = a.y; ms.last.fh = b.x; ms.last.rh = b.y; ms.min_wo_first = c.x; ms.min_wo_last = c.y;
                 ms.h_first = min(a.x, a.y); ms.h_last = min(b.x, b.y);
-            } else
-            if (SHK_DBG(gt.dbg) != 2) ms = km_min_scan_lut<W>(x, k, gt.gm, lut, all_a);      // (2: timing experiment without the scan)
+            } else ms = km_min_scan_lut<W>(x, k, gt.gm, lut, all_a);
             if (ranges && ((ms.min_all() & gt.gp_mask) != P)) *overflow = 2u;         // (the row is not of this group's minimiser)
             out_b = km_base<W>(x, k, k - (int)gm);                 // first base of the last gm-mer
             last_b = km_base<W>(x, k, (int)gm - 1);                // last base of the first gm-mer
@@ -491,9 +489,7 @@ __global__ __launch_bounds__(NT) void k_graph_local(KeyArr<W> keys, int k, Graph
                 p = hmin & gt.gp_mask;
                 if (gt.world > 1) { xowner = gt.owner_of(hmin); cross = xowner != gt.rank; }     // (sharded assembly: the candidate lives on another rank)
                 remote = cross || p != P || !in_lds;
-                if (SHK_DBG(gt.dbg) == 3) remote = false;                       // timing experiment: scan + candidates only
-                if (SHK_DBG(gt.dbg) == 4 && remote) { remote = false; }         // timing experiment: no remote queue
-                else if (!remote && SHK_DBG(gt.dbg) != 3) {
+                if (!remote) {
                     bool o; const Kmer<W> c = adj_candidate<W>(x, rx, k, j, o);
                     const uint64_t h = gt_hash<W>(c);
                     const uint32_t fp = (uint32_t)(h >> 32);

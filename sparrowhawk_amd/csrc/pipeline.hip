@@ -102,7 +102,6 @@ struct GraphTable {                            // entry = fingerprint<<32 | node
     const uint32_t *msk;                       // [GP] its size - 1 (power of two)
     uint32_t gp_mask;                          // GP - 1
     int gm;                                    // minimiser length of the graph partition function
-    uint32_t dbg;                              // timing experiments only (SHK_DEBUG_G)
     // sharded assembly (one process per GPU): a k-mer lives on rank ((minimiser hash & cp_mask) % world) — the owner of
     // its counting partition.  world == 1: everything is local.  world_inv = ceil(2^32 / world) (exact quotients below 2^16)
     uint32_t cp_mask = 0, world = 1, rank = 0, world_inv = 0;
@@ -369,14 +368,6 @@ struct EvTimer {
 static inline uint64_t env_u64(const char *name, uint64_t dflt) {
     const char *v = getenv(name);
     return (v && *v) ? strtoull(v, nullptr, 10) : dflt;
-}
-// SHK_DEBUG_* (timing experiments: results are wrong) are read by `make ABLATE=1` builds only
-static inline uint32_t env_dbg(const char *name) {
-#if SHK_ABLATE
-    return (uint32_t)env_u64(name, 0);
-#else
-    (void)name; return 0u;
-#endif
 }
 
 // Two fills in one launch (a step of the pipeline made sixteen hipMemsetAsync calls, 5-6 us of the GPU each and most of them a
@@ -646,21 +637,7 @@ public:
         const uint64_t inst_ub = n_bases - n_seg * (uint64_t)(k_ - 1);
         const int cus = n_cus_;
         const uint64_t n_super = (n_seg + PART_THREADS - 1) / PART_THREADS;
-        pp_.k = k_; pp_.m = k_ - wblk + 1; pp_.dbg_nostore = env_dbg("SHK_DEBUG_NOSTORE");
-        pp_.dbg_clk = nullptr; pp_.dbg_flush_at = env_dbg("SHK_DEBUG_P1FLUSH");
-#if SHK_ABLATE
-        if (env_dbg("SHK_DEBUG_P1CLK")) {                   // (timing experiment: the buffer is leaked on purpose, the report goes to stderr)
-            static unsigned long long *clk = nullptr;
-            if (!clk) (void)hipMalloc((void **)&clk, 64);
-            else {
-                unsigned long long h[8] = {0};
-                (void)hipDeviceSynchronize(); (void)hipMemcpy(h, clk, 64, hipMemcpyDeviceToHost);
-                if (h[4]) fprintf(stderr, "[p1clk] per wave: pre %.0f walk(incl. flush) %.0f flush %.0f tail %.0f cycles (%llu waves)\n", (double)h[0] / h[4], (double)h[1] / h[4], (double)h[2] / h[4], (double)h[3] / h[4], h[4]);
-            }
-            (void)hipMemset(clk, 0, 64);
-            pp_.dbg_clk = clk;
-        }
-#endif
+        pp_.k = k_; pp_.m = k_ - wblk + 1;
         pp_.max_n = std::min<uint32_t>(32u * RW - 3u - (uint32_t)(k_ - 1), 63u);
         if (uint64_t mn = env_u64("SHK_PART_MAXN", 0)) pp_.max_n = std::min<uint32_t>(pp_.max_n, (uint32_t)mn);
         pp_.G = (uint32_t)std::min<uint64_t>((uint64_t)std::min(cus, 256), n_super);
@@ -783,7 +760,7 @@ public:
                            (uint32_t)RW, run_off_.p, run_cnt_.p);
         HIPCHK(hipGetLastError());
         run_view_.run_addr16 = run_off_.p; run_view_.run_cnt = run_cnt_.p;
-        run_view_.S = pp_.G; run_view_.k = k_; n_count_parts_ = pp_.P; run_view_.dbg = env_dbg("SHK_DEBUG_P2");
+        run_view_.S = pp_.G; run_view_.k = k_; n_count_parts_ = pp_.P;
         return 0;
     }
 
@@ -871,7 +848,7 @@ public:
         HIPCHK(hipMemcpyAsync(run_cnt_.p, cnt.data(), n_runs * 4, hipMemcpyHostToDevice, stream_));
         WAIT_STREAM();
         run_view_.run_addr16 = run_off_.p; run_view_.run_cnt = run_cnt_.p;
-        run_view_.S = nb; run_view_.k = k_; n_count_parts_ = pp_.P; run_view_.dbg = 0;
+        run_view_.S = nb; run_view_.k = k_; n_count_parts_ = pp_.P;
         have_parts_ = true;
         return 0;
     }
@@ -968,8 +945,7 @@ public:
                                    dd_recs_.p, dd_w_.p, dd_base_.p, dd_n_.p, 0u, n_parts, merge, rv.k, threshold, dh.p, ok, cnt.p, (unsigned long long)cap,
                                    // (ctl_[14]: the groups handed out and, in its high word, this kernel's tally — it starts at the dedupe's verdict
                                    // and covers reads whose records repeat but whose k-mers do not fit)
-                                   ctl_.p + 0, ctl_.p + 1, d_ovf.p, (uint32_t *)(ctl_.p + 3), ctl_.p + 14, 0u, defer_after,
-                                   env_dbg("SHK_DEBUG_P2"), er);
+                                   ctl_.p + 0, ctl_.p + 1, d_ovf.p, (uint32_t *)(ctl_.p + 3), ctl_.p + 14, 0u, defer_after, er);
             } else {
                 // (persistent workgroups, one per CU: the tables take the whole LDS)
                 auto kern = rv.weights ? k_count_partitions<W, true> : k_count_partitions<W, false>;
@@ -1078,8 +1054,7 @@ public:
                         const uint32_t bgrid = (uint32_t)std::min<unsigned long long>(n_list, 2ull * (unsigned long long)n_cus_);
                         hipLaunchKernelGGL(k_count_buckets<W>, dim3(bgrid), dim3(COUNT_THREADS), 0, stream_,
                                            d_blist.p, (uint32_t)n_list, d_kmers.p, threshold, dh.p, ok, cnt.p, (unsigned long long)cap,
-                                           ctl_.p + 0, ctl_.p + 1, (uint32_t *)(ctl_.p + 2), env_dbg("SHK_DEBUG_B"),
-                                           bloom ? 1u : 0u, ctl_.p + 9);
+                                           ctl_.p + 0, ctl_.p + 1, (uint32_t *)(ctl_.p + 2), bloom ? 1u : 0u, ctl_.p + 9);
                         HIPCHK(hipGetLastError());
                         WAIT_STREAM();      // d_items / d_kmers are reused by the next pass
                     }
@@ -1410,7 +1385,7 @@ public:
         }
         shard_recv_ = d_recv;
         run_view_.run_addr16 = run_off_.p; run_view_.run_cnt = run_cnt_.p;
-        run_view_.S = n_sources; run_view_.k = k_; n_count_parts_ = n_owned; run_view_.dbg = 0;
+        run_view_.S = n_sources; run_view_.k = k_; n_count_parts_ = n_owned;
         run_view_.weights = (const uint32_t *)d_recv_w; run_view_.rec_base16 = (unsigned long long)(uintptr_t)d_recv >> 4;
         uint64_t total_recs = 0;
         for (uint32_t j = 0; j < n_owned; j++) {          // a partition's record index is 32 bits wide in pass 2
@@ -1469,7 +1444,7 @@ public:
         Graph<W> g;
         for (int j = 0; j < W; j++) g.keys.w[j] = skeys_[j].p;
         g.cnt = scnt_.p; g.adj = adj_.p; g.nb = nb_.p; g.k = k_;
-        g.gt.e = gt_.p; g.gt.occ = gt_occ_.p; g.gt.scan = gt_scan_.p; g.gt.scan_n = gt_scan_.p ? (uint32_t)n_solid_ : 0u; g.gt.off = gt_off_.p; g.gt.msk = gt_msk_.p; g.gt.gp_mask = gp_ - 1u; g.gt.gm = part_m(k_); g.gt.dbg = env_dbg("SHK_DEBUG_G");
+        g.gt.e = gt_.p; g.gt.occ = gt_occ_.p; g.gt.scan = gt_scan_.p; g.gt.scan_n = gt_scan_.p ? (uint32_t)n_solid_ : 0u; g.gt.off = gt_off_.p; g.gt.msk = gt_msk_.p; g.gt.gp_mask = gp_ - 1u; g.gt.gm = part_m(k_);
         g.n = (uint32_t)n_solid_;
         if (sh_active_) {                                   // sharded assembly: which rank owns a neighbour candidate
             g.gt.cp_mask = sh_P_ - 1u; g.gt.world = sh_world_; g.gt.rank = sh_rank_;
