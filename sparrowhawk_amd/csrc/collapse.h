@@ -340,7 +340,10 @@ __global__ __launch_bounds__(256) void k_orphan_cycles(Graph<W> g, const uint8_t
         if (!ok) { flags[0] = 1; continue; }
         if (best != v || (v & 1u)) continue;                // not the cut point / the mirror strand
         const uint32_t idx = atomicAdd(n_spl, 1u);
-        if (idx >= seg_cap) { flags[0] = 2; continue; }
+        // (no room: the count goes back, so that it never stays above seg_cap — the ranking kernels behind this one index their
+        // arrays by it before the host has seen flag 2 and repeated the pass.  Once the count has reached seg_cap it never drops
+        // below it again, so every entry below the final count has been written.)
+        if (idx >= seg_cap) { flags[0] = 2; atomicSub(n_spl, 1u); continue; }
         spl[idx] = v;
         cur = v;
         for (uint32_t j = 0; j < n; j++) {                     // every node a fragment of its own, owned by the new splitter

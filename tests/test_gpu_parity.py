@@ -9,7 +9,7 @@ import pytest
 import cases
 from sparrowhawk_amd import AssemblyHelper, ShkError, synth
 from util import (compare_all, int_to_words, make_dataset, parse_fastq, py_count, revcomp,
-                  run_oracle, sorted_table)
+                  run_oracle, sorted_table, with_env as _with_env)
 
 pytestmark = pytest.mark.gpu
 
@@ -430,20 +430,6 @@ def test_device_packed_entry_matches_host_entry():
     h.assemble()
     assert a.get_assembly() == h.get_assembly()
     assert a.get_preprocessing_info() == h.get_preprocessing_info()
-
-
-def _with_env(env, fn):
-    import os
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update({k: str(v) for k, v in env.items()})
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def test_counting_modes_agree():

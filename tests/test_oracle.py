@@ -202,12 +202,14 @@ def test_output_formats():
 
 
 # ---- the graph stages (SPEC S8-S11) against a brute-force Python graph written from the SPEC alone -------------
-def _random_graph_case(rng, case):
+def _random_graph_case(rng, case, wide=False):
     """<= 3 kbp of sequence built to exercise the correction and collapse rules: substitution errors (tips at read
     ends, bubbles inside), exact and inverted repeats (forks, hairpins), circular plasmids (rings), low coverage
-    (dead ends, gaps).  Returns (fastq bytes, k, min_count, flags)."""
-    k = int(rng.choice([15, 17, 21, 25, 31, 33, 41]))
-    L = int(rng.integers(300, 3001 if case % 8 == 0 else 1501))
+    (dead ends, gaps).  Returns (fastq bytes, k, min_count, flags).
+    wide: keys of two to eight words (k = 63 ... 255), the genome 4 k longer and the reads k + 20 / 60 / 150 long, so
+    that the same structures still form; off, no draw changes."""
+    k = int(rng.choice([63, 65, 95, 127, 129, 191, 255] if wide else [15, 17, 21, 25, 31, 33, 41]))
+    L = int(rng.integers(300, 3001 if case % 8 == 0 else 1501)) + (4 * k if wide else 0)
     g = "".join(rng.choice(list("ACGT"), L))
     style = case % 6
     if style in (1, 4):                                   # a direct repeat longer than k
@@ -226,7 +228,7 @@ def _random_graph_case(rng, case):
         p = int(rng.integers(0, L)); replicons[0] = (g[:p] + u * int(rng.integers(2, 5)) + g[p:], False)
     cov = float(rng.choice([6, 10, 16, 30]))
     err = float(rng.choice([0.0, 0.003, 0.01, 0.03]))
-    rl = int(rng.choice([60, 100, 150]))
+    rl = k + int(rng.choice([20, 60, 150])) if wide else int(rng.choice([60, 100, 150]))
     recs = []
     for seq, circ in replicons:
         n = max(2, int(len(seq) * cov / rl))
@@ -256,6 +258,40 @@ def _int_to_kmer(v, k):
     return "".join("ACGT"[(v >> (2 * (k - 1 - i))) & 3] for i in range(k))
 
 
+def _pin_case_with_pygraph(fq, k, min_count, flags, case, stats):
+    """One input through tests/pygraph.py and through the oracle: solid set, counts, initial adjacency bytes, the node set
+    and adjacency after correction, the ordered contig list with its count sums, FASTA, GFA1 and the removal counts."""
+    from pygraph import PyGraph
+    W = (2 * k + 63) // 64
+    counts = {}                                           # (every base is ACGT at quality 'I': S2 masks nothing)
+    for rd, _q in parse_fastq(fq):
+        for i in range(len(rd) - k + 1):
+            s = rd[i:i + k]
+            r = revcomp(s)
+            x = s if s < r else r
+            counts[x] = counts.get(x, 0) + 1
+    pg = PyGraph(counts, k, min_count)
+    o = run_oracle([fq], k=k, min_count=min_count, min_qual=0, **flags)
+    keys, cnt = o.solid()
+    ok = [_int_to_kmer(sum(int(keys[i, j]) << (64 * j) for j in range(W)), k) for i in range(len(cnt))]
+    assert ok == sorted(pg.alive), f"case {case}: solid sets differ"
+    assert [int(c) for c in cnt] == [pg.count[x] for x in ok]
+    assert o.adjacency().tolist() == [pg.adjacency_byte(x) for x in ok], f"case {case}: initial adjacency differs"
+    pg.correct(tips=not flags["no_dead_end_removal"], bubbles=not flags["no_bubble_collapse"])
+    o.assemble()
+    assert [bool(a) for a in o.alive()] == [x in pg.alive for x in ok], f"case {case}: node set after correction differs"
+    assert o.adjacency().tolist() == [pg.adjacency_byte(x) if x in pg.alive else a for x, a in zip(ok, o.adjacency().tolist())], \
+        f"case {case}: adjacency after correction differs"
+    contigs, fasta, gfa = pg.assembly()
+    assert o.contigs() == [s for s, _ in contigs], f"case {case}: contigs differ"
+    assert [int(x) for x in o.contig_kc()] == [kc for _, kc in contigs]
+    assert o.fasta() == fasta and o.gfa1() == gfa, f"case {case}: FASTA / GFA1 differ"
+    assert (o.tips_removed, o.bubbles_removed) == (pg.tips_removed, pg.bubbles_removed), f"case {case}: removal counts differ"
+    stats["tips"] += pg.tips_removed; stats["bubbles"] += pg.bubbles_removed
+    stats["rings"] += pg.n_rings
+    stats["contigs"] += len(contigs); stats["links"] += gfa.count("\nL\t")
+
+
 @pytest.mark.parametrize("block", range(8))
 def test_graph_stages_against_a_brute_force_python_graph(block):
     """VERDICT r2 'weak' 2: S8-S10 of the oracle were pinned only by hand cases and by cpu_mt.cpp (same author, same
@@ -263,38 +299,79 @@ def test_graph_stages_against_a_brute_force_python_graph(block):
     oriented nodes, the rules of S9/S10 spelled literally.  320 random inputs (40 per block) with errors, repeats,
     hairpins, plasmids and tandem rings: initial adjacency bytes, the node set after correction, the ordered contig
     list with its count sums, the FASTA and the GFA1 (links included) must be identical."""
-    from pygraph import PyGraph
     rng = np.random.default_rng(int(os.environ.get("SHK_UG_FUZZ_SEED", 7000)) + block)      # (another seed: a longer campaign)
     stats = dict(tips=0, bubbles=0, rings=0, contigs=0, links=0)
     for case in range(block * 40, block * 40 + 40):
         fq, k, min_count, flags = _random_graph_case(rng, case)
-        W = (2 * k + 63) // 64
-        counts = {}                                       # (every base is ACGT at quality 'I': S2 masks nothing)
-        for rd, _q in parse_fastq(fq):
-            for i in range(len(rd) - k + 1):
-                s = rd[i:i + k]
-                r = revcomp(s)
-                x = s if s < r else r
-                counts[x] = counts.get(x, 0) + 1
-        pg = PyGraph(counts, k, min_count)
-        o = run_oracle([fq], k=k, min_count=min_count, min_qual=0, **flags)
-        keys, cnt = o.solid()
-        ok = [_int_to_kmer(sum(int(keys[i, j]) << (64 * j) for j in range(W)), k) for i in range(len(cnt))]
-        assert ok == sorted(pg.alive), f"case {case}: solid sets differ"
-        assert [int(c) for c in cnt] == [pg.count[x] for x in ok]
-        assert o.adjacency().tolist() == [pg.adjacency_byte(x) for x in ok], f"case {case}: initial adjacency differs"
-        pg.correct(tips=not flags["no_dead_end_removal"], bubbles=not flags["no_bubble_collapse"])
-        o.assemble()
-        assert [bool(a) for a in o.alive()] == [x in pg.alive for x in ok], f"case {case}: node set after correction differs"
-        assert o.adjacency().tolist() == [pg.adjacency_byte(x) if x in pg.alive else a for x, a in zip(ok, o.adjacency().tolist())], \
-            f"case {case}: adjacency after correction differs"
-        contigs, fasta, gfa = pg.assembly()
-        assert o.contigs() == [s for s, _ in contigs], f"case {case}: contigs differ"
-        assert [int(x) for x in o.contig_kc()] == [kc for _, kc in contigs]
-        assert o.fasta() == fasta and o.gfa1() == gfa, f"case {case}: FASTA / GFA1 differ"
-        assert (o.tips_removed, o.bubbles_removed) == (pg.tips_removed, pg.bubbles_removed), f"case {case}: removal counts differ"
-        stats["tips"] += pg.tips_removed; stats["bubbles"] += pg.bubbles_removed
-        stats["rings"] += pg.n_rings
-        stats["contigs"] += len(contigs); stats["links"] += gfa.count("\nL\t")
+        _pin_case_with_pygraph(fq, k, min_count, flags, case, stats)
     # the campaign really exercises every rule
     assert stats["tips"] > 0 and stats["bubbles"] > 0 and stats["rings"] > 0 and stats["links"] > 0, stats
+
+
+WIDE_BLOCKS, WIDE_PER_BLOCK = 2, 12
+
+
+def wide_graph_cases(block):
+    """The wide-key campaign's inputs of one block: (case, fastq, k, min_count, flags).  Shared with the GPU run of the
+    same inputs (test_gpu_graph_small.py)."""
+    rng = np.random.default_rng(int(os.environ.get("SHK_WIDE_GRAPH_SEED", 9300)) + block)
+    for case in range(block * WIDE_PER_BLOCK, (block + 1) * WIDE_PER_BLOCK):
+        yield (case,) + _random_graph_case(rng, case, wide=True)
+
+
+@pytest.mark.parametrize("block", range(WIDE_BLOCKS))
+def test_graph_stages_against_a_brute_force_python_graph_wide_keys(block):
+    """The same pin for keys of two to eight words (k = 63 ... 255): the GPU tests at those widths trust the oracle's graph
+    stage, which the campaign above pins only up to k = 41.  24 inputs, the assertions of the test above.
+    Measured with seed 9300 — block 0: 8806 tips, 219 bubbles, 2 rings, 300 contigs, 48 links; block 1: 7130 tips, no
+    bubble, 1 ring, 461 contigs, 250 links.  The closing assert names what each block reaches."""
+    stats = dict(tips=0, bubbles=0, rings=0, contigs=0, links=0)
+    for case, fq, k, min_count, flags in wide_graph_cases(block):
+        _pin_case_with_pygraph(fq, k, min_count, flags, case, stats)
+    print("wide-key campaign, block", block, stats)
+    assert stats["tips"] > 0 and stats["rings"] > 0 and stats["links"] > 0 and (block != 0 or stats["bubbles"] > 0), stats
+
+
+SMALL_GRAPH_CASES = 160
+
+
+def small_graph_cases(upto=SMALL_GRAPH_CASES):
+    """Cases 0 ... upto-1 of the small-graph campaign, always drawn from case 0 of one generator, so that a case is the same
+    whichever part of the campaign asks for it: (case, fastq, k, min_count, flags)."""
+    seed = int(os.environ.get("SHK_SMALL_GRAPH_SEED", 9100))
+    rng, got = _small_graph_cache.setdefault(seed, (np.random.default_rng(seed), []))
+    while len(got) < upto:                                 # (drawn once per session, in order: 14 ms a case)
+        got.append((len(got),) + _random_graph_case(rng, len(got)))
+    return got[:upto]
+
+
+_small_graph_cache = {}
+
+
+def test_small_graph_campaign_reaches_every_class():
+    """test_gpu_graph_small.py sends cases 0 ... 159 of seed 9100 through every path of the one-GPU graph stage and ties its
+    path markers to the oracle's contig count.  That is worth what the 160 cases reach: this says so on the CPU, so that a
+    change to the generator or the seed cannot hollow the GPU test out unnoticed."""
+    from test_gpu_graph_small import VARIANTS
+    n1 = n_mid = n_big = none_removed = some_removed = self_links = other_links = 0
+    per_variant = {name: 0 for name, _, _ in VARIANTS}
+    for case, fq, k, min_count, flags in small_graph_cases():
+        o = run_oracle([fq], k=k, min_count=min_count, min_qual=0, **flags)
+        o.assemble()
+        nc = len(o.contigs())
+        assert nc > 0, f"case {case}: empty assembly"
+        n1 += nc == 1; n_mid += 257 <= nc <= 512; n_big += nc > 512
+        removed = o.tips_removed + o.bubbles_removed
+        none_removed += removed == 0; some_removed += removed > 0
+        for l in o.gfa1().split("\n"):
+            if l.startswith("L\t"):
+                f = l.split("\t")
+                self_links += f[1] == f[3] and f[2] == f[4]; other_links += f[1] != f[3]      # (a ring links to itself on one strand)
+        for i in range(2):
+            per_variant[VARIANTS[(2 * case + i) % len(VARIANTS)][0]] += 1
+    got = dict(one_contig=n1, contigs_257_512=n_mid, contigs_above_512=n_big, none_removed=none_removed, some_removed=some_removed,
+               self_links=self_links, other_links=other_links)
+    assert n1 >= 1 and n_mid >= 1 and n_big >= 1, got
+    assert none_removed >= 20 and some_removed >= 20, got
+    assert self_links >= 1 and other_links >= 1, got
+    assert min(per_variant.values()) >= 12, per_variant

@@ -1,6 +1,7 @@
 """Shared helpers for the parity tests: pure-Python restatements used to pin the oracle,
 and the stage-by-stage product-vs-oracle comparison."""
 import json
+import os
 
 import numpy as np
 
@@ -149,6 +150,25 @@ def run_oracle(fq_list, **kw):
         o.add_fastq(fq)
     o.count(naive=False)
     return o
+
+
+def with_env(env, fn):
+    """fn() with these environment variables set (a value of None: removed), everything restored afterwards.  The product
+    reads its knobs when a handle is made and while it works, so fn makes the handle and runs it."""
+    old = {k: os.environ.get(k) for k in env}
+    for k, v in env.items():
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = str(v)
+    try:
+        return fn()
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
 
 
 def compare_all(helper, oracle, check_graph=True):
