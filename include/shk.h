@@ -254,10 +254,16 @@ int shk_device_gunzip(const uint8_t *gz, size_t n, uint8_t **out, size_t *out_n,
  * one record per strand of a unitig; first / last: [n_recs][W] words of its first / last k-mer as spelled; min_*: the
  * smallest oriented node of a record and its position, read for the records of rings only).  Exposed for the CPU tests.
  * Returns a malloc'd text (shk_host_free): "removed <tip nodes> <bubble nodes>", then one line per contig
- * "<ring> <rot> <nodes> <kc> : <record> <record> ...", or NULL on inconsistent input. */
+ * "<ring> <rot> <nodes> <kc> : <record> <record> ...", "error: <what>" on inconsistent records, or NULL on bad parameters. */
 char *shk_host_unitig_assemble(uint32_t k, uint64_t n_recs, const uint64_t *first, const uint64_t *last, const uint64_t *len,
                                const uint64_t *kc, const uint8_t *circ, const uint64_t *min_key, const uint8_t *min_o,
                                const uint64_t *min_pos, int tips, int bubbles);
+/* The same on the current HIP device (csrc/unitig_graph_gpu.h: the index of chain starts, the links, the tip and bubble
+ * rounds and the simple successors as kernels; the chains are walked by the host code from what comes back).  Same
+ * parameters, the same text byte for byte, "error: ..." included; needs a GPU. */
+char *shk_device_unitig_assemble(uint32_t k, uint64_t n_recs, const uint64_t *first, const uint64_t *last, const uint64_t *len,
+                                 const uint64_t *kc, const uint8_t *circ, const uint64_t *min_key, const uint8_t *min_o,
+                                 const uint64_t *min_pos, int tips, int bubbles);
 
 /* Device buffers of freed handles are cached process-wide for the next handle (a handle lives
  * for one preprocess+assemble); this returns the cache to the driver.  SHK_NO_POOL=1 disables it. */

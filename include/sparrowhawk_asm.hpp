@@ -1,7 +1,9 @@
 // sparrowhawk_asm.hpp — header-only C++ mirror of the reference's AssemblyHelper
 // (/root/reference/www/src/workers/Assembler.ts:15-39) over the C ABI in shk.h.  Same five
 // members, same argument order; throws std::runtime_error where the Rust crate panics
-// (Assembler.ts:93-106 catches that as a JS exception).
+// (Assembler.ts:93-106 catches that as a JS exception).  The stage-level helpers of shk.h — the host-only
+// shk_host_* self tests, shk_device_gunzip, shk_device_unitig_assemble — have no counterpart in the
+// reference's interface and are not mirrored here: call them through shk.h.
 #pragma once
 #include <stdexcept>
 #include <string>

@@ -18,6 +18,7 @@
 #include "inflate_mt.h"
 #include "preprocess.h"
 #include "unitig_graph.h"
+#include "unitig_graph_gpu.h"
 
 namespace shk { bool spectrum_fit(const uint64_t *histo500, uint32_t *out); }   // fit.cpp
 
@@ -835,9 +836,10 @@ int shk_host_gunzip(const uint8_t *gz, size_t n, uint8_t **out, size_t *out_n, u
         return SHK_OK;
     } catch (...) { return SHK_E_OOM; }
 }
-char *shk_host_unitig_assemble(uint32_t k, uint64_t n_recs, const uint64_t *first, const uint64_t *last, const uint64_t *len,
-                               const uint64_t *kc, const uint8_t *circ, const uint64_t *min_key, const uint8_t *min_o,
-                               const uint64_t *min_pos, int tips, int bubbles) {
+// the text of both unitig-graph entry points: "removed a b", then one line per contig, or "error: ..."
+static char *unitig_assemble_text(bool on_device, uint32_t k, uint64_t n_recs, const uint64_t *first, const uint64_t *last, const uint64_t *len,
+                                  const uint64_t *kc, const uint8_t *circ, const uint64_t *min_key, const uint8_t *min_o,
+                                  const uint64_t *min_pos, int tips, int bubbles) {
     try {
         if ((k & 1u) == 0 || k < SHK_K_MIN || k > SHK_K_MAX || (n_recs && (!first || !last || !len || !kc || !circ))) return nullptr;
         const uint32_t W = (2 * k + 63) / 64;
@@ -848,7 +850,12 @@ char *shk_host_unitig_assemble(uint32_t k, uint64_t n_recs, const uint64_t *firs
         }
         UnitigGraphResult res; std::string err;
         auto fail_text = [](const std::string &e) -> char * { const std::string t = "error: " + e; char *o = (char *)malloc(t.size() + 1); if (o) memcpy(o, t.c_str(), t.size() + 1); return o; };
-        if (unitig_assemble((int)k, recs, tips != 0, bubbles != 0, res, err)) return fail_text(err);
+        if (on_device) {
+            // (1 — no device memory — is the caller's cue to run the host code: here it is reported, the caller asked for the device)
+            const int rc = unitig_assemble_device((int)k, recs, tips != 0, bubbles != 0, current_device(), nullptr, res, err);
+            if (rc == 1) return fail_text("out of device memory");
+            if (rc) return fail_text(err);
+        } else if (unitig_assemble((int)k, recs, tips != 0, bubbles != 0, res, err)) return fail_text(err);
         std::vector<UnitigMinKey> mk((size_t)n_recs);
         for (uint32_t r : res.need_min) {
             if (!min_key || !min_o || !min_pos) return nullptr;
@@ -867,6 +874,16 @@ char *shk_host_unitig_assemble(uint32_t k, uint64_t n_recs, const uint64_t *firs
         memcpy(out, text.c_str(), text.size() + 1);
         return out;
     } catch (...) { return nullptr; }
+}
+char *shk_host_unitig_assemble(uint32_t k, uint64_t n_recs, const uint64_t *first, const uint64_t *last, const uint64_t *len,
+                               const uint64_t *kc, const uint8_t *circ, const uint64_t *min_key, const uint8_t *min_o,
+                               const uint64_t *min_pos, int tips, int bubbles) {
+    return unitig_assemble_text(false, k, n_recs, first, last, len, kc, circ, min_key, min_o, min_pos, tips, bubbles);
+}
+char *shk_device_unitig_assemble(uint32_t k, uint64_t n_recs, const uint64_t *first, const uint64_t *last, const uint64_t *len,
+                                 const uint64_t *kc, const uint8_t *circ, const uint64_t *min_key, const uint8_t *min_o,
+                                 const uint64_t *min_pos, int tips, int bubbles) {
+    return unitig_assemble_text(true, k, n_recs, first, last, len, kc, circ, min_key, min_o, min_pos, tips, bubbles);
 }
 
 }  // extern "C"

@@ -31,6 +31,7 @@
 #include "pipeline.h"
 #include "shard_comm.h"
 #include "unitig_graph.h"
+#include "unitig_graph_gpu.h"
 
 namespace shk {
 
@@ -61,6 +62,10 @@ static constexpr int CTL_ER = 22;                  // ctl_[22]: table slots rese
 static constexpr uint32_t GP_MAX = 131072;         // graph partitions at most (17 bits of a queued neighbour query)
 static constexpr uint64_t EMPTY64 = ~0ull;
 static constexpr int MAX_PROBE = 4096;
+// sharded assembly: unitig records from which the unitig graph is corrected on the device (SHK_UNITIG_DEVICE_MIN).  Measured
+// (profiles/unitig_device/): the device twin beats the host code in every run from 20 000 records on; the default is never
+// below 65 536, the size from which the host code itself treats a graph as large.
+static constexpr uint64_t UNITIG_DEVICE_MIN_DEFAULT = 65536;
 static constexpr int SPLIT_LOG_DEFAULT = 6;    // one sampled splitter every ~64 oriented nodes (the walk hops over LDS-built fragments: 5 -> 6 measured best)
 
 // ------------------------------------------------------------------------------------------
@@ -2515,10 +2520,29 @@ public:
         });
         lap("records");
         UnitigGraphResult res;
-        int rc_ug = unitig_assemble(k_, recs, tips, bubbles, res, err);
+        // SHK_UNITIG_DEVICE: 1 — the device twin (unitig_graph_gpu.h), 0 — the host code; unset: the device from
+        // SHK_UNITIG_DEVICE_MIN records on (UNITIG_DEVICE_MIN_DEFAULT: DESIGN.md §5 says where the figure comes from).  The
+        // two compute the same result from the same records, so a rank whose device has no room falls back alone.
+        const double t_ug0 = now_ms_();
+        bool ug_device;
+        {
+            const char *ud = getenv("SHK_UNITIG_DEVICE"), *um = getenv("SHK_UNITIG_DEVICE_MIN");
+            const uint64_t ug_min = (um && *um) ? strtoull(um, nullptr, 10) : UNITIG_DEVICE_MIN_DEFAULT;
+            ug_device = (ud && *ud == '1') || (!(ud && *ud == '0') && (uint64_t)n_u >= ug_min);
+        }
+        int rc_ug = 1;
+        if (ug_device) {
+            rc_ug = unitig_assemble_device(k_, recs, tips, bubbles, stream_dev_, stream_, res, err);
+            if (rc_ug == 1) times_.add("shard_graph_unitig_device_declined_x1", 1.0);
+            else times_.add("shard_graph_unitig_device_x1", 1.0);
+        }
+        if (rc_ug == 1) rc_ug = unitig_assemble(k_, recs, tips, bubbles, res, err);
+        times_.add("shard_graph_unitig_graph", now_ms_() - t_ug0);
         lap("unitig graph");
-        // (the same code on the same records: it fails on every rank or on none — an agreement round is only paid where the
-        // graph is large enough for one host to run out of memory alone)
+        // (the same code on the same records: inconsistent records fail on every rank or on none — an agreement round is only
+        // paid where the graph is large enough for one host to run out of memory alone.  A HIP error of the device twin is
+        // rank-local like that: below 2^20 records this rank leaves with -6 without a round, as it does after a host failure
+        // of its own, and the others meet the communicator's time limit in their next collective)
         if (n_u >= (1u << 20)) { if (int rc = agree(rc_ug ? -6 : 0, "the unitig graph")) return rc; }
         else if (rc_ug) { sh_agreed_ = true; return -6; }
         tips_removed_ = res.tips_removed; bubbles_removed_ = res.bubbles_removed; rounds_ = res.rounds;

@@ -62,21 +62,8 @@ template <int W> struct UG {
     UG(int k_, const std::vector<UnitigRec> &recs) : k(k_), R(recs), n((uint32_t)recs.size()), T_LEN(2ull * (uint64_t)k_) {}
 
     static Kmer<W> load(const uint64_t *w) { Kmer<W> x; for (int i = 0; i < W; i++) x.w[i] = w[i]; return x; }
-    Kmer<W> prefix(const Kmer<W> &x) const {      // the first k-1 bases as a 2(k-1)-bit integer
-        Kmer<W> r;
-        for (int i = 0; i < W; i++) r.w[i] = (x.w[i] >> 2) | (i + 1 < W ? x.w[i + 1] << 62 : 0ull);
-        return r;
-    }
-    Kmer<W> suffix(const Kmer<W> &x) const {      // the last k-1 bases
-        Kmer<W> r = x;
-        const int bits = 2 * (k - 1);
-        for (int i = 0; i < W; i++) {
-            const int lo = 64 * i;
-            if (bits <= lo) r.w[i] = 0;
-            else if (bits < lo + 64) r.w[i] &= (1ull << (bits - lo)) - 1ull;
-        }
-        return r;
-    }
+    Kmer<W> prefix(const Kmer<W> &x) const { return ug_prefix<W>(x); }      // the first k-1 bases as a 2(k-1)-bit integer
+    Kmer<W> suffix(const Kmer<W> &x) const { return ug_suffix<W>(x, k); }   // the last k-1 bases
     Kmer<W> canon(const Kmer<W> &x, int &o) const { return km_canonical<W>(x, k, o); }
 
     // Index of the chain starts: an open-addressing table of record numbers, placed by a hash of the first k-1 bases of the
@@ -84,8 +71,7 @@ template <int W> struct UG {
     // k-1 bases" (its out-neighbours, <= 4) and "which record starts with revcomp(my last k-mer)" (its mirror strand).  Built
     // and read by all threads (one CAS per insert); replaces two sorts of all records and two binary searches per record
     // (4 M records: 2.3 s -> 0.3 s on 8 cores).
-    static uint64_t mix(uint64_t x) { x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31; return x; }
-    uint64_t hash_of(const Kmer<W> &p) const { uint64_t h = 0x9E3779B97F4A7C15ull; for (int i = 0; i < W; i++) h = mix(h ^ p.w[i]); return h; }
+    uint64_t hash_of(const Kmer<W> &p) const { return ug_hash_of<W>(p); }
 
     int init(std::string &err) {
         const bool dbg = getenv("SHK_UG_DEBUG") != nullptr;
@@ -300,66 +286,76 @@ template <int W> struct UG {
         return s;
     }
 
-    void chains(UnitigGraphResult &out) {
-        const bool dbg = getenv("SHK_UG_DEBUG") != nullptr;
-        auto t0 = std::chrono::steady_clock::now();
-        auto lap = [&](const char *what) {
-            if (!dbg) return;
-            const auto t1 = std::chrono::steady_clock::now();
-            fprintf(stderr, "[unitig graph]   chains: %-8s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-            t0 = t1;
-        };
-        std::vector<uint32_t> succ(n, UG_NIL), pred(n, UG_NIL);
+    // succ[r] of every alive linear record (the last use of outn)
+    std::vector<uint32_t> successors() const {
+        std::vector<uint32_t> succ(n, UG_NIL);
         par_ranges(n, [&](size_t a, size_t b, unsigned) { for (size_t r = a; r < b; r++) if (alive[r] && !R[r].circ) succ[r] = simple_succ((uint32_t)r); });
-        par_ranges(n, [&](size_t a, size_t b, unsigned) { for (size_t r = a; r < b; r++) if (succ[r] != UG_NIL) pred[succ[r]] = (uint32_t)r; });   // (a record has one simple predecessor)
-        lap("succ");
-        std::vector<uint8_t> seen(n, 0);
-        auto finish = [&](UnitigContig &c, std::vector<UnitigContig> &to) {
-            for (uint32_t r : c.recs) { c.len_nodes += R[r].len; c.kc += R[r].kc; }
-            to.push_back(std::move(c));
-        };
-        // Linear chains start at the records without a simple predecessor; every chain exists on both strands, as two chains
-        // with two different first nodes.  SPEC S10 emits min(spelling, revcomp(spelling)), which the first k-mers decide:
-        // the strand with the smaller first k-mer is the one handed on (the writer never has to reverse-complement a
-        // chromosome), its mirror chain is walked — to mark its records — and dropped.  A chain that is its own mirror
-        // (it starts at the reverse complement of its last node) is handed on once.  The heads are independent: several
-        // threads, each over a range of records, their contigs appended in the order of the ranges.
-        const unsigned TH = ug_threads(n);
-        std::vector<std::vector<UnitigContig>> part(TH);
-        par_ranges(n, [&](size_t a, size_t b, unsigned t) {
-            for (size_t r = a; r < b; r++) {
-                if (!alive[r] || R[r].circ || pred[r] != UG_NIL) continue;
-                uint32_t tail = (uint32_t)r;
-                seen[r] = 1;
-                for (uint32_t cur = succ[r]; cur != UG_NIL; cur = succ[cur]) { seen[cur] = 1; tail = cur; }
-                const uint32_t mirror_first = mirror[tail];
-                if (mirror_first != (uint32_t)r && !km_less<W>(F[r], F[mirror_first])) continue;     // the other strand is the smaller one
-                UnitigContig c;
-                for (uint32_t cur = (uint32_t)r; cur != UG_NIL; cur = succ[cur]) c.recs.push_back(cur);
-                finish(c, part[t]);
-            }
-        });
-        lap("heads");
-        size_t total = 0;
-        for (auto &p : part) total += p.size();
-        out.contigs.reserve(out.contigs.size() + total);
-        for (auto &p : part) { for (auto &c : p) out.contigs.push_back(std::move(c)); std::vector<UnitigContig>().swap(p); }
-        lap("gather");
-        for (uint32_t r = 0; r < n; r++) {                           // what is left closes on itself: a ring made of several records
-            if (!alive[r] || R[r].circ || seen[r]) continue;
-            UnitigContig c; c.ring = true;
-            for (uint32_t cur = r;;) { c.recs.push_back(cur); seen[cur] = 1; cur = succ[cur]; if (cur == r || cur == UG_NIL) break; }
-            for (uint32_t x : c.recs) { seen[mirror[x]] = 1; out.need_min.push_back(x); out.need_min.push_back(mirror[x]); }
-            finish(c, out.contigs);
-        }
-        for (uint32_t r = 0; r < n; r++) {                           // rings from the start: each strand a record of its own
-            if (!alive[r] || !R[r].circ) continue;
-            UnitigContig c; c.ring = true; c.recs.push_back(r);
-            out.need_min.push_back(r);
-            finish(c, out.contigs);
-        }
+        return succ;
     }
 };
+
+// S10 from settled arrays (unitig_chains): no lookups, the first k-mers are only compared
+template <int W> void chains_t(const std::vector<UnitigRec> &R, const std::vector<uint8_t> &alive, const std::vector<uint32_t> &mirror,
+                               const std::vector<uint32_t> &succ, UnitigGraphResult &out) {
+    const uint32_t n = (uint32_t)R.size();
+    auto first_of = [&](uint32_t r) { Kmer<W> x; for (int i = 0; i < W; i++) x.w[i] = R[r].first[i]; return x; };
+    const bool dbg = getenv("SHK_UG_DEBUG") != nullptr;
+    auto t0 = std::chrono::steady_clock::now();
+    auto lap = [&](const char *what) {
+        if (!dbg) return;
+        const auto t1 = std::chrono::steady_clock::now();
+        fprintf(stderr, "[unitig graph]   chains: %-8s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
+        t0 = t1;
+    };
+    std::vector<uint32_t> pred(n, UG_NIL);
+    par_ranges(n, [&](size_t a, size_t b, unsigned) { for (size_t r = a; r < b; r++) if (succ[r] != UG_NIL) pred[succ[r]] = (uint32_t)r; });   // (a record has one simple predecessor)
+    lap("succ");
+    std::vector<uint8_t> seen(n, 0);
+    auto finish = [&](UnitigContig &c, std::vector<UnitigContig> &to) {
+        for (uint32_t r : c.recs) { c.len_nodes += R[r].len; c.kc += R[r].kc; }
+        to.push_back(std::move(c));
+    };
+    // Linear chains start at the records without a simple predecessor; every chain exists on both strands, as two chains
+    // with two different first nodes.  SPEC S10 emits min(spelling, revcomp(spelling)), which the first k-mers decide:
+    // the strand with the smaller first k-mer is the one handed on (the writer never has to reverse-complement a
+    // chromosome), its mirror chain is walked — to mark its records — and dropped.  A chain that is its own mirror
+    // (it starts at the reverse complement of its last node) is handed on once.  The heads are independent: several
+    // threads, each over a range of records, their contigs appended in the order of the ranges.
+    const unsigned TH = ug_threads(n);
+    std::vector<std::vector<UnitigContig>> part(TH);
+    par_ranges(n, [&](size_t a, size_t b, unsigned t) {
+        for (size_t r = a; r < b; r++) {
+            if (!alive[r] || R[r].circ || pred[r] != UG_NIL) continue;
+            uint32_t tail = (uint32_t)r;
+            seen[r] = 1;
+            for (uint32_t cur = succ[r]; cur != UG_NIL; cur = succ[cur]) { seen[cur] = 1; tail = cur; }
+            const uint32_t mirror_first = mirror[tail];
+            if (mirror_first != (uint32_t)r && !km_less<W>(first_of((uint32_t)r), first_of(mirror_first))) continue;     // the other strand is the smaller one
+            UnitigContig c;
+            for (uint32_t cur = (uint32_t)r; cur != UG_NIL; cur = succ[cur]) c.recs.push_back(cur);
+            finish(c, part[t]);
+        }
+    });
+    lap("heads");
+    size_t total = 0;
+    for (auto &p : part) total += p.size();
+    out.contigs.reserve(out.contigs.size() + total);
+    for (auto &p : part) { for (auto &c : p) out.contigs.push_back(std::move(c)); std::vector<UnitigContig>().swap(p); }
+    lap("gather");
+    for (uint32_t r = 0; r < n; r++) {                           // what is left closes on itself: a ring made of several records
+        if (!alive[r] || R[r].circ || seen[r]) continue;
+        UnitigContig c; c.ring = true;
+        for (uint32_t cur = r;;) { c.recs.push_back(cur); seen[cur] = 1; cur = succ[cur]; if (cur == r || cur == UG_NIL) break; }
+        for (uint32_t x : c.recs) { seen[mirror[x]] = 1; out.need_min.push_back(x); out.need_min.push_back(mirror[x]); }
+        finish(c, out.contigs);
+    }
+    for (uint32_t r = 0; r < n; r++) {                           // rings from the start: each strand a record of its own
+        if (!alive[r] || !R[r].circ) continue;
+        UnitigContig c; c.ring = true; c.recs.push_back(r);
+        out.need_min.push_back(r);
+        finish(c, out.contigs);
+    }
+}
 
 template <int W> int assemble_t(int k, const std::vector<UnitigRec> &recs, bool tips, bool bubbles, UnitigGraphResult &out, std::string &err) {
     const bool dbg = getenv("SHK_UG_DEBUG") != nullptr;            // stage times on stderr
@@ -384,9 +380,10 @@ template <int W> int assemble_t(int k, const std::vector<UnitigRec> &recs, bool 
             if (a + b == 0) break;
         }
     }
-    g.chains(out);
+    const std::vector<uint32_t> succ = g.successors();
+    chains_t<W>(recs, g.alive, g.mirror, succ, out);
     lap("chains");
-    out.mirror = g.mirror;
+    out.mirror = std::move(g.mirror);
     return 0;
 }
 
@@ -463,6 +460,24 @@ int unitig_assemble(int k, const std::vector<UnitigRec> &recs, bool tips, bool b
         case 8: return assemble_t<8>(k, recs, tips, bubbles, out, err);
     }
     err = "k too large"; return -1;
+}
+int unitig_chains(int k, const std::vector<UnitigRec> &recs, const std::vector<uint8_t> &alive, std::vector<uint32_t> &&mirror,
+                  const std::vector<uint32_t> &succ, UnitigGraphResult &out, std::string &err) {
+    const size_t n = recs.size();
+    if (alive.size() != n || mirror.size() != n || succ.size() != n) { err = "unitig graph: arrays of another size than the records"; return -1; }
+    switch ((2 * k + 63) / 64) {
+        case 1: chains_t<1>(recs, alive, mirror, succ, out); break;
+        case 2: chains_t<2>(recs, alive, mirror, succ, out); break;
+        case 3: chains_t<3>(recs, alive, mirror, succ, out); break;
+        case 4: chains_t<4>(recs, alive, mirror, succ, out); break;
+        case 5: chains_t<5>(recs, alive, mirror, succ, out); break;
+        case 6: chains_t<6>(recs, alive, mirror, succ, out); break;
+        case 7: chains_t<7>(recs, alive, mirror, succ, out); break;
+        case 8: chains_t<8>(recs, alive, mirror, succ, out); break;
+        default: err = "k too large"; return -1;
+    }
+    out.mirror = std::move(mirror);
+    return 0;
 }
 int unitig_resolve_rings(int k, const std::vector<UnitigRec> &recs, const std::vector<UnitigMinKey> &min_of, UnitigGraphResult &out, std::string &err) {
     switch ((2 * k + 63) / 64) {

@@ -17,9 +17,38 @@
 #include <string>
 #include <vector>
 
+#include "kmer.h"
+
 namespace shk {
 
 static constexpr uint32_t UG_NIL = 0xFFFFFFFFu;
+
+// The k-mer arithmetic of the index of chain starts, shared by the host code (unitig_graph.cpp) and its device twin
+// (unitig_graph_gpu.hip): the first k-1 bases of a k-mer as a 2(k-1)-bit integer, the last k-1 bases, and the placement hash.
+template <int W> SHK_HD Kmer<W> ug_prefix(const Kmer<W> &x) {
+    Kmer<W> r;
+#pragma unroll
+    for (int i = 0; i < W; i++) r.w[i] = (x.w[i] >> 2) | (i + 1 < W ? x.w[i + 1] << 62 : 0ull);
+    return r;
+}
+template <int W> SHK_HD Kmer<W> ug_suffix(const Kmer<W> &x, int k) {
+    Kmer<W> r = x;
+    const int bits = 2 * (k - 1);
+#pragma unroll
+    for (int i = 0; i < W; i++) {
+        const int lo = 64 * i;
+        if (bits <= lo) r.w[i] = 0;
+        else if (bits < lo + 64) r.w[i] &= (1ull << (bits - lo)) - 1ull;
+    }
+    return r;
+}
+SHK_HD uint64_t ug_mix(uint64_t x) { x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31; return x; }
+template <int W> SHK_HD uint64_t ug_hash_of(const Kmer<W> &p) {
+    uint64_t h = 0x9E3779B97F4A7C15ull;
+#pragma unroll
+    for (int i = 0; i < W; i++) h = ug_mix(h ^ p.w[i]);
+    return h;
+}
 
 // One STRAND of a unitig: the chain v_1 -> ... -> v_n as it is spelled.  Its mirror strand rc(v_n) -> ... -> rc(v_1) is
 // a record of its own (first = revcomp(last of this one)).  K-mers: 2k-bit integers, first base most significant, in
@@ -56,6 +85,12 @@ struct UnitigGraphResult {
 // S9 rounds on the records (tips unless !tips, bubbles unless !bubbles), then S10 chains over what is left.
 // Returns 0, or -1 with err (inconsistent input: a linear record without its mirror strand).
 int unitig_assemble(int k, const std::vector<UnitigRec> &recs, bool tips, bool bubbles, UnitigGraphResult &out, std::string &err);
+// The S10 walk alone, from arrays that are already settled (by unitig_assemble itself, or by its device twin,
+// unitig_graph_gpu.h): alive[r], mirror[r] (UG_NIL for rings) and succ[r], the simple successor of an alive linear
+// record (UG_NIL: none).  Looks nothing up: heads, the strand with the smaller first k-mer, rings of several records,
+// rings from the start.  Appends to out.contigs / out.need_min and sets out.mirror.
+int unitig_chains(int k, const std::vector<UnitigRec> &recs, const std::vector<uint8_t> &alive, std::vector<uint32_t> &&mirror,
+                  const std::vector<uint32_t> &succ, UnitigGraphResult &out, std::string &err);
 // min_of[r] must be valid for every r in out.need_min.  Fixes strand and rotation of the ring contigs, drops the
 // mirror-strand duplicates of rings that were rings from the start.
 int unitig_resolve_rings(int k, const std::vector<UnitigRec> &recs, const std::vector<UnitigMinKey> &min_of, UnitigGraphResult &out,

@@ -1,0 +1,571 @@
+// unitig_graph_gpu.hip — SPEC S9 on unitig records as gfx950 kernels: the device twin of UG<W> in unitig_graph.cpp
+// (unitig_graph.h says why the rules are exact at this level).  The k-mer-level kernels of graph_part.h are the model:
+// 256-thread workgroups, grid-stride loops, candidate lists compacted by ballot, counts that stay on the device, a round
+// that decides on a snapshot and applies afterwards.  What differs is the vertex: a record with a length and a summed
+// count, whose neighbours are found once through an index of chain starts instead of through adjacency bits.
+//
+// Every loop is bounded whatever the records say: probes by the capacity of the index, walks by 2k steps (a step adds at
+// least one node to a length that may not exceed 2k), lists of tips by the number of tips, rounds by 32.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <chrono>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "inflate_gpu.h"
+#include "kmer.h"
+#include "pipeline.h"
+#include "unitig_graph_gpu.h"
+
+namespace shk {
+namespace {
+
+constexpr unsigned long long UG_EMPTY = ~0ull;
+// flags word (ctl[0])
+constexpr unsigned int UGF_NO_MIRROR = 1u, UGF_SAME_START = 2u, UGF_UNPAIRED = 4u, UGF_PROBE_BOUND = 8u;
+// ctl: 8 words of 8 bytes — [0] flags, [1] tip candidates, [2] tips, [3] fork candidates, [4] nodes removed as tips,
+// [5] nodes removed as bubble branches (this round)
+constexpr int CTL_FLAGS = 0, CTL_NCAND = 1, CTL_NTIPS = 2, CTL_NFORK = 3, CTL_TIP_NODES = 4, CTL_BUB_NODES = 5, CTL_WORDS = 8;
+
+struct UTip { uint32_t start, junction, nrec, next; unsigned long long len, sum; };
+
+// The records as structure-of-arrays (word w of record r's first k-mer: F[w * n + r]) and the links found for them.
+template <int W> struct UGraph {
+    const uint64_t *F, *T, *len, *kc;
+    const uint8_t *circ;
+    uint32_t *mirror;                          // [n]
+    uint32_t *outn;                            // [n][4], ascending record numbers, UG_NIL padded
+    uint8_t *alive;                            // [n]
+    uint32_t n;
+    int k;
+
+    __device__ __forceinline__ Kmer<W> first(uint32_t r) const {
+        Kmer<W> x;
+#pragma unroll
+        for (int i = 0; i < W; i++) x.w[i] = F[(size_t)i * n + r];
+        return x;
+    }
+    __device__ __forceinline__ Kmer<W> last(uint32_t r) const {
+        Kmer<W> x;
+#pragma unroll
+        for (int i = 0; i < W; i++) x.w[i] = T[(size_t)i * n + r];
+        return x;
+    }
+    // the alive out-neighbours of r's last node: bit b of the mask says entry b of o is one (UG::outs without the compaction;
+    // the order of the entries is the host's)
+    __device__ __forceinline__ uint32_t outs(uint32_t r, uint4 &o) const {
+        o = make_uint4(UG_NIL, UG_NIL, UG_NIL, UG_NIL);
+        if (circ[r]) return 0u;
+        o = *reinterpret_cast<const uint4 *>(outn + (size_t)r * 4);
+        uint32_t m = 0;
+        if (o.x != UG_NIL && alive[o.x]) m |= 1u;
+        if (o.y != UG_NIL && alive[o.y]) m |= 2u;
+        if (o.z != UG_NIL && alive[o.z]) m |= 4u;
+        if (o.w != UG_NIL && alive[o.w]) m |= 8u;
+        return m;
+    }
+    __device__ __forceinline__ uint32_t outdeg(uint32_t r) const { uint4 o; return (uint32_t)__popc(outs(r, o)); }
+    // in-degree of r's first node: the out-degree of its mirror strand's last node
+    __device__ __forceinline__ uint32_t indeg(uint32_t r) const { return circ[r] ? 0u : outdeg(mirror[r]); }
+    // the one alive out-neighbour (outs() returned a mask of one bit)
+    static __device__ __forceinline__ uint32_t only(const uint4 &o, uint32_t m) {
+        return (m & 1u) ? o.x : (m & 2u) ? o.y : (m & 4u) ? o.z : o.w;
+    }
+    static __device__ __forceinline__ uint32_t entry(const uint4 &o, int b) { return b == 0 ? o.x : b == 1 ? o.y : b == 2 ? o.z : o.w; }
+};
+
+__device__ __forceinline__ void ug_compact(bool p, uint32_t value, uint32_t *__restrict__ list, unsigned int *__restrict__ count) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long m = __ballot(p);
+    if (!m) return;
+    unsigned int base = 0;
+    if (lane == 0) base = atomicAdd(count, (unsigned int)__popcll(m));
+    base = __shfl(base, 0);
+    if (p) list[base + __popcll(m & ((1ull << lane) - 1ull))] = value;
+}
+
+// ------------------------------------------------------------------------------------------
+// the index of chain starts and the links (UG::init)
+// ------------------------------------------------------------------------------------------
+template <int W>
+__global__ __launch_bounds__(256) void k_ug_insert(UGraph<W> g, unsigned long long *__restrict__ slot, uint64_t cap,
+                                                   unsigned int *__restrict__ flags) {
+    const uint64_t cmask = cap - 1;
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < g.n; r += gridDim.x * blockDim.x) {
+        g.alive[r] = 1;
+        if (g.circ[r]) continue;                                  // rings have no ends: not indexed
+        const Kmer<W> f = g.first(r);
+        const uint64_t h = ug_hash_of<W>(ug_prefix<W>(f));
+        const unsigned long long mine = (h & 0xFFFFFFFF00000000ull) | (unsigned long long)r;
+        uint64_t i = h & cmask, probes = 0;
+        for (; probes < cap; probes++, i = (i + 1) & cmask) {
+            unsigned long long e = __atomic_load_n(&slot[i], __ATOMIC_RELAXED);
+            if (e == UG_EMPTY) { e = atomicCAS(&slot[i], UG_EMPTY, mine); if (e == UG_EMPTY) break; }
+            // (e is the slot's entry) a record with the same start: of two such records the later one meets the earlier
+            if ((e >> 32) == (mine >> 32) && km_eq<W>(g.first((uint32_t)e), f)) { atomicOr(flags, UGF_SAME_START); break; }
+        }
+        if (probes == cap) atomicOr(flags, UGF_PROBE_BOUND);
+    }
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void k_ug_links(UGraph<W> g, const unsigned long long *__restrict__ slot, uint64_t cap,
+                                                  unsigned int *__restrict__ flags) {
+    const uint64_t cmask = cap - 1;
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < g.n; r += gridDim.x * blockDim.x) {
+        if (g.circ[r]) continue;
+        const Kmer<W> t = g.last(r);
+        // the mirror strand: the record that starts with revcomp(my last k-mer)
+        const Kmer<W> want = km_revcomp<W>(t, g.k);
+        const uint64_t hw = ug_hash_of<W>(ug_prefix<W>(want));
+        uint32_t m = UG_NIL;
+        uint64_t i = hw & cmask, probes = 0;
+        for (; probes < cap; probes++, i = (i + 1) & cmask) {
+            const unsigned long long e = slot[i];
+            if (e == UG_EMPTY) break;
+            if ((e >> 32) == (hw >> 32) && km_eq<W>(g.first((uint32_t)e), want)) { m = (uint32_t)e; break; }
+        }
+        if (probes == cap) atomicOr(flags, UGF_PROBE_BOUND);
+        if (m == UG_NIL) { atomicOr(flags, UGF_NO_MIRROR); continue; }
+        g.mirror[r] = m;
+        // the out-neighbours: the records whose first k-1 bases are my last k-1 bases, kept sorted while they are found
+        // (the order of the slots must not show: f0 <= f1 <= f2 <= f3, UG_NIL is the largest number)
+        const Kmer<W> sfx = ug_suffix<W>(t, g.k);
+        const uint64_t hs = ug_hash_of<W>(sfx);
+        uint32_t f0 = UG_NIL, f1 = UG_NIL, f2 = UG_NIL, f3 = UG_NIL, c = 0;
+        for (i = hs & cmask, probes = 0; probes < cap; probes++, i = (i + 1) & cmask) {
+            const unsigned long long e = slot[i];
+            if (e == UG_EMPTY) break;
+            if (c < 4 && (e >> 32) == (hs >> 32) && km_eq<W>(ug_prefix<W>(g.first((uint32_t)e)), sfx)) {
+                uint32_t x = (uint32_t)e, lo;
+                lo = min(f0, x); x = max(f0, x); f0 = lo;
+                lo = min(f1, x); x = max(f1, x); f1 = lo;
+                lo = min(f2, x); x = max(f2, x); f2 = lo;
+                f3 = min(f3, x);
+                c++;
+            }
+        }
+        if (probes == cap) atomicOr(flags, UGF_PROBE_BOUND);
+        *reinterpret_cast<uint4 *>(g.outn + (size_t)r * 4) = make_uint4(f0, f1, f2, f3);
+    }
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void k_ug_pairs(UGraph<W> g, unsigned int *__restrict__ flags) {
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < g.n; r += gridDim.x * blockDim.x) {
+        if (g.circ[r]) continue;
+        const uint32_t m = g.mirror[r];
+        if (m >= g.n) continue;                                   // (no mirror: UGF_NO_MIRROR is up already)
+        if (g.mirror[m] != r) atomicOr(flags, UGF_UNPAIRED);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// tips (UG::tip_round)
+// ------------------------------------------------------------------------------------------
+template <int W>
+__global__ __launch_bounds__(256) void k_ug_tip_candidates(UGraph<W> g, uint32_t *__restrict__ cand, unsigned int *__restrict__ n_cand) {
+    const uint64_t T_LEN = 2ull * (uint64_t)g.k;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t n_round = ((uint64_t)g.n + stride - 1) / stride * stride;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += stride) {
+        bool p = false;
+        if (i < g.n) {
+            const uint32_t r = (uint32_t)i;
+            p = g.alive[r] && !g.circ[r] && g.len[r] <= T_LEN && g.outdeg(r) == 1 && g.indeg(r) == 0;
+        }
+        ug_compact(p, (uint32_t)i, cand, n_cand);
+    }
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void k_ug_tip_walk(UGraph<W> g, const uint32_t *__restrict__ cand, const unsigned int *__restrict__ n_cand_p,
+                                                     UTip *__restrict__ tips, unsigned int *__restrict__ n_tips, uint32_t *__restrict__ tip_head) {
+    const uint64_t T_LEN = 2ull * (uint64_t)g.k;
+    const uint32_t n_cand = *n_cand_p;
+    for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n_cand; c += gridDim.x * blockDim.x) {
+        const uint32_t v = cand[c];
+        unsigned long long len = g.len[v], sum = g.kc[v];
+        uint32_t cur = v, nrec = 1, J = UG_NIL;
+        for (uint64_t step = 0; step < T_LEN; step++) {           // (T_LEN more records of >= 1 node each cannot stay within T_LEN)
+            uint4 o;
+            const uint32_t m = g.outs(cur, o);
+            if (__popc(m) != 1) break;                            // not a tip
+            const uint32_t nx = UGraph<W>::only(o, m);
+            if (g.indeg(nx) >= 2) { J = nx; break; }
+            nrec++; len += g.len[nx]; sum += g.kc[nx]; cur = nx;
+            if (len > T_LEN) break;                               // not a tip
+        }
+        if (J == UG_NIL) continue;
+        const uint32_t t = atomicAdd(n_tips, 1u);
+        UTip rec; rec.start = v; rec.junction = J; rec.nrec = nrec; rec.len = len; rec.sum = sum;
+        rec.next = atomicExch(&tip_head[J], t);
+        tips[t] = rec;
+    }
+}
+
+// per junction on the snapshot: t < d -> all go, t == d -> the best stays; best by (len, sum, smaller canonical first k-mer),
+// then — the host keeps the first of fully equal tips, and its candidates ascend — the lower start record
+template <int W>
+__global__ __launch_bounds__(256) void k_ug_tip_decide(UGraph<W> g, const UTip *__restrict__ tips, const unsigned int *__restrict__ n_tips_p,
+                                                       const uint32_t *__restrict__ tip_head, uint8_t *__restrict__ kill) {
+    const uint32_t n_tips = *n_tips_p;
+    for (uint32_t a = blockIdx.x * blockDim.x + threadIdx.x; a < n_tips; a += gridDim.x * blockDim.x) {
+        const UTip me = tips[a];
+        const uint32_t d = g.indeg(me.junction);
+        int om;
+        const Kmer<W> mine = km_canonical<W>(g.first(me.start), g.k, om);
+        uint32_t t = 0, walked = 0; bool best = true;
+        for (uint32_t b = tip_head[me.junction]; b < n_tips && walked < n_tips; b = tips[b].next, walked++) {
+            t++;
+            if (b == a) continue;
+            const UTip o = tips[b];
+            bool better;                                          // is o better than me?
+            if (o.len != me.len) better = o.len > me.len;
+            else if (o.sum != me.sum) better = o.sum > me.sum;
+            else {
+                int oo;
+                const Kmer<W> theirs = km_canonical<W>(g.first(o.start), g.k, oo);
+                if (km_less<W>(theirs, mine)) better = true;
+                else if (km_less<W>(mine, theirs)) better = false;
+                else better = o.start < me.start;
+            }
+            if (better) best = false;
+        }
+        kill[a] = (t == d && best) ? 0 : 1;
+    }
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void k_ug_tip_remove(UGraph<W> g, const UTip *__restrict__ tips, const unsigned int *__restrict__ n_tips_p,
+                                                       const uint8_t *__restrict__ kill, uint8_t *__restrict__ mark) {
+    const uint32_t n_tips = *n_tips_p;
+    for (uint32_t a = blockIdx.x * blockDim.x + threadIdx.x; a < n_tips; a += gridDim.x * blockDim.x) {
+        if (!kill[a]) continue;
+        const UTip me = tips[a];
+        uint32_t cur = me.start;
+        for (uint32_t i = 0; i < me.nrec; i++) {                  // the path again (alive is the snapshot's until k_ug_apply)
+            mark[cur] = 1;
+            if (i + 1 == me.nrec) break;
+            uint4 o;
+            const uint32_t m = g.outs(cur, o);
+            if (__popc(m) != 1) break;
+            cur = UGraph<W>::only(o, m);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// bubbles (UG::bubble_round)
+// ------------------------------------------------------------------------------------------
+template <int W>
+__global__ __launch_bounds__(256) void k_ug_fork_candidates(UGraph<W> g, uint32_t *__restrict__ cand, unsigned int *__restrict__ n_cand) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t n_round = ((uint64_t)g.n + stride - 1) / stride * stride;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += stride) {
+        bool p = false;
+        if (i < g.n) { const uint32_t r = (uint32_t)i; p = g.alive[r] && !g.circ[r] && g.outdeg(r) >= 2; }
+        ug_compact(p, (uint32_t)i, cand, n_cand);
+    }
+}
+
+// a * b > c * d, a * b == c * d in 128 bits (sums of counts are u64, lengths <= 2k)
+__device__ __forceinline__ void ug_cross(unsigned long long a, unsigned long long b, unsigned long long c, unsigned long long d, bool &gt, bool &eq) {
+    const unsigned long long lh = __umul64hi(a, b), ll = a * b, rh = __umul64hi(c, d), rl = c * d;
+    eq = lh == rh && ll == rl;
+    gt = lh != rh ? lh > rh : ll > rl;
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void k_ug_bubble(UGraph<W> g, const uint32_t *__restrict__ cand, const unsigned int *__restrict__ n_cand_p,
+                                                   uint8_t *__restrict__ mark) {
+    const uint64_t T_LEN = 2ull * (uint64_t)g.k;
+    const uint32_t n_cand = *n_cand_p;
+    for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n_cand; c += gridDim.x * blockDim.x) {
+        const uint32_t S = cand[c];
+        uint4 ob;
+        const uint32_t om = g.outs(S, ob);
+        uint32_t first[4], end[4], nrec[4];
+        unsigned long long len[4], sum[4];
+        bool ok[4];
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            ok[b] = false; first[b] = UG_NIL; end[b] = UG_NIL; nrec[b] = 0; len[b] = 0; sum[b] = 0;
+            if (!((om >> b) & 1u)) continue;
+            const uint32_t bn = UGraph<W>::entry(ob, b);
+            if (g.indeg(bn) != 1) continue;
+            first[b] = bn;
+            unsigned long long l = g.len[bn], s = g.kc[bn];
+            uint32_t cur = bn, nr = 1;
+            if (l <= T_LEN) {                                     // (else: too long inside the first chain)
+                for (uint64_t step = 0; step < T_LEN; step++) {
+                    uint4 o;
+                    const uint32_t m = g.outs(cur, o);
+                    if (__popc(m) != 1) break;                    // dead end or fork
+                    const uint32_t nx = UGraph<W>::only(o, m);
+                    if (g.indeg(nx) >= 2) { end[b] = nx; ok[b] = true; break; }
+                    nr++; l += g.len[nx]; s += g.kc[nx]; cur = nx;
+                    if (l > T_LEN) break;                         // too long
+                }
+            }
+            nrec[b] = nr; len[b] = l; sum[b] = s;
+        }
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            if (!ok[a]) continue;
+            const uint32_t E = end[a];
+            {   // evaluated only from the side with key(S) <= key(rc(E)): S = last node of record S, E = first node of record E
+                int os, oe;
+                const Kmer<W> ks = km_canonical<W>(g.last(S), g.k, os), ke = km_canonical<W>(g.first(E), g.k, oe);
+                const int oe_m = 1 - oe;
+                bool le;
+                if (km_less<W>(ks, ke)) le = true; else if (km_less<W>(ke, ks)) le = false; else le = os <= oe_m;
+                if (!le) continue;
+            }
+            int grp = 0; bool best = true;
+            int o1;
+            const Kmer<W> fa = km_canonical<W>(g.first(first[a]), g.k, o1);
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                if (!ok[b] || end[b] != E) continue;
+                grp++;
+                if (b == a) continue;
+                bool gt, eq, better;                              // is b better than a?  exact means by cross-multiplication
+                ug_cross(sum[b], len[a], sum[a], len[b], gt, eq);
+                if (!eq) better = gt;
+                else if (len[b] != len[a]) better = len[b] < len[a];
+                else { int o2; better = km_less<W>(km_canonical<W>(g.first(first[b]), g.k, o2), fa); }
+                if (better) best = false;
+            }
+            if (grp >= 2 && !best) {
+                uint32_t cur = first[a];
+                for (uint32_t i = 0; i < nrec[a]; i++) {
+                    mark[cur] = 1;
+                    if (i + 1 == nrec[a]) break;
+                    uint4 o;
+                    const uint32_t m = g.outs(cur, o);
+                    if (__popc(m) != 1) break;
+                    cur = UGraph<W>::only(o, m);
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// apply (UG::kill): one thread per mirror pair, taken at min(r, mirror[r]) — a record that is its own mirror counts once
+// ------------------------------------------------------------------------------------------
+template <int W>
+__global__ __launch_bounds__(256) void k_ug_apply(UGraph<W> g, uint8_t *__restrict__ mark, unsigned long long *__restrict__ nodes) {
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < g.n; r += gridDim.x * blockDim.x) {
+        if (g.circ[r]) continue;
+        const uint32_t m = g.mirror[r];
+        if (m < r || m >= g.n) continue;
+        if (!(mark[r] | mark[m])) continue;
+        mark[r] = 0; mark[m] = 0;
+        if (!g.alive[r]) continue;
+        g.alive[r] = 0; g.alive[m] = 0;
+        atomicAdd(nodes, (unsigned long long)g.len[r]);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// S10 on what is left (UG::simple_succ)
+// ------------------------------------------------------------------------------------------
+template <int W>
+__global__ __launch_bounds__(256) void k_ug_succ(UGraph<W> g, uint32_t *__restrict__ succ) {
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < g.n; r += gridDim.x * blockDim.x) {
+        uint32_t s = UG_NIL;
+        if (g.alive[r] && !g.circ[r]) {
+            uint4 o;
+            const uint32_t m = g.outs(r, o);
+            if (__popc(m) == 1) {
+                const uint32_t cand = UGraph<W>::only(o, m);
+                if (g.indeg(cand) == 1) {
+                    const Kmer<W> f = g.first(cand), t = g.last(r);
+                    if (!km_eq<W>(f, t) && !km_eq<W>(f, km_revcomp<W>(t, g.k))) s = cand;
+                }
+            }
+        }
+        succ[r] = s;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------
+#define UGCHK(call)                                                                                  \
+    do {                                                                                             \
+        hipError_t e_ = (call);                                                                      \
+        if (e_ != hipSuccess) {                                                                      \
+            err = std::string("unitig graph on the device: " #call ": ") + hipGetErrorString(e_);    \
+            return -5;                                                                               \
+        }                                                                                            \
+    } while (0)
+
+// workgroups per launch: two per CU of a 256-CU card (8 waves per CU keep the dependent reads of the probes and walks in
+// flight), the rest of the records by the grid stride — from 131 072 records on every thread takes more than one
+unsigned ug_grid(uint64_t n) {
+    const uint64_t b = (n + 255) / 256;
+    return (unsigned)(b < 1 ? 1 : (b > 512 ? 512 : b));
+}
+
+// the blocks go back to the pool when the caller returns: nothing may still be running on them then
+struct DrainOnExit { hipStream_t st; ~DrainOnExit() { (void)hipStreamSynchronize(st); } };
+
+template <int W> int assemble_device_t(int k, const std::vector<UnitigRec> &recs, bool tips, bool bubbles, hipStream_t st,
+                                       UnitigGraphResult &out, std::string &err) {
+    const bool dbg = getenv("SHK_UG_DEBUG") != nullptr;            // stage times on stderr, as the host code prints them
+    auto t0 = std::chrono::steady_clock::now();
+    auto lap = [&](const char *what) {
+        if (!dbg) return;
+        (void)hipStreamSynchronize(st);
+        const auto t1 = std::chrono::steady_clock::now();
+        fprintf(stderr, "[unitig graph, device] %-10s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
+        t0 = t1;
+    };
+    const size_t n = recs.size();
+    out = UnitigGraphResult();
+    if (n >= (size_t)UG_NIL) { err = "unitig graph: more records than 32-bit record numbers"; return -1; }
+    if (n == 0) {                                                 // (nothing to launch; the host makes one empty round)
+        if (tips || bubbles) out.rounds = 1;
+        return unitig_chains(k, recs, std::vector<uint8_t>(), std::vector<uint32_t>(), std::vector<uint32_t>(), out, err);
+    }
+    uint64_t cap = 64;
+    while (cap < (uint64_t)n * 2 + 16) cap <<= 1;
+    // (host ends of the copies: declared first, so that they outlive the drain of the stream on every way out)
+    std::vector<uint64_t> h_rec;
+    std::vector<uint8_t> h_circ, alive;
+    std::vector<uint32_t> mirror, succ;
+    unsigned long long h_ctl[CTL_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // ---- device blocks: all of them before any work, so that "no memory" leaves nothing behind
+    const size_t rec_words = (size_t)(2 * W + 2) * n;             // first[W][n], last[W][n], len[n], kc[n]
+    Blk d_rec, d_circ, d_slot, d_mirror, d_outn, d_alive, d_mark, d_succ, d_cand, d_tips, d_kill, d_head, d_ctl;
+    if (!d_rec.get(rec_words * 8) || !d_circ.get(n) || !d_slot.get((size_t)cap * 8) || !d_mirror.get(n * 4) || !d_outn.get(n * 16) ||
+        !d_alive.get(n) || !d_mark.get(n) || !d_succ.get(n * 4) || !d_cand.get(n * 4) || !d_tips.get(n * sizeof(UTip)) ||
+        !d_kill.get(n) || !d_head.get(n * 4) || !d_ctl.get(CTL_WORDS * 8)) {
+        (void)hipGetLastError();
+        return 1;
+    }
+    DrainOnExit drain{st};
+    // ---- records as structure-of-arrays (several host threads from the size on at which the host code uses them)
+    h_rec.resize(rec_words); h_circ.resize(n);
+    {
+        unsigned T = 1;
+        if (n >= 65536) { T = std::thread::hardware_concurrency(); T = T < 1 ? 1 : (T > 16 ? 16 : T); }
+        auto fill = [&](size_t a, size_t b) {
+            uint64_t *F = h_rec.data(), *L = F + (size_t)W * n, *len = L + (size_t)W * n, *kc = len + n;
+            for (size_t r = a; r < b; r++) {
+                const UnitigRec &R = recs[r];
+                for (int w = 0; w < W; w++) { F[(size_t)w * n + r] = R.first[w]; L[(size_t)w * n + r] = R.last[w]; }
+                len[r] = R.len; kc[r] = R.kc; h_circ[r] = R.circ ? 1 : 0;
+            }
+        };
+        std::vector<std::thread> ts;
+        for (unsigned t = 1; t < T; t++) ts.emplace_back(fill, n * t / T, n * (t + 1) / T);
+        fill(0, n / T);
+        for (auto &t : ts) t.join();
+    }
+    lap("transpose");
+    UGCHK(hipMemcpyAsync(d_rec.p, h_rec.data(), rec_words * 8, hipMemcpyHostToDevice, st));
+    UGCHK(hipMemcpyAsync(d_circ.p, h_circ.data(), n, hipMemcpyHostToDevice, st));
+    UGCHK(hipMemsetAsync(d_slot.p, 0xFF, (size_t)cap * 8, st));
+    UGCHK(hipMemsetAsync(d_mirror.p, 0xFF, n * 4, st));
+    UGCHK(hipMemsetAsync(d_outn.p, 0xFF, n * 16, st));
+    UGCHK(hipMemsetAsync(d_mark.p, 0, n, st));
+    UGCHK(hipMemsetAsync(d_ctl.p, 0, CTL_WORDS * 8, st));
+    lap("upload");
+    UGraph<W> g;
+    g.F = (const uint64_t *)d_rec.p; g.T = g.F + (size_t)W * n; g.len = g.T + (size_t)W * n; g.kc = g.len + n;
+    g.circ = (const uint8_t *)d_circ.p; g.mirror = (uint32_t *)d_mirror.p; g.outn = (uint32_t *)d_outn.p; g.alive = (uint8_t *)d_alive.p;
+    g.n = (uint32_t)n; g.k = k;
+    unsigned long long *ctl = (unsigned long long *)d_ctl.p;
+    unsigned int *flags = (unsigned int *)(ctl + CTL_FLAGS);
+    unsigned int *n_cand = (unsigned int *)(ctl + CTL_NCAND), *n_tips = (unsigned int *)(ctl + CTL_NTIPS), *n_fork = (unsigned int *)(ctl + CTL_NFORK);
+    uint8_t *mark = (uint8_t *)d_mark.p;
+    const dim3 grid(ug_grid(n)), block(256);
+    // ---- index and links; one read of the flags
+    hipLaunchKernelGGL(k_ug_insert<W>, grid, block, 0, st, g, (unsigned long long *)d_slot.p, cap, flags);
+    hipLaunchKernelGGL(k_ug_links<W>, grid, block, 0, st, g, (const unsigned long long *)d_slot.p, cap, flags);
+    hipLaunchKernelGGL(k_ug_pairs<W>, grid, block, 0, st, g, flags);
+    UGCHK(hipGetLastError());
+    UGCHK(hipMemcpyAsync(h_ctl, ctl, 8, hipMemcpyDeviceToHost, st));
+    UGCHK(hipStreamSynchronize(st));
+    lap("init");
+    {
+        const unsigned int f = (unsigned int)h_ctl[CTL_FLAGS];
+        if (f & UGF_SAME_START) { err = "unitig graph: two chains start at the same oriented node"; return -1; }
+        if (f & UGF_NO_MIRROR) { err = "unitig graph: a chain without its mirror strand"; return -1; }
+        if (f & UGF_UNPAIRED) { err = "unitig graph: mirror strands do not pair up"; return -1; }
+        if (f & UGF_PROBE_BOUND) { err = "unitig graph: a probe of the index of chain starts did not end"; return -1; }
+    }
+    // ---- S9 rounds: one host read per round, of the two node counts
+    if (tips || bubbles) {
+        for (int round = 0; round < 32; round++) {                // MAX_ROUNDS (S9)
+            UGCHK(hipMemsetAsync(ctl + 1, 0, (CTL_WORDS - 1) * 8, st));
+            if (tips) {
+                UGCHK(hipMemsetAsync(d_head.p, 0xFF, n * 4, st));
+                hipLaunchKernelGGL(k_ug_tip_candidates<W>, grid, block, 0, st, g, (uint32_t *)d_cand.p, n_cand);
+                hipLaunchKernelGGL(k_ug_tip_walk<W>, grid, block, 0, st, g, (const uint32_t *)d_cand.p, n_cand, (UTip *)d_tips.p, n_tips, (uint32_t *)d_head.p);
+                hipLaunchKernelGGL(k_ug_tip_decide<W>, grid, block, 0, st, g, (const UTip *)d_tips.p, n_tips, (const uint32_t *)d_head.p, (uint8_t *)d_kill.p);
+                hipLaunchKernelGGL(k_ug_tip_remove<W>, grid, block, 0, st, g, (const UTip *)d_tips.p, n_tips, (const uint8_t *)d_kill.p, mark);
+                hipLaunchKernelGGL(k_ug_apply<W>, grid, block, 0, st, g, mark, ctl + CTL_TIP_NODES);
+            }
+            if (bubbles) {                                        // on the graph the tip round left
+                hipLaunchKernelGGL(k_ug_fork_candidates<W>, grid, block, 0, st, g, (uint32_t *)d_cand.p, n_fork);
+                hipLaunchKernelGGL(k_ug_bubble<W>, grid, block, 0, st, g, (const uint32_t *)d_cand.p, n_fork, mark);
+                hipLaunchKernelGGL(k_ug_apply<W>, grid, block, 0, st, g, mark, ctl + CTL_BUB_NODES);
+            }
+            UGCHK(hipGetLastError());
+            UGCHK(hipMemcpyAsync(h_ctl + CTL_TIP_NODES, ctl + CTL_TIP_NODES, 16, hipMemcpyDeviceToHost, st));
+            UGCHK(hipStreamSynchronize(st));
+            const uint64_t a = h_ctl[CTL_TIP_NODES], b = h_ctl[CTL_BUB_NODES];
+            out.tips_removed += a; out.bubbles_removed += b; out.rounds++;
+            if (a + b == 0) break;
+        }
+    }
+    lap("rounds");
+    // ---- simple successors; alive / mirror / succ go home, the host's own walk makes the contigs
+    hipLaunchKernelGGL(k_ug_succ<W>, grid, block, 0, st, g, (uint32_t *)d_succ.p);
+    UGCHK(hipGetLastError());
+    alive.resize(n); mirror.resize(n); succ.resize(n);
+    UGCHK(hipMemcpyAsync(alive.data(), d_alive.p, n, hipMemcpyDeviceToHost, st));
+    UGCHK(hipMemcpyAsync(mirror.data(), d_mirror.p, n * 4, hipMemcpyDeviceToHost, st));
+    UGCHK(hipMemcpyAsync(succ.data(), d_succ.p, n * 4, hipMemcpyDeviceToHost, st));
+    UGCHK(hipStreamSynchronize(st));
+    lap("succ");
+    const int rc = unitig_chains(k, recs, alive, std::move(mirror), succ, out, err);
+    lap("chains");
+    return rc;
+}
+
+}  // namespace
+
+int unitig_assemble_device(int k, const std::vector<UnitigRec> &recs, bool tips, bool bubbles, int device, void *stream,
+                           UnitigGraphResult &out, std::string &err) {
+    int before = 0;
+    if (hipGetDevice(&before) != hipSuccess || (before != device && hipSetDevice(device) != hipSuccess)) {
+        err = std::string("unitig graph on the device: no such device: ") + hipGetErrorString(hipGetLastError());
+        return -5;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    switch ((2 * k + 63) / 64) {
+        case 1: rc = assemble_device_t<1>(k, recs, tips, bubbles, st, out, err); break;
+        case 2: rc = assemble_device_t<2>(k, recs, tips, bubbles, st, out, err); break;
+        case 3: rc = assemble_device_t<3>(k, recs, tips, bubbles, st, out, err); break;
+        case 4: rc = assemble_device_t<4>(k, recs, tips, bubbles, st, out, err); break;
+        case 5: rc = assemble_device_t<5>(k, recs, tips, bubbles, st, out, err); break;
+        case 6: rc = assemble_device_t<6>(k, recs, tips, bubbles, st, out, err); break;
+        case 7: rc = assemble_device_t<7>(k, recs, tips, bubbles, st, out, err); break;
+        case 8: rc = assemble_device_t<8>(k, recs, tips, bubbles, st, out, err); break;
+        default: err = "k too large"; rc = -1;
+    }
+    if (before != device) (void)hipSetDevice(before);
+    return rc;
+}
+
+}  // namespace shk

@@ -1,32 +1,86 @@
-"""Host unitig graph (csrc/unitig_graph.cpp) at metagenome scale: N isolated unitigs + a share of linked / forked ones, both
-strands.  Usage: SHK_UG_DEBUG=1 python tools/unitig_bench.py [n_unitigs]"""
-import ctypes as C, os, sys, time
+"""Unitig graph of the sharded assembly at metagenome scale: N unitigs on both strands — most isolated, a tenth joined in
+pairs by a simple link, one in fifty a fork with a 5-node dead end (a tip: removed in round 1, the link it leaves is simple
+in round 2).  Times the host entry point (csrc/unitig_graph.cpp) and, with --device, the device entry point
+(csrc/unitig_graph_gpu.hip) on the same records, alternating, and checks that the two texts are equal.
+Usage: [SHK_UG_DEBUG=1] python tools/unitig_bench.py [n_unitigs ...] [--device] [--runs R] [--lib PATH]
+--lib: load this build of the library instead of the tree's own (the parent commit's, as the reference for the host path: a
+process holds one build — a second one's internal calls would bind to the first's symbols)."""
+import argparse, ctypes as C, hashlib, json, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from sparrowhawk_amd import _lib
-L = _lib.load()
+
+ap = argparse.ArgumentParser()
+ap.add_argument("n_unitigs", nargs="*", type=int, default=[4_000_000])
+ap.add_argument("--device", action="store_true")
+ap.add_argument("--runs", type=int, default=3)
+ap.add_argument("--lib", default=None)
+a = ap.parse_args()
+if a.device:
+    import torch                                            # noqa: F401  (the HIP runtime the tests load first, too)
+if a.lib:
+    L = C.CDLL(a.lib, mode=C.RTLD_GLOBAL)
+    for name in ("shk_host_unitig_assemble", "shk_host_free") + (("shk_device_unitig_assemble",) if a.device else ()):
+        getattr(L, name).restype, getattr(L, name).argtypes = _lib.SIGNATURES[name]
+else:
+    L = _lib.load()
 k = 31
-n_u = int(sys.argv[1]) if len(sys.argv) > 1 else 4_000_000
-rng = np.random.default_rng(3)
 MASK = (1 << 62) - 1
-def revcomp(x):                                         # 31-mers in 62 bits, first base most significant
+
+
+def revcomp(x):                                             # 31-mers in 62 bits, first base most significant
     x = (~x) & np.uint64(MASK)
     out = np.zeros_like(x)
     for i in range(31):
         out |= ((x >> np.uint64(2 * i)) & np.uint64(3)) << np.uint64(2 * (30 - i))
     return out
-f = rng.integers(0, MASK, n_u, dtype=np.uint64); l = rng.integers(0, MASK, n_u, dtype=np.uint64)
-# a tenth of the unitigs: i -> i+1 joined by a simple link (last of i overlaps first of i+1 by k-1)
-j = np.arange(0, n_u // 10 * 2, 2)
-l[j] = (l[j] & np.uint64(3 << 60)) | (f[j + 1] >> np.uint64(2))
-n = 2 * n_u
-first = np.zeros(n, dtype=np.uint64); last = np.zeros(n, dtype=np.uint64)
-first[0::2] = f; last[0::2] = l; first[1::2] = revcomp(l); last[1::2] = revcomp(f)
-ln = np.full(n, 40, dtype=np.uint64); kc = np.full(n, 400, dtype=np.uint64); circ = np.zeros(n, dtype=np.uint8)
-L.shk_host_unitig_assemble.restype = C.c_void_p
-t0 = time.time()
-ptr = L.shk_host_unitig_assemble(k, n, first.ctypes.data, last.ctypes.data, ln.ctypes.data, kc.ctypes.data, circ.ctypes.data, None, None, None, 1, 1)
-dt = time.time() - t0
-text = C.string_at(ptr)[:200].decode()
-print("%d records: %.2f s (including the text of the result)" % (n, dt), text.split("\n")[0])
-L.shk_host_free(C.c_void_p(ptr))
+
+
+def records(n_u):
+    rng = np.random.default_rng(3)
+    f = rng.integers(0, MASK, n_u, dtype=np.uint64); l = rng.integers(0, MASK, n_u, dtype=np.uint64)
+    nodes = np.full(n_u, 40, dtype=np.uint64)
+    # a tenth of the unitigs: i -> i+1 joined by a simple link (last of i overlaps first of i+1 by k-1)
+    j = np.arange(0, n_u // 10 * 2, 2)
+    l[j] = (l[j] & np.uint64(3 << 60)) | (f[j + 1] >> np.uint64(2))
+    # one in fifty, behind them: J = i, a long chain i+1 and a 5-node dead end i+2 both run into J's first node
+    t = np.arange(n_u // 10 * 2, n_u // 10 * 2 + n_u // 50 * 3, 3)
+    t = t[t + 2 < n_u]
+    pre = f[t] >> np.uint64(2)
+    l[t + 1] = pre; l[t + 2] = pre | np.uint64(1 << 60)
+    nodes[t + 1] = 200; nodes[t + 2] = 5
+    n = 2 * n_u
+    first = np.zeros(n, dtype=np.uint64); last = np.zeros(n, dtype=np.uint64)
+    first[0::2] = f; last[0::2] = l; first[1::2] = revcomp(l); last[1::2] = revcomp(f)
+    ln = np.repeat(nodes, 2); kc = ln * np.uint64(10); circ = np.zeros(n, dtype=np.uint8)
+    return n, first, last, ln, kc, circ
+
+
+def timed(lib, name, n, first, last, ln, kc, circ):
+    fn = getattr(lib, name)
+    t0 = time.perf_counter()
+    ptr = fn(k, n, first.ctypes.data, last.ctypes.data, ln.ctypes.data, kc.ctypes.data, circ.ctypes.data, None, None, None, 1, 1)
+    dt = time.perf_counter() - t0
+    assert ptr, name + " failed"
+    text = C.string_at(ptr)
+    lib.shk_host_free(ptr)
+    assert not text.startswith(b"error:"), text[:200]
+    return dt, text[:text.index(b"\n")].decode(), hashlib.sha256(text).hexdigest()
+
+
+for n_u in a.n_unitigs:
+    n, *arrs = records(n_u)
+    paths = [("host", L, "shk_host_unitig_assemble")]
+    if a.device:
+        paths.append(("device", L, "shk_device_unitig_assemble"))
+        timed(L, "shk_device_unitig_assemble", n, *arrs)    # (first launches load the code object: not timed)
+    times = {p[0]: [] for p in paths}
+    digests = set()
+    for run in range(a.runs):                               # alternating: the paths see the same state of the box
+        for label, lib, name in paths:
+            dt, head, digest = timed(lib, name, n, *arrs)
+            times[label].append(dt); digests.add((head, digest))
+    assert len(digests) == 1, "the paths disagree: %r" % (digests,)
+    print(json.dumps({"library": a.lib or "this tree's", "n_unitigs": n_u, "records": n, "result": sorted(digests)[0][0],
+                      "seconds_including_the_text_of_the_result": {p: [round(x, 4) for x in v] for p, v in times.items()},
+                      "median": {p: round(statistics.median(v), 4) for p, v in times.items()}}), flush=True)
