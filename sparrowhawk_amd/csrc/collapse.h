@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void k_succ_split(Graph<W> g, const uint8_t *_
                                                     uint2 *__restrict__ winfo, uint32_t *__restrict__ spl,
                                                     uint2 *__restrict__ ol, unsigned int *__restrict__ n_spl,
                                                     uint32_t split_mask, unsigned long long *__restrict__ n_alive /* += alive oriented nodes */,
-                                                    const unsigned long long *__restrict__ skip = nullptr /* two counters: return at once unless both are 0 */) {
+                                                    const unsigned long long *__restrict__ skip = nullptr /* two counters (GraphWords::r0_tips_removed, r0_bubbles_removed): return at once unless both are 0 */) {
     // (launched behind a correction round whose outcome the host does not know yet: if that round removed nodes the graph
     // is not final and this launch is repeated later — pipeline.hip: rank_chains)
     if (skip && (skip[0] | skip[1])) return;
@@ -652,8 +652,8 @@ __global__ __launch_bounds__(256) void k_ring_rot(Graph<W> g, HeadRec *__restric
 // chain (which spells its whole k-mer).
 // The emission plan of an assembly with few chains, on the device (a fragmented one is planned by writer_gpu.h, any other by
 // the host): which chain records are emitted and where their text starts — so that k_emit and the download of the text can be
-// launched BEHIND the ranking, before the host has seen a single chain record.  plan[0] = 1: done, plan[1] = bytes of text,
-// plan[2] = chains emitted; plan[0] = 2: not planned (more chains than max_heads, more text than out_cap, or none ranked:
+// launched BEHIND the ranking, before the host has seen a single chain record.  plan (GraphWords::plan_state, plan_bytes, plan_emitted): [0] = 1: done, [1] = bytes of text,
+// [2] = chains emitted; [0] = 2: not planned (more chains than max_heads, more text than out_cap, or none ranked:
 // the host does it).  One workgroup.  Offsets in chain-record order, as the host's loop assigns them.
 __global__ __launch_bounds__(1024) void k_plan_emit(const HeadRec *__restrict__ heads, const unsigned int *__restrict__ n_heads_p, uint32_t k,
                                                    uint32_t max_heads, unsigned long long out_cap, const uint32_t *__restrict__ flags,

@@ -704,7 +704,7 @@ __device__ __forceinline__ uint32_t gp_table_size(uint32_t rows) {
 // The cursor counts the recorded ROWS too (high word; slots in the low word, which the host keeps below 2^32): the host
 // takes the ranges only when they hold every row, so a group whose rows left unrecorded is noticed without the flag.
 struct EmitRanges {
-    unsigned long long *tab_cursor = nullptr;   // nullptr: nothing recorded; else rows << 32 | slots
+    unsigned long long *tab_cursor = nullptr;   // nullptr: nothing recorded; else rows << 32 | slots (CountWords::er_cursor; broken: er_broken)
     unsigned long long *off = nullptr;
     uint32_t *msk = nullptr, *start = nullptr, *cnt = nullptr, *broken = nullptr;
 };
@@ -1188,7 +1188,7 @@ __global__ __launch_bounds__(COUNT_THREADS) void k_count_partitions(
 // ovf != nullptr (single GPU): reads with errors do not deduplicate and their partitions do not fit the k-mer table of
 // the counting kernel.  The partitions tried here are the sample: each reports "tried" and, if it ended with more distinct
 // records than the k-mer table has room for keys (kmer_cap) or lost less than half of its records as duplicates, "handed
-// over" (ovf_n[1]: tried | handed over << 16; n_out[p] = 0 and an entry in ovf[]: the k-mer-level repartition counts it
+// over" (ovf_n[1], CountWords::tally: tried | handed over << 16; n_out[p] = 0 and an entry in ovf[]: the k-mer-level repartition counts it
 // from its raw records).  The report returns the tally: once >= defer_after were handed over and they are at least HALF of
 // those tried, the workgroup only reads its further partitions for their k-mer counts and reports them "not tried".
 // (HALF, not the 3/4 k_count_partitions asks of its sample of whole counts: the records' repeats are the weaker sign — with
@@ -1208,7 +1208,7 @@ __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_dedupe_partit
                                                                      uint32_t *__restrict__ n_out, uint32_t *__restrict__ work_counter,
                                                                      OvfRec *__restrict__ ovf /* nullable */, uint32_t *__restrict__ ovf_n,
                                                                      uint32_t defer_after, uint32_t kmer_cap,
-                                                                     uint32_t *__restrict__ verdict_out /* nullable: k_count_weighted's tally word — the verdict is passed on */) {
+                                                                     uint32_t *__restrict__ verdict_out /* nullable: k_count_weighted's tally (CountWords::group_tally) — the verdict is passed on */) {
     constexpr int RW = 2 * W;
     __shared__ DedupeShared<W> tb;
     __shared__ CountCtl ctl;

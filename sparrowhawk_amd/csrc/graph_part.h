@@ -368,7 +368,7 @@ template <int W, uint32_t SLOTS, int NT>
 __global__ __launch_bounds__(NT) void k_graph_local(KeyArr<W> keys, int k, GraphTable gt, GpRows gr,
                                                     uint8_t *__restrict__ adj, uint32_t *__restrict__ nb,
                                                     unsigned long long *__restrict__ queries, uint32_t *__restrict__ qcnt,
-                                                    uint32_t *__restrict__ overflow, uint32_t lds_slots /* <= SLOTS */,
+                                                    uint32_t *__restrict__ overflow /* GraphWords::table_flag */, uint32_t lds_slots /* <= SLOTS */,
                                                     uint8_t *__restrict__ alive, uint32_t *__restrict__ row_bits, uint32_t lowmask) {
     const unsigned gm = (unsigned)gt.gm;
     __shared__ uint2 lut[16];

@@ -27,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "ctl_words.h"
 #include "kmer.h"
 #include "pipeline.h"
 #include "shard_comm.h"
@@ -54,11 +55,6 @@ namespace shk {
     } while (0)
 
 static constexpr uint32_t NIL = 0xFFFFFFFFu;
-// device-side counters and flags of a pipeline (ctl_): 0-2 count / graph build, 3-6 correction rounds, 5-10 collapse, 8-9
-// pass 1, 11-12 / 14 pass 2, 13 shard layer, 16-17 what the FIRST correction round removed (tips, bubbles: read back with
-// the collapse's first counters — the round costs no host round trip of its own)
-static constexpr int CTL_WORDS = 32;
-static constexpr int CTL_ER = 22;                  // ctl_[22]: table slots reserved by the counting groups (EmitRanges), [23]: a group broken up
 static constexpr uint32_t GP_MAX = 131072;         // graph partitions at most (17 bits of a queued neighbour query)
 static constexpr uint64_t EMPTY64 = ~0ull;
 static constexpr int MAX_PROBE = 4096;
@@ -558,19 +554,19 @@ public:
         }
         pending_.push_back({d_bases, d_seg_off, n_seg});
         for (;;) {
-            HIPCHK(hipMemsetAsync(ctl_.p, 0, CTL_WORDS * sizeof(unsigned long long), stream_));
+            HIPCHK(hipMemsetAsync(ctl_.p, 0, sizeof(CountWords), stream_));
             EvTimer t(stream_);
             hipLaunchKernelGGL(k_count_segments<W>, dim3(grid_for(n_seg)), dim3(256), 0, stream_, d_bases,
-                               d_seg_off, (uint32_t)n_seg, k_, table_view(), (uint32_t *)(ctl_.p + 1),
-                               ctl_.p + 0);
+                               d_seg_off, (uint32_t)n_seg, k_, table_view(), (uint32_t *)ctl(&CountWords::g_overflow),
+                               ctl(&CountWords::g_instances));
             HIPCHK(hipGetLastError());
             double ms = t.stop();
-            unsigned long long h[2];
-            HIPCHK(hipMemcpyAsync(h, ctl_.p, sizeof h, hipMemcpyDeviceToHost, stream_));
+            CountWords h;
+            HIPCHK(fetch_ctl(&h, &CountWords::g_instances, &CountWords::g_overflow));
             WAIT_STREAM();
-            if ((uint32_t)h[1] == 0) {
+            if ((uint32_t)h.g_overflow == 0) {
                 times_.add("count_kernel", ms);
-                total_instances_ += h[0];
+                total_instances_ += h.g_instances;
                 return 0;
             }
             // table too small: grow 4x and recount every batch seen so far
@@ -584,7 +580,7 @@ public:
     template <int WBLK, int NBLK>
     void launch_partition_t(const uint32_t *d_bases, const uint32_t *d_seg_off, uint32_t n_seg) {
         hipLaunchKernelGGL((k_partition<W, WBLK, NBLK>), dim3(pp_.G), dim3(PART_THREADS), 0, stream_, d_bases, d_seg_off,
-                           n_seg, pp_, recs_.p, fill_.p, (uint32_t *)(ctl_.p + 8));
+                           n_seg, pp_, recs_.p, fill_.p, ctl(&CountWords::p1_spare));
     }
     void launch_partition(int win, const uint32_t *d_bases, const uint32_t *d_seg_off, uint32_t n_seg) {
         if (win == 20) launch_partition_t<10, 2>(d_bases, d_seg_off, n_seg);
@@ -671,7 +667,7 @@ public:
             const uint64_t n_slices = (uint64_t)P * pp_.G;
             if (int rc = recs_.alloc(n_slices * cap * RW, err)) return rc;
             if (int rc = fill_.alloc(n_slices, err)) return rc;
-            HIPCHK(fill2_async(fill_.p, n_slices * 4, 0u, ctl_.p, CTL_WORDS * sizeof(unsigned long long), 0u, stream_));
+            HIPCHK(fill2_async(fill_.p, n_slices * 4, 0u, ctl_.p, sizeof(CountWords), 0u, stream_));
             EvTimer t(stream_);
             if (h_bases && attempt == 0) {
                 // ---- upload and pass 1, piece by piece
@@ -703,24 +699,23 @@ public:
                 HIPCHK(hipGetLastError());
                 times_.add("h2d_pieces_x1", (double)C);
                 if (defer_p1_ && batches_.empty()) {            // (as below: pass 2 follows without a host round trip)
-                    HIPCHK(hipMemcpyAsync(mbox64() + MB_P1, ctl_.p + 8, 16, hipMemcpyDeviceToHost, stream_));
+                    HIPCHK(fetch_ctl(mb_p1(), &CountWords::p1_spare, &CountWords::p1_max_fill));
                     t.stop_later("partition_with_upload", pending_timers_);
                     p1_ = P1Pending{true, d_bases, d_seg_off, n_seg, n_bases, cap};
                     return finish_partition(n_slices, err);
                 }
                 t.mark();
-                unsigned long long h[2];
-                HIPCHK(hipMemcpyAsync(h, ctl_.p + 8, sizeof h, hipMemcpyDeviceToHost, stream_));
+                CountWords h;
+                HIPCHK(fetch_ctl(&h, &CountWords::p1_spare, &CountWords::p1_max_fill));
                 WAIT_STREAM();
-                const uint32_t *fl = (const uint32_t *)&h[0];
-                if (fl[1]) { err = "a read segment exceeds 32768 bases (split it on the host)"; return -1; }
-                if ((uint32_t)h[1] <= cap) {
+                if (h.p1_seg_too_long) { err = "a read segment exceeds 32768 bases (split it on the host)"; return -1; }
+                if ((uint32_t)h.p1_max_fill <= cap) {
                     times_.add("partition_with_upload", t.elapsed());
                     if (int rc = finish_partition(n_slices, err)) return rc;
                     return 0;
                 }
                 times_.add("partition_retry", t.elapsed());
-                cap = (uint64_t)(uint32_t)h[1] + 8;               // (the reads are on the device now: the retry is one launch)
+                cap = (uint64_t)(uint32_t)h.p1_max_fill + 8;      // (the reads are on the device now: the retry is one launch)
                 continue;
             }
             launch_partition_all(wblk, d_bases, d_seg_off, n_seg);
@@ -730,19 +725,18 @@ public:
                 // host round trip; the flags land in pinned memory and are looked at after pass 2's own read-back.  A slice
                 // that overflowed stored nothing beyond its room (wave_flush) and its run is clamped (k_make_runs): pass 2 then
                 // ran on a part of the records and both passes are repeated with the exact room (histogram()).
-                HIPCHK(hipMemcpyAsync(mbox64() + MB_P1, ctl_.p + 8, 16, hipMemcpyDeviceToHost, stream_));
+                HIPCHK(fetch_ctl(mb_p1(), &CountWords::p1_spare, &CountWords::p1_max_fill));
                 t.stop_later("partition_kernel", pending_timers_);
                 p1_ = P1Pending{true, d_bases, d_seg_off, n_seg, n_bases, cap};
                 return finish_partition(n_slices, err);
             }
             t.mark();
-            unsigned long long h[2];
-            HIPCHK(hipMemcpyAsync(h, ctl_.p + 8, sizeof h, hipMemcpyDeviceToHost, stream_));
+            CountWords h;
+            HIPCHK(fetch_ctl(&h, &CountWords::p1_spare, &CountWords::p1_max_fill));
             WAIT_STREAM();          // (one host round trip: flags and the timer together)
             const double ms = t.elapsed();
-            const uint32_t *fl = (const uint32_t *)&h[0];
-            if (fl[1]) { err = "a read segment exceeds 32768 bases (split it on the host)"; return -1; }
-            const uint32_t max_fill = (uint32_t)h[1];
+            if (h.p1_seg_too_long) { err = "a read segment exceeds 32768 bases (split it on the host)"; return -1; }
+            const uint32_t max_fill = (uint32_t)h.p1_max_fill;
             if (max_fill <= cap) {
                 times_.add("partition_kernel", ms);
                 if (int rc = finish_partition(n_slices, err)) return rc;
@@ -897,7 +891,7 @@ public:
             bloom_new = 0; bloom_kmer_bytes = 0; bloom_kmer_bytes_exact = 0;
             for (int j = 0; j < W; j++) if (int rc = keys[j].alloc(cap, err)) return rc;
             if (int rc = cnt.alloc(cap, err)) return rc;
-            HIPCHK(fill2_async(dh.p, 500 * 8, 0u, ctl_.p, CTL_WORDS * sizeof(unsigned long long), 0u, stream_));
+            HIPCHK(fill2_async(dh.p, 500 * 8, 0u, ctl_.p, sizeof(CountWords), 0u, stream_));
             KeyArr<W> ok; for (int j = 0; j < W; j++) ok.w[j] = keys[j].p;
             const uint32_t probe_parts = (uint32_t)env_u64("SHK_PROBE_PARTS", 512);     // 0 = off
             const uint32_t n_probe = (repartition && probe_parts && n_parts / 4 >= probe_parts) ? probe_parts : 0u;
@@ -917,8 +911,8 @@ public:
                 const uint32_t defer_after = n_probe / 8;
                 EvTimer t_a(stream_, stage_timers_);
                 hipLaunchKernelGGL(k_dedupe_partitions<W>, dim3(std::min<uint32_t>(n_parts, 2u * (uint32_t)n_cus_)), dim3(COUNT_THREADS), 0, stream_,
-                                   rv, 0u, n_parts, dd_base_.p, dd_recs_.p, dd_w_.p, dd_n_.p, (uint32_t *)(ctl_.p + 12),
-                                   d_ovf.p, (uint32_t *)(ctl_.p + 3), defer_after, (S / 10) * 9, (uint32_t *)(ctl_.p + 14) + 1);
+                                   rv, 0u, n_parts, dd_base_.p, dd_recs_.p, dd_w_.p, dd_n_.p, (uint32_t *)ctl(&CountWords::dedupe_work),
+                                   d_ovf.p, ctl(&CountWords::n_handed_over), defer_after, (S / 10) * 9, ctl(&CountWords::group_tally));
                 HIPCHK(hipGetLastError());
                 if (attempt == 0) t_a.stop_later("count_dedupe_kernel", pending_timers_);
                 const uint32_t per_cu = 2u;
@@ -942,34 +936,35 @@ public:
                     if (int rc = er_msk_.alloc(n_groups, err)) return rc;
                     if (int rc = er_start_.alloc(n_groups, err)) return rc;
                     if (int rc = er_cnt_.alloc(n_groups, err)) return rc;
-                    er.tab_cursor = ctl_.p + CTL_ER; er.broken = (uint32_t *)(ctl_.p + CTL_ER + 1);
+                    er.tab_cursor = ctl(&CountWords::er_cursor); er.broken = (uint32_t *)ctl(&CountWords::er_broken);
                     er.off = er_off_.p; er.msk = er_msk_.p; er.start = er_start_.p; er.cnt = er_cnt_.p;
                     er_groups_ = n_groups;
                 }
                 hipLaunchKernelGGL(k_count_weighted<W>, dim3(std::min<uint32_t>(n_groups, per_cu * (uint32_t)n_cus_)), dim3(COUNT_THREADS), 0, stream_,
                                    dd_recs_.p, dd_w_.p, dd_base_.p, dd_n_.p, 0u, n_parts, merge, rv.k, threshold, dh.p, ok, cnt.p, (unsigned long long)cap,
-                                   // (ctl_[14]: the groups handed out and, in its high word, this kernel's tally — it starts at the dedupe's verdict
+                                   // (groups_out and, in the word's high half, this kernel's tally — it starts at the dedupe's verdict
                                    // and covers reads whose records repeat but whose k-mers do not fit)
-                                   ctl_.p + 0, ctl_.p + 1, d_ovf.p, (uint32_t *)(ctl_.p + 3), ctl_.p + 14, 0u, defer_after, er);
+                                   ctl(&CountWords::row_cursor), ctl(&CountWords::instances), d_ovf.p, ctl(&CountWords::n_handed_over),
+                                   (unsigned long long *)ctl(&CountWords::groups_out), 0u, defer_after, er);
             } else {
                 // (persistent workgroups, one per CU: the tables take the whole LDS)
                 auto kern = rv.weights ? k_count_partitions<W, true> : k_count_partitions<W, false>;
                 hipLaunchKernelGGL(kern, dim3(std::min<uint32_t>(n_parts, (uint32_t)n_cus_)), dim3(COUNT_THREADS), 0, stream_, rv, n_parts, threshold,
-                                   dh.p, ok, cnt.p, (unsigned long long)cap, ctl_.p + 0, ctl_.p + 1,
-                                   (uint32_t *)(ctl_.p + 2), (const uint32_t *)nullptr, repartition ? d_ovf.p : (OvfRec *)nullptr,
-                                   (uint32_t *)(ctl_.p + 3), (uint32_t *)(ctl_.p + 11), n_probe / 2, n_probe / 8);
+                                   dh.p, ok, cnt.p, (unsigned long long)cap, ctl(&CountWords::row_cursor), ctl(&CountWords::instances),
+                                   ctl(&CountWords::part_too_large), (const uint32_t *)nullptr, repartition ? d_ovf.p : (OvfRec *)nullptr,
+                                   ctl(&CountWords::n_handed_over), (uint32_t *)ctl(&CountWords::probe_work), n_probe / 2, n_probe / 8);
             }
             HIPCHK(hipGetLastError());
             t.mark();
-            unsigned long long h[4], her[2] = {0, 0};
-            HIPCHK(hipMemcpyAsync(h, ctl_.p, sizeof h, hipMemcpyDeviceToHost, stream_));
+            CountWords h{};
+            HIPCHK(fetch_ctl(&h, &CountWords::row_cursor, &CountWords::tally));
             HIPCHK(hipMemcpyAsync(hist_out, dh.p, 500 * 8, hipMemcpyDeviceToHost, stream_));   // (final unless partitions overflowed)
-            if (split && er_groups_) HIPCHK(hipMemcpyAsync(her, ctl_.p + CTL_ER, sizeof her, hipMemcpyDeviceToHost, stream_));
+            if (split && er_groups_) HIPCHK(fetch_ctl(&h, &CountWords::er_cursor, &CountWords::er_broken));
             WAIT_STREAM();          // one host round trip: counters, histogram, the groups' ranges' verdict and the timer
             ms_out = t.elapsed();      // (sample + dedupe + count)
-            const uint32_t n_ovf = (uint32_t)h[3];
+            const uint32_t n_ovf = h.n_handed_over;
             if (env_u64("SHK_VERBOSE_TALLY", 0)) fprintf(stderr, "[shk] pass 2: %u partitions, %u handed over, tally tried %u / over %u, split %d\n", n_parts, n_ovf,
-                                                    (unsigned)((h[3] >> 32) & 0xFFFFu), (unsigned)(h[3] >> 48), (int)split);
+                                                    tally_tried(h.tally), tally_over(h.tally), (int)split);
             // rows written by the bucket path are ordered by key hash, not grouped by minimiser partition (build_graph regroups)
             rows_scattered_ = (uint64_t)n_ovf * 4u > n_parts;
             if (n_ovf) {
@@ -1027,18 +1022,17 @@ public:
                     unsigned long long n_buckets_ub = 0;
                     for (auto &it : items) n_buckets_ub += it.F;
                     if (int rc = d_blist.alloc(n_buckets_ub, err)) return rc;
-                    HIPCHK(fill2_async(ctl_.p + 4, sizeof(unsigned long long), 0u, nullptr, 0, 0u, stream_));
+                    HIPCHK(fill2_async(ctl(&CountWords::bucket_list_len), ctl_span(&CountWords::bucket_list_len), 0u, nullptr, 0, 0u, stream_));
                     if (int rc = d_sumfill.alloc(ni, err)) return rc;
                     hipLaunchKernelGGL(k_ovf_check, dim3(grid_for(ni)), dim3(256), 0, stream_, d_items.p, d_fill.p, ni, d_maxfill.p,
-                                       d_blist.p, (uint32_t *)(ctl_.p + 4), d_sumfill.p);
+                                       d_blist.p, (uint32_t *)ctl(&CountWords::bucket_list_len), d_sumfill.p);
                     HIPCHK(hipGetLastError());
                     std::vector<uint32_t> mxf(ni), newc(bloom ? ni : 0);
                     std::vector<unsigned long long> smf(ni);
-                    unsigned long long n_list = 0;
                     HIPCHK(hipMemcpyAsync(smf.data(), d_sumfill.p, (size_t)ni * 8, hipMemcpyDeviceToHost, stream_));
                     if (bloom) HIPCHK(hipMemcpyAsync(newc.data(), d_new.p, (size_t)ni * 4, hipMemcpyDeviceToHost, stream_));
                     HIPCHK(hipMemcpyAsync(mxf.data(), d_maxfill.p, (size_t)ni * 4, hipMemcpyDeviceToHost, stream_));
-                    HIPCHK(hipMemcpyAsync(&n_list, ctl_.p + 4, sizeof n_list, hipMemcpyDeviceToHost, stream_));
+                    HIPCHK(fetch_ctl(&h, &CountWords::bucket_list_len, &CountWords::bucket_list_len));
                     WAIT_STREAM();
                     std::vector<OvfItem> again;
                     uint32_t n_good = 0;
@@ -1054,12 +1048,12 @@ public:
                             OvfItem it = items[i]; it.cap = mxf[i] + 256; again.push_back(it);       // the exact need is known now
                         } else bad.push_back(items[i].p);
                     }
-                    if ((uint32_t)n_list) {
+                    if (const uint32_t n_list = (uint32_t)h.bucket_list_len) {
                         // persistent workgroups, two per CU (the k-mer table is half the LDS)
-                        const uint32_t bgrid = (uint32_t)std::min<unsigned long long>(n_list, 2ull * (unsigned long long)n_cus_);
+                        const uint32_t bgrid = (uint32_t)std::min<unsigned long long>(h.bucket_list_len, 2ull * (unsigned long long)n_cus_);
                         hipLaunchKernelGGL(k_count_buckets<W>, dim3(bgrid), dim3(COUNT_THREADS), 0, stream_,
-                                           d_blist.p, (uint32_t)n_list, d_kmers.p, threshold, dh.p, ok, cnt.p, (unsigned long long)cap,
-                                           ctl_.p + 0, ctl_.p + 1, (uint32_t *)(ctl_.p + 2), bloom ? 1u : 0u, ctl_.p + 9);
+                                           d_blist.p, n_list, d_kmers.p, threshold, dh.p, ok, cnt.p, (unsigned long long)cap,
+                                           ctl(&CountWords::row_cursor), ctl(&CountWords::instances), ctl(&CountWords::part_too_large), bloom ? 1u : 0u, ctl(&CountWords::bloom_keys));
                         HIPCHK(hipGetLastError());
                         WAIT_STREAM();      // d_items / d_kmers are reused by the next pass
                     }
@@ -1070,27 +1064,27 @@ public:
                     if (int rc = d_list.alloc(bad.size(), err)) return rc;
                     HIPCHK(hipMemcpyAsync(d_list.p, bad.data(), bad.size() * 4, hipMemcpyHostToDevice, stream_));
                     hipLaunchKernelGGL(k_count_partitions<W>, dim3(std::min<uint32_t>((uint32_t)bad.size(), (uint32_t)n_cus_)), dim3(COUNT_THREADS), 0, stream_, rv, (uint32_t)bad.size(), threshold,
-                                       dh.p, ok, cnt.p, (unsigned long long)cap, ctl_.p + 0, ctl_.p + 1,
-                                       (uint32_t *)(ctl_.p + 2), (const uint32_t *)d_list.p, (OvfRec *)nullptr, (uint32_t *)nullptr, (uint32_t *)(ctl_.p + 12), 0u, 0u);
+                                       dh.p, ok, cnt.p, (unsigned long long)cap, ctl(&CountWords::row_cursor), ctl(&CountWords::instances),
+                                       ctl(&CountWords::part_too_large), (const uint32_t *)d_list.p, (OvfRec *)nullptr, (uint32_t *)nullptr, (uint32_t *)ctl(&CountWords::dedupe_work), 0u, 0u);
                     HIPCHK(hipGetLastError());
                 }
                 ms_out += t2.stop();
                 times_.add("count_repartitioned_x1", (double)n_good_total);
                 times_.add("count_deferred_untried_x1", (double)n_untried);
                 times_.add("count_residue_rerun_x1", (double)bad.size());
-                HIPCHK(hipMemcpyAsync(h, ctl_.p, sizeof h, hipMemcpyDeviceToHost, stream_));
+                HIPCHK(fetch_ctl(&h, &CountWords::row_cursor, &CountWords::tally));
                 HIPCHK(hipMemcpyAsync(hist_out, dh.p, 500 * 8, hipMemcpyDeviceToHost, stream_));
                 WAIT_STREAM();
-                times_.add("count_bucket_splits_x1", (double)(h[2] >> 32));
+                times_.add("count_bucket_splits_x1", (double)h.bucket_splits);
                 if (bloom) {
                     // k-mers the filter took as new: each is one distinct k-mer (less the false positives) and one
                     // instance that never reached a table.  Those that came back later sit in the tables (n_keys);
                     // the rest were seen once: the histogram's first bin (SPEC S4/S5, Bloom mode: statistical)
                     unsigned long long n_keys = 0;
-                    HIPCHK(hipMemcpy(&n_keys, ctl_.p + 9, 8, hipMemcpyDeviceToHost));
+                    HIPCHK(hipMemcpy(&n_keys, ctl(&CountWords::bloom_keys), ctl_span(&CountWords::bloom_keys), hipMemcpyDeviceToHost));
                     const unsigned long long singles = bloom_new > n_keys ? bloom_new - n_keys : 0ull;
                     hist_out[0] += singles;
-                    h[1] += bloom_new;
+                    h.instances += bloom_new;
                     for (uint32_t i = 0; i < n_ovf; i++) bloom_kmer_bytes_exact += ov[i].instances * 8ull * W;
                     times_.add("bloom_new_kmers_x1e-6", (double)bloom_new * 1e-6);
                     times_.add("bloom_singletons_never_stored_x1e-6", (double)singles * 1e-6);
@@ -1098,11 +1092,11 @@ public:
                     times_.add("bloom_kmer_instances_MB_without_filter", (double)bloom_kmer_bytes_exact / 1e6);
                 }
             }
-            if ((uint32_t)h[2]) { err = "partition too large for the LDS table even after 4096-way residue splitting"; return -6; }
-            n_rows = h[0]; inst_out = h[1];
+            if (h.part_too_large) { err = "partition too large for the LDS table even after 4096-way residue splitting"; return -6; }
+            n_rows = h.row_cursor; inst_out = h.instances;
             // (every row lies in the recorded range of its group: no group broken up, none handed to the repartition, and the
             // recorded ranges hold all the rows)
-            er_ok_ = split && er_groups_ && (uint32_t)her[1] == 0u && n_ovf == 0 && (her[0] >> 32) == h[0];
+            er_ok_ = split && er_groups_ && (uint32_t)h.er_broken == 0u && n_ovf == 0 && er_rows(h.er_cursor) == h.row_cursor;
             er_rows_ = n_rows;
             if (n_rows <= cap) {
                 return 0;
@@ -1145,13 +1139,12 @@ public:
                     // pass 1's flags arrived with pass 2's read-back (count_batch_impl): look at them now
                     if (rc_p2) { std::string e2; (void)e2; (void)hipStreamSynchronize(stream_); }
                     p1_.on = false;
-                    const unsigned long long *h = mbox64() + MB_P1;
-                    const uint32_t *fl = (const uint32_t *)&h[0];
-                    if (fl[1]) { split_ready_ = false; err = "a read segment exceeds 32768 bases (split it on the host)"; return -1; }
-                    if ((uint32_t)h[1] > p1_.cap) {
+                    const CountWords &h = *mb_p1();
+                    if (h.p1_seg_too_long) { split_ready_ = false; err = "a read segment exceeds 32768 bases (split it on the host)"; return -1; }
+                    if ((uint32_t)h.p1_max_fill > p1_.cap) {
                         // a slice overflowed: both passes again, pass 1 with the exact room (the reads are still on the device)
                         times_.add("partition_retry", 1.0);
-                        cap_override_ = (uint64_t)(uint32_t)h[1] + 8;
+                        cap_override_ = (uint64_t)(uint32_t)h.p1_max_fill + 8;
                         have_parts_ = false; split_ready_ = false;
                         const bool d = defer_p1_; defer_p1_ = false;
                         const int rc1 = count_batch_impl(p1_.d_bases, p1_.d_seg_off, nullptr, nullptr, p1_.n_seg, p1_.n_bases, err);
@@ -1197,13 +1190,13 @@ public:
         for (int j = 0; j < W; j++) if (int rc = keys[j].alloc(expect, err)) return rc;
         if (int rc = cnt.alloc(expect, err)) return rc;
         if (!tslots_ || !expect) return 0;
-        HIPCHK(hipMemsetAsync(ctl_.p, 0, CTL_WORDS * sizeof(unsigned long long), stream_));
+        HIPCHK(hipMemsetAsync(ctl_.p, 0, sizeof(CountWords), stream_));
         KeyArr<W> ok; for (int j = 0; j < W; j++) ok.w[j] = keys[j].p;
         hipLaunchKernelGGL(k_compact<W>, dim3(grid_for(tslots_)), dim3(256), 0, stream_, table_view(), tslots_,
-                           threshold, ok, cnt.p, ctl_.p + 0);
+                           threshold, ok, cnt.p, ctl(&CountWords::row_cursor));
         HIPCHK(hipGetLastError());
         unsigned long long got = 0;
-        HIPCHK(hipMemcpyAsync(&got, ctl_.p, 8, hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipMemcpyAsync(&got, ctl(&CountWords::row_cursor), ctl_span(&CountWords::row_cursor), hipMemcpyDeviceToHost, stream_));
         WAIT_STREAM();
         if (got != expect) { err = "compaction count mismatch"; return -6; }
         return 0;
@@ -1228,14 +1221,14 @@ public:
             er_ok_ = false;                                 // (the rows move)
             for (int j = 0; j < W; j++) if (int rc = skeys_[j].alloc(expect, err)) return rc;
             if (int rc = scnt_.alloc(expect, err)) return rc;
-            HIPCHK(hipMemsetAsync(ctl_.p, 0, CTL_WORDS * sizeof(unsigned long long), stream_));
+            HIPCHK(hipMemsetAsync(ctl_.p, 0, sizeof(CountWords), stream_));
             KeyArr<W> ik, ok;
             for (int j = 0; j < W; j++) { ik.w[j] = ekeys_[j].p; ok.w[j] = skeys_[j].p; }
             hipLaunchKernelGGL(k_compact_rows<W>, dim3(grid_for(n_emitted_)), dim3(256), 0, stream_, ik, ecnt_.p,
-                               n_emitted_, threshold, ok, scnt_.p, ctl_.p + 0);
+                               n_emitted_, threshold, ok, scnt_.p, ctl(&CountWords::row_cursor));
             HIPCHK(hipGetLastError());
             unsigned long long got = 0;
-            HIPCHK(hipMemcpyAsync(&got, ctl_.p, 8, hipMemcpyDeviceToHost, stream_));
+            HIPCHK(hipMemcpyAsync(&got, ctl(&CountWords::row_cursor), ctl_span(&CountWords::row_cursor), hipMemcpyDeviceToHost, stream_));
             WAIT_STREAM();
             if (got != expect) { err = "row compaction count mismatch"; return -6; }
             for (int j = 0; j < W; j++) ekeys_[j].release();
@@ -1336,12 +1329,12 @@ public:
         if (int rc = dd_recs_.alloc(n_raw * 2 * W + 2, err)) return rc;
         if (int rc = dd_w_.alloc(n_raw + 2, err)) return rc;
         HIPCHK(hipMemcpyAsync(dd_base_.p, base.data(), (size_t)pp_.P * 8, hipMemcpyHostToDevice, stream_));
-        HIPCHK(fill2_async(ctl_.p + 12, 8, 0u, nullptr, 0, 0u, stream_));
+        HIPCHK(fill2_async(ctl(&CountWords::dedupe_work), ctl_span(&CountWords::dedupe_work), 0u, nullptr, 0, 0u, stream_));
         EvTimer t(stream_, stage_timers_);
         // (two workgroups per CU where the kernel's registers allow it, as on one GPU: with one, 588 us against 418 for the
         // bench isolate — found in the timeline of the one-rank leg, profiles/r04_final/sharded_one_rank_timeline.txt)
         hipLaunchKernelGGL(k_dedupe_partitions<W>, dim3(std::min<uint32_t>(pp_.P, (W <= 2 ? 2u : 1u) * (uint32_t)n_cus_)), dim3(COUNT_THREADS), 0, stream_,
-                           run_view_, 0u, pp_.P, dd_base_.p, dd_recs_.p, dd_w_.p, dd_n_.p, (uint32_t *)(ctl_.p + 12),
+                           run_view_, 0u, pp_.P, dd_base_.p, dd_recs_.p, dd_w_.p, dd_n_.p, (uint32_t *)ctl(&CountWords::dedupe_work),
                            (OvfRec *)nullptr, (uint32_t *)nullptr, 0u, 0u, (uint32_t *)nullptr);
         HIPCHK(hipGetLastError());
         t.mark();
@@ -1521,8 +1514,8 @@ public:
         // (the mini tables are initialised by their builders; no fills for adj_ and alive_: k_graph_local writes the adjacency
         // byte of every row before k_graph_remote ORs into it, k_row_starts — or k_graph_local on partitions from the counting
         // groups — sets the alive flags.  The row-start bits are zeroed for k_graph_local, which sets one per group that needs it)
-        if (ranges) HIPCHK(fill2_async(row_starts_.p, row_starts_.bytes, 0u, ctl_.p, CTL_WORDS * sizeof(unsigned long long), 0u, stream_));
-        else HIPCHK(fill2_async(gp_cnt.p, (size_t)gp_ * 4, 0u, ctl_.p, CTL_WORDS * sizeof(unsigned long long), 0u, stream_));
+        if (ranges) HIPCHK(fill2_async(row_starts_.p, row_starts_.bytes, 0u, ctl_.p, sizeof(GraphWords), 0u, stream_));
+        else HIPCHK(fill2_async(gp_cnt.p, (size_t)gp_ * 4, 0u, ctl_.p, sizeof(GraphWords), 0u, stream_));
         // (sharded assembly: a rank that holds NO solid k-mer still owns partitions and is asked about neighbour candidates by
         // the others — its (empty) mini tables must exist: found by the 250-case campaign on 4 ranks, where such a rank answered
         // from tables nobody had built and took a memory fault)
@@ -1537,7 +1530,7 @@ public:
                 const GpRows gr{gp_roff.p, gp_n.p, nullptr};
                 const uint32_t lds_slots = (uint32_t)std::min<uint64_t>(env_u64("SHK_GRAPH_LDS_SLOTS", ADJ_LDS_SLOTS_RANGES), ADJ_LDS_SLOTS_RANGES);
                 hipLaunchKernelGGL((k_graph_local<W, ADJ_LDS_SLOTS_RANGES, ADJ_THREADS_RANGES>), dim3(gp_), dim3(ADJ_THREADS_RANGES), 0, stream_,
-                                   g.keys, k_, g.gt, gr, adj_.p, nb_.p, queries.p, gp_cnt.p, (uint32_t *)(ctl_.p + 1), lds_slots,
+                                   g.keys, k_, g.gt, gr, adj_.p, nb_.p, queries.p, gp_cnt.p, (uint32_t *)ctl(&GraphWords::table_flag), lds_slots,
                                    alive_.p, row_starts_.p, lowmask);
                 hipLaunchKernelGGL(k_graph_remote<W>, dim3(gp_), dim3(256), 0, stream_, g.keys, k_, g.gt, gr, queries.p,
                                    gp_cnt.p, adj_.p, nb_.p);
@@ -1549,7 +1542,7 @@ public:
                 hipLaunchKernelGGL(k_gp_count<W>, dim3(grid_for(n)), dim3(256), 0, stream_, g.keys, (uint32_t)n, k_, g.gt,
                                    gp_of.p, gp_cnt.p);
                 hipLaunchKernelGGL(k_gp_scan, dim3(1), dim3(1024), 0, stream_, gp_cnt.p, gp_, gt_off_.p, gt_msk_.p, gp_roff.p,
-                                   ctl_.p + 2);
+                                   ctl(&GraphWords::slots_used));
                 // (gp_cnt is reused as the row-list cursors: k_gp_scan left it zeroed)
                 hipLaunchKernelGGL(k_gp_rows, dim3(grid_for(n)), dim3(256), 0, stream_, gp_of.p, (uint32_t)n, gp_roff.p, gp_cnt.p,
                                    gp_rows.p);
@@ -1580,7 +1573,7 @@ public:
                 EvTimer t2(stream_, stage_timers_);
                 const GpRows gr{gp_roff.p, nullptr, gp_rows.p};
                 hipLaunchKernelGGL((k_graph_local<W, ADJ_LDS_SLOTS, 256>), dim3(gp_), dim3(256), 0, stream_, g.keys, k_, g.gt, gr,
-                                   adj_.p, nb_.p, queries.p, gp_cnt.p, (uint32_t *)(ctl_.p + 1), ADJ_LDS_SLOTS,
+                                   adj_.p, nb_.p, queries.p, gp_cnt.p, (uint32_t *)ctl(&GraphWords::table_flag), ADJ_LDS_SLOTS,
                                    (uint8_t *)nullptr, (uint32_t *)nullptr, 0u);
                 hipLaunchKernelGGL(k_graph_remote<W>, dim3(gp_), dim3(256), 0, stream_, g.keys, k_, g.gt, gr, queries.p,
                                    gp_cnt.p, adj_.p, nb_.p);
@@ -1590,18 +1583,18 @@ public:
             }
             if (sh_active_ && sh_world_ > 1) {
                 // the candidates that live on other ranks: staged compactly before `queries` goes (shard_cross_adjacency)
-                HIPCHK(fill2_async(ctl_.p + 13, 8, 0u, nullptr, 0, 0u, stream_));
-                hipLaunchKernelGGL(k_xq_total, dim3(gp_), dim3(256), 0, stream_, gp_roff.p, queries.p, gp_cnt.p, (unsigned int *)(ctl_.p + 13));
+                HIPCHK(fill2_async(ctl(&GraphWords::xq_count), ctl_span(&GraphWords::xq_count), 0u, nullptr, 0, 0u, stream_));
+                hipLaunchKernelGGL(k_xq_total, dim3(gp_), dim3(256), 0, stream_, gp_roff.p, queries.p, gp_cnt.p, (unsigned int *)ctl(&GraphWords::xq_count));
                 unsigned int n_x = 0;
-                if (int rc = read_ctl(n_x, 13, err)) return rc;
+                if (int rc = read_ctl(n_x, &GraphWords::xq_count, err)) return rc;
                 xq_n_ = n_x;
                 if (int rc = xq_dest_.alloc(n_x, err)) return rc;
                 if (int rc = xq_pay_.alloc((size_t)n_x * (W + 1), err)) return rc;
                 if (int rc = xq_meta_.alloc(n_x, err)) return rc;
                 if (n_x) {
-                    HIPCHK(fill2_async(ctl_.p + 13, 8, 0u, nullptr, 0, 0u, stream_));
+                    HIPCHK(fill2_async(ctl(&GraphWords::xq_count), ctl_span(&GraphWords::xq_count), 0u, nullptr, 0, 0u, stream_));
                     hipLaunchKernelGGL(k_xq_stage<W>, dim3(gp_), dim3(256), 0, stream_, g.keys, k_, gp_roff.p, queries.p, gp_cnt.p,
-                                       (unsigned int *)(ctl_.p + 13), n_x, xq_dest_.p, xq_pay_.p, xq_meta_.p);
+                                       (unsigned int *)ctl(&GraphWords::xq_count), n_x, xq_dest_.p, xq_pay_.p, xq_meta_.p);
                     HIPCHK(hipGetLastError());
                 }
             }
@@ -1610,7 +1603,7 @@ public:
             // collapse's: check_graph_flags(); the sharded assembly reads them here)
             graph_check_pending_ = true;
             if (sh_active_) {
-                HIPCHK(hipMemcpyAsync(mbox64() + MB_CTL, ctl_.p, 3 * 8, hipMemcpyDeviceToHost, stream_));
+                HIPCHK(fetch_ctl(mb_graph(), &GraphWords::spare0, &GraphWords::slots_used));
                 WAIT_STREAM();
                 if (int rc = check_graph_flags(err)) return rc;
             }
@@ -1621,35 +1614,35 @@ public:
         return 0;
     }
 
-    // mbox64()[MB_CTL ..] holds a fresh copy of ctl_[0..2]: the graph tables' overflow flags (build_graph)
+    // the mailbox's graph image holds a fresh copy of the graph tables' overflow flags (build_graph)
     int check_graph_flags(std::string &err) {
         if (!graph_check_pending_) return 0;
         graph_check_pending_ = false;
-        const unsigned long long *h = mbox64() + MB_CTL;
-        if ((uint32_t)h[1] == 2u) { err = "graph partition: a row lies outside its counting group's minimiser range"; return -6; }
-        if ((uint32_t)h[1] || h[2] > gt_slots_) { err = "graph table overflow"; return -6; }
+        const GraphWords &h = *mb_graph();
+        if ((uint32_t)h.table_flag == 2u) { err = "graph partition: a row lies outside its counting group's minimiser range"; return -6; }
+        if ((uint32_t)h.table_flag || h.slots_used > gt_slots_) { err = "graph table overflow"; return -6; }
         return 0;
     }
-    int read_ctl(unsigned int &v, int slot, std::string &err) {
+    int read_ctl(unsigned int &v, unsigned long long GraphWords::*m, std::string &err) {
         unsigned long long h = 0;
-        HIPCHK(hipMemcpyAsync(&h, ctl_.p + slot, 8, hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipMemcpyAsync(&h, ctl(m), ctl_span(m), hipMemcpyDeviceToHost, stream_));
         WAIT_STREAM();
         v = (unsigned int)h;
         return 0;
     }
 
-    // marked alive nodes -> removed list (count at ctl_[slot]) -> their edges cleared in the neighbours
-    int apply_marks(Graph<W> &g, DevBuf<uint8_t> &mark, DevBuf<uint32_t> &removed, int slot, std::string &err) {
+    // marked alive nodes -> removed list (count at the member `m`) -> their edges cleared in the neighbours
+    int apply_marks(Graph<W> &g, DevBuf<uint8_t> &mark, DevBuf<uint32_t> &removed, unsigned long long GraphWords::*m, std::string &err) {
         const uint32_t n = (uint32_t)n_solid_;
         hipLaunchKernelGGL(k_collect_marked, dim3(grid_for(n)), dim3(256), 0, stream_, n, mark.p, alive_.p,
-                           removed.p, (unsigned int *)(ctl_.p + slot));
+                           removed.p, (unsigned int *)ctl(m));
         hipLaunchKernelGGL(k_apply_removed<W>, dim3(1024), dim3(256), 0, stream_, g, removed.p,
-                           (const unsigned int *)(ctl_.p + slot));
+                           (const unsigned int *)ctl(m));
         HIPCHK(hipGetLastError());
         return 0;
     }
 
-    // SPEC S9.  The FIRST round is launched without waiting for its outcome: what it removed (ctl_[16], ctl_[17]) comes back
+    // SPEC S9.  The FIRST round is launched without waiting for its outcome: what it removed (r0_tips_removed, r0_bubbles_removed) comes back
     // with the first counters of the collapse, whose first two kernels return at once when the round did remove something
     // (rank_chains) — an error-free isolate, where the round finds nothing, pays no host round trip for the correction.
     // Further rounds (reads with errors) run from finish_correction(), one read-back per round as before.
@@ -1665,7 +1658,7 @@ public:
         if (!tips) HIPCHK(hipMemsetAsync(corr_.mark.p, 0, n, stream_));       // (with tips: k_tip_candidates clears it in the first round)
         if (tips) {
             // every candidate may turn out to be a tip: sized for all oriented nodes, so that no count has to
-            // come back to the host inside a round (the counters live in ctl_: 3 candidates, 4 tips, 5/6 removed)
+            // come back to the host inside a round (the counters live in ctl_: n_cand, n_tips, tips_removed / bubbles_removed)
             if (int rc = corr_.tip_head.alloc(2ull * n, err)) return rc;
             if (int rc = corr_.tiprec.alloc(2ull * n, err)) return rc;
             if (int rc = corr_.kill.alloc(2ull * n, err)) return rc;
@@ -1679,34 +1672,35 @@ public:
     }
     struct CorrScratch { DevBuf<uint32_t> cand, tip_head, removed; DevBuf<uint8_t> mark, kill; DevBuf<TipRec> tiprec;
                          void release() { cand.release(); tip_head.release(); removed.release(); mark.release(); kill.release(); tiprec.release(); } };
-    // one round of S9 on the stream; removal counts go to ctl_[16], ctl_[17] (round 0) or ctl_[5], ctl_[6]
+    // one round of S9 on the stream; removal counts go to r0_tips_removed, r0_bubbles_removed (round 0) or tips_removed, bubbles_removed
     int correction_round(int round, std::string &err) {
         const uint32_t n = (uint32_t)n_solid_;
         Graph<W> g = graph_view();
         const dim3 G(1024), B(256);
         const bool tips = corr_tips_, bubbles = corr_bubbles_;
-        const int s_tip = round == 0 ? 16 : 5, s_bub = round == 0 ? 17 : 6;
-        HIPCHK(fill2_async(ctl_.p + 3, 4 * 8, 0u, nullptr, 0, 0u, stream_));      // (one launch: a small hipMemsetAsync at an odd offset came out as three fill kernels)
+        const auto s_tip = round == 0 ? &GraphWords::r0_tips_removed : &GraphWords::tips_removed, s_bub = round == 0 ? &GraphWords::r0_bubbles_removed : &GraphWords::bubbles_removed;
+        HIPCHK(fill2_async(ctl(&GraphWords::n_cand), ctl_span(&GraphWords::n_cand, &GraphWords::bubbles_removed), 0u, nullptr, 0, 0u, stream_));      // (one launch: a small hipMemsetAsync at an odd offset came out as three fill kernels)
+        unsigned int *const d_ncand = (unsigned int *)ctl(&GraphWords::n_cand), *const d_ntips = (unsigned int *)ctl(&GraphWords::n_tips);
         if (tips) {
             hipLaunchKernelGGL(k_tip_candidates<W>, dim3(grid_for(n)), B, 0, stream_, g, alive_.p,
-                               corr_.cand.p, (unsigned int *)(ctl_.p + 3), round == 0 ? (uint2 *)corr_.tip_head.p : (uint2 *)nullptr,
+                               corr_.cand.p, d_ncand, round == 0 ? (uint2 *)corr_.tip_head.p : (uint2 *)nullptr,
                                round == 0 ? corr_.mark.p : (uint8_t *)nullptr);
-            hipLaunchKernelGGL(k_tip_walk<W>, G, B, 0, stream_, g, corr_.cand.p, (const unsigned int *)(ctl_.p + 3),
-                               corr_.tiprec.p, (unsigned int *)(ctl_.p + 4), corr_.tip_head.p);
-            hipLaunchKernelGGL(k_tip_decide<W>, G, B, 0, stream_, g, corr_.tiprec.p, (const unsigned int *)(ctl_.p + 4),
+            hipLaunchKernelGGL(k_tip_walk<W>, G, B, 0, stream_, g, corr_.cand.p, (const unsigned int *)d_ncand,
+                               corr_.tiprec.p, d_ntips, corr_.tip_head.p);
+            hipLaunchKernelGGL(k_tip_decide<W>, G, B, 0, stream_, g, corr_.tiprec.p, (const unsigned int *)d_ntips,
                                corr_.tip_head.p, corr_.kill.p);
-            hipLaunchKernelGGL(k_tip_remove<W>, G, B, 0, stream_, g, corr_.tiprec.p, (const unsigned int *)(ctl_.p + 4),
+            hipLaunchKernelGGL(k_tip_remove<W>, G, B, 0, stream_, g, corr_.tiprec.p, (const unsigned int *)d_ntips,
                                corr_.kill.p, corr_.tip_head.p, corr_.mark.p);
-            hipLaunchKernelGGL(k_tip_reset_heads, G, B, 0, stream_, corr_.tiprec.p, (const unsigned int *)(ctl_.p + 4),
+            hipLaunchKernelGGL(k_tip_reset_heads, G, B, 0, stream_, corr_.tiprec.p, (const unsigned int *)d_ntips,
                                corr_.tip_head.p);
             HIPCHK(hipGetLastError());
             if (int rc = apply_marks(g, corr_.mark, corr_.removed, s_tip, err)) return rc;
         }
         if (bubbles) {
-            HIPCHK(fill2_async(ctl_.p + 3, 8, 0u, nullptr, 0, 0u, stream_));
+            HIPCHK(fill2_async(ctl(&GraphWords::n_cand), ctl_span(&GraphWords::n_cand), 0u, nullptr, 0, 0u, stream_));
             hipLaunchKernelGGL(k_fork_candidates<W>, dim3(grid_for(n)), B, 0, stream_, g, alive_.p,
-                               corr_.cand.p, (unsigned int *)(ctl_.p + 3));
-            hipLaunchKernelGGL(k_bubble<W>, G, B, 0, stream_, g, corr_.cand.p, (const unsigned int *)(ctl_.p + 3), corr_.mark.p);
+                               corr_.cand.p, d_ncand);
+            hipLaunchKernelGGL(k_bubble<W>, G, B, 0, stream_, g, corr_.cand.p, (const unsigned int *)d_ncand, corr_.mark.p);
             HIPCHK(hipGetLastError());
             if (int rc = apply_marks(g, corr_.mark, corr_.removed, s_bub, err)) return rc;
         }
@@ -1719,9 +1713,10 @@ public:
         EvTimer t(stream_, stage_timers_);
         for (int round = 1; round < 32 && n1 + n2 != 0; round++) {
             if (int rc = correction_round(round, err)) return rc;
-            HIPCHK(hipMemcpyAsync(mbox64() + MB_MISC, ctl_.p + 5, 16, hipMemcpyDeviceToHost, stream_));
+            GraphWords *const h = (GraphWords *)(mbox64() + MB_MISC);
+            HIPCHK(fetch_ctl(h, &GraphWords::tips_removed, &GraphWords::bubbles_removed));
             WAIT_STREAM();
-            n1 = (unsigned int)mbox64()[MB_MISC]; n2 = (unsigned int)mbox64()[MB_MISC + 1];
+            n1 = (unsigned int)h->tips_removed; n2 = (unsigned int)h->bubbles_removed;
             tips_removed_ += n1; bubbles_removed_ += n2; rounds_++;
         }
         if (rounds_ > 1) if (t.on()) times_.add("correct_total", t.stop());
@@ -1742,8 +1737,6 @@ public:
     }
 
     // ---- collapse ----------------------------------------------------------------------------
-    // Counters in ctl_: 5 = splitters (k_succ_split, then appended to by k_orphan_cycles), 6 = chains reported
-    // (k_rank_tails), 7 = splitters that sit on a circular unitig (statistic), 8 = flags of k_orphan_cycles.
     struct ChainState {                // the ranking of the chains of simple links: per node (chain record, position), per chain a HeadRec
         DevBuf<uint32_t> spl, slot_of;
         DevBuf<uint2> winfo, ol;
@@ -1793,7 +1786,7 @@ public:
         constexpr unsigned int HEADS_SPEC = 512;                           // (40 bytes each, into the pinned mailbox)
         static_assert(MB_MISC * 8 + HEADS_SPEC * sizeof(HeadRec) <= MBOX_BYTES, "mailbox");
         std::vector<HeadRec> &heads = cs.heads;
-        unsigned long long hc[4] = {0, 0, 0, 0};
+        GraphWords hc{};
         uint32_t seg_cap = 0;
         EvTimer tr(stream_, stage_timers_);
         for (int attempt = 0;; attempt++) {
@@ -1807,23 +1800,23 @@ public:
             if (int rc = cs.fin.alloc(seg_cap, err)) return rc;
             if (int rc = cs.d_heads.alloc(seg_cap, err)) return rc;
             if (int rc = cs.ringmin.alloc(seg_cap, err)) return rc;
-            const unsigned long long *skip = corr_pending_ ? ctl_.p + 16 : (const unsigned long long *)nullptr;
-            // 5 splitters, 6 chains, 7 ring splitters, 8 flags, 9 alive oriented nodes, 10 nodes walked
-            HIPCHK(fill2_async(ctl_.p + 5, 6 * 8, 0u, cs.slot_of.p, (size_t)seg_cap * 4, 0xFFFFFFFFu, stream_));
-            unsigned int *d_nspl = (unsigned int *)(ctl_.p + 5);
-            uint32_t *d_flags = (uint32_t *)(ctl_.p + 8);
+            const unsigned long long *skip = corr_pending_ ? ctl(&GraphWords::r0_tips_removed) : (const unsigned long long *)nullptr;   // (and r0_bubbles_removed behind it)
+            HIPCHK(fill2_async(ctl(&GraphWords::n_splitters), ctl_span(&GraphWords::n_splitters, &GraphWords::n_walked), 0u, cs.slot_of.p, (size_t)seg_cap * 4, 0xFFFFFFFFu, stream_));
+            unsigned int *d_nspl = (unsigned int *)ctl(&GraphWords::n_splitters), *d_nheads = (unsigned int *)ctl(&GraphWords::n_chains);
+            uint32_t *d_flags = ctl(&GraphWords::collapse_flag);
+            unsigned long long *d_plan = ctl(&GraphWords::plan_state);                 // (plan_bytes and plan_emitted behind it)
             hipLaunchKernelGGL(k_succ_split<W>, dim3((total + 256 * SS_ITEMS - 1) / (256 * SS_ITEMS)), dim3(256), 0, stream_, g,
-                               alive_.p, cs.winfo.p, cs.spl.p, cs.ol.p, d_nspl, split_mask, ctl_.p + 9, skip);
+                               alive_.p, cs.winfo.p, cs.spl.p, cs.ol.p, d_nspl, split_mask, ctl(&GraphWords::n_alive), skip);
             stage("k_succ_split");
             hipLaunchKernelGGL(k_local_frag<W>, dim3(lf_grid), dim3(LF_THREADS), 0, stream_, n, row_starts_.p, tile_rows, alive_.p, cs.winfo.p, cs.ol.p, cs.frag.p, split_mask, skip,
                                d_nspl, seg_cap, d_flags);
             stage("k_local_frag");
             // (grids: the expected 1/64 sample plus a margin; the kernels loop to the device-side count)
             hipLaunchKernelGGL(k_walk_frags<W>, dim3(grid_for((uint64_t)total / 64u + 16384u, 256, 1 << 20)), dim3(256), 0, stream_,
-                               cs.spl.p, (const unsigned int *)d_nspl, cs.frag.p, cs.segs.p, split_mask, ctl_.p + 10, total, d_flags);
+                               cs.spl.p, (const unsigned int *)d_nspl, cs.frag.p, cs.segs.p, split_mask, ctl(&GraphWords::n_walked), total, d_flags);
             stage("k_walk_frags");
             hipLaunchKernelGGL(k_orphan_cycles<W>, dim3(grid_for(total)), dim3(256), 0, stream_, g, alive_.p, cs.winfo.p, cs.ol.p,
-                               cs.frag.p, cs.spl.p, cs.segs.p, d_nspl, seg_cap, d_flags, ctl_.p + 9, ctl_.p + 10);
+                               cs.frag.p, cs.spl.p, cs.segs.p, d_nspl, seg_cap, d_flags, ctl(&GraphWords::n_alive), ctl(&GraphWords::n_walked));
             HIPCHK(hipGetLastError());
             stage("k_orphan_cycles");
             // ---- rank the splitter list on the device: prefix sums by pointer jumping, rings in the same pass (collapse.h)
@@ -1837,9 +1830,9 @@ public:
                 std::swap(Ri, Ro);
             }
             stage("k_rank_jump");
-            const unsigned int *d_ncyc = (const unsigned int *)(ctl_.p + 7);
+            unsigned int *d_ncyc = (unsigned int *)ctl(&GraphWords::n_ring_splitters);
             hipLaunchKernelGGL(k_rank_tails<W>, dim3(gr), dim3(256), 0, stream_, g, cs.segs.p, (const unsigned int *)d_nspl, Ri, cs.d_heads.p, cs.slot_of.p, cs.ringmin.p,
-                               (unsigned int *)(ctl_.p + 6), (unsigned int *)(ctl_.p + 7));
+                               d_nheads, d_ncyc);
             hipLaunchKernelGGL(k_rank_fin, dim3(gr), dim3(256), 0, stream_, cs.segs.p, (const unsigned int *)d_nspl, Ri, cs.slot_of.p, cs.fin.p);
             stage("k_rank_tails + k_rank_fin");
             hipLaunchKernelGGL(k_tile_final, dim3(lf_grid), dim3(LF_THREADS), 0, stream_, n, row_starts_.p, tile_rows, cs.ol.p, cs.frag.p, cs.fin.p, skip, (const uint32_t *)d_flags);
@@ -1848,47 +1841,47 @@ public:
                 // rings: their smallest k-mer (these three return at once when there is none)
                 hipLaunchKernelGGL(k_ring_min1<W>, dim3(1024), dim3(256), 0, stream_, g, alive_.p, cs.ol.p, cs.ringmin.p, d_ncyc);
                 hipLaunchKernelGGL(k_ring_min2<W>, dim3(1024), dim3(256), 0, stream_, g, alive_.p, cs.ol.p, cs.ringmin.p, d_ncyc);
-                hipLaunchKernelGGL(k_ring_rot<W>, dim3(gr), dim3(256), 0, stream_, g, cs.d_heads.p, (const unsigned int *)(ctl_.p + 6), cs.ringmin.p,
+                hipLaunchKernelGGL(k_ring_rot<W>, dim3(gr), dim3(256), 0, stream_, g, cs.d_heads.p, (const unsigned int *)d_nheads, cs.ringmin.p,
                                    cs.winfo.p, cs.ol.p, d_ncyc, d_flags);
             }
             if (plan) {
-                HIPCHK(fill2_async(ctl_.p + 18, 3 * 8, 0u, nullptr, 0, 0u, stream_));
-                hipLaunchKernelGGL(k_plan_emit, dim3(1), dim3(1024), 0, stream_, cs.d_heads.p, (const unsigned int *)(ctl_.p + 6), (uint32_t)k_, plan->max_heads,
-                                   plan->out_cap, (const uint32_t *)d_flags, plan->d_off, ctl_.p + 18);
-                hipLaunchKernelGGL(k_emit<W>, dim3(grid_for(n)), dim3(256), 0, stream_, g, alive_.p, cs.ol.p, plan->d_off, plan->d_out, (const unsigned long long *)(ctl_.p + 18));
-                hipLaunchKernelGGL(k_text_to_host_planned, dim3(64), dim3(256), 0, stream_, plan->d_out, plan->h_out, (const unsigned long long *)(ctl_.p + 18));
+                HIPCHK(fill2_async(d_plan, ctl_span(&GraphWords::plan_state, &GraphWords::plan_emitted), 0u, nullptr, 0, 0u, stream_));
+                hipLaunchKernelGGL(k_plan_emit, dim3(1), dim3(1024), 0, stream_, cs.d_heads.p, (const unsigned int *)d_nheads, (uint32_t)k_, plan->max_heads,
+                                   plan->out_cap, (const uint32_t *)d_flags, plan->d_off, d_plan);
+                hipLaunchKernelGGL(k_emit<W>, dim3(grid_for(n)), dim3(256), 0, stream_, g, alive_.p, cs.ol.p, plan->d_off, plan->d_out, (const unsigned long long *)d_plan);
+                hipLaunchKernelGGL(k_text_to_host_planned, dim3(64), dim3(256), 0, stream_, plan->d_out, plan->h_out, (const unsigned long long *)d_plan);
             }
             HIPCHK(hipGetLastError());
             // (the first chain records travel with the counters: an isolate has a handful of chains, and a second
             // round trip just for them is 30-40 us of idle GPU)
             heads.assign(HEADS_SPEC, HeadRec());
-            HIPCHK(hipMemcpyAsync(mbox64() + MB_CTL, ctl_.p, CTL_WORDS * 8, hipMemcpyDeviceToHost, stream_));
+            HIPCHK(hipMemcpyAsync(mb_graph(), ctl_.p, sizeof(GraphWords), hipMemcpyDeviceToHost, stream_));
             HIPCHK(hipMemcpyAsync(mbox64() + MB_MISC, cs.d_heads.p, (size_t)std::min<uint32_t>(HEADS_SPEC, seg_cap) * sizeof(HeadRec), hipMemcpyDeviceToHost, stream_));
             WAIT_STREAM();
-            const unsigned long long *hc0 = mbox64() + MB_CTL;
+            const GraphWords &hc0 = *mb_graph();
             if (int rc = check_graph_flags(err)) return rc;
             if (corr_pending_) {
                 // the first correction round's outcome: if it removed nodes the kernels above returned at once (or did nothing:
                 // no splitters) — the remaining rounds run now, then the pass is repeated on the final graph
-                const unsigned int r1 = (unsigned int)hc0[16], r2 = (unsigned int)hc0[17];
+                const unsigned int r1 = (unsigned int)hc0.r0_tips_removed, r2 = (unsigned int)hc0.r0_bubbles_removed;
                 if (int rc = finish_correction(r1, r2, err)) return rc;
                 if (r1 + r2 != 0) continue;
             }
-            memcpy(hc, hc0 + 5, sizeof hc);
-            const uint32_t flag = (uint32_t)hc[3];
+            hc = hc0;
+            const uint32_t flag = hc.collapse_flag;
             if ((flag == 4 || flag == 2) && seg_cap64 < cap_all) {        // more splitters (4) or orphan rings (2) than the room: once more with room for all
                 times_.add("collapse_seg_cap_retry_x1", 1.0);
                 seg_cap64 = cap_all;
                 continue;
             }
             memcpy(heads.data(), mbox64() + MB_MISC, (size_t)std::min<uint32_t>(HEADS_SPEC, seg_cap) * sizeof(HeadRec));
-            if (plan && hc0[18] == 1ull) { plan->planned = true; plan->out_bytes = hc0[19]; plan->n_emit = (uint32_t)hc0[20]; }
+            if (plan && hc.plan_state == 1ull) { plan->planned = true; plan->out_bytes = hc.plan_bytes; plan->n_emit = (uint32_t)hc.plan_emitted; }
             break;
         }
-        if ((uint32_t)hc[3]) { err = (uint32_t)hc[3] == 2 ? "collapse: too many short circular unitigs" : ((uint32_t)hc[3] == 3 ? "collapse: ring without a smallest k-mer" : "collapse: broken cycle"); return -6; }
-        times_.add("collapse_n_splitters_x1e-3", (double)(unsigned int)hc[0] * 1e-3);
-        times_.add("collapse_cycle_splitters_x1e-3", (double)(unsigned int)hc[2] * 1e-3);
-        const unsigned int n_heads = (unsigned int)hc[1];
+        if (hc.collapse_flag) { err = hc.collapse_flag == 2 ? "collapse: too many short circular unitigs" : (hc.collapse_flag == 3 ? "collapse: ring without a smallest k-mer" : "collapse: broken cycle"); return -6; }
+        times_.add("collapse_n_splitters_x1e-3", (double)(unsigned int)hc.n_splitters * 1e-3);
+        times_.add("collapse_cycle_splitters_x1e-3", (double)(unsigned int)hc.n_ring_splitters * 1e-3);
+        const unsigned int n_heads = (unsigned int)hc.n_chains;
         if (tr.on()) times_.add("collapse_rank_device", tr.stop());
         cs.n_heads = n_heads;
         // (sharded assembly, and fragmented assemblies headed for the device writer: the chain records stay on the device —
@@ -1966,13 +1959,13 @@ public:
             if (int rc = d_off2.alloc(nh, err)) return rc;
             if (int rc = d_c.alloc(n_emit + 1, err)) return rc;
             if (int rc = d_out2.alloc(out_bytes2 + 16, err)) return rc;
-            HIPCHK(fill2_async(ctl_.p + 14, 8, 0u, nullptr, 0, 0u, stream_));
-            hipLaunchKernelGGL(k_w_plan_fill, dim3(grid_for(nh)), dim3(256), 0, stream_, cs.d_heads.p, nh, (uint32_t)k_, off.p, idx.p, d_off2.p, d_c.p, (uint32_t *)(ctl_.p + 14));
+            HIPCHK(fill2_async(ctl(&GraphWords::writer_flag), ctl_span(&GraphWords::writer_flag), 0u, nullptr, 0, 0u, stream_));
+            hipLaunchKernelGGL(k_w_plan_fill, dim3(grid_for(nh)), dim3(256), 0, stream_, cs.d_heads.p, nh, (uint32_t)k_, off.p, idx.p, d_off2.p, d_c.p, (uint32_t *)ctl(&GraphWords::writer_flag));
             EvTimer t3(stream_, stage_timers_);
             hipLaunchKernelGGL(k_emit<W>, dim3(grid_for(n)), dim3(256), 0, stream_, g, alive_.p, cs.ol.p, d_off2.p, d_out2.p);
             HIPCHK(hipGetLastError());
             unsigned int fl9 = 0;
-            if (int rc = read_ctl(fl9, 14, err)) return rc;
+            if (int rc = read_ctl(fl9, &GraphWords::writer_flag, err)) return rc;
             if (t3.on()) times_.add("collapse_emit", t3.stop());
             if (fl9) { err = "device writer: a contig beyond 2^32 bases"; return -1; }
             if (n_emit == 0) { if (json) *json = nullptr; return 0; }
@@ -2346,7 +2339,7 @@ public:
         DevBuf<uint32_t> xpred;                          // per local oriented node: record of hl.recv that names its simple predecessor on another rank
         if (int rc = xpred.alloc(2ull * n + 2, err)) return rc;
         HIPCHK(hipMemsetAsync(xpred.p, 0xFF, (2ull * n + 2) * 4, stream_));
-        HIPCHK(fill2_async(ctl_.p + 13, 8, 0u, nullptr, 0, 0u, stream_));
+        HIPCHK(fill2_async(ctl(&GraphWords::halflink_flags), ctl_span(&GraphWords::halflink_flags), 0u, nullptr, 0, 0u, stream_));
         if (world > 1) {
             if (int rc = hdest.alloc(2ull * n + 1, err)) return rc;
             if (int rc = hpay.alloc(4ull * n + 2, err)) return rc;
@@ -2356,7 +2349,7 @@ public:
             }
             if (int rc = route_exchange<2>(c, hdest.p, hpay.p, 2u * n, hl, err)) return rc;
             if (hl.n_recv) {
-                hipLaunchKernelGGL(k_hl_apply, dim3(grid_for(hl.n_recv)), dim3(256), 0, stream_, hl.recv.p, hl.n_recv, gbase, n, adj_.p, xpred.p, (uint32_t *)(ctl_.p + 13));
+                hipLaunchKernelGGL(k_hl_apply, dim3(grid_for(hl.n_recv)), dim3(256), 0, stream_, hl.recv.p, hl.n_recv, gbase, n, adj_.p, xpred.p, (uint32_t *)ctl(&GraphWords::halflink_flags));
                 HIPCHK(hipGetLastError());
             }
         } else if (int rc = hl.recv.alloc(2, err)) return rc;
@@ -2402,7 +2395,7 @@ public:
                 if (int rc = lans.alloc(ls.n_recv + 1, err)) return rc;
                 if (ls.n_recv) {
                     hipLaunchKernelGGL(k_ls_answer, dim3(grid_for(ls.n_recv)), dim3(256), 0, stream_, ls.recv.p, ls.n_recv, gbase, n, cs.ol.p,
-                                       (uint32_t)lbase[rank], lans.p, (uint32_t *)(ctl_.p + 13));
+                                       (uint32_t)lbase[rank], lans.p, (uint32_t *)ctl(&GraphWords::halflink_flags));
                     HIPCHK(hipGetLastError());
                 }
                 if (int rc = reply_exchange(c, ls, lans.p, lback, err)) return rc;
@@ -2442,7 +2435,7 @@ public:
             unsigned int hM2[2] = {0, 0};
             unsigned long long h_fl = 0;
             HIPCHK(hipMemcpyAsync(hM2, d_M.p, 8, hipMemcpyDeviceToHost, stream_));
-            HIPCHK(hipMemcpyAsync(&h_fl, ctl_.p + 13, 8, hipMemcpyDeviceToHost, stream_));      // (flags of k_hl_apply / k_ls_answer, read with the counts)
+            HIPCHK(hipMemcpyAsync(&h_fl, ctl(&GraphWords::halflink_flags), ctl_span(&GraphWords::halflink_flags), hipMemcpyDeviceToHost, stream_));      // (flags of k_hl_apply / k_ls_answer, read with the counts)
             WAIT_STREAM();
             // (these flags are LOCAL: the verdict must be every rank's — a rank that left alone would leave the others in the
             // next collective and itself one collective ahead for the rest of the process)
@@ -2679,11 +2672,18 @@ private:
     StageTimes times_;
     std::vector<EvTimer::Pending> pending_timers_;
     int n_cus_ = 256;
-    DevBuf<unsigned long long> ctl_;
+    DevBuf<unsigned long long> ctl_;                 // the device control words: a CountWords or a GraphWords, by era (ctl_words.h)
+    template <class S, class T> T *ctl(T S::*m) { return &(reinterpret_cast<S *>(ctl_.p)->*m); }
+    // bytes from member `a` through member `b`: what a partial fill or read-back covers
+    template <class S, class A, class B> static size_t ctl_span(A S::*a, B S::*b) { static const S z{}; return (size_t)((const char *)&(z.*b) - (const char *)&(z.*a)) + sizeof(B); }
+    template <class S, class A> static size_t ctl_span(A S::*a) { return sizeof(A); }
+    // the members `a` through `b` of the host image `img` := the device's (one asynchronous copy)
+    template <class S, class A, class B> hipError_t fetch_ctl(S *img, A S::*a, B S::*b) { return hipMemcpyAsync(&(img->*a), ctl(a), ctl_span(a, b), hipMemcpyDeviceToHost, stream_); }
     PinnedBuf mbox_;                                 // pinned host words the small device-to-host copies land in (truly asynchronous)
     unsigned long long *mbox64() { return (unsigned long long *)mbox_.p; }
     static constexpr size_t MBOX_BYTES = 32768;
-    static constexpr int MB_P1 = 0 /* 2 words: pass 1's flags */, MB_CTL = 8 /* CTL_WORDS words: a copy of ctl_ */, MB_MISC = 64;
+    static constexpr int MB_P1 = 0 /* a CountWords image: pass 1's flags */, MB_CTL = CTL_WORDS /* a GraphWords image */, MB_MISC = 2 * CTL_WORDS;
+    CountWords *mb_p1() { return (CountWords *)(mbox64() + MB_P1); }  GraphWords *mb_graph() { return (GraphWords *)(mbox64() + MB_CTL); }
     struct P1Pending { bool on; const uint32_t *d_bases, *d_seg_off; uint64_t n_seg, n_bases, cap; };
     P1Pending p1_{false, nullptr, nullptr, 0, 0, 0};
     uint64_t n_host_waits_ = 0;                      // host waits on the stream so far (WAIT_STREAM, host-side collectives)

@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void k_hl_stage(const uint8_t *__restrict__ ad
 }
 // w's owner: the link v -> w is simple iff w has this one in-edge; then xpred[w] = index of the record (it holds v)
 __global__ __launch_bounds__(256) void k_hl_apply(const uint64_t *__restrict__ recv, uint64_t n_recv, unsigned long long gbase, uint32_t n_nodes,
-                                                  const uint8_t *__restrict__ adj, uint32_t *__restrict__ xpred, uint32_t *__restrict__ flags) {
+                                                  const uint8_t *__restrict__ adj, uint32_t *__restrict__ xpred, uint32_t *__restrict__ flags /* GraphWords::halflink_flags */) {
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_recv; t += (uint64_t)gridDim.x * blockDim.x) {
         const unsigned long long w = recv[2 * t];
         if (w < 2ull * gbase || w - 2ull * gbase >= 2ull * n_nodes) { flags[0] = 1; continue; }     // misrouted: the ownership rules disagree

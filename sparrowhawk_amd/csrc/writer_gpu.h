@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void k_w_plan_sizes(const HeadRec *__restrict_
 }
 __global__ __launch_bounds__(256) void k_w_plan_fill(const HeadRec *__restrict__ heads, uint32_t n_heads, uint32_t k,
                                                      const unsigned long long *__restrict__ off, const unsigned long long *__restrict__ idx,
-                                                     EmitRec *__restrict__ head_off, WContig *__restrict__ c, uint32_t *__restrict__ flags) {
+                                                     EmitRec *__restrict__ head_off, WContig *__restrict__ c, uint32_t *__restrict__ flags /* GraphWords::writer_flag */) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_heads; i += gridDim.x * blockDim.x) {
         const HeadRec h = heads[i];
         EmitRec e; e.off = ~0ull; e.rot = h.rot; e.len = (uint32_t)h.len;
