@@ -12,6 +12,7 @@ os.environ.setdefault("SHK_KEEP_STAGES", "1")               # quiet handles keep
 import numpy as np
 import torch  # noqa: F401
 from sparrowhawk_amd import AssemblyHelper, synth
+from lowcomplexity import low_complexity_genome
 from util import compare_all, run_oracle
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
@@ -22,6 +23,9 @@ for case in range(n_cases):
     k = int(rng.choice([15, 21, 27, 31, 33, 41, 51, 63, 65, 77, 89, 95, 101, 127, 129, 161, 191, 193, 225, 255]))   # one- to eight-word keys
     glen = int(rng.integers(GLEN_LO, GLEN_HI))
     g = synth.random_genome(glen, int(rng.integers(1 << 30)))
+    lowc = bool(rng.random() < 0.25)                         # the low-complexity family (tests/lowcomplexity.py): skewed composition, homopolymers, microsatellites
+    if lowc:
+        g = low_complexity_genome(rng, glen, k); glen = len(g)
     if rng.random() < 0.4:                                   # planted repeats -> branching graph
         L = min(int(rng.integers(k + 5, 4 * k)), glen - 1)           # (a genome shorter than the repeat: the repeat shrinks)
         src = int(rng.integers(0, glen - L)); dst = int(rng.integers(0, glen - L))
@@ -90,7 +94,7 @@ for case in range(n_cases):
     if rng.random() < 0.2: env["SHK_GUNZIP_DEVICE_WINDOW"] = str(int(rng.choice([65536, 100000, 1 << 20])))   # BGZF input beyond it is inflated, parsed and counted window by window
     old = {e: os.environ.get(e) for e in env}
     os.environ.update(env)
-    desc = dict(case=case, k=k, glen=glen, rl=rl, cov=cov, err=err, circ=circular, mc=min_count, mq=min_qual, fit=do_fit,
+    desc = dict(case=case, k=k, lowc=lowc, glen=glen, rl=rl, cov=cov, err=err, circ=circular, mc=min_count, mq=min_qual, fit=do_fit,
                 bloom=do_bloom, csize=csize, nb=nb, nd=nd, nfiles=len(files), env=env)
     sharded_case = False
     try:
