@@ -157,6 +157,7 @@ int shk_shard_set_solid(shk_handle *h, const void *const *d_keys /* [W] */, cons
  * whole graph, on every rank.  A Rust host binds these five functions and never writes a collective itself. */
 #define SHK_UNIQUE_ID_BYTES 128
 typedef struct shk_comm shk_comm;
+struct shk_packed;                       /* below: the host-side packer */
 int shk_comm_unique_id(uint8_t id[SHK_UNIQUE_ID_BYTES]);
 shk_comm *shk_comm_init(const uint8_t id[SHK_UNIQUE_ID_BYTES], int rank, int world);   /* NULL on failure */
 const char *shk_comm_error(void);        /* message of the last failed shk_comm_* call on this thread */
@@ -165,6 +166,47 @@ int shk_comm_world(const shk_comm *c);
 void shk_comm_free(shk_comm *c);
 int shk_shard_preprocess(shk_handle *h, shk_comm *c, const void *d_bases, const void *d_seg_off, uint64_t n_seg,
                          uint64_t n_bases, uint64_t n_reads, uint32_t n_partitions);
+/* The same call from FASTQ FILES: every rank reads its share into ONE packed batch in HBM — inflated (csrc/inflate_gpu.hip)
+ * and parsed (csrc/fastq_gpu.hip) on the device, so the compressed bytes are what crosses PCIe — and the batch goes through
+ * shk_shard_preprocess as it is: the same progress strings, the same SHK_E_STATE rules, the handle ends "preprocessed", the
+ * graph stays sharded by default and shk_assemble is collective as above.  Collective over c.
+ *   split = 0: the buffers are this rank's OWN reads — plain text, a gzip member, BGZF, or a pair; fq1 == NULL && n1 == 0: this
+ *              rank has none.
+ *   split = 1: every rank passes the SAME file(s) and rank r takes slice r of `world` of each; the two files of a pair are
+ *              sliced independently and pooled (SPEC S1).
+ * The slice rule: with c_r the nominal cut — floor(r * n / world) in plain text and in the text of a plain gzip member, the
+ * text offset at which a block begins in a BGZF chain (shk_plan_fastq_slices) — slice r is [s_r, s_(r+1)), s_0 = 0, s_world =
+ * the end of the text without its trailing blank lines, and otherwise s_r = the first record start at or after c_r
+ * (shk_host_first_record_start; the end where there is none).  Slices may be empty.
+ * What crosses PCIe: of a BGZF file, the blocks of the rank's run, the one in front and a few behind (1 / world of the file:
+ * the route that scales); of plain text, the slice.  A plain gzip member is inflated WHOLE by every rank, which then keeps its
+ * slice: redundant work by construction — a deflate stream cannot be entered in the middle; compress with bgzip where the
+ * ranks are many.  What the device declines (several members, a damaged block, text that is not regular 4-line FASTQ) is
+ * read on the host, whole, and cut by the same rule; the host reader and the host parser own those messages, and the RECORD
+ * NUMBERS in them count from the start of the rank's SLICE, not of the file.
+ * A share of more than one batch (SHK_BATCH_BASES, default 2^31 packed bases) is SHK_E_PARAM: several batches per rank are
+ * not supported.  A rank whose reading fails (a parse error, a damaged stream, memory, an oversized share) still enters the
+ * first collective: it returns its own code and message, every other rank SHK_E_DEVICE "another rank failed during
+ * reading", and nobody hangs.  The environment switches that choose a route (SHK_GUNZIP_DEVICE_MIN, ...) must be the same on
+ * every rank.  The buffers are not retained. */
+int shk_shard_preprocess_fastq(shk_handle *h, shk_comm *c, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2,
+                               uint32_t n_partitions, int split);
+/* The routes of split = 1 without a communicator (tests, staging; needs a GPU): slice `rank` of `world` of the file(s) as one
+ * packed batch, copied back to the host (shk_packed_free).  *uploaded_bytes (optional): the compressed or text bytes that
+ * crossed PCIe; *route (optional): "bgzf_slice", "member_whole", "text_slice" or "host" ('+' between two files that went
+ * different ways) — on failure, the message. */
+int shk_device_pack_fastq_slice(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual,
+                                uint32_t rank, uint32_t world, struct shk_packed *out, uint64_t *uploaded_bytes, const char **route);
+/* host-only: where those slices are cut — the smallest p >= from that begins a line, holds '@', and whose line after next
+ * begins with '+' (the rule of shk_host_last_record_start, read forwards).  A line whose line after next has not begun inside
+ * the text is undecided: the search stops there and never passes it over.  UINT64_MAX: none / undecided.
+ * shk_device_first_record_start (needs a GPU): the device kernel that finds the same. */
+uint64_t shk_host_first_record_start(const uint8_t *text, size_t n, uint64_t from);
+int shk_device_first_record_start(const uint8_t *text, size_t n, uint64_t from, uint64_t *at);
+/* host-only: the runs of blocks the ranks take of a BGZF chain.  isize[n_blocks] as for shk_plan_bgzf_windows; run r is the
+ * blocks first_block[r] ... first_block[r + 1] - 1 and starts at the first block whose text offset is >= r * text / world;
+ * first_block[0] = 0, first_block[world] = n_blocks; more ranks than blocks gives empty runs.  Returns world, or SHK_E_PARAM. */
+int64_t shk_plan_fastq_slices(const uint32_t *isize, uint64_t n_blocks, uint32_t world, uint64_t *first_block /* [world + 1] */);
 /* host-only: the exchange plan shk_shard_preprocess derives from the gathered record counts (exposed for the
  * CPU tests).  part_records_all: [world][n_partitions].  Outputs (caller-allocated): base [n_partitions],
  * send_counts / recv_counts [world], run_off / run_cnt [n_owned][world], n_owned = partitions p with

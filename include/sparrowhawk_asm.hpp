@@ -32,6 +32,14 @@ public:
         check(shk_preprocess(h_, file1.data(), file1.size(), file2 ? file2->data() : nullptr,
                              file2 ? file2->size() : 0));
     }
+    // preprocess(file1, file2 | null) across the ranks of a communicator (shk.h: shk_shard_preprocess_fastq; collective, and
+    // so is assemble() after it).  split: every rank passes the same file(s) and takes its slice; otherwise the files are
+    // this rank's own reads (file1 == nullptr: it has none).
+    void sharded_preprocess_fastq(shk_comm *comm, const std::vector<uint8_t> *file1, const std::vector<uint8_t> *file2 = nullptr,
+                                  bool split = true, uint32_t n_partitions = 0) {
+        check(shk_shard_preprocess_fastq(h_, comm, file1 ? file1->data() : nullptr, file1 ? file1->size() : 0,
+                                         file2 ? file2->data() : nullptr, file2 ? file2->size() : 0, n_partitions, split ? 1 : 0));
+    }
     std::string get_preprocessing_info() {
         const char *s = shk_get_preprocessing_info(h_);
         if (!s) throw std::runtime_error(shk_last_error(h_));

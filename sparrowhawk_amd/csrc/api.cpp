@@ -360,7 +360,7 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
     auto peer_failed = [&](const char *stage) {
         return fail(h, SHK_E_DEVICE, std::string("shard_preprocess: another rank failed during ") + stage + " (this rank's state is intact up to there; free the handle)");
     };
-    // SHK_FAULT_INJECT=<step> (pass1 | pack | count | rows | keep | alloc) makes that local step of THIS process fail: the tests
+    // SHK_FAULT_INJECT=<step> (read — shk_shard_preprocess_fastq alone — | pass1 | pack | count | rows | keep | alloc) makes that local step of THIS process fail: the tests
     // set it on one rank to see every rank leave with an error instead of hanging.  It never changes a result.
     const char *inject = getenv("SHK_FAULT_INJECT");
     auto injected = [&](const char *step) -> int {
@@ -572,6 +572,43 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
     return SHK_OK;
 }
 
+// shk_shard_preprocess from FASTQ files: this rank's share is read into ONE packed batch in HBM (preprocess.cpp:
+// read_fastq_share — split: slice `rank` of `world` of the same files on every rank; else the rank's own files, whole), the
+// ranks agree that all of them have their reads, and the batch goes through shard_preprocess_impl as it is.
+static int shard_preprocess_fastq_impl(shk_handle *h, shk_comm *cm, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2,
+                                       uint32_t n_partitions, int split) {
+    if (!cm || !cm->c) return fail(h, SHK_E_PARAM, "shard_preprocess_fastq: null communicator");
+    if (h->st != St::Fresh) return fail(h, SHK_E_STATE, "shard_preprocess_fastq: handle already used");
+    if (comm_device(cm->c) != h->pipe->device()) return fail(h, SHK_E_PARAM, "shard_preprocess_fastq: communicator and handle live on different devices");
+    ShardComm *c = cm->c;
+    void *st = h->pipe->stream();
+    const double t0 = now_ms();
+    FastqShare sh;
+    // (declared after the share: its blocks go back to the pool with the stream idle, on every way out)
+    struct DrainOnExit { void *st; ~DrainOnExit() { std::string e; (void)device_stream_sync(st, e); } } drain{st};
+    // A rank whose reading fails (a parse error, a damaged stream, memory, an oversized share) enters the first collective all
+    // the same, with "I failed": it returns its own code and message, every other rank "another rank failed during reading".
+    std::string err;
+    int rc_read = read_fastq_share(fq1, n1, fq2, n2, h->k, h->min_qual, split ? (uint32_t)comm_rank(c) : 0u, split ? (uint32_t)comm_world(c) : 1u,
+                                   h->pipe->device(), st, sh, err);
+    if (rc_read) rc_read = fail(h, rc_read, err);
+    const char *inject = getenv("SHK_FAULT_INJECT");      // (step `read`: see shard_preprocess_impl)
+    if (!rc_read && inject && !strcmp(inject, "read")) rc_read = fail(h, SHK_E_INTERNAL, "injected fault (SHK_FAULT_INJECT=read)");
+    uint64_t failed = rc_read ? 1u : 0u;
+    std::string e2;
+    if (int rc = comm_allreduce_host_u64(c, &failed, 1, st, e2)) return rc_read ? rc_read : fail_rc(h, Rc::Device, rc, e2);
+    if (rc_read) return rc_read;
+    if (failed) return fail(h, SHK_E_DEVICE, "shard_preprocess_fastq: another rank failed during reading (this rank's handle is untouched; free it)");
+    auto &t = h->pipe->times();
+    if (sh.n_bgzf_slice) t.add("shard_fastq_bgzf_slice_x1", (double)sh.n_bgzf_slice);
+    if (sh.n_member_whole) t.add("shard_fastq_member_whole_x1", (double)sh.n_member_whole);
+    if (sh.n_text_slice) t.add("shard_fastq_text_slice_x1", (double)sh.n_text_slice);
+    if (sh.n_host) t.add("shard_fastq_host_x1", (double)sh.n_host);
+    t.add("shard_fastq_uploaded_bytes", (double)sh.uploaded_bytes);
+    t.add("shard_fastq_read_host_clock", now_ms() - t0);
+    return shard_preprocess_impl(h, cm, sh.n_seg ? sh.d_bases : nullptr, sh.n_seg ? sh.d_seg_off : nullptr, sh.n_seg, sh.n_bases, sh.n_reads, n_partitions);
+}
+
 int shk_comm_unique_id(uint8_t id[SHK_UNIQUE_ID_BYTES]) {
     try { return comm_unique_id(id, g_comm_err) == 0 ? SHK_OK : SHK_E_DEVICE; }
     catch (...) { g_comm_err = "unexpected exception"; return SHK_E_INTERNAL; }
@@ -607,6 +644,14 @@ int shk_shard_preprocess(shk_handle *h, shk_comm *c, const void *d_bases, const 
         return rc;
     });
 }
+int shk_shard_preprocess_fastq(shk_handle *h, shk_comm *c, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2,
+                               uint32_t n_partitions, int split) {
+    return guarded(h, Poison::AfterFirstBatch, [&] {
+        const int rc = shard_preprocess_fastq_impl(h, c, fq1, n1, fq2, n2, n_partitions, split);
+        if (rc != SHK_OK && c && c->c && comm_broken(c->c)) comm_abort_now(c->c);
+        return rc;
+    });
+}
 int shk_plan_exchange(const uint64_t *part_records_all, uint32_t world, uint32_t n_partitions, uint32_t rank,
                       uint64_t *base, uint64_t *send_counts, uint64_t *recv_counts, uint64_t *run_off, uint32_t *run_cnt) {
     try {
@@ -637,6 +682,56 @@ int shk_device_last_record_start(const uint8_t *text, size_t n, uint64_t *at) {
         std::string err;
         const int rc = gpu_last_record_start(text, n, current_device(), *at, err);
         return rc ? code_of(Rc::DeviceNoParam, rc) : SHK_OK;
+    } catch (...) { return SHK_E_OOM; }
+}
+uint64_t shk_host_first_record_start(const uint8_t *text, size_t n, uint64_t from) { return (text || !n) ? first_record_start(text, n, (size_t)std::min<uint64_t>(from, n)) : UINT64_MAX; }
+int shk_device_first_record_start(const uint8_t *text, size_t n, uint64_t from, uint64_t *at) {
+    try {
+        if ((!text && n) || !at) return SHK_E_PARAM;
+        std::string err;
+        const int rc = gpu_first_record_start(text, n, from, current_device(), *at, err);
+        return rc ? code_of(Rc::DeviceNoParam, rc) : SHK_OK;
+    } catch (...) { return SHK_E_OOM; }
+}
+int64_t shk_plan_fastq_slices(const uint32_t *isize, uint64_t n_blocks, uint32_t world, uint64_t *first_block) {
+    try {
+        if ((!isize && n_blocks) || !first_block || !world) return SHK_E_PARAM;
+        for (uint64_t i = 0; i < n_blocks; i++) if (isize[i] > 65536) return SHK_E_PARAM;
+        std::vector<uint64_t> first;
+        plan_fastq_slices(isize, (size_t)n_blocks, world, first);
+        memcpy(first_block, first.data(), first.size() * 8);
+        return (int64_t)world;
+    } catch (...) { return SHK_E_OOM; }
+}
+// the routes of shk_shard_preprocess_fastq with split = 1, without a communicator: the packed batch of slice `rank` of
+// `world` comes back to the host (shk_packed_free)
+int shk_device_pack_fastq_slice(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual,
+                                uint32_t rank, uint32_t world, shk_packed *out, uint64_t *uploaded_bytes, const char **route) {
+    static thread_local std::string msg, route_s;
+    try {
+        if (!out) return SHK_E_PARAM;
+        *out = shk_packed();
+        if (route) *route = "";
+        if ((k & 1u) == 0 || k < SHK_K_MIN || k > SHK_K_MAX) { msg = "k must be odd and within [15, 255]"; if (route) *route = msg.c_str(); return SHK_E_PARAM; }
+        FastqShare sh;
+        const int rc = read_fastq_share(fq1, n1, fq2, n2, k, min_qual, rank, world, current_device(), nullptr, sh, msg);
+        if (uploaded_bytes) *uploaded_bytes = sh.uploaded_bytes;
+        if (rc) { if (route) *route = msg.c_str(); return rc; }      // (on failure *route carries the message)
+        const size_t nw = (size_t)(sh.n_bases >> 4) + 2;
+        out->bases = (uint32_t *)calloc(nw, 4);
+        out->seg_off = (uint32_t *)calloc((size_t)sh.n_seg + 1, 4);
+        if (!out->bases || !out->seg_off) { shk_packed_free(out); return SHK_E_OOM; }
+        if (sh.n_seg) {
+            if (device_download(out->bases, sh.d_bases, nw * 4, msg) || device_download(out->seg_off, sh.d_seg_off, ((size_t)sh.n_seg + 1) * 4, msg)) {
+                shk_packed_free(out);
+                if (route) *route = msg.c_str();
+                return SHK_E_DEVICE;
+            }
+        }
+        out->n_seg = sh.n_seg; out->n_bases = sh.n_bases; out->n_reads = sh.n_reads; out->n_input_bases = sh.n_input_bases;
+        route_s = sh.route;
+        if (route) *route = route_s.c_str();
+        return SHK_OK;
     } catch (...) { return SHK_E_OOM; }
 }
 uint32_t shk_choose_partitions(uint64_t total_instances_ub, uint32_t world, uint32_t key_words) {

@@ -181,6 +181,52 @@ uint64_t last_record_start(const uint8_t *t, size_t n) {
     }
 }
 
+uint64_t first_record_start(const uint8_t *t, size_t n, size_t from) {
+    size_t p = from;
+    if (p >= n) return UINT64_MAX;
+    if (p > 0 && t[p - 1] != '\n') {                      // `from` lies inside a line: the next line is the first candidate
+        const void *nl = memchr(t + p, '\n', n - p);
+        if (!nl) return UINT64_MAX;
+        p = (size_t)((const uint8_t *)nl - t) + 1;
+    }
+    // p: a line start; b / c: the starts of the next line and of the line after next
+    while (p < n) {
+        const void *e0 = memchr(t + p, '\n', n - p);
+        if (!e0) return UINT64_MAX;
+        const size_t b = (size_t)((const uint8_t *)e0 - t) + 1;
+        if (b >= n) return UINT64_MAX;
+        const void *e1 = memchr(t + b, '\n', n - b);
+        if (!e1) return UINT64_MAX;
+        const size_t c = (size_t)((const uint8_t *)e1 - t) + 1;
+        if (c >= n) return UINT64_MAX;                    // undecided: never passed over
+        if (t[p] == '@' && t[c] == '+') return p;
+        p = b;
+    }
+    return UINT64_MAX;
+}
+
+void fastq_slice_bounds(const uint8_t *t, size_t e, uint32_t rank, uint32_t world, uint64_t cut0, uint64_t cut1, uint64_t &s0, uint64_t &s1) {
+    auto bound = [&](uint32_t r, uint64_t cut) -> uint64_t {
+        if (r == 0) return 0;
+        if (r >= world) return e;
+        const uint64_t p = first_record_start(t, e, (size_t)std::min<uint64_t>(cut, e));
+        return p == UINT64_MAX ? e : p;                   // (the whole text is in view: undecided = none)
+    };
+    s0 = bound(rank, cut0); s1 = bound(rank + 1, cut1);
+}
+
+void plan_fastq_slices(const uint32_t *isize, size_t n_blocks, uint32_t world, std::vector<uint64_t> &first) {
+    uint64_t text = 0;
+    for (size_t i = 0; i < n_blocks; i++) text += isize[i];
+    first.assign((size_t)world + 1, n_blocks);
+    size_t b = 0; uint64_t off = 0;                       // off: the text offset of block b
+    for (uint32_t r = 0; r < world; r++) {
+        const uint64_t want = r ? slice_cut(text, r, world) : 0;
+        while (b < n_blocks && off < want) off += isize[b++];
+        first[r] = b;
+    }
+}
+
 static int inflate_bgzf(const uint8_t *in, size_t n, ByteVec &out, std::string &err, bool &is_bgzf) {
     struct Blk { size_t in_off, in_len, out_off, out_len, hdr; };
     std::vector<Blk> blocks;

@@ -51,6 +51,22 @@ int plan_bgzf_windows(const uint32_t *isize, size_t n_blocks, uint64_t budget, s
 // after next is a sequence).  A line whose line after next has not begun inside t is undecided and is passed over.  Byte 0
 // begins a line.  UINT64_MAX: no such line.  The device states the same rule in k_last_record_start (inflate_gpu.hip).
 uint64_t last_record_start(const uint8_t *t, size_t n);
+// The same rule read forwards — where the slices of the sharded FASTQ entry point are cut: the smallest p >= from that
+// begins a line (p == 0 or t[p - 1] == '\n'), holds '@', and whose line after next begins with '+'.  A line whose line
+// after next has not begun inside t is undecided: the search stops there and never passes it over (a caller that sees only
+// a part of the text widens its view and asks again; two callers with different views of one text so arrive at the same
+// start).  UINT64_MAX: none, or undecided.  The device states the same rule in k_first_record_start (inflate_gpu.hip).
+uint64_t first_record_start(const uint8_t *t, size_t n, size_t from);
+// Slice `rank` of `world` of the text t[0..e) (e: without its trailing blank lines), [s0, s1): s_0 = 0, s_world = e, and in
+// between s_r = the first record start at or after the nominal cut c_r (e where there is none).  cut0 / cut1: c_rank and
+// c_(rank + 1) — floor(r * e / world) for plain text and the text of a plain gzip member (slice_cut), for a BGZF chain the
+// text offset at which block first_block[r] of plan_fastq_slices begins.
+inline uint64_t slice_cut(uint64_t e, uint32_t r, uint32_t world) { return (uint64_t)((unsigned __int128)e * r / world); }
+void fastq_slice_bounds(const uint8_t *t, size_t e, uint32_t rank, uint32_t world, uint64_t cut0, uint64_t cut1, uint64_t &s0, uint64_t &s1);
+// The runs of a BGZF chain that the ranks of the sharded FASTQ entry point inflate: world runs of consecutive blocks,
+// first[r] = the first block whose text offset (the sum of the ISIZE fields in front of it) is >= r * text / world, first[0]
+// = 0, first[world] = n_blocks.  Empty blocks may sit anywhere; more ranks than blocks gives empty runs.
+void plan_fastq_slices(const uint32_t *isize, size_t n_blocks, uint32_t world, std::vector<uint64_t> &first);
 // gzip sniff (1F 8B) + multi-member inflate; plain input is passed through (p/n point at buf or at `storage`)
 int maybe_inflate(const uint8_t *buf, size_t n, ByteVec &storage, const uint8_t *&p, size_t &pn,
                   std::string &err);

@@ -430,7 +430,7 @@ __global__ __launch_bounds__(256) void k_nl_total(const uint8_t *__restrict__ te
 
 
 // bytes of a FASTQ text without its trailing blank lines (the host parser skips them)
-static size_t trimmed_len(const uint8_t *t, size_t n) {
+size_t trimmed_len(const uint8_t *t, size_t n) {
     size_t e = n;
     for (;;) {
         if (e >= 2 && t[e - 1] == '\n' && t[e - 2] == '\n') { e -= 1; continue; }

@@ -110,5 +110,26 @@ class BgzfWindows {
 
 // k_last_record_start alone on n bytes of host text (the tests compare it with last_record_start)
 int gpu_last_record_start(const uint8_t *t, size_t n, int device, uint64_t &at, std::string &err);
+// its forward twin, k_first_record_start, alone (the tests compare it with first_record_start); at = UINT64_MAX: none / undecided
+int gpu_first_record_start(const uint8_t *t, size_t n, uint64_t from, int device, uint64_t &at, std::string &err);
+
+// ---- one rank's slice of a file, for the sharded FASTQ entry point (preprocess.cpp: read_fastq_share) --------------------
+// The slice rule is stated in fastq.h (first_record_start, fastq_slice_bounds, plan_fastq_slices); here it is applied to text
+// that is born on the device.  A span is a run of text inside a device block it owns.
+struct DevSpan { Blk blk; uint64_t off = 0, len = 0; bool unterminated = false; };
+// A walked BGZF chain: rank r uploads and inflates the blocks of run r only (plan_fastq_slices), the non-empty block in front
+// of the run (whether the run's first byte begins a line is written there) and the follow-on blocks of run r + 1 in which its
+// slice ends — 2 first, then twice as many while the boundary is undecided, up to BgzfWindows::CARRY_MAX of text — with
+// inflate_block_run, and finds s_r and s_(r + 1) with k_first_record_start.  uploaded: the compressed bytes that crossed PCIe.
+// 0: out is the slice (possibly empty); 1: declined (*why: a damaged block, no boundary within reach, out of device memory) —
+// the caller reads the file on the host and cuts the same slice there; -5.
+int gpu_bgzf_slice(const uint8_t *gz, const BgzfChain &chain, uint32_t rank, uint32_t world, int device, void *stream, DevSpan &out,
+                   uint64_t &uploaded, const char *&why, std::string &err);
+// A whole text on the device (a plain gzip member inflated by gpu_inflate_member; nominal cuts floor(r * e / world)): its
+// block becomes the span's.  0; -4; -5.
+int gpu_text_slice(GpuText &text, uint32_t rank, uint32_t world, void *stream, DevSpan &out, std::string &err);
+// The spans back to back in one text as the parser wants it (16-byte aligned start, 32 zero bytes behind, a newline between
+// two files where the first ends without one).  0; -4; -5.
+int gpu_join_spans(const DevSpan *spans, int n_spans, void *stream, GpuText &out, std::string &err);
 
 }  // namespace shk

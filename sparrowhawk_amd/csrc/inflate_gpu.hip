@@ -759,6 +759,38 @@ __global__ __launch_bounds__(64) void k_last_record_start(const uint8_t *__restr
     if (lane == 0) out[0] = found;
 }
 
+// The forward twin — the rule of first_record_start (fastq.cpp), which this kernel must agree with byte for byte: the first
+// line at or after `from` that begins with '@' and whose line after next begins with '+'.  One wave walks [from, limit)
+// from the front, 64 bytes a step: a ballot over the newlines of the step, its bits taken from the bottom; the starts of the
+// current line and of the two before it are kept (all of it wave-uniform).  A line is decided when its line after next
+// begins — inside [0, n) and behind a newline in front of `limit`; `from` begins a line only where it is 0 or text[from - 1]
+// is a newline.  limit <= n.  out[0] = the start, or ~0 when nothing was decided inside [from, limit): the host then widens
+// the limit, and at limit == n takes "undecided" as the text's last word.
+__global__ __launch_bounds__(64) void k_first_record_start(const uint8_t *__restrict__ text, unsigned long long n, unsigned long long from,
+                                                          unsigned long long limit, unsigned long long *__restrict__ out) {
+    const uint32_t lane = threadIdx.x;
+    const unsigned long long none = ~0ull;
+    unsigned long long s1 = none, s2 = none, found = none;       // the starts of the line before the current one and of the one before that
+    bool stop = false;                                           // the walk ends with the first start
+    auto line = [&](unsigned long long p) -> bool {              // a line starts at p < n
+        if (s2 != none && text[s2] == '@' && text[p] == '+') { found = s2; return true; }
+        s2 = s1; s1 = p;
+        return false;
+    };
+    if (from < limit && (from == 0 || text[from - 1] == '\n')) stop = line(from);
+    for (unsigned long long lo = from; lo < limit && !stop; lo += 64ull) {
+        const unsigned long long at = lo + lane;
+        unsigned long long m = __ballot(at < limit && text[at] == '\n');
+        while (m) {
+            const int b = __ffsll((long long)m) - 1;
+            m &= m - 1ull;
+            const unsigned long long p = lo + (unsigned)b + 1ull;
+            if (p < n && line(p)) { stop = true; break; }
+        }
+    }
+    if (lane == 0) out[0] = found;
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 // CRC-32 of A || B from crc(A), crc(B): crc(A) advanced over len(B) zero bytes (a GF(2) matrix), XOR crc(B).  The slices
 // have one length, so the matrix is built once (zlib 1.2.11 has no crc32_combine_gen).
@@ -1148,6 +1180,23 @@ int device_last_start(const uint8_t *d_text, uint64_t n, unsigned long long *d_o
         if (from == 0 || tail >= max_tail) return 0;
     }
 }
+
+// the first record start of d_text[0..n) at or after `from`: 1 MiB behind `from` first, a wider reach while nothing is
+// decided.  at = UINT64_MAX: undecided at the end of the text
+int device_first_start(const uint8_t *d_text, uint64_t n, uint64_t from, unsigned long long *d_out, hipStream_t st, uint64_t &at, std::string &err) {
+    at = UINT64_MAX;
+    if (from >= n) return 0;
+    for (uint64_t reach = 1ull << 20;; reach *= 16) {
+        const uint64_t limit = n - from > reach ? from + reach : n;
+        hipLaunchKernelGGL(k_first_record_start, dim3(1), dim3(64), 0, st, d_text, (unsigned long long)n, (unsigned long long)from, (unsigned long long)limit, d_out);
+        GZCHK(hipGetLastError());
+        unsigned long long got = 0;
+        GZCHK(hipMemcpyAsync(&got, d_out, 8, hipMemcpyDeviceToHost, st));
+        GZCHK(hipStreamSynchronize(st));
+        if (got != ~0ull) { at = got; return 0; }
+        if (limit == n) return 0;
+    }
+}
 }  // namespace
 
 BgzfWindowKnob bgzf_window_knob(uint64_t max_bytes) {
@@ -1253,6 +1302,137 @@ int gpu_last_record_start(const uint8_t *t, size_t n, int device, uint64_t &at, 
     const int rc = device_last_start((const uint8_t *)d_text.p, n, (unsigned long long *)d_out.p, st, at, err);
     (void)hipStreamSynchronize(st);
     return rc;
+}
+
+int gpu_first_record_start(const uint8_t *t, size_t n, uint64_t from, int device, uint64_t &at, std::string &err) {
+    hipStream_t st = nullptr;
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); err = "hipSetDevice failed"; return -5; }
+    Blk d_text, d_out;
+    if (!d_text.get(n + 64) || !d_out.get(64)) { err = "out of device memory"; return -4; }
+    if (n) GZCHK(hipMemcpyAsync(d_text.p, t, n, hipMemcpyHostToDevice, st));
+    const int rc = device_first_start((const uint8_t *)d_text.p, n, from, (unsigned long long *)d_out.p, st, at, err);
+    (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+// ---- slices for the sharded FASTQ entry point (inflate_gpu.h) -----------------------------------------------------------
+int gpu_bgzf_slice(const uint8_t *gz, const BgzfChain &chain, uint32_t rank, uint32_t world, int device, void *stream, DevSpan &out,
+                   uint64_t &uploaded, const char *&why, std::string &err) {
+    hipStream_t st = (hipStream_t)stream;
+    out.blk.put(); out.off = out.len = 0; out.unterminated = false;
+    uploaded = 0;
+    const size_t B = chain.blocks.size();
+    if (rank >= world) { err = "rank beyond world"; return -1; }
+    if (chain.text == 0) return 0;                          // (no text: every slice is empty)
+    std::vector<uint32_t> isize(B);
+    for (size_t i = 0; i < B; i++) isize[i] = chain.blocks[i].isize;
+    std::vector<uint64_t> first;
+    plan_fastq_slices(isize.data(), B, world, first);
+    const size_t b0 = (size_t)first[rank], b1 = (size_t)first[rank + 1];
+    // the block in front of the run is inflated too: whether the run's first byte begins a line is written there
+    size_t pb = b0;
+    while (rank > 0 && pb > 0) { pb--; if (isize[pb]) break; }
+    uint64_t lead = 0, own = 0;
+    for (size_t b = pb; b < b0; b++) lead += isize[b];
+    for (size_t b = b0; b < b1; b++) own += isize[b];
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); err = "hipSetDevice failed"; return -5; }
+    const bool last_rank = rank + 1 == world;
+    // the follow-on blocks of run rank + 1, in which this slice ends: 2 first, then twice as many, up to CARRY_MAX of text
+    for (size_t extra = last_rank ? 0 : 2;; extra *= 2) {
+        size_t ve = b1;                                     // the view: blocks [pb, ve)
+        uint64_t follow = 0;
+        for (size_t got = 0; ve < B && got < extra && follow < BgzfWindows::CARRY_MAX; ve++) { follow += isize[ve]; got += isize[ve] != 0; }
+        while (ve < B && !isize[ve]) ve++;                  // (empty blocks at the end of the file ride along: the view then reaches the end)
+        const bool at_end = ve == B;
+        const uint64_t n_view = lead + own + follow;
+        uint32_t nb = 0;
+        for (size_t b = pb; b < ve; b++) nb += isize[b] != 0;
+        if (!nb) return 0;                                  // (only empty blocks from here to the end of the file)
+        const uint64_t in_base = chain.blocks[pb].in_off;
+        const size_t in_n = (size_t)(chain.blocks[ve - 1].in_off + chain.blocks[ve - 1].bsize - in_base);
+        if (n_view >= (1ull << 32) - 64 || in_n >= ((size_t)1 << 34)) { why = "a slice beyond 4 GiB of text"; return 1; }
+        Blk d_in, d_desc, d_status, d_bad, d_text;
+        if (!d_in.get(((in_n + 3) & ~(size_t)3) + WIN_IN_PAD) || !d_desc.get((size_t)nb * sizeof(BgzfDesc)) || !d_status.get((size_t)nb * 4) ||
+            !d_bad.get(128) || !d_text.get((size_t)n_view + 64)) { why = "out of device memory"; return 1; }
+        // (on every way out of this attempt the stream is idle before the blocks go back to the pool: GZCHK waits)
+        GZCHK(hipMemsetAsync((char *)d_in.p + (in_n & ~(size_t)3), 0, ((in_n + 3) & ~(size_t)3) - (in_n & ~(size_t)3) + WIN_IN_PAD, st));
+        GZCHK(hipMemcpyAsync(d_in.p, gz + in_base, in_n, hipMemcpyHostToDevice, st));
+        GZCHK(hipMemsetAsync((char *)d_text.p + n_view, 0, 64, st));
+        uploaded += in_n;
+        double ms = 0;
+        Tail tail;
+        if (const int rc = inflate_block_run(chain, pb, ve, d_in.p, in_base, (uint8_t *)d_text.p, 0, d_desc, d_status, d_bad, st, ms, nullptr, at_end ? &tail : nullptr, why, err)) return rc;
+        uint64_t e = n_view; bool unterminated = false;
+        if (at_end) if (const int rc = trim_text_end((uint8_t *)d_text.p, n_view, tail, false, st, e, unterminated, why, err)) return rc;
+        // s_rank inside the own run (or behind it), s_(rank + 1) inside the follow-on text
+        uint64_t s[2] = {0, e};
+        bool widen = false;
+        for (int i = 0; i < 2; i++) {
+            if (i == 0 ? rank == 0 : last_rank) continue;
+            const uint64_t from = i == 0 ? lead : lead + own;
+            uint64_t at = UINT64_MAX;
+            if (const int rc = device_first_start((const uint8_t *)d_text.p, e, from, (unsigned long long *)d_bad.p + 8, st, at, err)) return rc;
+            if (at == UINT64_MAX && !at_end) { widen = true; break; }
+            s[i] = at == UINT64_MAX ? e : at;
+        }
+        if (widen) {
+            if (follow >= BgzfWindows::CARRY_MAX) { why = "no record start within reach behind the run"; return 1; }
+            GZCHK(hipStreamSynchronize(st));
+            continue;
+        }
+        if (rank == 0) s[0] = 0;
+        if (s[0] > s[1]) s[0] = s[1];
+        out.off = s[0]; out.len = s[1] - s[0];
+        out.unterminated = at_end && s[1] == e && unterminated && out.len != 0;
+        out.blk.bytes = d_text.bytes; out.blk.p = d_text.take();
+        GZCHK(hipStreamSynchronize(st));
+        return 0;
+    }
+}
+
+int gpu_text_slice(GpuText &text, uint32_t rank, uint32_t world, void *stream, DevSpan &out, std::string &err) {
+    hipStream_t st = (hipStream_t)stream;
+    out.blk.put(); out.off = out.len = 0; out.unterminated = false;
+    if (rank >= world) { err = "rank beyond world"; return -1; }
+    const uint64_t e = text.e;
+    Blk d_out;
+    if (!d_out.get(64)) { err = "out of device memory"; return -4; }
+    uint64_t s[2] = {0, e};
+    for (int i = 0; i < 2; i++) {
+        const uint32_t r = rank + (uint32_t)i;
+        if (r == 0 || r == world) continue;
+        uint64_t at = UINT64_MAX;
+        if (const int rc = device_first_start(text.d, e, slice_cut(e, r, world), (unsigned long long *)d_out.p, st, at, err)) return rc;
+        s[i] = at == UINT64_MAX ? e : at;
+    }
+    out.off = s[0]; out.len = s[1] - s[0];
+    out.unterminated = s[1] == e && text.unterminated && out.len != 0;
+    out.blk.bytes = text.pool_bytes; out.blk.p = text.d;      // the text's block is the span's now
+    text = GpuText();
+    return 0;
+}
+
+int gpu_join_spans(const DevSpan *spans, int n_spans, void *stream, GpuText &out, std::string &err) {
+    hipStream_t st = (hipStream_t)stream;
+    out = GpuText();
+    uint64_t total = 0;
+    for (int i = 0; i < n_spans; i++) total += spans[i].len + 1;
+    size_t bytes = (size_t)total + 32;
+    out.d = (uint8_t *)device_pool_alloc(bytes);
+    if (!out.d) { err = "out of device memory for the FASTQ text"; return -4; }
+    out.pool_bytes = bytes;
+    uint64_t at = 0;
+    for (int i = 0; i < n_spans; i++) {
+        if (!spans[i].len) continue;
+        if (out.unterminated) { GZCHK(hipMemsetAsync(out.d + at, '\n', 1, st)); at++; }      // (a file that ends without a newline)
+        GZCHK(hipMemcpyAsync(out.d + at, (const uint8_t *)spans[i].blk.p + spans[i].off, (size_t)spans[i].len, hipMemcpyDeviceToDevice, st));
+        at += spans[i].len;
+        out.unterminated = spans[i].unterminated;
+    }
+    GZCHK(hipMemsetAsync(out.d + at, 0, 32, st));
+    GZCHK(hipStreamSynchronize(st));
+    out.e = (size_t)at;
+    return 0;
 }
 
 }  // namespace shk

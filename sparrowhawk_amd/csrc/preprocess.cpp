@@ -18,6 +18,9 @@
 //   6 route_host                 SHK_HOST_PARSER=1, or every route above declined.  Never declines.
 //   7 push_reads_impl            the streaming entry point: the device parser for a chunk of >= SHK_STREAM_DEVICE_MIN bytes
 //                                that is regular 4-line FASTQ, else the host parser
+//   8 read_fastq_share           the sharded entry point from files (shk_shard_preprocess_fastq): one rank's slice of every file
+//                                as ONE packed batch — per file a BGZF slice, a whole member or a text slice on the device, the
+//                                host reader and the host parser for what the device declines (preprocess.h)
 // The device parser (fastq_gpu.hip) takes regular 4-line FASTQ only; irregular framing and every malformed record go to
 // the host parser (fastq.cpp), which owns the error messages.
 #include "preprocess.h"
@@ -645,4 +648,144 @@ int preprocess_packed_host_impl(shk_handle *h, const uint32_t *bases, const uint
     h->pipe->times().add("h2d_packed_reads_MB", (double)(want_b + want_s) / 1e6);
     h->pipe->times().add("preprocess_from_host_total_host_clock", now_ms() - t0);
     return rc;
+}
+
+// ---- one rank's share of FASTQ files as one packed batch (preprocess.h) --------------------------------------------------
+FastqShare::~FastqShare() {
+    gpu_packed_free(gp);
+    device_free(up_bases); device_free(up_seg_off);
+}
+
+namespace {
+// the nominal cuts c_rank and c_(rank + 1) of a walked BGZF chain: the text offsets at which the rank's run and the next begin
+void bgzf_slice_cuts(const BgzfChain &chain, uint32_t rank, uint32_t world, uint64_t &c0, uint64_t &c1) {
+    std::vector<uint32_t> isize(chain.blocks.size());
+    for (size_t i = 0; i < isize.size(); i++) isize[i] = chain.blocks[i].isize;
+    std::vector<uint64_t> first;
+    plan_fastq_slices(isize.data(), isize.size(), world, first);
+    uint64_t off = 0;
+    c0 = c1 = chain.text;
+    for (size_t b = 0; b <= isize.size(); b++) {
+        if (b == first[rank]) c0 = off;
+        if (b == first[rank + 1]) { c1 = off; break; }
+        if (b < isize.size()) off += isize[b];
+    }
+}
+}  // namespace
+
+int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual, uint32_t rank,
+                     uint32_t world, int device, void *stream, FastqShare &out, std::string &err) {
+    if ((!fq1 && (n1 || fq2)) || (!fq2 && n2)) { err = "shard_preprocess_fastq: a null file with a size, or a second file without a first"; return SHK_E_PARAM; }
+    if (world == 0 || rank >= world) { err = "shard_preprocess_fastq: rank beyond world"; return SHK_E_PARAM; }
+    const Knobs kn;
+    const uint8_t *const fq[2] = {fq1, fq2}; const size_t fn[2] = {n1, fq2 ? n2 : 0};
+    const int nf = fq2 ? 2 : (fq1 ? 1 : 0);
+    enum Route { None, BgzfSlice, MemberWhole, TextSlice, Host };
+    static const char *const route_name[] = {"", "bgzf_slice", "member_whole", "text_slice", "host"};
+    struct File {
+        BgzfChain chain; bool walked = false, gz = false;      // walked: a complete BGZF chain — its cuts lie at block starts, on every route
+        ByteVec st; const uint8_t *t = nullptr; size_t l = 0, e = 0; bool host_text = false;
+        uint64_t s0 = 0, s1 = 0;                                // the slice inside the host text
+        Route route = None;
+    } f[2];
+    for (int i = 0; i < nf; i++) {
+        f[i].gz = fn[i] >= 18 && fq[i][0] == 0x1F && fq[i][1] == 0x8B;
+        size_t bs = 0; const char *why = "";
+        f[i].walked = f[i].gz && bgzf_block(fq[i], fn[i], bs) && bgzf_walk(fq[i], fn[i], f[i].chain, why) == 0;
+    }
+    // the host's text of file i (read once) and the slice in it
+    auto host_slice = [&](int i) -> int {
+        File &F = f[i];
+        if (F.host_text) return SHK_OK;
+        if (int ri = maybe_inflate(fq[i], fn[i], F.st, F.t, F.l, err)) return code_of(Rc::Inflater, ri);
+        F.e = trimmed_len(F.t, F.l);
+        uint64_t c0 = slice_cut(F.e, rank, world), c1 = slice_cut(F.e, rank + 1, world);
+        if (F.walked) bgzf_slice_cuts(F.chain, rank, world, c0, c1);
+        fastq_slice_bounds(F.t, F.e, rank, world, c0, c1, F.s0, F.s1);
+        F.host_text = true;
+        return SHK_OK;
+    };
+    auto too_large = [&](uint64_t bases_or_half_bytes) -> bool {
+        if (bases_or_half_bytes <= kn.batch_bases) return false;
+        err = "shard_preprocess_fastq: this rank's share exceeds one batch (SHK_BATCH_BASES = " + std::to_string(kn.batch_bases) +
+              " packed bases); several batches per rank are not supported: use more ranks or split the input";
+        return true;
+    };
+    auto finish = [&](bool host_parsed) -> int {
+        for (int i = 0; i < nf; i++) {
+            const Route r = host_parsed ? Host : f[i].route;
+            out.n_bgzf_slice += r == BgzfSlice; out.n_member_whole += r == MemberWhole; out.n_text_slice += r == TextSlice; out.n_host += r == Host;
+            if (out.route.find(route_name[r]) == std::string::npos) out.route += (out.route.empty() ? "" : "+") + std::string(route_name[r]);
+        }
+        return SHK_OK;
+    };
+    // ---- the device: every file's slice as a span of text in HBM, joined, parsed
+    bool host_parser = kn.host_parser;
+    if (!host_parser) {
+        DevSpan spans[2];
+        for (int i = 0; i < nf; i++) {
+            File &F = f[i];
+            if (F.gz && kn.gunzip_device) {
+                int rc = 1;
+                if (F.walked) {
+                    const char *why = ""; uint64_t up = 0;
+                    rc = gpu_bgzf_slice(fq[i], F.chain, rank, world, device, stream, spans[i], up, why, err);
+                    out.uploaded_bytes += up;
+                    if (!rc) F.route = BgzfSlice;
+                } else {
+                    Text text;
+                    rc = gpu_inflate_member(fq[i], fn[i], device, stream, text, err);
+                    if (!rc) {
+                        out.uploaded_bytes += fn[i];
+                        if ((rc = gpu_text_slice(text, rank, world, stream, spans[i], err)) == 0) F.route = MemberWhole;
+                    }
+                }
+                if (rc < 0) return code_of(Rc::DeviceNoParam, rc);
+            }
+            if (F.route != None) continue;
+            // plain text, or what the device inflater declined: cut on the host, the slice alone is uploaded
+            if (int rc = host_slice(i)) return rc;
+            Text text;
+            if (int rc = gpu_upload_text(F.t + F.s0, (size_t)(F.s1 - F.s0), device, text, err)) return code_of(Rc::DeviceNoParam, rc);
+            out.uploaded_bytes += text.e;
+            spans[i].len = text.e; spans[i].unterminated = text.unterminated;
+            spans[i].blk.bytes = text.pool_bytes; spans[i].blk.p = text.d;
+            static_cast<GpuText &>(text) = GpuText();      // (the block is the span's now)
+            F.route = F.gz ? Host : TextSlice;
+        }
+        uint64_t bytes = 0;
+        for (int i = 0; i < nf; i++) bytes += spans[i].len;
+        if (too_large(bytes / 2)) return SHK_E_PARAM;
+        Text joined;
+        if (int rc = gpu_join_spans(spans, nf, stream, joined, err)) return code_of(Rc::DeviceNoParam, rc);
+        for (int i = 0; i < nf; i++) spans[i].blk.put();
+        const int rc = gpu_pack_fastq(nullptr, 0, nullptr, 0, k, min_qual, 0, stream, out.gp, err, 0, &joined);
+        if (rc < 0) { gpu_packed_free(out.gp); out.gp = GpuPacked(); return code_of(Rc::Device, rc); }
+        if (rc == 0) {
+            if (too_large(out.gp.n_bases)) return SHK_E_PARAM;
+            out.d_bases = out.gp.d_bases; out.d_seg_off = out.gp.d_seg_off;
+            out.n_seg = out.gp.n_seg; out.n_bases = out.gp.n_bases; out.n_reads = out.gp.n_reads; out.n_input_bases = out.gp.n_input_bases;
+            return finish(false);
+        }
+        gpu_packed_free(out.gp); out.gp = GpuPacked();
+        host_parser = true;                               // not regular 4-line FASTQ: the host parser owns the messages
+    }
+    // ---- the host parser on the same slices
+    PackedReads pr;
+    for (int i = 0; i < nf; i++) {
+        if (int rc = host_slice(i)) return rc;
+        if (int rc = pack_fastq(f[i].t + f[i].s0, (size_t)(f[i].s1 - f[i].s0), k, min_qual, pr, err)) return code_of(Rc::Parser, rc);
+    }
+    if (too_large(pr.n_bases)) return SHK_E_PARAM;
+    out.n_reads = pr.n_reads; out.n_input_bases = pr.n_input_bases;
+    if (pr.n_seg()) {
+        pr.finish();
+        int rc = device_upload(pr.bases.data(), pr.bases.size() * 4, &out.up_bases, err);
+        if (!rc) rc = device_upload(pr.seg_off.data(), pr.seg_off.size() * 4, &out.up_seg_off, err);
+        if (rc) return SHK_E_OOM;
+        out.uploaded_bytes += (pr.bases.size() + pr.seg_off.size()) * 4;
+        out.d_bases = (const uint32_t *)out.up_bases; out.d_seg_off = (const uint32_t *)out.up_seg_off;
+        out.n_seg = pr.n_seg(); out.n_bases = pr.n_bases;
+    }
+    return finish(true);
 }

@@ -2,6 +2,7 @@
 // of the C ABI.  api.cpp runs each of them under guarded().
 #pragma once
 #include "handle.h"
+#include "fastq_gpu.h"
 
 int preprocess_impl(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2);
 int push_reads_impl(shk_handle *h, const uint8_t *chunk, size_t n);
@@ -12,3 +13,27 @@ int preprocess_packed_host_impl(shk_handle *h, const uint32_t *bases, const uint
                                 uint64_t n_bases, uint64_t n_reads);
 // the count below which pass 2 emits no row (the shard layer's pass 2 uses the same)
 uint32_t emit_threshold_of(const shk_handle *h);
+
+// ---- one rank's share of FASTQ files as ONE packed batch in HBM: what shk_shard_preprocess_fastq hands to the shard layer
+// and shk_device_pack_fastq_slice copies back (preprocess.cpp).  Slice `rank` of `world` of every file (fastq.h: the slice
+// rule; world 1: the whole file), both files of a pair pooled into the one batch.  Routes, per file: a BGZF chain — the blocks
+// of the rank's run alone are uploaded and inflated (inflate_gpu.h: gpu_bgzf_slice); a plain gzip member — inflated whole on
+// the device, then cut (a deflate stream cannot be entered in the middle); plain text — cut on the host, the slice alone is
+// uploaded.  Whatever the device declines is read on the host, whole, and cut there by the same rule; a slice that is not
+// regular 4-line FASTQ goes through the host parser, which owns the messages (record numbers count from the slice's start).
+struct FastqShare {
+    shk::GpuPacked gp;                                    // parsed on the device
+    void *up_bases = nullptr, *up_seg_off = nullptr;      // parsed on the host, uploaded
+    const uint32_t *d_bases = nullptr, *d_seg_off = nullptr;
+    uint64_t n_seg = 0, n_bases = 0, n_reads = 0, n_input_bases = 0;
+    uint64_t uploaded_bytes = 0;                          // compressed or text (or host-packed) bytes that crossed PCIe
+    uint32_t n_bgzf_slice = 0, n_member_whole = 0, n_text_slice = 0, n_host = 0;      // files by route; n_host: read or parsed on the host
+    std::string route;                                    // the routes' names, '+' between two that differ
+    FastqShare() = default;
+    FastqShare(const FastqShare &) = delete;
+    FastqShare &operator=(const FastqShare &) = delete;
+    ~FastqShare();
+};
+// SHK_OK, or the SHK_E_* code with its message in err; an oversized share (beyond one batch) is SHK_E_PARAM
+int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual, uint32_t rank,
+                     uint32_t world, int device, void *stream, FastqShare &out, std::string &err);

@@ -27,7 +27,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .helper import AssemblyHelper, ShkError
+from .helper import AssemblyHelper, ShkError, _as_bytes
 
 
 def choose_partitions(total_instances_ub, world, per_part=100_000):
@@ -183,6 +183,17 @@ def sharded_preprocess_rccl(helper: AssemblyHelper, d_bases_ptr, d_seg_off_ptr, 
     helper._check(helper._L.shk_shard_preprocess(helper._h, comm._c, d_bases_ptr if n_seg else None,
                                                  d_seg_off_ptr if n_seg else None, int(n_seg), int(n_bases),
                                                  int(n_reads), int(n_partitions or 0)))
+
+
+def sharded_preprocess_fastq(helper: AssemblyHelper, comm: LibComm, file1, file2=None, split=True, n_partitions=0):
+    """Collective over `comm`: the sharded preprocess straight from FASTQ files (plain, .gz or BGZF; bytes, a path or a
+    file object).  split=True: every rank passes the SAME file(s) and takes slice `rank` of `world` of each — of a BGZF
+    file only the blocks of its own run cross PCIe.  split=False: the files are this rank's own reads (file1=None: it has
+    none).  One C call (shk_shard_preprocess_fastq), no Python collectives; helper.assemble() is collective next."""
+    b1, b2 = _as_bytes(file1), _as_bytes(file2)
+    helper._check(helper._L.shk_shard_preprocess_fastq(helper._h, comm._c, b1, len(b1) if b1 is not None else 0,
+                                                       b2, len(b2) if b2 is not None else 0, int(n_partitions or 0),
+                                                       1 if split else 0))
 
 
 def lib_plan_exchange(part_records_all, rank):
