@@ -507,8 +507,7 @@ __global__ __launch_bounds__(1024) void k_gz_win_init(const uint16_t *__restrict
         W[j] = i >= 0 ? S[i] : (uint16_t)(GZ_MARK + (uint32_t)((long long)j + n));      // the chunk is shorter than a window: the rest comes from ITS window
     }
 }
-__global__ __launch_bounds__(1024) void k_gz_win_round(const uint16_t *__restrict__ Min, uint16_t *__restrict__ Mout, uint32_t n_chunks, uint32_t step,
-                                                      uint32_t *__restrict__ bad) {
+__global__ __launch_bounds__(1024) void k_gz_win_round(const uint16_t *__restrict__ Min, uint16_t *__restrict__ Mout, uint32_t n_chunks, uint32_t step) {
     const uint32_t c = blockIdx.x + 1;
     if (c >= n_chunks) return;
     const uint16_t *A = Min + (size_t)c * GZ_WSIZE;
@@ -517,10 +516,8 @@ __global__ __launch_bounds__(1024) void k_gz_win_round(const uint16_t *__restric
     const uint16_t *B = Min + (size_t)(have_src ? c - step : 0) * GZ_WSIZE;
     for (uint32_t j = threadIdx.x; j < GZ_WSIZE; j += 1024) {
         uint32_t e = A[j];
-        if (e >= GZ_MARK) {
-            if (have_src) e = B[(e - GZ_MARK) & (GZ_WSIZE - 1)];
-            else { atomicOr(bad, 1u); e = 0; }                   // a reference in front of the stream's first byte
-        }
+        // (no window c - step: a byte in front of the stream's first.  The entry stays a pointer; k_gz_resolve refuses its use)
+        if (e >= GZ_MARK && have_src) e = B[(e - GZ_MARK) & (GZ_WSIZE - 1)];
         O[j] = (uint16_t)e;
     }
 }
@@ -538,7 +535,7 @@ __global__ __launch_bounds__(256) void k_gz_resolve(const uint16_t *__restrict__
         uint32_t s = S[i];
         if (s >= GZ_MARK) {
             if (c == 0) { atomicOr(bad, 2u); s = 0; }
-            else { s = W[(s - GZ_MARK) & (GZ_WSIZE - 1)]; if (s >= GZ_MARK) { atomicOr(bad, 4u); s = 0; } }      // (a window byte nobody resolved: never)
+            else { s = W[(s - GZ_MARK) & (GZ_WSIZE - 1)]; if (s >= GZ_MARK) { atomicOr(bad, 4u); s = 0; } }      // (a byte in front of the stream's first: k_gz_win_round)
         }
         T[i] = (uint8_t)s;
     }
@@ -1062,7 +1059,7 @@ int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, Gp
                        (uint16_t *)d_ma.p);
     uint16_t *Mi = (uint16_t *)d_ma.p, *Mo = (uint16_t *)d_mb.p;
     for (uint32_t step = 1; step < C; step *= 2) {
-        hipLaunchKernelGGL(k_gz_win_round, dim3(C - 1), dim3(1024), 0, st, (const uint16_t *)Mi, Mo, C, step, (uint32_t *)d_bad.p);
+        hipLaunchKernelGGL(k_gz_win_round, dim3(C - 1), dim3(1024), 0, st, (const uint16_t *)Mi, Mo, C, step);
         std::swap(Mi, Mo);
     }
     GZCHK(hipGetLastError());

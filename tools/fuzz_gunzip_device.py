@@ -6,7 +6,11 @@ messages): it must NEVER return other bytes.  Needs a GPU.  Usage: python tools/
 bgzf: BGZF (bgzip) files instead — blocks of random sizes (1 ... 65 280 bytes of text) and levels, empty blocks anywhere,
 with or without the end-of-file block.  Every intact file must be TAKEN with its text's bytes (this path has no speculative
 step); a damaged one (cut short, bits flipped, BSIZE / ISIZE / CRC-32 fields changed) is declined or comes back as the host
-reader (shk_host_gunzip) reads it."""
+reader (shk_host_gunzip) reads it.
+bgzf written: the same campaign on files whose blocks come from the bit-level writer of the tests (tests/deflate_writer.py)
+instead of zlib's encoder: random token lists (greedy parses with random match limits), stored, fixed and dynamic blocks in
+turn, random complete code-length sets with a longest code of 7 ... 15 bits, the header's length list written literally, with
+greedy runs or with runs that stop at the literal/distance boundary.  Texts are smaller (the writer is pure Python)."""
 import ctypes as C
 import os
 import sys
@@ -17,6 +21,7 @@ from collections import Counter
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))             # (deflate_writer, for `bgzf written`)
 os.environ.setdefault("SHK_GUNZIP_DEVICE_MIN", "32768")
 import torch  # noqa: F401  (one HIP runtime)
 import fuzz_gunzip as fg
@@ -55,14 +60,60 @@ def bgzf_file(text):
     return b"".join(parts), offs
 
 
+def written_bgzf_file(text):
+    """(file, [(offset, BSIZE)]): `text` in BGZF blocks of 1 ... 20 000 bytes, each a stream of one to four blocks written bit by bit"""
+    import deflate_writer as dw
+
+    def noisy_lengths(freqs):
+        f = [x * float(rng.integers(1, 50)) if x else 0 for x in freqs]
+        n = sum(1 for x in f if x)
+        if n < 2:
+            return dw.huffman_lengths(f, 15)
+        m = int(rng.integers(7, 16))
+        if m + 1 <= n <= m + (1 << (m - 1)) and rng.random() < 0.5:
+            return dw.lengths_with_max(f, m)
+        return dw.huffman_lengths(f, max(m, n.bit_length()))
+    parts, p = [], 0
+    while p < len(text):
+        n = int(rng.choice([int(rng.integers(1, 40)), int(rng.integers(1, 3000)), int(rng.integers(1, 20000))]))
+        piece, s, q = text[p:p + n], dw.Stream(), 0
+        cuts = sorted({len(piece)} | {int(rng.integers(0, len(piece) + 1)) for _ in range(int(rng.integers(0, 4)))})
+        for i, e in enumerate(cuts):
+            final, kind = i + 1 == len(cuts), int(rng.integers(0, 3))
+            toks = dw.tokenize(piece[q:e], piece[:q], min_match=int(rng.integers(3, 8)), max_dist=int(rng.choice([4, 300, 5000, 32768])),
+                               max_len=int(rng.choice([3, 10, 64, 258])))
+            if kind == 0:
+                s.stored(piece[q:e], final)
+            elif kind == 1:
+                s.fixed(toks, final)
+            else:
+                fl, fd = dw.symbol_freqs(toks)
+                nd = sum(1 for x in fd if x)
+                dist = dw.no_codes() if nd == 0 else dw.one_code(fd.index(max(fd)), 30) if nd == 1 else noisy_lengths(fd)
+                s.dynamic(toks, noisy_lengths(fl), dist, final, cl_plan={"mode": str(rng.choice(["literal", "greedy", "split"]))})
+            q = e
+        assert zlib.decompress(s.bytes(), -15) == piece, "the writer and zlib disagree"
+        parts.append(dw.bgzf_block(s.bytes(), piece))
+        p += n
+        if rng.random() < 0.02:
+            parts.append(dw.BGZF_EOF)
+    if rng.random() < 0.7:
+        parts.append(dw.BGZF_EOF)
+    offs, o = [], 0
+    for b in parts:
+        offs.append((o, len(b))); o += len(b)
+    return b"".join(parts), offs
+
+
 def fuzz_bgzf():
     import struct
+    written = "written" in sys.argv[1:]
     os.environ["SHK_GUNZIP_DEVICE_MIN"] = "0"                # (every file, however small)
     t0 = time.time()
     reasons = Counter()
     for case in range(n_cases):
-        text = fg.make_text(int(rng.choice([70000, 300_000, 3_000_000, 8_000_000])))
-        z, offs = bgzf_file(text)
+        text = fg.make_text(int(rng.choice([70000, 300_000] if written else [70000, 300_000, 3_000_000, 8_000_000])))
+        z, offs = written_bgzf_file(text) if written else bgzf_file(text)
         # at times through the windows of the large-file route: text per window from one block's worth up (csrc/preprocess.cpp, route 2)
         os.environ.pop("SHK_GUNZIP_DEVICE_WINDOW", None)
         if rng.random() < 0.5:
