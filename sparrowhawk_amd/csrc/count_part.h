@@ -1203,7 +1203,8 @@ template <int W> struct DedupeShared {
 template <int W>
 __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_dedupe_partitions(   // one- and two-word keys: 8 waves per SIMD = two workgroups per CU, <= 64 VGPRs
                                                                      RunView rvw, uint32_t p_first, uint32_t n_parts,
-                                                                     const unsigned long long *__restrict__ base,
+                                                                     const unsigned long long *__restrict__ base /* nullptr: base[p] = p * base_stride */,
+                                                                     unsigned long long base_stride,
                                                                      uint64_t *__restrict__ out_recs, uint32_t *__restrict__ out_w,
                                                                      uint32_t *__restrict__ n_out, uint32_t *__restrict__ work_counter,
                                                                      OvfRec *__restrict__ ovf /* nullable */, uint32_t *__restrict__ ovf_n,
@@ -1289,8 +1290,9 @@ __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_dedupe_partit
                 if (R) { const uint32_t slot = atomicAdd(ovf_n, 1u); OvfRec o; o.p = p; o.est_distinct = 0u; o.instances = ctl.part_inst; ovf[slot] = o; }
             }
         };
-        uint64_t *dst = out_recs + base[p] * RW;
-        uint32_t *dst_w = out_w + base[p];
+        const unsigned long long base_p = base ? base[p] : (unsigned long long)p * base_stride;
+        uint64_t *dst = out_recs + base_p * RW;
+        uint32_t *dst_w = out_w + base_p;
         const uint32_t per_wave = (((R + (COUNT_THREADS / 64) - 1) / (COUNT_THREADS / 64)) + 63u) & ~63u;
         const uint32_t w_begin = min(R, (threadIdx.x >> 6) * per_wave), w_end = min(R, w_begin + per_wave);
         uint32_t run_lo = 0, run_next = 0;
@@ -1391,8 +1393,8 @@ __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_dedupe_partit
 // in-launch sample decides when later partitions are handed over untried.
 template <int W>
 __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_count_weighted(
-    const uint64_t *__restrict__ recs, const uint32_t *__restrict__ weights, const unsigned long long *__restrict__ base,
-    const uint32_t *__restrict__ n_recs, uint32_t p_first, uint32_t n_parts, uint32_t merge /* partitions counted together in one table (1..4) */, int k, uint32_t threshold,
+    const uint64_t *__restrict__ recs, const uint32_t *__restrict__ weights, const unsigned long long *__restrict__ base /* nullptr: base[p] = p * base_stride */,
+    unsigned long long base_stride, const uint32_t *__restrict__ n_recs, uint32_t p_first, uint32_t n_parts, uint32_t merge /* partitions counted together in one table (1..4) */, int k, uint32_t threshold,
     unsigned long long *__restrict__ histo, KeyArr<W> out_keys, uint32_t *__restrict__ out_cnt,
     unsigned long long out_cap, unsigned long long *__restrict__ out_cursor,
     unsigned long long *__restrict__ n_inst, OvfRec *__restrict__ ovf, uint32_t *__restrict__ ovf_n,
@@ -1427,7 +1429,7 @@ __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_count_weighte
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const bool in = (uint32_t)j < nm;
-            Rj[j] = in ? n_recs[pm[j]] : 0u; bj[j] = in ? base[pm[j]] : 0ull;
+            Rj[j] = in ? n_recs[pm[j]] : 0u; bj[j] = in ? (base ? base[pm[j]] : (unsigned long long)pm[j] * base_stride) : 0ull;
             Rt += Rj[j];
         }
         auto fetch = [&](uint32_t r, Rec<RW> &rec, uint32_t &wgt) {
@@ -1500,8 +1502,9 @@ __global__ __launch_bounds__(COUNT_THREADS, W <= 2 ? 8 : 4) void k_count_weighte
     bool in_sample = true;                               // (this workgroup's first group: see the loop below)
     auto defer = [&](uint32_t p, bool was_tried) {
         const uint32_t R = n_recs[p];
-        const uint64_t *src = recs + base[p] * RW;
-        const uint32_t *src_w = weights + base[p];
+        const unsigned long long base_p = base ? base[p] : (unsigned long long)p * base_stride;
+        const uint64_t *src = recs + base_p * RW;
+        const uint32_t *src_w = weights + base_p;
         mark_broken();                                   // (its rows come out of the repartition, elsewhere)
         __syncthreads();
         if (threadIdx.x == 0) { ctl.tried = 0; ctl.part_inst = 0; }

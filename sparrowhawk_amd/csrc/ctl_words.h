@@ -20,10 +20,8 @@ struct CountWords {
     uint32_t part_too_large, bucket_splits;            // `flags` of k_count_partitions / k_count_buckets: residue splitting gave up; bucket rounds split (statistic)
     uint32_t n_handed_over, tally;                     // `ovf_n`: partitions listed in ovf[]; tried | overflowed << 16 of the sampled ones
     unsigned long long bucket_list_len;                // k_ovf_check: buckets listed for k_count_buckets
-    unsigned long long spare5[3];
-    uint32_t p1_spare, p1_seg_too_long;                // `flags` of k_partition, [0] and [1]
-    union { unsigned long long p1_max_fill;            // ... and [2]: the fullest slice of pass 1
-            unsigned long long bloom_keys; };          // pass 2, Bloom mode: distinct k-mers that reached a table (k_count_buckets)
+    unsigned long long spare5[4];
+    unsigned long long bloom_keys;                     // pass 2, Bloom mode: distinct k-mers that reached a table (k_count_buckets)
     unsigned long long spare10;
     unsigned long long probe_work;                     // work counter of the fused k_count_partitions
     unsigned long long dedupe_work;                    // work counter of k_dedupe_partitions, then of the residue re-run
@@ -34,6 +32,23 @@ struct CountWords {
     unsigned long long er_broken;                      // EmitRanges::broken: a group left in more than one piece
     unsigned long long spare24[8];
 };
+// Pass 1's flags (`flags` of k_partition: [0], [1] and, 64 bits wide, [2]).  They lie outside the 32 words: pass 2 may be
+// launched behind pass 1 before the host has looked at them, and zeroes the words for its own era.
+struct P1Words {
+    uint32_t spare, seg_too_long;                      // [1]: a read segment beyond 32768 bases
+    unsigned long long max_fill;                       // [2]: the fullest slice of pass 1
+};
+// What Pipeline::ctl_ holds during the counting era, and the image of it that ONE transfer brings to the host's mailbox at the
+// wait of pass 2: the words, the histogram of pass 2, pass 1's flags.  The fill in front of pass 1 zeroes all of it; an attempt
+// of pass 2 that does not follow pass 1 directly zeroes `w` and `hist`.  (The graph era uses the first 32 words only.)
+struct CountMail {
+    CountWords w;
+    unsigned long long hist[500];                      // k_count_weighted / k_count_partitions / k_count_buckets: distinct k-mers by count
+    P1Words p1;
+};
+static constexpr int COUNT_MAIL_WORDS = (int)(sizeof(CountMail) / 8);
+static_assert(sizeof(CountMail) == (CTL_WORDS + 500 + 2) * 8 && offsetof(CountMail, hist) == CTL_WORDS * 8 && offsetof(CountMail, p1) == (CTL_WORDS + 500) * 8,
+              "CountMail: words, histogram, pass 1's flags, contiguous");
 static inline unsigned tally_tried(uint32_t t) { return t & 0xFFFFu; }
 static inline unsigned tally_over(uint32_t t) { return t >> 16; }
 static inline unsigned long long er_rows(unsigned long long cursor) { return cursor >> 32; }
@@ -43,7 +58,7 @@ struct GraphWords {
     unsigned long long spare0;                         // (read back with the two below, never written)
     unsigned long long table_flag;                     // k_graph_local: 1 a mini table overflowed, 2 a row outside its group's range
     unsigned long long slots_used;                     // k_gp_scan: slots of all mini tables
-    unsigned long long n_cand, n_tips;                 // correction scratch of a round: candidates (tips, then forks), tips walked
+    unsigned long long n_cand, n_tips;                 // correction scratch of a round: tip candidates, tips walked
     union { unsigned long long tips_removed;           // correction rounds >= 1
             unsigned long long n_splitters; };         // rank_chains: k_succ_split, appended to by k_orphan_cycles
     union { unsigned long long bubbles_removed;        // correction rounds >= 1
@@ -52,7 +67,8 @@ struct GraphWords {
     uint32_t collapse_flag, n_spl_wanted;              // `flags` of the collapse: 2 / 3 / 4 ...; the splitter count that did not fit
     unsigned long long n_alive;                        // alive oriented nodes (k_succ_split)
     unsigned long long n_walked;                       // nodes covered by the fragment walk (k_walk_frags)
-    unsigned long long spare11[2];
+    unsigned long long n_fork_cand;                    // correction scratch of a round: fork candidates (k_fork_candidates; a word of its own, so that one fill opens a round)
+    unsigned long long spare12;
     union { unsigned long long xq_count;               // build_graph, sharded: neighbour queries that go to other ranks
             unsigned long long halflink_flags; };      // shard_assemble: k_hl_apply / k_ls_answer found the ranks disagreeing
     unsigned long long writer_flag;                    // k_w_plan_fill: a contig beyond 2^32 bases
@@ -69,8 +85,7 @@ SHK_CTL_AT(CountWords, instances, 1, 0);      SHK_CTL_AT(CountWords, g_overflow,
 SHK_CTL_AT(CountWords, part_too_large, 2, 0); SHK_CTL_AT(CountWords, bucket_splits, 2, 1);
 SHK_CTL_AT(CountWords, n_handed_over, 3, 0);  SHK_CTL_AT(CountWords, tally, 3, 1);
 SHK_CTL_AT(CountWords, bucket_list_len, 4, 0);
-SHK_CTL_AT(CountWords, p1_spare, 8, 0);       SHK_CTL_AT(CountWords, p1_seg_too_long, 8, 1);
-SHK_CTL_AT(CountWords, p1_max_fill, 9, 0);    SHK_CTL_AT(CountWords, bloom_keys, 9, 0);
+SHK_CTL_AT(CountWords, bloom_keys, 9, 0);
 SHK_CTL_AT(CountWords, probe_work, 11, 0);    SHK_CTL_AT(CountWords, dedupe_work, 12, 0);
 SHK_CTL_AT(CountWords, groups_out, 14, 0);    SHK_CTL_AT(CountWords, group_tally, 14, 1);
 SHK_CTL_AT(CountWords, er_cursor, 22, 0);     SHK_CTL_AT(CountWords, er_broken, 23, 0);
@@ -82,6 +97,7 @@ SHK_CTL_AT(GraphWords, bubbles_removed, 6, 0); SHK_CTL_AT(GraphWords, n_chains, 
 SHK_CTL_AT(GraphWords, n_ring_splitters, 7, 0);
 SHK_CTL_AT(GraphWords, collapse_flag, 8, 0);  SHK_CTL_AT(GraphWords, n_spl_wanted, 8, 1);
 SHK_CTL_AT(GraphWords, n_alive, 9, 0);        SHK_CTL_AT(GraphWords, n_walked, 10, 0);
+SHK_CTL_AT(GraphWords, n_fork_cand, 11, 0);
 SHK_CTL_AT(GraphWords, xq_count, 13, 0);      SHK_CTL_AT(GraphWords, halflink_flags, 13, 0);
 SHK_CTL_AT(GraphWords, writer_flag, 14, 0);
 SHK_CTL_AT(GraphWords, r0_tips_removed, 16, 0); SHK_CTL_AT(GraphWords, r0_bubbles_removed, 17, 0);

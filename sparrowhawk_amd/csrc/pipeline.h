@@ -115,7 +115,9 @@ public:
     virtual bool sharded_graph() const = 0;
     virtual uint64_t n_solid_global() const = 0;
     virtual int shard_assemble(ShardComm *comm, bool tips, bool bubbles, std::vector<RawContig> &out, std::string &err) = 0;
-    virtual StageTimes &times() = 0;
+    virtual StageTimes &times() = 0;                 // (waits for the events of timers that were stopped without waiting)
+    // a host-clock figure added without that wait: for callers with work still to launch behind what the stream holds
+    virtual void add_time(const char *name, double ms) = 0;
     // waits until nothing is in flight on the pipeline's streams (through the shard layer's watchdog while a collective call
     // of several ranks runs); never fails — an error stays on the stream for the next call to find
     virtual void drain() = 0;

@@ -371,26 +371,33 @@ static inline uint64_t env_u64(const char *name, uint64_t dflt) {
     return (v && *v) ? strtoull(v, nullptr, 10) : dflt;
 }
 
-// Two fills in one launch (a step of the pipeline made sixteen hipMemsetAsync calls, 5-6 us of the GPU each and most of them a
-// few dozen bytes): regions of whole 32-bit words.
-__global__ __launch_bounds__(256) void k_fill2(uint32_t *a, unsigned long long na, uint32_t va, uint32_t *b, unsigned long long nb, uint32_t vb) {
+// Up to four fills in one launch (a step of the pipeline made sixteen hipMemsetAsync calls, 5-6 us of the GPU each and most of
+// them a few dozen bytes): regions of whole 32-bit words.
+struct FillRegion { uint32_t *p; unsigned long long n; uint32_t v; };      // p[0 .. n) := v
+struct FillList { FillRegion r[4]; };
+static inline FillRegion fill_region(void *p, size_t bytes, uint32_t v) { return FillRegion{(uint32_t *)p, (unsigned long long)(bytes / 4), v}; }
+__global__ __launch_bounds__(256) void k_fill(FillList f) {
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < na + nb; i += stride) {
-        if (i < na) a[i] = va; else b[i - na] = vb;
+    const unsigned long long total = f.r[0].n + f.r[1].n + f.r[2].n + f.r[3].n;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        unsigned long long j = i;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            if (j < f.r[q].n) { f.r[q].p[j] = f.r[q].v; break; }
+            j -= f.r[q].n;
+        }
     }
 }
-// out[i] = i * stride (the places of the partitions' deduplicated records when one batch sits in its slices: a launch instead of
-// a copy from pageable host memory, which the runtime only starts once the stream has drained — the host then fell behind
-// pass 1 and the launches after it reached the GPU one by one, 36 us of idle time behind k_partition)
-__global__ __launch_bounds__(256) void k_stride_fill(unsigned long long *out, uint32_t n, unsigned long long stride) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = (unsigned long long)i * stride;
+static inline hipError_t fill_async(hipStream_t st, FillRegion a, FillRegion b = FillRegion{nullptr, 0, 0u}, FillRegion c = FillRegion{nullptr, 0, 0u},
+                                    FillRegion d = FillRegion{nullptr, 0, 0u}) {
+    const FillList f{{a, b, c, d}};
+    const unsigned long long blocks = std::min<unsigned long long>((a.n + b.n + c.n + d.n + 255) / 256, 2048ull);
+    if (!blocks) return hipSuccess;
+    hipLaunchKernelGGL(k_fill, dim3((uint32_t)blocks), dim3(256), 0, st, f);
+    return hipGetLastError();
 }
 static inline hipError_t fill2_async(void *a, size_t bytes_a, uint32_t va, void *b, size_t bytes_b, uint32_t vb, hipStream_t st) {
-    const unsigned long long na = bytes_a / 4, nb = bytes_b / 4;
-    const unsigned long long blocks = std::min<unsigned long long>((na + nb + 255) / 256, 2048ull);
-    if (!blocks) return hipSuccess;
-    hipLaunchKernelGGL(k_fill2, dim3((uint32_t)blocks), dim3(256), 0, st, (uint32_t *)a, na, va, (uint32_t *)b, nb, vb);
-    return hipGetLastError();
+    return fill_async(st, fill_region(a, bytes_a, va), fill_region(b, bytes_b, vb));
 }
 
 // ---- the contig text goes to the host by a KERNEL that writes pinned host memory slab by slab and raises a flag per slab
@@ -431,16 +438,19 @@ __global__ __launch_bounds__(1024) void k_ends_to_host(const char *__restrict__ 
     __syncthreads();
     if (threadIdx.x == 0) __hip_atomic_store(flag_host, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-// the same copy when the host does not know the size yet (k_plan_emit's plan): plan[0] == 1 or nothing is copied, plan[1] = bytes
-__global__ __launch_bounds__(256) void k_text_to_host_planned(const char *__restrict__ src, char *__restrict__ dst_host,
-                                                              const unsigned long long *__restrict__ plan) {
-    if (plan[0] != 1ull) return;
-    const unsigned long long bytes = plan[1];
-    const unsigned long long nv = bytes >> 4;
-    const uint4 *a = reinterpret_cast<const uint4 *>(src);
-    uint4 *d = reinterpret_cast<uint4 *>(dst_host);
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x; i < nv; i += (unsigned long long)gridDim.x * 256u) d[i] = a[i];
-    if (blockIdx.x == 0 && threadIdx.x < (bytes & 15ull)) dst_host[(nv << 4) + threadIdx.x] = src[(nv << 4) + threadIdx.x];
+// The small results of a host wait, in ONE transfer to the pinned mailbox (two or three hipMemcpyAsync calls cost a blit kernel
+// each and 10-20 us of idle GPU beside every one): the control words, and behind them `rec_words` 64-bit words for each of the
+// first min(*n_recs_p, max_recs) records of `recs` (the chain records of rank_chains; n_recs_p nullptr: max_recs of them).
+// The host reads the mailbox after it has waited for the stream.  ONE workgroup.
+__global__ __launch_bounds__(256) void k_mail_home(const unsigned long long *__restrict__ ctl_words, uint32_t n_ctl,
+                                                   const unsigned long long *__restrict__ recs, const unsigned int *__restrict__ n_recs_p,
+                                                   uint32_t max_recs, uint32_t rec_words,
+                                                   unsigned long long *__restrict__ mail_ctl, unsigned long long *__restrict__ mail_recs) {
+    for (uint32_t i = threadIdx.x; i < n_ctl; i += 256u) mail_ctl[i] = ctl_words[i];
+    uint32_t n = max_recs;
+    if (n_recs_p) n = min(*n_recs_p, max_recs);
+    const uint32_t nw = n * rec_words;
+    for (uint32_t i = threadIdx.x; i < nw; i += 256u) mail_recs[i] = recs[i];
 }
 class SlabArrival : public TextArrival {
 public:
@@ -503,11 +513,12 @@ public:
         { int cus = 0; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, stream_dev_); n_cus_ = cus > 0 ? cus : 256; }
         stream_ = stream_pool_get(stream_dev_);
         if (!stream_) HIPCHK(hipStreamCreate(&stream_));
-        HIPCHK(ctl_.alloc(CTL_WORDS, err) ? hipErrorOutOfMemory : hipSuccess);
+        HIPCHK(ctl_.alloc(COUNT_MAIL_WORDS, err) ? hipErrorOutOfMemory : hipSuccess);      // (the counting era's layout is the larger one: ctl_words.h)
         if (mbox_.alloc(MBOX_BYTES, err)) return -4;
         return 0;
     }
     StageTimes &times() override { EvTimer::resolve(pending_timers_, times_); return times_; }
+    void add_time(const char *name, double ms) override { times_.add(name, ms); }
     void drain() override {
         if (copy_stream_) (void)hipStreamSynchronize(copy_stream_);
         if (!stream_) return;
@@ -580,7 +591,7 @@ public:
     template <int WBLK, int NBLK>
     void launch_partition_t(const uint32_t *d_bases, const uint32_t *d_seg_off, uint32_t n_seg) {
         hipLaunchKernelGGL((k_partition<W, WBLK, NBLK>), dim3(pp_.G), dim3(PART_THREADS), 0, stream_, d_bases, d_seg_off,
-                           n_seg, pp_, recs_.p, fill_.p, ctl(&CountWords::p1_spare));
+                           n_seg, pp_, recs_.p, fill_.p, &d_count()->p1.spare);
     }
     void launch_partition(int win, const uint32_t *d_bases, const uint32_t *d_seg_off, uint32_t n_seg) {
         if (win == 20) launch_partition_t<10, 2>(d_bases, d_seg_off, n_seg);
@@ -667,7 +678,9 @@ public:
             const uint64_t n_slices = (uint64_t)P * pp_.G;
             if (int rc = recs_.alloc(n_slices * cap * RW, err)) return rc;
             if (int rc = fill_.alloc(n_slices, err)) return rc;
-            HIPCHK(fill2_async(fill_.p, n_slices * 4, 0u, ctl_.p, sizeof(CountWords), 0u, stream_));
+            // (the words and the histogram of pass 2 with them: nothing but k_make_runs stands between the two passes)
+            HIPCHK(fill2_async(fill_.p, n_slices * 4, 0u, ctl_.p, sizeof(CountMail), 0u, stream_));
+            p2_prefilled_ = false;
             EvTimer t(stream_);
             if (h_bases && attempt == 0) {
                 // ---- upload and pass 1, piece by piece
@@ -699,44 +712,45 @@ public:
                 HIPCHK(hipGetLastError());
                 times_.add("h2d_pieces_x1", (double)C);
                 if (defer_p1_ && batches_.empty()) {            // (as below: pass 2 follows without a host round trip)
-                    HIPCHK(fetch_ctl(mb_p1(), &CountWords::p1_spare, &CountWords::p1_max_fill));
                     t.stop_later("partition_with_upload", pending_timers_);
                     p1_ = P1Pending{true, d_bases, d_seg_off, n_seg, n_bases, cap};
+                    p2_prefilled_ = true;
                     return finish_partition(n_slices, err);
                 }
                 t.mark();
-                CountWords h;
-                HIPCHK(fetch_ctl(&h, &CountWords::p1_spare, &CountWords::p1_max_fill));
+                HIPCHK(fetch_p1());
                 WAIT_STREAM();
-                if (h.p1_seg_too_long) { err = "a read segment exceeds 32768 bases (split it on the host)"; return -1; }
-                if ((uint32_t)h.p1_max_fill <= cap) {
+                const P1Words h = mb_count()->p1;
+                if (h.seg_too_long) { err = "a read segment exceeds 32768 bases (split it on the host)"; return -1; }
+                if ((uint32_t)h.max_fill <= cap) {
                     times_.add("partition_with_upload", t.elapsed());
                     if (int rc = finish_partition(n_slices, err)) return rc;
                     return 0;
                 }
                 times_.add("partition_retry", t.elapsed());
-                cap = (uint64_t)(uint32_t)h.p1_max_fill + 8;      // (the reads are on the device now: the retry is one launch)
+                cap = (uint64_t)(uint32_t)h.max_fill + 8;      // (the reads are on the device now: the retry is one launch)
                 continue;
             }
             launch_partition_all(wblk, d_bases, d_seg_off, n_seg);
             HIPCHK(hipGetLastError());
             if (defer_p1_ && attempt == 0 && batches_.empty() && piece_list_.empty()) {
                 // ONE batch whose reads outlive histogram() (the packed entry points): pass 2 is launched behind pass 1 without a
-                // host round trip; the flags land in pinned memory and are looked at after pass 2's own read-back.  A slice
+                // host round trip; the flags come home with pass 2's own read-back (CountMail) and are looked at after it — a copy
+                // of their own here made the host wait for pass 1, and everything behind it reached the GPU late.  A slice
                 // that overflowed stored nothing beyond its room (wave_flush) and its run is clamped (k_make_runs): pass 2 then
                 // ran on a part of the records and both passes are repeated with the exact room (histogram()).
-                HIPCHK(fetch_ctl(mb_p1(), &CountWords::p1_spare, &CountWords::p1_max_fill));
                 t.stop_later("partition_kernel", pending_timers_);
                 p1_ = P1Pending{true, d_bases, d_seg_off, n_seg, n_bases, cap};
+                p2_prefilled_ = true;
                 return finish_partition(n_slices, err);
             }
             t.mark();
-            CountWords h;
-            HIPCHK(fetch_ctl(&h, &CountWords::p1_spare, &CountWords::p1_max_fill));
+            HIPCHK(fetch_p1());
             WAIT_STREAM();          // (one host round trip: flags and the timer together)
             const double ms = t.elapsed();
-            if (h.p1_seg_too_long) { err = "a read segment exceeds 32768 bases (split it on the host)"; return -1; }
-            const uint32_t max_fill = (uint32_t)h.p1_max_fill;
+            const P1Words h = mb_count()->p1;
+            if (h.seg_too_long) { err = "a read segment exceeds 32768 bases (split it on the host)"; return -1; }
+            const uint32_t max_fill = (uint32_t)h.max_fill;
             if (max_fill <= cap) {
                 times_.add("partition_kernel", ms);
                 if (int rc = finish_partition(n_slices, err)) return rc;
@@ -868,12 +882,14 @@ public:
         // (weighted records — sharded counting, deduplicated by their sources — stay in k_count_partitions: the bucket path
         // counts one per entry; a partition that does not fit is re-run by residue classes there)
         const bool repartition = env_u64("SHK_NO_REPARTITION", 0) == 0 && rv.weights == nullptr;
-        DevBuf<unsigned long long> dh;
+        unsigned long long *const d_hist = d_count()->hist;      // (beside the control words: they come home together, mail_count)
         DevBuf<OvfRec> d_ovf; DevBuf<OvfItem> d_items; DevBuf<uint32_t> d_fill, d_list, d_maxfill, d_new; DevBuf<uint64_t> d_kmers; DevBuf<BucketRef> d_blist; DevBuf<unsigned long long> d_sumfill;
         const bool bloom = bloom_ && !bloom_off_once_;          // (do_bloom: Bloom pre-filter in the k-mer-level repartition)
         unsigned long long bloom_new = 0, bloom_kmer_bytes = 0, bloom_kmer_bytes_exact = 0;
-        if (int rc = dh.alloc(500, err)) return rc;
         if (repartition) if (int rc = d_ovf.alloc(n_parts, err)) return rc;
+        // (behind a pass 1 that was not waited for — count_batch_impl — the words and the histogram are zero already: its fill covered them)
+        const bool prefilled = p2_prefilled_ && p1_.on;
+        p2_prefilled_ = false;
         // Two-kernel pass 2 (default for local reads): k_dedupe_partitions writes every partition's DISTINCT records with
         // their multiplicities (sorted by length), k_count_weighted expands them — each needs half of a CU's LDS, so two
         // workgroups per CU hide each other's latencies (the fused k_count_partitions owns the whole LDS: 0.87 ms on the
@@ -891,27 +907,30 @@ public:
             bloom_new = 0; bloom_kmer_bytes = 0; bloom_kmer_bytes_exact = 0;
             for (int j = 0; j < W; j++) if (int rc = keys[j].alloc(cap, err)) return rc;
             if (int rc = cnt.alloc(cap, err)) return rc;
-            HIPCHK(fill2_async(dh.p, 500 * 8, 0u, ctl_.p, sizeof(CountWords), 0u, stream_));
+            if (!(prefilled && attempt == 0)) HIPCHK(fill_async(stream_, fill_region(ctl_.p, offsetof(CountMail, p1), 0u)));      // (the words and the histogram; pass 1's flags stay)
             KeyArr<W> ok; for (int j = 0; j < W; j++) ok.w[j] = keys[j].p;
             const uint32_t probe_parts = (uint32_t)env_u64("SHK_PROBE_PARTS", 512);     // 0 = off
             const uint32_t n_probe = (repartition && probe_parts && n_parts / 4 >= probe_parts) ? probe_parts : 0u;
             EvTimer t(stream_);
             if (split) {
                 // (every attempt: the partitions the dedupe hands over are reported in d_ovf / ctl_, which an attempt starts empty)
-                if (int rc = dd_base_.alloc(n_parts, err)) return rc;
                 if (int rc = dd_n_.alloc(n_parts, err)) return rc;
                 if (int rc = dd_recs_.alloc(split_total_ * 2 * W + 2, err)) return rc;
                 if (int rc = dd_w_.alloc(split_total_ + 2, err)) return rc;
-                if (split_stride_) {
-                    hipLaunchKernelGGL(k_stride_fill, dim3((n_parts + 255) / 256), dim3(256), 0, stream_, dd_base_.p, n_parts, split_stride_);
-                    HIPCHK(hipGetLastError());
-                } else HIPCHK(hipMemcpyAsync(dd_base_.p, split_base_.data(), (size_t)n_parts * 8, hipMemcpyHostToDevice, stream_));
+                // where partition p's distinct records go: p * split_stride_ when one batch sits in its slices (the kernels compute
+                // it: no table, no launch and no copy between the passes), else the table (several batches)
+                const unsigned long long *d_base = nullptr;
+                if (!split_stride_) {
+                    if (int rc = dd_base_.alloc(n_parts, err)) return rc;
+                    HIPCHK(hipMemcpyAsync(dd_base_.p, split_base_.data(), (size_t)n_parts * 8, hipMemcpyHostToDevice, stream_));
+                    d_base = dd_base_.p;
+                }
                 // (no sample launch in front: the partitions the dedupe tries are the sample, and its verdict is where the counting
                 // kernel's own tally starts — count_part.h)
                 const uint32_t defer_after = n_probe / 8;
                 EvTimer t_a(stream_, stage_timers_);
                 hipLaunchKernelGGL(k_dedupe_partitions<W>, dim3(std::min<uint32_t>(n_parts, 2u * (uint32_t)n_cus_)), dim3(COUNT_THREADS), 0, stream_,
-                                   rv, 0u, n_parts, dd_base_.p, dd_recs_.p, dd_w_.p, dd_n_.p, (uint32_t *)ctl(&CountWords::dedupe_work),
+                                   rv, 0u, n_parts, d_base, split_stride_, dd_recs_.p, dd_w_.p, dd_n_.p, (uint32_t *)ctl(&CountWords::dedupe_work),
                                    d_ovf.p, ctl(&CountWords::n_handed_over), defer_after, (S / 10) * 9, ctl(&CountWords::group_tally));
                 HIPCHK(hipGetLastError());
                 if (attempt == 0) t_a.stop_later("count_dedupe_kernel", pending_timers_);
@@ -941,7 +960,7 @@ public:
                     er_groups_ = n_groups;
                 }
                 hipLaunchKernelGGL(k_count_weighted<W>, dim3(std::min<uint32_t>(n_groups, per_cu * (uint32_t)n_cus_)), dim3(COUNT_THREADS), 0, stream_,
-                                   dd_recs_.p, dd_w_.p, dd_base_.p, dd_n_.p, 0u, n_parts, merge, rv.k, threshold, dh.p, ok, cnt.p, (unsigned long long)cap,
+                                   dd_recs_.p, dd_w_.p, d_base, split_stride_, dd_n_.p, 0u, n_parts, merge, rv.k, threshold, d_hist, ok, cnt.p, (unsigned long long)cap,
                                    // (groups_out and, in the word's high half, this kernel's tally — it starts at the dedupe's verdict
                                    // and covers reads whose records repeat but whose k-mers do not fit)
                                    ctl(&CountWords::row_cursor), ctl(&CountWords::instances), d_ovf.p, ctl(&CountWords::n_handed_over),
@@ -950,17 +969,16 @@ public:
                 // (persistent workgroups, one per CU: the tables take the whole LDS)
                 auto kern = rv.weights ? k_count_partitions<W, true> : k_count_partitions<W, false>;
                 hipLaunchKernelGGL(kern, dim3(std::min<uint32_t>(n_parts, (uint32_t)n_cus_)), dim3(COUNT_THREADS), 0, stream_, rv, n_parts, threshold,
-                                   dh.p, ok, cnt.p, (unsigned long long)cap, ctl(&CountWords::row_cursor), ctl(&CountWords::instances),
+                                   d_hist, ok, cnt.p, (unsigned long long)cap, ctl(&CountWords::row_cursor), ctl(&CountWords::instances),
                                    ctl(&CountWords::part_too_large), (const uint32_t *)nullptr, repartition ? d_ovf.p : (OvfRec *)nullptr,
                                    ctl(&CountWords::n_handed_over), (uint32_t *)ctl(&CountWords::probe_work), n_probe / 2, n_probe / 8);
             }
             HIPCHK(hipGetLastError());
             t.mark();
-            CountWords h{};
-            HIPCHK(fetch_ctl(&h, &CountWords::row_cursor, &CountWords::tally));
-            HIPCHK(hipMemcpyAsync(hist_out, dh.p, 500 * 8, hipMemcpyDeviceToHost, stream_));   // (final unless partitions overflowed)
-            if (split && er_groups_) HIPCHK(fetch_ctl(&h, &CountWords::er_cursor, &CountWords::er_broken));
-            WAIT_STREAM();          // one host round trip: counters, histogram, the groups' ranges' verdict and the timer
+            HIPCHK(mail_count());
+            WAIT_STREAM();          // one host round trip, one transfer: counters, histogram, the groups' ranges' verdict, pass 1's flags, and the timer
+            CountWords h = mb_count()->w;
+            memcpy(hist_out, mb_count()->hist, 500 * 8);       // (final unless partitions overflowed)
             ms_out = t.elapsed();      // (sample + dedupe + count)
             const uint32_t n_ovf = h.n_handed_over;
             if (env_u64("SHK_VERBOSE_TALLY", 0)) fprintf(stderr, "[shk] pass 2: %u partitions, %u handed over, tally tried %u / over %u, split %d\n", n_parts, n_ovf,
@@ -1032,8 +1050,9 @@ public:
                     HIPCHK(hipMemcpyAsync(smf.data(), d_sumfill.p, (size_t)ni * 8, hipMemcpyDeviceToHost, stream_));
                     if (bloom) HIPCHK(hipMemcpyAsync(newc.data(), d_new.p, (size_t)ni * 4, hipMemcpyDeviceToHost, stream_));
                     HIPCHK(hipMemcpyAsync(mxf.data(), d_maxfill.p, (size_t)ni * 4, hipMemcpyDeviceToHost, stream_));
-                    HIPCHK(fetch_ctl(&h, &CountWords::bucket_list_len, &CountWords::bucket_list_len));
+                    HIPCHK(fetch_ctl(&mb_count()->w, &CountWords::bucket_list_len, &CountWords::bucket_list_len));
                     WAIT_STREAM();
+                    h.bucket_list_len = mb_count()->w.bucket_list_len;
                     std::vector<OvfItem> again;
                     uint32_t n_good = 0;
                     for (uint32_t i = 0; i < ni; i++) {
@@ -1052,7 +1071,7 @@ public:
                         // persistent workgroups, two per CU (the k-mer table is half the LDS)
                         const uint32_t bgrid = (uint32_t)std::min<unsigned long long>(h.bucket_list_len, 2ull * (unsigned long long)n_cus_);
                         hipLaunchKernelGGL(k_count_buckets<W>, dim3(bgrid), dim3(COUNT_THREADS), 0, stream_,
-                                           d_blist.p, n_list, d_kmers.p, threshold, dh.p, ok, cnt.p, (unsigned long long)cap,
+                                           d_blist.p, n_list, d_kmers.p, threshold, d_hist, ok, cnt.p, (unsigned long long)cap,
                                            ctl(&CountWords::row_cursor), ctl(&CountWords::instances), ctl(&CountWords::part_too_large), bloom ? 1u : 0u, ctl(&CountWords::bloom_keys));
                         HIPCHK(hipGetLastError());
                         WAIT_STREAM();      // d_items / d_kmers are reused by the next pass
@@ -1064,7 +1083,7 @@ public:
                     if (int rc = d_list.alloc(bad.size(), err)) return rc;
                     HIPCHK(hipMemcpyAsync(d_list.p, bad.data(), bad.size() * 4, hipMemcpyHostToDevice, stream_));
                     hipLaunchKernelGGL(k_count_partitions<W>, dim3(std::min<uint32_t>((uint32_t)bad.size(), (uint32_t)n_cus_)), dim3(COUNT_THREADS), 0, stream_, rv, (uint32_t)bad.size(), threshold,
-                                       dh.p, ok, cnt.p, (unsigned long long)cap, ctl(&CountWords::row_cursor), ctl(&CountWords::instances),
+                                       d_hist, ok, cnt.p, (unsigned long long)cap, ctl(&CountWords::row_cursor), ctl(&CountWords::instances),
                                        ctl(&CountWords::part_too_large), (const uint32_t *)d_list.p, (OvfRec *)nullptr, (uint32_t *)nullptr, (uint32_t *)ctl(&CountWords::dedupe_work), 0u, 0u);
                     HIPCHK(hipGetLastError());
                 }
@@ -1072,9 +1091,14 @@ public:
                 times_.add("count_repartitioned_x1", (double)n_good_total);
                 times_.add("count_deferred_untried_x1", (double)n_untried);
                 times_.add("count_residue_rerun_x1", (double)bad.size());
-                HIPCHK(fetch_ctl(&h, &CountWords::row_cursor, &CountWords::tally));
-                HIPCHK(hipMemcpyAsync(hist_out, dh.p, 500 * 8, hipMemcpyDeviceToHost, stream_));
+                HIPCHK(mail_count());
                 WAIT_STREAM();
+                {   // (the counters and the histogram after the repartition; the ranges' verdict is the first transfer's)
+                    const CountWords &m = mb_count()->w;
+                    h.row_cursor = m.row_cursor; h.instances = m.instances; h.part_too_large = m.part_too_large; h.bucket_splits = m.bucket_splits;
+                    h.n_handed_over = m.n_handed_over; h.tally = m.tally;
+                    memcpy(hist_out, mb_count()->hist, 500 * 8);
+                }
                 times_.add("count_bucket_splits_x1", (double)h.bucket_splits);
                 if (bloom) {
                     // k-mers the filter took as new: each is one distinct k-mer (less the false positives) and one
@@ -1136,15 +1160,16 @@ public:
                 int rc_p2 = run_count_partitions(run_view_, n_count_parts_, emit_threshold, ekeys_, ecnt_, n_emitted_, histo, inst,
                                                  inst_ub_rows, ms, err);
                 if (p1_.on) {
-                    // pass 1's flags arrived with pass 2's read-back (count_batch_impl): look at them now
-                    if (rc_p2) { std::string e2; (void)e2; (void)hipStreamSynchronize(stream_); }
+                    // pass 1's flags arrived with pass 2's read-back (CountMail): look at them now
+                    // (pass 2 failed, perhaps before its read-back: fetch them; no attempt of pass 2 touches them on the device)
+                    if (rc_p2) { (void)hipStreamSynchronize(stream_); if (fetch_p1() == hipSuccess) (void)hipStreamSynchronize(stream_); }
                     p1_.on = false;
-                    const CountWords &h = *mb_p1();
-                    if (h.p1_seg_too_long) { split_ready_ = false; err = "a read segment exceeds 32768 bases (split it on the host)"; return -1; }
-                    if ((uint32_t)h.p1_max_fill > p1_.cap) {
+                    const P1Words h = mb_count()->p1;
+                    if (h.seg_too_long) { split_ready_ = false; err = "a read segment exceeds 32768 bases (split it on the host)"; return -1; }
+                    if ((uint32_t)h.max_fill > p1_.cap) {
                         // a slice overflowed: both passes again, pass 1 with the exact room (the reads are still on the device)
                         times_.add("partition_retry", 1.0);
-                        cap_override_ = (uint64_t)(uint32_t)h.p1_max_fill + 8;
+                        cap_override_ = (uint64_t)(uint32_t)h.max_fill + 8;
                         have_parts_ = false; split_ready_ = false;
                         const bool d = defer_p1_; defer_p1_ = false;
                         const int rc1 = count_batch_impl(p1_.d_bases, p1_.d_seg_off, nullptr, nullptr, p1_.n_seg, p1_.n_bases, err);
@@ -1334,7 +1359,7 @@ public:
         // (two workgroups per CU where the kernel's registers allow it, as on one GPU: with one, 588 us against 418 for the
         // bench isolate — found in the timeline of the one-rank leg, profiles/r04_final/sharded_one_rank_timeline.txt)
         hipLaunchKernelGGL(k_dedupe_partitions<W>, dim3(std::min<uint32_t>(pp_.P, (W <= 2 ? 2u : 1u) * (uint32_t)n_cus_)), dim3(COUNT_THREADS), 0, stream_,
-                           run_view_, 0u, pp_.P, dd_base_.p, dd_recs_.p, dd_w_.p, dd_n_.p, (uint32_t *)ctl(&CountWords::dedupe_work),
+                           run_view_, 0u, pp_.P, dd_base_.p, 0ull, dd_recs_.p, dd_w_.p, dd_n_.p, (uint32_t *)ctl(&CountWords::dedupe_work),
                            (OvfRec *)nullptr, (uint32_t *)nullptr, 0u, 0u, (uint32_t *)nullptr);
         HIPCHK(hipGetLastError());
         t.mark();
@@ -1679,8 +1704,12 @@ public:
         const dim3 G(1024), B(256);
         const bool tips = corr_tips_, bubbles = corr_bubbles_;
         const auto s_tip = round == 0 ? &GraphWords::r0_tips_removed : &GraphWords::tips_removed, s_bub = round == 0 ? &GraphWords::r0_bubbles_removed : &GraphWords::bubbles_removed;
-        HIPCHK(fill2_async(ctl(&GraphWords::n_cand), ctl_span(&GraphWords::n_cand, &GraphWords::bubbles_removed), 0u, nullptr, 0, 0u, stream_));      // (one launch: a small hipMemsetAsync at an odd offset came out as three fill kernels)
+        // (one launch for the round: a small hipMemsetAsync at an odd offset came out as three fill kernels, and the fork candidates
+        // count in a word of their own instead of n_cand zeroed again between the tips and the bubbles)
+        HIPCHK(fill_async(stream_, fill_region(ctl(&GraphWords::n_cand), ctl_span(&GraphWords::n_cand, &GraphWords::bubbles_removed), 0u),
+                          fill_region(ctl(&GraphWords::n_fork_cand), ctl_span(&GraphWords::n_fork_cand), 0u)));
         unsigned int *const d_ncand = (unsigned int *)ctl(&GraphWords::n_cand), *const d_ntips = (unsigned int *)ctl(&GraphWords::n_tips);
+        unsigned int *const d_nfork = (unsigned int *)ctl(&GraphWords::n_fork_cand);
         if (tips) {
             hipLaunchKernelGGL(k_tip_candidates<W>, dim3(grid_for(n)), B, 0, stream_, g, alive_.p,
                                corr_.cand.p, d_ncand, round == 0 ? (uint2 *)corr_.tip_head.p : (uint2 *)nullptr,
@@ -1697,10 +1726,9 @@ public:
             if (int rc = apply_marks(g, corr_.mark, corr_.removed, s_tip, err)) return rc;
         }
         if (bubbles) {
-            HIPCHK(fill2_async(ctl(&GraphWords::n_cand), ctl_span(&GraphWords::n_cand), 0u, nullptr, 0, 0u, stream_));
             hipLaunchKernelGGL(k_fork_candidates<W>, dim3(grid_for(n)), B, 0, stream_, g, alive_.p,
-                               corr_.cand.p, d_ncand);
-            hipLaunchKernelGGL(k_bubble<W>, G, B, 0, stream_, g, corr_.cand.p, (const unsigned int *)d_ncand, corr_.mark.p);
+                               corr_.cand.p, d_nfork);
+            hipLaunchKernelGGL(k_bubble<W>, G, B, 0, stream_, g, corr_.cand.p, (const unsigned int *)d_nfork, corr_.mark.p);
             HIPCHK(hipGetLastError());
             if (int rc = apply_marks(g, corr_.mark, corr_.removed, s_bub, err)) return rc;
         }
@@ -1801,7 +1829,10 @@ public:
             if (int rc = cs.d_heads.alloc(seg_cap, err)) return rc;
             if (int rc = cs.ringmin.alloc(seg_cap, err)) return rc;
             const unsigned long long *skip = corr_pending_ ? ctl(&GraphWords::r0_tips_removed) : (const unsigned long long *)nullptr;   // (and r0_bubbles_removed behind it)
-            HIPCHK(fill2_async(ctl(&GraphWords::n_splitters), ctl_span(&GraphWords::n_splitters, &GraphWords::n_walked), 0u, cs.slot_of.p, (size_t)seg_cap * 4, 0xFFFFFFFFu, stream_));
+            // (one launch: the counters, the emission plan's state — k_plan_emit — and the chains' slots)
+            HIPCHK(fill_async(stream_, fill_region(ctl(&GraphWords::n_splitters), ctl_span(&GraphWords::n_splitters, &GraphWords::n_walked), 0u),
+                              fill_region(ctl(&GraphWords::plan_state), ctl_span(&GraphWords::plan_state, &GraphWords::plan_emitted), 0u),
+                              fill_region(cs.slot_of.p, (size_t)seg_cap * 4, 0xFFFFFFFFu)));
             unsigned int *d_nspl = (unsigned int *)ctl(&GraphWords::n_splitters), *d_nheads = (unsigned int *)ctl(&GraphWords::n_chains);
             uint32_t *d_flags = ctl(&GraphWords::collapse_flag);
             unsigned long long *d_plan = ctl(&GraphWords::plan_state);                 // (plan_bytes and plan_emitted behind it)
@@ -1845,18 +1876,22 @@ public:
                                    cs.winfo.p, cs.ol.p, d_ncyc, d_flags);
             }
             if (plan) {
-                HIPCHK(fill2_async(d_plan, ctl_span(&GraphWords::plan_state, &GraphWords::plan_emitted), 0u, nullptr, 0, 0u, stream_));
                 hipLaunchKernelGGL(k_plan_emit, dim3(1), dim3(1024), 0, stream_, cs.d_heads.p, (const unsigned int *)d_nheads, (uint32_t)k_, plan->max_heads,
                                    plan->out_cap, (const uint32_t *)d_flags, plan->d_off, d_plan);
                 hipLaunchKernelGGL(k_emit<W>, dim3(grid_for(n)), dim3(256), 0, stream_, g, alive_.p, cs.ol.p, plan->d_off, plan->d_out, (const unsigned long long *)d_plan);
-                hipLaunchKernelGGL(k_text_to_host_planned, dim3(64), dim3(256), 0, stream_, plan->d_out, plan->h_out, (const unsigned long long *)d_plan);
             }
             HIPCHK(hipGetLastError());
-            // (the first chain records travel with the counters: an isolate has a handful of chains, and a second
-            // round trip just for them is 30-40 us of idle GPU)
+            // (the first chain records travel with the counters, in ONE transfer: an isolate has a handful of chains, and a second
+            // round trip just for them is 30-40 us of idle GPU.  As many records as n_chains says, HEADS_SPEC at most.)
+            static_assert(sizeof(HeadRec) % 8 == 0, "chain records travel as 64-bit words");
             heads.assign(HEADS_SPEC, HeadRec());
-            HIPCHK(hipMemcpyAsync(mb_graph(), ctl_.p, sizeof(GraphWords), hipMemcpyDeviceToHost, stream_));
-            HIPCHK(hipMemcpyAsync(mbox64() + MB_MISC, cs.d_heads.p, (size_t)std::min<uint32_t>(HEADS_SPEC, seg_cap) * sizeof(HeadRec), hipMemcpyDeviceToHost, stream_));
+            hipLaunchKernelGGL(k_mail_home, dim3(1), dim3(256), 0, stream_, (const unsigned long long *)ctl_.p, (uint32_t)CTL_WORDS, (const unsigned long long *)cs.d_heads.p,
+                               (const unsigned int *)d_nheads, std::min<uint32_t>(HEADS_SPEC, seg_cap), (uint32_t)(sizeof(HeadRec) / 8), mbox64() + MB_CTL, mbox64() + MB_MISC);
+            HIPCHK(hipGetLastError());
+            // the planned text through the copy engine, its size unknown here: the bound it was given room for (an isolate's
+            // text is 0.3 % shorter).  Behind the mailbox's kernel: nothing that the host still has to launch follows a copy.
+            // Where the plan declined, or the pass is repeated, these bytes mean nothing and nobody reads them.
+            if (plan) HIPCHK(hipMemcpyAsync(plan->h_out, plan->d_out, plan->out_cap, hipMemcpyDeviceToHost, stream_));
             WAIT_STREAM();
             const GraphWords &hc0 = *mb_graph();
             if (int rc = check_graph_flags(err)) return rc;
@@ -1874,7 +1909,8 @@ public:
                 seg_cap64 = cap_all;
                 continue;
             }
-            memcpy(heads.data(), mbox64() + MB_MISC, (size_t)std::min<uint32_t>(HEADS_SPEC, seg_cap) * sizeof(HeadRec));
+            // (what k_mail_home sent: beyond it the mailbox holds an earlier assembly's records)
+            memcpy(heads.data(), mbox64() + MB_MISC, (size_t)std::min<uint32_t>((uint32_t)std::min<unsigned long long>(hc.n_chains & 0xFFFFFFFFull, HEADS_SPEC), seg_cap) * sizeof(HeadRec));
             if (plan && hc.plan_state == 1ull) { plan->planned = true; plan->out_bytes = hc.plan_bytes; plan->n_emit = (uint32_t)hc.plan_emitted; }
             break;
         }
@@ -1909,10 +1945,12 @@ public:
         constexpr uint32_t PLAN_HEADS = 512;
         EmitPlan plan{}; EmitPlan *use_plan = nullptr;
         DevBuf<EmitRec> d_plan_off; DevBuf<char> d_plan_out;
-        // (off by default — SHK_DEVICE_PLAN=1: measured on the bench isolate, three alternating runs of 30 steps each: 3.30 / 3.22 /
-        // 3.20 ms per step with the plan on the host against 3.37 / 3.22 / 3.27 with it on the device — the round trip it saves is
-        // paid back by the text crossing PCIe through a kernel instead of the copy engine.  DESIGN.md section 4)
-        if (env_u64("SHK_DEVICE_PLAN", 0) != 0 && dw_min > PLAN_HEADS) {
+        // (on by default, SHK_DEVICE_PLAN=0 plans on the host: the host's round trip between the ranking and k_emit — two small
+        // copies, the wait, the upload of the plan, ~60 us of an idle GPU on the bench isolate — goes, and the text takes the copy
+        // engine as it does with the host's plan.  Paired with a copy KERNEL for the text, the device plan had measured no gain.
+        // An assembly of 257 ... dw_min contigs pays one wasted copy of ~n bytes.  Not with SHK_ARRIVAL_MIN set: that path sends
+        // the text itself, slab by slab.  Figures: profiles/step_chain/)
+        if (env_u64("SHK_DEVICE_PLAN", 1) != 0 && dw_min > PLAN_HEADS && getenv("SHK_ARRIVAL_MIN") == nullptr) {
             const unsigned long long cap = (unsigned long long)n + (unsigned long long)PLAN_HEADS * (unsigned long long)(k_ - 1) + 64ull;
             if (int rc = d_plan_off.alloc(PLAN_HEADS, err)) return rc;
             if (int rc = d_plan_out.alloc(cap + 16, err)) return rc;
@@ -2682,10 +2720,20 @@ private:
     PinnedBuf mbox_;                                 // pinned host words the small device-to-host copies land in (truly asynchronous)
     unsigned long long *mbox64() { return (unsigned long long *)mbox_.p; }
     static constexpr size_t MBOX_BYTES = 32768;
-    static constexpr int MB_P1 = 0 /* a CountWords image: pass 1's flags */, MB_CTL = CTL_WORDS /* a GraphWords image */, MB_MISC = 2 * CTL_WORDS;
-    CountWords *mb_p1() { return (CountWords *)(mbox64() + MB_P1); }  GraphWords *mb_graph() { return (GraphWords *)(mbox64() + MB_CTL); }
+    static constexpr int MB_COUNT = 0 /* a CountMail image */, MB_CTL = COUNT_MAIL_WORDS /* a GraphWords image */, MB_MISC = MB_CTL + CTL_WORDS;
+    CountMail *mb_count() { return (CountMail *)(mbox64() + MB_COUNT); }  GraphWords *mb_graph() { return (GraphWords *)(mbox64() + MB_CTL); }
+    CountMail *d_count() { return reinterpret_cast<CountMail *>(ctl_.p); }
+    // pass 1's flags alone, where the host looks at them before pass 2 is launched
+    hipError_t fetch_p1() { return hipMemcpyAsync(&mb_count()->p1, &d_count()->p1, sizeof(P1Words), hipMemcpyDeviceToHost, stream_); }
+    // one transfer: the words, the histogram and pass 1's flags -> mb_count() (k_mail_home)
+    hipError_t mail_count() {
+        hipLaunchKernelGGL(k_mail_home, dim3(1), dim3(256), 0, stream_, (const unsigned long long *)ctl_.p, (uint32_t)COUNT_MAIL_WORDS, (const unsigned long long *)nullptr,
+                           (const unsigned int *)nullptr, 0u, 0u, mbox64() + MB_COUNT, (unsigned long long *)nullptr);
+        return hipGetLastError();
+    }
     struct P1Pending { bool on; const uint32_t *d_bases, *d_seg_off; uint64_t n_seg, n_bases, cap; };
     P1Pending p1_{false, nullptr, nullptr, 0, 0, 0};
+    bool p2_prefilled_ = false;                      // the fill in front of that pass 1 zeroed pass 2's words and histogram, and nothing has written them since
     uint64_t n_host_waits_ = 0;                      // host waits on the stream so far (WAIT_STREAM, host-side collectives)
     bool stage_timers_ = env_u64("SHK_STAGE_TIMERS", 0) != 0;    // per-stage HIP-event timers (the two counting passes are always timed: the roofline needs them)
     bool keep_stages_ = env_u64("SHK_KEEP_STAGES", 0) != 0;      // keep what only the stage inspection reads (the initial adjacency bytes)

@@ -98,7 +98,9 @@ int count_one_batch(shk_handle *h, const uint32_t *d_bases, const uint32_t *d_se
     const double t0 = now_ms();
     h->batches_started++;
     int rc = h->pipe->count_batch(d_bases, d_seg_off, n_seg, n_bases, err);
-    h->pipe->times().add("preprocess_device_total_host_clock", now_ms() - t0);
+    // (not through times(): that waits for the event behind pass 1 when pass 1 was not waited for, and pass 2, which
+    // finish_counting is about to launch behind it, would reach the GPU late)
+    h->pipe->add_time("preprocess_device_total_host_clock", now_ms() - t0);
     return rc ? fail_rc(h, Rc::Device, rc, err) : SHK_OK;
 }
 // the packed pieces of ONE batch -> pass 1 (the pieces with no segment are left out by the caller)
@@ -107,7 +109,7 @@ int count_pieces(shk_handle *h, const std::vector<DevPiece> &pcs) {
     const double t0 = now_ms();
     h->batches_started++;
     const int rc = h->pipe->count_batch_pieces(pcs.data(), pcs.size(), err);
-    h->pipe->times().add("preprocess_device_total_host_clock", now_ms() - t0);
+    h->pipe->add_time("preprocess_device_total_host_clock", now_ms() - t0);
     return rc ? fail_rc(h, Rc::Device, rc, err) : SHK_OK;
 }
 

@@ -86,7 +86,7 @@ for case in range(n_cases):
     if rng.random() < 0.3: env["SHK_COUNT_MERGE"] = str(int(rng.choice([1, 4])))   # partitions per table of k_count_weighted
     if rng.random() < 0.5: env["SHK_TILE_ROWS"] = str(int(rng.choice([1, 3, 17, 64, 300, 1000, 4096])))   # collapse: many small LDS tiles
     if rng.random() < 0.25: env["SHK_SEG_CAP"] = str(int(rng.choice([1, 8, 64])))   # round 4: the splitter list outgrows its room -> the ranking is called off and repeated
-    if rng.random() < 0.3: env["SHK_DEVICE_PLAN"] = "1"            # round 4: emission planned on the device for <= 512 chain records (default: on the host)
+    if rng.random() < 0.3: env["SHK_DEVICE_PLAN"] = "0"            # emission planned on the host (default: on the device for <= 512 chain records)
     if rng.random() < 0.25: env["SHK_ARRIVAL_MIN"] = "1"           # round 4: the writer starts on contig text that is still arriving (slab-copy kernel + host flags)
     if rng.random() < 0.4: env["SHK_PART_G"] = str(int(rng.choice([1, 2, 5])))   # round 4: few workgroups -> every wave of pass 1 walks many tiles (prefetch of the next round)
     if rng.random() < 0.3: env["SHK_PART_WIN"] = str(int(rng.choice([16, 18, 20])))   # round 4: minimiser window of pass 1 for k >= 31 (one block of 16, two of 9, two of 10)
