@@ -301,11 +301,28 @@ char *shk_host_unitig_assemble(uint32_t k, uint64_t n_recs, const uint64_t *firs
                                const uint64_t *kc, const uint8_t *circ, const uint64_t *min_key, const uint8_t *min_o,
                                const uint64_t *min_pos, int tips, int bubbles);
 /* The same on the current HIP device (csrc/unitig_graph_gpu.h: the index of chain starts, the links, the tip and bubble
- * rounds and the simple successors as kernels; the chains are walked by the host code from what comes back).  Same
+ * rounds, the simple successors and the walk of the chains as kernels; only ring records go through the host's ring
+ * loops.  SHK_UNITIG_CHAINS_DEVICE=0 (environment): the chains are walked by the host code from what comes back).  Same
  * parameters, the same text byte for byte, "error: ..." included; needs a GPU. */
 char *shk_device_unitig_assemble(uint32_t k, uint64_t n_recs, const uint64_t *first, const uint64_t *last, const uint64_t *len,
                                  const uint64_t *kc, const uint8_t *circ, const uint64_t *min_key, const uint8_t *min_o,
                                  const uint64_t *min_pos, int tips, int bubbles);
+/* The S10 walk alone, from arrays that are already settled: alive[r], mirror[r] (the record of r's mirror strand) and
+ * succ[r] (the simple successor of an alive linear record, 0xFFFFFFFF: none); first: [n_recs][W] words.  The host walk
+ * (unitig_chains) and its device twin (unitig_chains_device; needs a GPU) give the same malloc'd text (shk_host_free),
+ * one line per contig in result order —
+ *     linear:                  "0 <nodes> <kc> <text offset> : <record>@<node offset> ..."
+ *     ring, before resolution: "1 <nodes> <kc> - : <record> ..."
+ * — and a last line "need_min : <record> ...".  Text offsets are the running sum of nodes + k - 1 over the linear contigs
+ * in front, node offsets the nodes of the contig's records in front.  Both check the arrays on the host first, with the
+ * same code: "error: unitig chains: <what>" unless succ is none or an alive linear record, no two records share a
+ * successor, mirror pairs up among the alive linear records, mirror[succ[r]] has mirror[r] as its successor, and dead and
+ * circ records carry no successor.  The device entry reports "error: out of device memory" instead of falling back.
+ * NULL on bad parameters. */
+char *shk_host_unitig_chains(uint32_t k, uint64_t n_recs, const uint64_t *first, const uint64_t *len, const uint64_t *kc, const uint8_t *circ,
+                             const uint8_t *alive, const uint32_t *mirror, const uint32_t *succ);
+char *shk_device_unitig_chains(uint32_t k, uint64_t n_recs, const uint64_t *first, const uint64_t *len, const uint64_t *kc, const uint8_t *circ,
+                               const uint8_t *alive, const uint32_t *mirror, const uint32_t *succ);
 
 /* Device buffers of freed handles are cached process-wide for the next handle (a handle lives
  * for one preprocess+assemble); this returns the cache to the driver.  SHK_NO_POOL=1 disables it. */

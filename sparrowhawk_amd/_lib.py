@@ -82,6 +82,8 @@ SIGNATURES = {
     "shk_device_gunzip": (_int, [_cp, _sz, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(C.c_char_p), C.POINTER(C.c_double)]),
     "shk_host_unitig_assemble": (_vp, [_u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int]),
     "shk_device_unitig_assemble": (_vp, [_u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int]),
+    "shk_host_unitig_chains": (_vp, [_u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "shk_device_unitig_chains": (_vp, [_u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "shk_release_cached_memory": (None, []),
     "shk_measure_stream_read": (_int, [_sz, _int, C.POINTER(C.c_double)]),
     "shk_version": (_cp, []),

@@ -959,6 +959,11 @@ static char *unitig_assemble_text(bool on_device, uint32_t k, uint64_t n_recs, c
         }
         if (unitig_resolve_rings((int)k, recs, mk, res, err)) return fail_text(err);
         std::string text = "removed " + std::to_string(res.tips_removed) + " " + std::to_string(res.bubbles_removed) + "\n";
+        for (const UnitigFlatContig &c : res.lin) {                 // (the walk ran on the device: the linear contigs, then the rings)
+            text += "0 0 " + std::to_string(c.len_nodes) + " " + std::to_string(c.kc) + " :";
+            for (uint32_t i = 0; i < c.n_recs; i++) text += " " + std::to_string(res.recs_flat[c.rec_off + i]);
+            text += "\n";
+        }
         for (const UnitigContig &c : res.contigs) {
             text += std::to_string(c.ring ? 1 : 0) + " " + std::to_string(c.rot) + " " + std::to_string(c.len_nodes) + " " + std::to_string(c.kc) + " :";
             for (uint32_t r : c.recs) text += " " + std::to_string(r);
@@ -979,6 +984,67 @@ char *shk_device_unitig_assemble(uint32_t k, uint64_t n_recs, const uint64_t *fi
                                  const uint64_t *kc, const uint8_t *circ, const uint64_t *min_key, const uint8_t *min_o,
                                  const uint64_t *min_pos, int tips, int bubbles) {
     return unitig_assemble_text(true, k, n_recs, first, last, len, kc, circ, min_key, min_o, min_pos, tips, bubbles);
+}
+// the text of both entry points of the S10 walk: one line per contig — "0 nodes kc text_offset : record@node_offset ..." for a
+// linear one, "1 nodes kc - : record ..." for a ring —, then "need_min : record ...", or "error: ..."
+static char *unitig_chains_text(bool on_device, uint32_t k, uint64_t n_recs, const uint64_t *first, const uint64_t *len, const uint64_t *kc,
+                                const uint8_t *circ, const uint8_t *alive, const uint32_t *mirror, const uint32_t *succ) {
+    try {
+        if ((k & 1u) == 0 || k < SHK_K_MIN || k > SHK_K_MAX || (n_recs && (!first || !len || !kc || !circ || !alive || !mirror || !succ))) return nullptr;
+        const uint32_t W = (2 * k + 63) / 64;
+        std::vector<UnitigRec> recs((size_t)n_recs);
+        for (uint64_t r = 0; r < n_recs; r++) {
+            for (uint32_t j = 0; j < W; j++) recs[r].first[j] = first[r * W + j];
+            recs[r].len = len[r]; recs[r].kc = kc[r]; recs[r].circ = circ[r];
+        }
+        std::vector<uint8_t> v_alive(alive, alive + n_recs);
+        std::vector<uint32_t> v_mirror(mirror, mirror + n_recs), v_succ(succ, succ + n_recs);
+        UnitigGraphResult res; std::string err;
+        auto fail_text = [](const std::string &e) -> char * { const std::string t = "error: " + e; char *o = (char *)malloc(t.size() + 1); if (o) memcpy(o, t.c_str(), t.size() + 1); return o; };
+        // (the same check in front of both: the kernels never see links that do not fit together)
+        if (unitig_chains_check(recs, v_alive, v_mirror, v_succ, err)) return fail_text(err);
+        std::string text;
+        if (on_device) {
+            const int rc = unitig_chains_device((int)k, recs, v_alive, v_mirror, v_succ, current_device(), nullptr, res, err);
+            if (rc == 1) return fail_text("out of device memory");
+            if (rc) return fail_text(err);
+            if (!res.flat || res.place.size() != (size_t)n_recs) return fail_text("unitig chains: the device handed over no flat form");
+            for (const UnitigFlatContig &c : res.lin) {
+                text += "0 " + std::to_string(c.len_nodes) + " " + std::to_string(c.kc) + " " + std::to_string(c.text_off) + " :";
+                for (uint32_t i = 0; i < c.n_recs; i++) {
+                    const uint32_t r = res.recs_flat[c.rec_off + i];
+                    text += " " + std::to_string(r) + "@" + std::to_string(res.place[r].node_off);
+                }
+                text += "\n";
+            }
+        } else if (unitig_chains((int)k, recs, v_alive, std::move(v_mirror), v_succ, res, err)) return fail_text(err);
+        uint64_t text_off = 0;
+        for (const UnitigContig &c : res.contigs) {
+            if (c.ring) { text += "1 " + std::to_string(c.len_nodes) + " " + std::to_string(c.kc) + " - :"; for (uint32_t r : c.recs) text += " " + std::to_string(r); }
+            else {
+                text += "0 " + std::to_string(c.len_nodes) + " " + std::to_string(c.kc) + " " + std::to_string(text_off) + " :";
+                uint64_t node_off = 0;
+                for (uint32_t r : c.recs) { text += " " + std::to_string(r) + "@" + std::to_string(node_off); node_off += recs[r].len; }
+                text_off += c.len_nodes + (uint64_t)(k - 1);
+            }
+            text += "\n";
+        }
+        text += "need_min :";
+        for (uint32_t r : res.need_min) text += " " + std::to_string(r);
+        text += "\n";
+        char *out = (char *)malloc(text.size() + 1);
+        if (!out) return nullptr;
+        memcpy(out, text.c_str(), text.size() + 1);
+        return out;
+    } catch (...) { return nullptr; }
+}
+char *shk_host_unitig_chains(uint32_t k, uint64_t n_recs, const uint64_t *first, const uint64_t *len, const uint64_t *kc, const uint8_t *circ,
+                             const uint8_t *alive, const uint32_t *mirror, const uint32_t *succ) {
+    return unitig_chains_text(false, k, n_recs, first, len, kc, circ, alive, mirror, succ);
+}
+char *shk_device_unitig_chains(uint32_t k, uint64_t n_recs, const uint64_t *first, const uint64_t *len, const uint64_t *kc, const uint8_t *circ,
+                               const uint8_t *alive, const uint32_t *mirror, const uint32_t *succ) {
+    return unitig_chains_text(true, k, n_recs, first, len, kc, circ, alive, mirror, succ);
 }
 
 }  // extern "C"

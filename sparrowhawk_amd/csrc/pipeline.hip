@@ -2634,13 +2634,27 @@ public:
         }
         lap("rings");
         // layout: contig text offsets, and for every unitig record where its nodes go
+        // (the walk on the device hands over the linear contigs flat, with every record's placement: the linear contigs
+        // come first, the rings — res.contigs — behind them, their text from the linear contigs' total on)
+        const size_t n_lin = res.flat ? res.lin.size() : 0, n_contigs = n_lin + res.contigs.size();
+        if (res.flat && (res.place.size() != (size_t)n_u || res.recs_flat.size() > (size_t)n_u)) { sh_agreed_ = true; err = "sharded assembly: the flat form of the unitig graph does not fit the records"; return -6; }
         std::vector<ULayout> lay(n_u + 1);
-        for (auto &L : lay) { L.off = ~0ull; L.node_off = 0; L.ring_len = 0; L.rot = 0; }
         uint64_t text_bytes = 0;
-        std::vector<uint64_t> c_off(res.contigs.size());
+        std::vector<uint64_t> c_off(n_contigs);
+        if (res.flat) {
+            host_par_ranges(n_u, [&](size_t a, size_t b) {
+                for (size_t r = a; r < b; r++) { ULayout &L = lay[r]; L.off = res.place[r].off; L.node_off = res.place[r].node_off; L.ring_len = 0; L.rot = 0; }
+            });
+            { ULayout &L = lay[n_u]; L.off = ~0ull; L.node_off = 0; L.ring_len = 0; L.rot = 0; }
+            host_par_ranges(n_lin, [&](size_t a, size_t b) { for (size_t i = a; i < b; i++) c_off[i] = res.lin[i].text_off; });
+            text_bytes = res.lin_text;
+        } else
+            for (auto &L : lay) { L.off = ~0ull; L.node_off = 0; L.ring_len = 0; L.rot = 0; }
+        if (res.flat) times_.add("shard_graph_unitig_chains_device_x1", 1.0);
+        times_.add("shard_graph_unitig_contigs_x1", (double)n_contigs);
         for (size_t i = 0; i < res.contigs.size(); i++) {
             const UnitigContig &ct = res.contigs[i];
-            c_off[i] = text_bytes;
+            c_off[n_lin + i] = text_bytes;
             uint64_t node_off = 0;
             for (uint32_t r : ct.recs) {
                 lay[r].off = text_bytes; lay[r].node_off = node_off; lay[r].ring_len = ct.ring ? ct.len_nodes : 0; lay[r].rot = ct.ring ? ct.rot : 0;
@@ -2680,11 +2694,16 @@ public:
         stage("6 emission kernels");
         WAIT_STREAM();
         if (te.on()) times_.add("shard_graph_emit", te.stop());
-        out.reserve(res.contigs.size());
+        out.resize(n_contigs);
+        host_par_ranges(n_lin, [&](size_t a, size_t b) {
+            for (size_t i = a; i < b; i++) {
+                RawContig &rcg = out[i]; rcg.kc = res.lin[i].kc;
+                rcg.ext = hout_.p + c_off[i]; rcg.ext_n = res.lin[i].len_nodes + (uint64_t)(k_ - 1);
+            }
+        });
         for (size_t i = 0; i < res.contigs.size(); i++) {
-            RawContig rcg; rcg.kc = res.contigs[i].kc;
-            rcg.ext = hout_.p + c_off[i]; rcg.ext_n = res.contigs[i].len_nodes + (uint64_t)(k_ - 1);
-            out.push_back(std::move(rcg));
+            RawContig &rcg = out[n_lin + i]; rcg.kc = res.contigs[i].kc;
+            rcg.ext = hout_.p + c_off[n_lin + i]; rcg.ext_n = res.contigs[i].len_nodes + (uint64_t)(k_ - 1);
         }
         times_.add("shard_assemble_host_clock", now_ms_() - t_all0);
         return 0;

@@ -479,6 +479,78 @@ int unitig_chains(int k, const std::vector<UnitigRec> &recs, const std::vector<u
     out.mirror = std::move(mirror);
     return 0;
 }
+int unitig_chains_check(const std::vector<UnitigRec> &recs, const std::vector<uint8_t> &alive, const std::vector<uint32_t> &mirror,
+                        const std::vector<uint32_t> &succ, std::string &err) {
+    const size_t n = recs.size();
+    auto fail = [&](const char *what) { err = std::string("unitig chains: ") + what; return -1; };
+    if (alive.size() != n || mirror.size() != n || succ.size() != n) return fail("arrays of another size than the records");
+    if (n >= (size_t)UG_NIL) return fail("more records than 32-bit record numbers");
+    auto linear = [&](uint32_t r) { return r < n && alive[r] && !recs[r].circ; };
+    for (size_t r = 0; r < n; r++) if (!linear((uint32_t)r) && succ[r] != UG_NIL) return fail("a dead or circular record with a successor");
+    for (size_t r = 0; r < n; r++) if (succ[r] != UG_NIL && !linear(succ[r])) return fail("a successor that is no alive linear record");
+    {
+        std::vector<uint8_t> taken(n, 0);
+        for (size_t r = 0; r < n; r++) {
+            if (succ[r] == UG_NIL) continue;
+            if (taken[succ[r]]) return fail("two records share a successor");
+            taken[succ[r]] = 1;
+        }
+    }
+    for (size_t r = 0; r < n; r++)
+        if (linear((uint32_t)r) && (!linear(mirror[r]) || mirror[mirror[r]] != (uint32_t)r)) return fail("mirror strands do not pair up");
+    for (size_t r = 0; r < n; r++)
+        if (succ[r] != UG_NIL && succ[mirror[succ[r]]] != mirror[r]) return fail("a link without its mirror link");
+    return 0;
+}
+
+int unitig_ring_chains(const std::vector<UnitigRec> &recs, std::vector<UnitigRingRec> &&rings, UnitigGraphResult &out, std::string &err) {
+    std::sort(rings.begin(), rings.end(), [](const UnitigRingRec &a, const UnitigRingRec &b) { return a.r < b.r; });
+    const size_t m = rings.size();
+    for (size_t i = 0; i < m; i++)
+        if (rings[i].r >= recs.size() || (i && rings[i].r == rings[i - 1].r)) { err = "unitig graph: the list of ring records is inconsistent"; return -1; }
+    // (a handful of records: the position of a record in the sorted list stands in for the host walk's arrays)
+    auto at = [&](uint32_t r) {
+        const auto it = std::lower_bound(rings.begin(), rings.end(), r, [](const UnitigRingRec &a, uint32_t x) { return a.r < x; });
+        return it != rings.end() && it->r == r ? (size_t)(it - rings.begin()) : m;
+    };
+    std::vector<uint8_t> seen(m, 0);
+    auto finish = [&](UnitigContig &c) {
+        for (uint32_t r : c.recs) { c.len_nodes += recs[r].len; c.kc += recs[r].kc; }
+        out.contigs.push_back(std::move(c));
+    };
+    bool any_linear = false;
+    for (size_t i = 0; i < m; i++) any_linear = any_linear || !recs[rings[i].r].circ;
+    if (any_linear) {
+        out.mirror.assign(recs.size(), UG_NIL);
+        for (size_t i = 0; i < m; i++) if (!recs[rings[i].r].circ) out.mirror[rings[i].r] = rings[i].mirror;
+    }
+    for (size_t i = 0; i < m; i++) {                             // a ring made of several records
+        if (recs[rings[i].r].circ || seen[i]) continue;
+        UnitigContig c; c.ring = true;
+        std::vector<size_t> pos;
+        for (size_t cur = i, steps = 0; steps < m; steps++) {    // (a walk cannot be longer than the list)
+            c.recs.push_back(rings[cur].r); pos.push_back(cur); seen[cur] = 1;
+            const uint32_t nx = rings[cur].succ;
+            if (nx == rings[i].r || nx == UG_NIL) break;
+            cur = at(nx);
+            if (cur == m) { err = "unitig graph: a ring leads to a record on a linear chain"; return -1; }
+        }
+        for (size_t p : pos) {
+            const size_t mp = at(rings[p].mirror);
+            if (mp < m) seen[mp] = 1;
+            out.need_min.push_back(rings[p].r); out.need_min.push_back(rings[p].mirror);
+        }
+        finish(c);
+    }
+    for (size_t i = 0; i < m; i++) {                             // rings from the start
+        if (!recs[rings[i].r].circ) continue;
+        UnitigContig c; c.ring = true; c.recs.push_back(rings[i].r);
+        out.need_min.push_back(rings[i].r);
+        finish(c);
+    }
+    return 0;
+}
+
 int unitig_resolve_rings(int k, const std::vector<UnitigRec> &recs, const std::vector<UnitigMinKey> &min_of, UnitigGraphResult &out, std::string &err) {
     switch ((2 * k + 63) / 64) {
         case 1: return resolve_t<1>(k, recs, min_of, out, err);

@@ -73,9 +73,31 @@ struct UnitigContig {
     uint64_t len_nodes = 0, kc = 0;
 };
 
+// The flat form of the linear contigs, as the device walk (unitig_graph_gpu.h) hands them over: no vector per contig.
+// Contig c spells the records recs_flat[rec_off .. rec_off + n_recs); contigs ascend by their head's record number,
+// which is the order unitig_chains appends them in.
+struct UnitigFlatContig {
+    uint64_t len_nodes, kc;
+    uint64_t text_off;           // sum of len_nodes + k - 1 over the linear contigs in front
+    uint64_t rec_off;            // into recs_flat
+    uint32_t head, n_recs;
+};
+// where a record's nodes go: off — the text offset of its contig, ~0 for a record of no linear contig that is handed on
+// (dead, ring, the dropped mirror strand); node_off — the nodes of the contig's records in front of it
+struct UnitigPlace { uint64_t off, node_off; };
+struct UnitigRingRec { uint32_t r, succ, mirror; };   // an alive record on no linear chain, with its links
+
 struct UnitigGraphResult {
-    std::vector<UnitigContig> contigs;      // every contig once, on one strand (the writer picks min(seq, revcomp) later)
-    std::vector<uint32_t> mirror;           // per record: its mirror strand's record, UG_NIL for rings / none
+    // every contig once, on one strand (the writer picks min(seq, revcomp) later); with `flat`: the rings only, which
+    // follow the linear contigs
+    std::vector<UnitigContig> contigs;
+    bool flat = false;                      // the walk ran on the device: the linear contigs are in the three vectors below
+    std::vector<UnitigFlatContig> lin;
+    std::vector<uint32_t> recs_flat;
+    std::vector<UnitigPlace> place;         // per record
+    uint64_t lin_text = 0;                  // sum of len_nodes + k - 1 over lin: where the rings' text starts
+    std::vector<uint32_t> mirror;           // per record: its mirror strand's record, UG_NIL for rings / none (with `flat`: known at
+                                            // the records of rings of several records only; empty when there is no such ring)
     // rings are only settled once the smallest k-mer of their records is known: resolve_rings()
     std::vector<uint32_t> need_min;         // records whose UnitigMinKey resolve_rings() wants
     uint64_t tips_removed = 0, bubbles_removed = 0;   // nodes (as the k-mer-level passes count them)
@@ -91,7 +113,16 @@ int unitig_assemble(int k, const std::vector<UnitigRec> &recs, bool tips, bool b
 // rings from the start.  Appends to out.contigs / out.need_min and sets out.mirror.
 int unitig_chains(int k, const std::vector<UnitigRec> &recs, const std::vector<uint8_t> &alive, std::vector<uint32_t> &&mirror,
                   const std::vector<uint32_t> &succ, UnitigGraphResult &out, std::string &err);
-// min_of[r] must be valid for every r in out.need_min.  Fixes strand and rotation of the ring contigs, drops the
+// What unitig_chains and its device twin take for granted, checked: -1 with err = "unitig chains: <what>" unless succ is
+// UG_NIL or an alive linear record, no two records share a successor, mirror pairs up among the alive linear records,
+// mirror[succ[r]] has mirror[r] as its successor, and dead and circ records carry succ == UG_NIL.
+int unitig_chains_check(const std::vector<UnitigRec> &recs, const std::vector<uint8_t> &alive, const std::vector<uint32_t> &mirror,
+                        const std::vector<uint32_t> &succ, std::string &err);
+// The two ring loops of unitig_chains over the ring records alone (in any order; sorted here): the alive linear records
+// that reach no head, and the alive circ records.  Appends to out.contigs / out.need_min; sets out.mirror (n_recs
+// entries, UG_NIL but at the ring records) when there is a ring of linear records.
+int unitig_ring_chains(const std::vector<UnitigRec> &recs, std::vector<UnitigRingRec> &&rings, UnitigGraphResult &out, std::string &err);
+// min_of[r] must be valid for every r in out.need_min.  Touches out.contigs only: the flat form holds no ring.  Fixes strand and rotation of the ring contigs, drops the
 // mirror-strand duplicates of rings that were rings from the start.
 int unitig_resolve_rings(int k, const std::vector<UnitigRec> &recs, const std::vector<UnitigMinKey> &min_of, UnitigGraphResult &out,
                          std::string &err);

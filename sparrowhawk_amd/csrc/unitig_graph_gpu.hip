@@ -6,10 +6,19 @@
 //
 // Every loop is bounded whatever the records say: probes by the capacity of the index, walks by 2k steps (a step adds at
 // least one node to a length that may not exceed 2k), lists of tips by the number of tips, rounds by 32.
+//
+// S10 follows on the device too (the twin of chains_t): predecessors, every record's head, index and node offset by
+// pointer jumping — one plain launch per round, each round from one set of arrays into the other, at most
+// ceil(log2 n) + 1 of them —, the strand choice at the tails, three exclusive sums over the heads in ascending record
+// number (contig index, record offset, text offset), and a placement per record.  What comes home is the flat form of
+// UnitigGraphResult; only the ring records (a handful) go through the host's ring loops.  SHK_UNITIG_CHAINS_DEVICE=0
+// keeps the earlier way: alive / mirror / succ go home and unitig_chains walks.
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <chrono>
 #include <string>
 #include <thread>
@@ -395,9 +404,169 @@ __global__ __launch_bounds__(256) void k_ug_succ(UGraph<W> g, uint32_t *__restri
 }
 
 // ------------------------------------------------------------------------------------------
+// S10, the walk (chains_t in unitig_graph.cpp): heads, ranks by pointer jumping, the strand choice, the placement
+// ------------------------------------------------------------------------------------------
+// What the walk reads: the records' first k-mers (word w of record r: F[w * n + r]), lengths and counts, and the settled
+// links.  succ is injective on the alive linear records, so they form paths (a head ... a tail) and cycles.
+struct UChainIn {
+    const uint64_t *F, *len, *kc;
+    const uint8_t *circ, *alive;
+    const uint32_t *mirror, *succ;
+    uint32_t n;
+    int k;
+    __device__ __forceinline__ bool linear(uint32_t r) const { return alive[r] && !circ[r]; }
+};
+// The rank of a record while it is being found: `up` is an ancestor (the record itself at a head), idx the records from up
+// to it, nodes / kc the sums over [up, r).  One round replaces up by up's up and adds up's sums: the distance doubles, a
+// record is finished once its up is a head (pred == UG_NIL).  A round reads one set of arrays and writes the other.
+struct URank { uint32_t *up, *idx; unsigned long long *nodes, *kc; };
+// ctl of the walk: [0] ring records, [1] contigs, [2] their records, [3] their text, [UC_ROUND0 + j] records unfinished
+// after round j (j = 0: before the first)
+constexpr int UC_NRING = 0, UC_NCONTIG = 1, UC_NREC = 2, UC_NTEXT = 3, UC_ROUND0 = 8, UC_MAX_ROUNDS = 34, UC_WORDS = UC_ROUND0 + UC_MAX_ROUNDS + 2;
+
+// one atomic per wave: count the lanes with p (every lane of the wave calls)
+__device__ __forceinline__ void ug_count(bool p, unsigned long long *count) {
+    const unsigned long long m = __ballot(p);
+    if (m && (threadIdx.x & 63) == 0) atomicAdd(count, (unsigned long long)__popcll(m));
+}
+
+__global__ __launch_bounds__(256) void k_uc_pred(UChainIn g, uint32_t *__restrict__ pred) {
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < g.n; r += gridDim.x * blockDim.x) {
+        const uint32_t s = g.succ[r];
+        if (s < g.n) pred[s] = r;                                 // (a record has one simple predecessor)
+    }
+}
+
+__global__ __launch_bounds__(256) void k_uc_init(UChainIn g, const uint32_t *__restrict__ pred, URank a, unsigned long long *__restrict__ unfinished) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t n_round = ((uint64_t)g.n + stride - 1) / stride * stride;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += stride) {
+        bool open = false;
+        if (i < g.n) {
+            const uint32_t r = (uint32_t)i;
+            uint32_t p = g.linear(r) ? pred[r] : UG_NIL;
+            if (p >= g.n) p = UG_NIL;
+            if (p == UG_NIL) { a.up[r] = r; a.idx[r] = 0; a.nodes[r] = 0; a.kc[r] = 0; }
+            else { a.up[r] = p; a.idx[r] = 1; a.nodes[r] = g.len[p]; a.kc[r] = g.kc[p]; open = pred[p] != UG_NIL; }
+        }
+        ug_count(open, unfinished);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_uc_jump(UChainIn g, const uint32_t *__restrict__ pred, URank a, URank b, unsigned long long *__restrict__ unfinished) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t n_round = ((uint64_t)g.n + stride - 1) / stride * stride;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += stride) {
+        bool open = false;
+        if (i < g.n && g.linear((uint32_t)i)) {
+            const uint32_t r = (uint32_t)i;
+            uint32_t u = a.up[r], x = a.idx[r];
+            unsigned long long nodes = a.nodes[r], kc = a.kc[r];
+            if (u < g.n && pred[u] != UG_NIL) {                   // not finished: up's rank is read from the same snapshot
+                const uint32_t uu = a.up[u];
+                x += a.idx[u]; nodes += a.nodes[u]; kc += a.kc[u];
+                u = uu;
+                open = u < g.n && pred[u] != UG_NIL;
+            }
+            b.up[r] = u; b.idx[r] = x; b.nodes[r] = nodes; b.kc[r] = kc;
+        }
+        ug_count(open, unfinished);
+    }
+}
+
+// at the tails: the chain's totals, filed under its head — if this strand is the one handed on (S10: the chain that is its
+// own mirror strand, else the strand with the smaller first k-mer).  h_cnt / h_text are zero everywhere else.
+template <int W>
+__global__ __launch_bounds__(256) void k_uc_tails(UChainIn g, const uint32_t *__restrict__ pred, URank a, uint32_t *__restrict__ h_cnt,
+                                                  unsigned long long *__restrict__ h_nodes, unsigned long long *__restrict__ h_kc,
+                                                  unsigned long long *__restrict__ h_text) {
+    for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < g.n; t += gridDim.x * blockDim.x) {
+        if (!g.linear(t) || g.succ[t] != UG_NIL) continue;
+        const uint32_t h = a.up[t];
+        if (h >= g.n || pred[h] != UG_NIL) continue;              // (no head within the rounds: left to the ring list)
+        const uint32_t mf = g.mirror[t];
+        bool emit = mf == h;
+        if (!emit && mf < g.n) {
+            Kmer<W> x, y;
+#pragma unroll
+            for (int i = 0; i < W; i++) { x.w[i] = g.F[(size_t)i * g.n + h]; y.w[i] = g.F[(size_t)i * g.n + mf]; }
+            emit = km_less<W>(x, y);
+        }
+        if (!emit) continue;
+        const unsigned long long nodes = a.nodes[t] + g.len[t];
+        h_cnt[h] = a.idx[t] + 1u; h_nodes[h] = nodes; h_kc[h] = a.kc[t] + g.kc[t]; h_text[h] = nodes + (unsigned long long)(g.k - 1);
+    }
+}
+
+struct UcIsHead { __host__ __device__ __forceinline__ uint32_t operator()(const uint32_t &c) const { return c ? 1u : 0u; } };
+
+// (the scans ran over n + 1 entries, the last one zero: entry n of each is the total)
+__global__ void k_uc_totals(uint32_t n, const uint32_t *__restrict__ c_idx, const uint32_t *__restrict__ rec_off,
+                            const unsigned long long *__restrict__ text_off, unsigned long long *__restrict__ ctl) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) { ctl[UC_NCONTIG] = c_idx[n]; ctl[UC_NREC] = rec_off[n]; ctl[UC_NTEXT] = text_off[n]; }
+}
+
+__global__ __launch_bounds__(256) void k_uc_contigs(uint32_t n, const uint32_t *__restrict__ h_cnt, const unsigned long long *__restrict__ h_nodes,
+                                                    const unsigned long long *__restrict__ h_kc, const uint32_t *__restrict__ c_idx,
+                                                    const uint32_t *__restrict__ rec_off, const unsigned long long *__restrict__ text_off,
+                                                    UnitigFlatContig *__restrict__ lin) {
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {
+        const uint32_t cnt = h_cnt[r];
+        if (!cnt) continue;
+        const uint32_t c = c_idx[r];
+        if (c >= n) continue;
+        UnitigFlatContig o;
+        o.len_nodes = h_nodes[r]; o.kc = h_kc[r]; o.text_off = text_off[r]; o.rec_off = rec_off[r]; o.head = r; o.n_recs = cnt;
+        lin[c] = o;
+    }
+}
+
+// every record: its placement, its slot in the flat record list — or its entry in the list of ring records (alive, and on no
+// chain with a head)
+__global__ __launch_bounds__(256) void k_uc_place(UChainIn g, const uint32_t *__restrict__ pred, URank a, const uint32_t *__restrict__ h_cnt,
+                                                  const uint32_t *__restrict__ rec_off, const unsigned long long *__restrict__ text_off,
+                                                  UnitigPlace *__restrict__ place, uint32_t *__restrict__ recs_flat,
+                                                  UnitigRingRec *__restrict__ rings, unsigned long long *__restrict__ n_ring) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t n_round = ((uint64_t)g.n + stride - 1) / stride * stride;
+    const int lane = threadIdx.x & 63;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += stride) {
+        bool ring = false;
+        const uint32_t r = (uint32_t)i;
+        if (i < g.n) {
+            UnitigPlace pl; pl.off = ~0ull; pl.node_off = 0;
+            if (g.alive[r]) {
+                if (g.circ[r]) ring = true;
+                else {
+                    const uint32_t h = a.up[r];
+                    if (h >= g.n || pred[h] != UG_NIL) ring = true;
+                    else {
+                        const uint32_t cnt = h_cnt[h], x = a.idx[r];
+                        if (x < cnt) {                            // (cnt == 0: the mirror strand's chain, dropped)
+                            const uint64_t slot = (uint64_t)rec_off[h] + x;
+                            if (slot < g.n) { recs_flat[slot] = r; pl.off = text_off[h]; pl.node_off = a.nodes[r]; }
+                        }
+                    }
+                }
+            }
+            place[r] = pl;
+        }
+        const unsigned long long m = __ballot(ring);
+        if (!m) continue;
+        unsigned long long base = 0;
+        if (lane == 0) base = atomicAdd(n_ring, (unsigned long long)__popcll(m));
+        base = __shfl(base, 0);
+        if (ring) {
+            const unsigned long long at = base + __popcll(m & ((1ull << lane) - 1ull));
+            if (at < g.n) { UnitigRingRec o; o.r = r; o.succ = g.succ[r]; o.mirror = g.mirror[r]; rings[at] = o; }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-#define UGCHK(call)                                                                                  \
+#define UGCHK(call)                                                                                \
     do {                                                                                             \
         hipError_t e_ = (call);                                                                      \
         if (e_ != hipSuccess) {                                                                      \
@@ -416,6 +585,108 @@ unsigned ug_grid(uint64_t n) {
 // the blocks go back to the pool when the caller returns: nothing may still be running on them then
 struct DrainOnExit { hipStream_t st; ~DrainOnExit() { (void)hipStreamSynchronize(st); } };
 
+// SHK_UNITIG_CHAINS_DEVICE=0: the chains are walked by the host's unitig_chains, from alive / mirror / succ copied home
+bool chains_on_device() { const char *e = getenv("SHK_UNITIG_CHAINS_DEVICE"); return !(e && *e == '0'); }
+// (hipcub counts its items in an int; the scans run over n + 1 of them)
+constexpr size_t UC_MAX_RECS = 0x7FFFFFFEu;
+
+// the three exclusive sums over the heads, in ascending record number: contig index, offset into the flat record list,
+// text offset.  tmp == nullptr: nothing runs, bytes := the largest temporary block one of them asks for
+hipError_t uc_scans(void *tmp, size_t &bytes, const uint32_t *h_cnt, const unsigned long long *h_text, uint32_t *c_idx, uint32_t *rec_off,
+                    unsigned long long *text_off, int items, hipStream_t st) {
+    hipcub::TransformInputIterator<uint32_t, UcIsHead, const uint32_t *> is_head(h_cnt, UcIsHead());
+    size_t b0 = bytes, b1 = bytes, b2 = bytes;
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum(tmp, b0, is_head, c_idx, items, st);
+    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, b1, h_cnt, rec_off, items, st);
+    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, b2, h_text, text_off, items, st);
+    if (!tmp) bytes = std::max(b0, std::max(b1, b2));
+    return e;
+}
+
+// The device blocks of the walk.  Taken by the caller together with its own, before any work.
+struct ChainBlocks {
+    Blk pred, up[2], idx[2], nodes[2], kc[2], h_text, c_idx, rec_off, text_off, lin, place, flat, rings, tmp, ctl;
+    size_t tmp_bytes = 0;
+    bool get(size_t n) {
+        if (uc_scans(nullptr, tmp_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, (int)(n + 1), nullptr) != hipSuccess) return false;
+        for (int i = 0; i < 2; i++)
+            if (!up[i].get(n * 4) || !idx[i].get((n + 1) * 4) || !nodes[i].get(n * 8) || !kc[i].get(n * 8)) return false;
+        return pred.get(n * 4) && h_text.get((n + 1) * 8) && c_idx.get((n + 1) * 4) && rec_off.get((n + 1) * 4) && text_off.get((n + 1) * 8) &&
+               lin.get(n * sizeof(UnitigFlatContig)) && place.get(n * sizeof(UnitigPlace)) && flat.get(n * 4) &&
+               rings.get(n * sizeof(UnitigRingRec)) && tmp.get(tmp_bytes) && ctl.get(UC_WORDS * 8);
+    }
+};
+
+// The walk: out.lin / recs_flat / place / lin_text from the device, the rings through unitig_ring_chains.  The caller holds
+// the blocks and drains the stream on its way out.  One host read per jumping round (the count of unfinished records), one
+// of the totals, then the results.
+template <int W> int chains_walk_t(const UChainIn &g, const std::vector<UnitigRec> &recs, ChainBlocks &b, hipStream_t st,
+                                   UnitigGraphResult &out, std::string &err) {
+    const size_t n = g.n;
+    const dim3 grid(ug_grid(n)), block(256);
+    unsigned long long *ctl = (unsigned long long *)b.ctl.p;
+    uint32_t *pred = (uint32_t *)b.pred.p;
+    URank rk[2];
+    for (int i = 0; i < 2; i++) rk[i] = URank{(uint32_t *)b.up[i].p, (uint32_t *)b.idx[i].p, (unsigned long long *)b.nodes[i].p, (unsigned long long *)b.kc[i].p};
+    unsigned long long h_ctl[UC_WORDS];
+    std::vector<UnitigRingRec> rings;
+    DrainOnExit drain{st};                                        // (behind the host ends of the copies: they outlive it)
+    UGCHK(hipMemsetAsync(ctl, 0, UC_WORDS * 8, st));
+    UGCHK(hipMemsetAsync(pred, 0xFF, n * 4, st));
+    hipLaunchKernelGGL(k_uc_pred, grid, block, 0, st, g, pred);
+    hipLaunchKernelGGL(k_uc_init, grid, block, 0, st, g, (const uint32_t *)pred, rk[0], ctl + UC_ROUND0);
+    UGCHK(hipGetLastError());
+    UGCHK(hipMemcpyAsync(h_ctl + UC_ROUND0, ctl + UC_ROUND0, 8, hipMemcpyDeviceToHost, st));
+    UGCHK(hipStreamSynchronize(st));
+    // every round finishes at least one record of a chain with a head while there is one (the unfinished record nearest
+    // to its head has a finished up); the records of a cycle never finish.  So: none left, or a count that did not
+    // move — the rest are rings — or ceil(log2 n) + 1 rounds, which no chain of n records needs.
+    int max_rounds = 1;
+    while (max_rounds < UC_MAX_ROUNDS - 1 && (1ull << (max_rounds - 1)) < n) max_rounds++;
+    int cur = 0;
+    unsigned long long open = h_ctl[UC_ROUND0];
+    for (int round = 1; round <= max_rounds && open; round++) {
+        hipLaunchKernelGGL(k_uc_jump, grid, block, 0, st, g, (const uint32_t *)pred, rk[cur], rk[cur ^ 1], ctl + UC_ROUND0 + round);
+        UGCHK(hipGetLastError());
+        UGCHK(hipMemcpyAsync(h_ctl + UC_ROUND0 + round, ctl + UC_ROUND0 + round, 8, hipMemcpyDeviceToHost, st));
+        UGCHK(hipStreamSynchronize(st));
+        cur ^= 1;
+        const unsigned long long now = h_ctl[UC_ROUND0 + round];
+        if (now == open) break;
+        open = now;
+    }
+    // the other set of arrays is free from here on: the totals by head go there
+    const URank a = rk[cur], o = rk[cur ^ 1];
+    uint32_t *h_cnt = o.idx, *c_idx = (uint32_t *)b.c_idx.p, *rec_off = (uint32_t *)b.rec_off.p;
+    unsigned long long *h_nodes = o.nodes, *h_kc = o.kc, *h_text = (unsigned long long *)b.h_text.p, *text_off = (unsigned long long *)b.text_off.p;
+    UGCHK(hipMemsetAsync(h_cnt, 0, (n + 1) * 4, st));
+    UGCHK(hipMemsetAsync(h_text, 0, (n + 1) * 8, st));
+    hipLaunchKernelGGL(k_uc_tails<W>, grid, block, 0, st, g, (const uint32_t *)pred, a, h_cnt, h_nodes, h_kc, h_text);
+    UGCHK(hipGetLastError());
+    size_t tmp_bytes = b.tmp_bytes;
+    UGCHK(uc_scans(b.tmp.p, tmp_bytes, h_cnt, h_text, c_idx, rec_off, text_off, (int)(n + 1), st));
+    hipLaunchKernelGGL(k_uc_totals, dim3(1), dim3(64), 0, st, (uint32_t)n, (const uint32_t *)c_idx, (const uint32_t *)rec_off, (const unsigned long long *)text_off, ctl);
+    hipLaunchKernelGGL(k_uc_contigs, grid, block, 0, st, (uint32_t)n, (const uint32_t *)h_cnt, (const unsigned long long *)h_nodes, (const unsigned long long *)h_kc,
+                       (const uint32_t *)c_idx, (const uint32_t *)rec_off, (const unsigned long long *)text_off, (UnitigFlatContig *)b.lin.p);
+    hipLaunchKernelGGL(k_uc_place, grid, block, 0, st, g, (const uint32_t *)pred, a, (const uint32_t *)h_cnt, (const uint32_t *)rec_off,
+                       (const unsigned long long *)text_off, (UnitigPlace *)b.place.p, (uint32_t *)b.flat.p, (UnitigRingRec *)b.rings.p, ctl + UC_NRING);
+    UGCHK(hipGetLastError());
+    UGCHK(hipMemcpyAsync(h_ctl, ctl, 4 * 8, hipMemcpyDeviceToHost, st));
+    UGCHK(hipStreamSynchronize(st));
+    const size_t n_ring = (size_t)h_ctl[UC_NRING], n_contig = (size_t)h_ctl[UC_NCONTIG], n_rec = (size_t)h_ctl[UC_NREC];
+    if (n_ring > n || n_contig > n || n_rec > n) { err = "unitig graph on the device: the walk of the chains counted more than there is"; return -5; }
+    out.flat = true;
+    out.lin_text = h_ctl[UC_NTEXT];
+    out.lin.resize(n_contig); out.recs_flat.resize(n_rec); out.place.resize(n);
+    rings.resize(n_ring);
+    if (n_contig) UGCHK(hipMemcpyAsync(out.lin.data(), b.lin.p, n_contig * sizeof(UnitigFlatContig), hipMemcpyDeviceToHost, st));
+    if (n_rec) UGCHK(hipMemcpyAsync(out.recs_flat.data(), b.flat.p, n_rec * 4, hipMemcpyDeviceToHost, st));
+    UGCHK(hipMemcpyAsync(out.place.data(), b.place.p, n * sizeof(UnitigPlace), hipMemcpyDeviceToHost, st));
+    if (n_ring) UGCHK(hipMemcpyAsync(rings.data(), b.rings.p, n_ring * sizeof(UnitigRingRec), hipMemcpyDeviceToHost, st));
+    UGCHK(hipStreamSynchronize(st));
+    return unitig_ring_chains(recs, std::move(rings), out, err);
+}
+
 template <int W> int assemble_device_t(int k, const std::vector<UnitigRec> &recs, bool tips, bool bubbles, hipStream_t st,
                                        UnitigGraphResult &out, std::string &err) {
     const bool dbg = getenv("SHK_UG_DEBUG") != nullptr;            // stage times on stderr, as the host code prints them
@@ -430,9 +701,11 @@ template <int W> int assemble_device_t(int k, const std::vector<UnitigRec> &recs
     const size_t n = recs.size();
     out = UnitigGraphResult();
     if (n >= (size_t)UG_NIL) { err = "unitig graph: more records than 32-bit record numbers"; return -1; }
+    const bool walk = chains_on_device() && n <= UC_MAX_RECS;     // S10 here as well; else the host's walk
     if (n == 0) {                                                 // (nothing to launch; the host makes one empty round)
         if (tips || bubbles) out.rounds = 1;
-        return unitig_chains(k, recs, std::vector<uint8_t>(), std::vector<uint32_t>(), std::vector<uint32_t>(), out, err);
+        out.flat = walk;                                          // (no record: the flat form is the empty one)
+        return 0;
     }
     uint64_t cap = 64;
     while (cap < (uint64_t)n * 2 + 16) cap <<= 1;
@@ -444,9 +717,10 @@ template <int W> int assemble_device_t(int k, const std::vector<UnitigRec> &recs
     // ---- device blocks: all of them before any work, so that "no memory" leaves nothing behind
     const size_t rec_words = (size_t)(2 * W + 2) * n;             // first[W][n], last[W][n], len[n], kc[n]
     Blk d_rec, d_circ, d_slot, d_mirror, d_outn, d_alive, d_mark, d_succ, d_cand, d_tips, d_kill, d_head, d_ctl;
+    ChainBlocks cb;
     if (!d_rec.get(rec_words * 8) || !d_circ.get(n) || !d_slot.get((size_t)cap * 8) || !d_mirror.get(n * 4) || !d_outn.get(n * 16) ||
         !d_alive.get(n) || !d_mark.get(n) || !d_succ.get(n * 4) || !d_cand.get(n * 4) || !d_tips.get(n * sizeof(UTip)) ||
-        !d_kill.get(n) || !d_head.get(n * 4) || !d_ctl.get(CTL_WORDS * 8)) {
+        !d_kill.get(n) || !d_head.get(n * 4) || !d_ctl.get(CTL_WORDS * 8) || (walk && !cb.get(n))) {
         (void)hipGetLastError();
         return 1;
     }
@@ -528,9 +802,19 @@ template <int W> int assemble_device_t(int k, const std::vector<UnitigRec> &recs
         }
     }
     lap("rounds");
-    // ---- simple successors; alive / mirror / succ go home, the host's own walk makes the contigs
+    // ---- simple successors; then the walk of the chains, here —
     hipLaunchKernelGGL(k_ug_succ<W>, grid, block, 0, st, g, (uint32_t *)d_succ.p);
     UGCHK(hipGetLastError());
+    if (walk) {
+        lap("succ");
+        UChainIn in;
+        in.F = g.F; in.len = g.len; in.kc = g.kc; in.circ = g.circ; in.alive = g.alive; in.mirror = g.mirror; in.succ = (const uint32_t *)d_succ.p;
+        in.n = g.n; in.k = k;
+        const int rc = chains_walk_t<W>(in, recs, cb, st, out, err);
+        lap("chains");
+        return rc;
+    }
+    // ---- or alive / mirror / succ go home, and the host's own walk makes the contigs
     alive.resize(n); mirror.resize(n); succ.resize(n);
     UGCHK(hipMemcpyAsync(alive.data(), d_alive.p, n, hipMemcpyDeviceToHost, st));
     UGCHK(hipMemcpyAsync(mirror.data(), d_mirror.p, n * 4, hipMemcpyDeviceToHost, st));
@@ -542,7 +826,72 @@ template <int W> int assemble_device_t(int k, const std::vector<UnitigRec> &recs
     return rc;
 }
 
+// the walk alone, from settled arrays: first k-mers, lengths, counts and the links go up, the walk runs
+template <int W> int chains_device_t(int k, const std::vector<UnitigRec> &recs, const std::vector<uint8_t> &alive, const std::vector<uint32_t> &mirror,
+                                     const std::vector<uint32_t> &succ, hipStream_t st, UnitigGraphResult &out, std::string &err) {
+    const size_t n = recs.size();
+    out = UnitigGraphResult();
+    if (alive.size() != n || mirror.size() != n || succ.size() != n) { err = "unitig graph: arrays of another size than the records"; return -1; }
+    if (n > UC_MAX_RECS) { err = "unitig graph: more records than the walk on the device takes"; return -1; }
+    if (n == 0) { out.flat = true; return 0; }
+    std::vector<uint64_t> h_rec;                                  // (declared first: outlives the drain of the stream)
+    std::vector<uint8_t> h_circ;
+    const size_t rec_words = (size_t)(W + 2) * n;                 // first[W][n], len[n], kc[n]
+    Blk d_rec, d_circ, d_alive, d_mirror, d_succ;
+    ChainBlocks cb;
+    if (!d_rec.get(rec_words * 8) || !d_circ.get(n) || !d_alive.get(n) || !d_mirror.get(n * 4) || !d_succ.get(n * 4) || !cb.get(n)) {
+        (void)hipGetLastError();
+        return 1;
+    }
+    DrainOnExit drain{st};
+    h_rec.resize(rec_words); h_circ.resize(n);
+    {
+        uint64_t *F = h_rec.data(), *len = F + (size_t)W * n, *kc = len + n;
+        for (size_t r = 0; r < n; r++) {
+            const UnitigRec &R = recs[r];
+            for (int w = 0; w < W; w++) F[(size_t)w * n + r] = R.first[w];
+            len[r] = R.len; kc[r] = R.kc; h_circ[r] = R.circ ? 1 : 0;
+        }
+    }
+    UGCHK(hipMemcpyAsync(d_rec.p, h_rec.data(), rec_words * 8, hipMemcpyHostToDevice, st));
+    UGCHK(hipMemcpyAsync(d_circ.p, h_circ.data(), n, hipMemcpyHostToDevice, st));
+    UGCHK(hipMemcpyAsync(d_alive.p, alive.data(), n, hipMemcpyHostToDevice, st));
+    UGCHK(hipMemcpyAsync(d_mirror.p, mirror.data(), n * 4, hipMemcpyHostToDevice, st));
+    UGCHK(hipMemcpyAsync(d_succ.p, succ.data(), n * 4, hipMemcpyHostToDevice, st));
+    UChainIn in;
+    in.F = (const uint64_t *)d_rec.p; in.len = in.F + (size_t)W * n; in.kc = in.len + n;
+    in.circ = (const uint8_t *)d_circ.p; in.alive = (const uint8_t *)d_alive.p;
+    in.mirror = (const uint32_t *)d_mirror.p; in.succ = (const uint32_t *)d_succ.p;
+    in.n = (uint32_t)n; in.k = k;
+    return chains_walk_t<W>(in, recs, cb, st, out, err);
+}
+
+// the device of the call, for its length
+struct OnDevice {
+    int before = 0, device; bool ok;
+    explicit OnDevice(int d) : device(d) { ok = hipGetDevice(&before) == hipSuccess && (before == device || hipSetDevice(device) == hipSuccess); }
+    ~OnDevice() { if (ok && before != device) (void)hipSetDevice(before); }
+};
+
 }  // namespace
+
+int unitig_chains_device(int k, const std::vector<UnitigRec> &recs, const std::vector<uint8_t> &alive, const std::vector<uint32_t> &mirror,
+                         const std::vector<uint32_t> &succ, int device, void *stream, UnitigGraphResult &out, std::string &err) {
+    OnDevice on(device);
+    if (!on.ok) { err = std::string("unitig graph on the device: no such device: ") + hipGetErrorString(hipGetLastError()); return -5; }
+    hipStream_t st = (hipStream_t)stream;
+    switch ((2 * k + 63) / 64) {
+        case 1: return chains_device_t<1>(k, recs, alive, mirror, succ, st, out, err);
+        case 2: return chains_device_t<2>(k, recs, alive, mirror, succ, st, out, err);
+        case 3: return chains_device_t<3>(k, recs, alive, mirror, succ, st, out, err);
+        case 4: return chains_device_t<4>(k, recs, alive, mirror, succ, st, out, err);
+        case 5: return chains_device_t<5>(k, recs, alive, mirror, succ, st, out, err);
+        case 6: return chains_device_t<6>(k, recs, alive, mirror, succ, st, out, err);
+        case 7: return chains_device_t<7>(k, recs, alive, mirror, succ, st, out, err);
+        case 8: return chains_device_t<8>(k, recs, alive, mirror, succ, st, out, err);
+    }
+    err = "k too large"; return -1;
+}
 
 int unitig_assemble_device(int k, const std::vector<UnitigRec> &recs, bool tips, bool bubbles, int device, void *stream,
                            UnitigGraphResult &out, std::string &err) {
