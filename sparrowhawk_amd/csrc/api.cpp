@@ -34,7 +34,7 @@ template <typename F> static int guarded(shk_handle *h, Poison poison, F &&body)
     DevGuard g(h->pipe ? h->pipe->device() : current_device());
     MemGuard mg(h->mem);
     // device buffers that go out of scope inside the call (early returns included) are parked until the handle's stream
-    // has drained, then go back to the pool: nothing in flight can be handed to another handle (pipeline.h)
+    // has drained, then go back to the pool: nothing in flight can be handed to another handle (device_mem.h)
     DeferScope park(h->pipe);
     int rc;
     try { rc = body(); }
@@ -426,10 +426,9 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
     const uint64_t rec_bytes = (uint64_t)h->pipe->rec_words() * 8u;
     uint64_t n_send = 0, n_recv = 0;
     // ---- pack (destination-major) and exchange
-    struct Block { void *p = nullptr; size_t bytes = 0; ~Block() { if (p) device_pool_release(p, bytes); } } send, recv, send_w, recv_w, gk[8], gc;
-    // (declared after the blocks, so it runs before they go back to the pool: on every way out — errors included —
-    // the stream is drained first; the pool has no stream-ordering bookkeeping)
-    struct DrainOnExit { ShardComm *c; void *st; ~DrainOnExit() { std::string e; (void)comm_stream_wait(c, st, e); } } drain{c, st};
+    // (on every way out — errors included — the stream is drained, through the watchdog, before the blocks go back)
+    PoolScope sc([c, st] { std::string e; (void)comm_stream_wait(c, st, e); });
+    uint8_t *send = nullptr, *recv = nullptr, *send_w = nullptr, *recv_w = nullptr, *gk[8] = {}, *gc = nullptr;
     {
         int rc_pack = SHK_OK;
         if (int rc = plan_exchange(all.data(), world, P, rank, plan, err)) rc_pack = fail_rc(h, Rc::Device, rc, err);
@@ -443,18 +442,19 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
         }
         if (!rc_pack) {
             for (uint32_t r = 0; r < world; r++) { n_send += plan.send_counts[r]; n_recv += plan.recv_counts[r]; }
-            send.bytes = (size_t)(n_send * rec_bytes + 64); send.p = device_pool_alloc(send.bytes);
-            recv.bytes = (size_t)(n_recv * rec_bytes + 64); recv.p = device_pool_alloc(recv.bytes);
+            std::string e2;
+            send = sc.get<uint8_t>((size_t)(n_send * rec_bytes + 64), e2);
+            recv = sc.get<uint8_t>((size_t)(n_recv * rec_bytes + 64), e2);
             if (weighted) {
-                send_w.bytes = (size_t)(n_send * 4 + 64); send_w.p = device_pool_alloc(send_w.bytes);
-                recv_w.bytes = (size_t)(n_recv * 4 + 64); recv_w.p = device_pool_alloc(recv_w.bytes);
+                send_w = sc.get<uint8_t>((size_t)(n_send * 4 + 64), e2);
+                recv_w = sc.get<uint8_t>((size_t)(n_recv * 4 + 64), e2);
             }
-            if (!send.p || !recv.p || (weighted && (!send_w.p || !recv_w.p))) rc_pack = fail(h, SHK_E_OOM, "shard_preprocess: device memory for the record exchange");
+            if (!send || !recv || (weighted && (!send_w || !recv_w))) rc_pack = fail(h, SHK_E_OOM, "shard_preprocess: device memory for the record exchange");
         }
         if (!rc_pack && weighted) {
             std::string e2;
-            if (int r2 = h->pipe->shard_pack_dedup(send.p, send_w.p, plan.base.data(), P, e2)) rc_pack = fail_rc(h, Rc::Device, r2, e2);
-        } else if (!rc_pack) rc_pack = shard_pack_impl(h, send.p, plan.base.data(), P);
+            if (int r2 = h->pipe->shard_pack_dedup(send, send_w, plan.base.data(), P, e2)) rc_pack = fail_rc(h, Rc::Device, r2, e2);
+        } else if (!rc_pack) rc_pack = shard_pack_impl(h, send, plan.base.data(), P);
         if (!rc_pack) rc_pack = injected("pack");
         stage("pack");
         if (int rc = agree(rc_pack, "the packing of the records")) return rc;
@@ -467,26 +467,26 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
             ro[r] = b; rb[r] = plan.recv_counts[r] * rec_bytes; b += rb[r];
         }
         const double tx = now_ms();
-        if (int rc = comm_alltoallv(c, send.p, so.data(), sb.data(), recv.p, ro.data(), rb.data(), st, err)) return fail_rc(h, Rc::Device, rc, err);
+        if (int rc = comm_alltoallv(c, send, so.data(), sb.data(), recv, ro.data(), rb.data(), st, err)) return fail_rc(h, Rc::Device, rc, err);
         if (weighted) {
             // the weights: same element offsets as the records, 4 bytes each
             for (uint32_t r = 0; r < world; r++) { so[r] = so[r] / rec_bytes * 4; sb[r] = plan.send_counts[r] * 4; ro[r] = ro[r] / rec_bytes * 4; rb[r] = plan.recv_counts[r] * 4; }
-            if (int rc = comm_alltoallv(c, send_w.p, so.data(), sb.data(), recv_w.p, ro.data(), rb.data(), st, err, 4)) return fail_rc(h, Rc::Device, rc, err);
+            if (int rc = comm_alltoallv(c, send_w, so.data(), sb.data(), recv_w, ro.data(), rb.data(), st, err, 4)) return fail_rc(h, Rc::Device, rc, err);
         }
         if (int rc = comm_stream_wait(c, st, err)) { comm_mark_broken(c); return fail_rc(h, Rc::Device, rc, err); }
         h->pipe->times().add("shard_exchange_host_clock", now_ms() - tx);
         h->pipe->times().add("shard_exchange_sent_MB", (double)(n_send * (rec_bytes + (weighted ? 4 : 0))) / 1e6);
     }
     stage("exchange");
-    if (send_w.p) { device_pool_release(send_w.p, send_w.bytes); send_w.p = nullptr; }
-    device_pool_release(send.p, send.bytes); send.p = nullptr;
+    sc.release(send_w); send_w = nullptr;          // (the stream is idle: the wait above)
+    sc.release(send); send = nullptr;
     // ---- pass 2 over the owned partitions, then the global histogram ([501] = ranks that failed)
     // ([500] k-mer instances counted, [501] ranks that failed, [502] k-mer instances this rank's READS hold: after the
     // all-reduce [500] must equal [502] — a record exchange that lost or duplicated data cannot pass unnoticed)
     uint64_t red[SHK_HISTO_BINS + 3] = {0};
     const uint64_t inst_in_reads = n_bases > n_seg * (uint64_t)(h->k - 1) ? n_bases - n_seg * (uint64_t)(h->k - 1) : 0;
-    int rc_cnt = shard_count_impl(h, recv.p, plan.run_off.data(), plan.run_cnt.data(), (uint32_t)plan.owned.size(), world, red,
-                                  &red[SHK_HISTO_BINS], weighted ? recv_w.p : nullptr);
+    int rc_cnt = shard_count_impl(h, recv, plan.run_off.data(), plan.run_cnt.data(), (uint32_t)plan.owned.size(), world, red,
+                                  &red[SHK_HISTO_BINS], weighted ? recv_w : nullptr);
     stage("pass 2");
     if (!rc_cnt) rc_cnt = injected("count");
     if (rc_cnt) memset(red, 0, sizeof red);
@@ -552,22 +552,24 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
     {
         int rc_alloc = SHK_OK;
         for (uint32_t j = 0; j < W && !rc_alloc; j++) {
-            gk[j].bytes = (size_t)(n_total * 8 + 64); gk[j].p = device_pool_alloc(gk[j].bytes);
-            if (!gk[j].p) rc_alloc = fail(h, SHK_E_OOM, "shard_preprocess: device memory for the solid set");
+            std::string e2;
+            gk[j] = sc.get<uint8_t>((size_t)(n_total * 8 + 64), e2);
+            if (!gk[j]) rc_alloc = fail(h, SHK_E_OOM, "shard_preprocess: device memory for the solid set");
         }
         if (!rc_alloc) {
-            gc.bytes = (size_t)(n_total * 4 + 64); gc.p = device_pool_alloc(gc.bytes);
-            if (!gc.p) rc_alloc = fail(h, SHK_E_OOM, "shard_preprocess: device memory for the solid set");
+            std::string e2;
+            gc = sc.get<uint8_t>((size_t)(n_total * 4 + 64), e2);
+            if (!gc) rc_alloc = fail(h, SHK_E_OOM, "shard_preprocess: device memory for the solid set");
         }
         if (!rc_alloc) rc_alloc = injected("alloc");
         if (int rc = agree(rc_alloc, "the allocation of the solid set")) return rc;
     }
     for (uint32_t j = 0; j < W; j++)
-        if (int rc = comm_allgatherv(c, keys[j], gk[j].p, off8.data(), len8.data(), st, err)) return fail_rc(h, Rc::Device, rc, err);
-    if (int rc = comm_allgatherv(c, cnt, gc.p, off4.data(), len4.data(), st, err)) return fail_rc(h, Rc::Device, rc, err);
+        if (int rc = comm_allgatherv(c, keys[j], gk[j], off8.data(), len8.data(), st, err)) return fail_rc(h, Rc::Device, rc, err);
+    if (int rc = comm_allgatherv(c, cnt, gc, off4.data(), len4.data(), st, err)) return fail_rc(h, Rc::Device, rc, err);
     if (int rc = comm_stream_wait(c, st, err)) { comm_mark_broken(c); return fail_rc(h, Rc::Device, rc, err); }
-    const void *kp[8] = {gk[0].p, gk[1].p, gk[2].p, gk[3].p, gk[4].p, gk[5].p, gk[6].p, gk[7].p};
-    if (int rc = shard_set_solid_impl(h, kp, gc.p, n_total, red[SHK_HISTO_BINS])) return rc;
+    const void *kp[8] = {gk[0], gk[1], gk[2], gk[3], gk[4], gk[5], gk[6], gk[7]};
+    if (int rc = shard_set_solid_impl(h, kp, gc, n_total, red[SHK_HISTO_BINS])) return rc;
     h->pipe->times().add("shard_preprocess_host_clock", now_ms() - t0);
     return SHK_OK;
 }

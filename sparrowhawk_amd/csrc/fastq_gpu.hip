@@ -18,19 +18,10 @@
 #include <string>
 #include <vector>
 
+#include "device_mem.h"
 #include "fastq_gpu.h"
-#include "pipeline.h"
 
 namespace shk {
-
-#define FQCHK(call)                                                                       \
-    do {                                                                                  \
-        hipError_t _e = (call);                                                           \
-        if (_e != hipSuccess) {                                                           \
-            err = std::string(#call) + ": " + hipGetErrorString(_e);                      \
-            return -5;                                                                    \
-        }                                                                                 \
-    } while (0)
 
 static constexpr uint32_t NL_CHUNK = 16384;      // text bytes per workgroup of the newline kernels
 
@@ -67,39 +58,19 @@ static inline unsigned grid1(uint64_t work, unsigned block = 256, unsigned cap =
     uint64_t b = (work + block - 1) / block; if (b < 1) b = 1; if (b > cap) b = cap; return (unsigned)b;
 }
 
-struct Scratch {                                  // blocks of the process-wide device pool, returned on scope exit
-    std::vector<std::pair<void *, size_t>> ptrs;
-    hipStream_t st = nullptr; bool bound = false;     // the stream the blocks are used on
-    void bind(hipStream_t s) { st = s; bound = true; }
-    // the pool has no stream-ordering bookkeeping: a block may be handed to another stream's user (the uploader
-    // thread) at once, so kernels still in flight on an early error return are waited for before the release
-    ~Scratch() {
-        if (bound && !ptrs.empty()) (void)hipStreamSynchronize(st);
-        for (auto &p : ptrs) if (p.first) device_pool_release(p.first, p.second);
-    }
-    template <typename T> T *get(size_t count, std::string &err) {
-        size_t bytes = (count ? count : 1) * sizeof(T);
-        void *p = device_pool_alloc(bytes);
-        if (!p) { err = "device allocation failed (FASTQ parser)"; return nullptr; }
-        ptrs.emplace_back(p, bytes);
-        return (T *)p;
-    }
-    size_t keep(void *p) { for (auto &q : ptrs) if (q.first == p) { q.first = nullptr; return q.second; } return 0; }
-};
-
 // in-place exclusive scan of a[0..n); *total (device) receives the sum
-static int exclusive_scan(unsigned long long *a, uint64_t n, unsigned long long *d_total, hipStream_t st, Scratch &sc,
+static int exclusive_scan(unsigned long long *a, uint64_t n, unsigned long long *d_total, hipStream_t st, PoolScope &sc,
                           std::string &err) {
     const uint64_t per = SCAN_T * SCAN_I;
     const uint64_t nb = (n + per - 1) / per;
-    if (n == 0) { FQCHK(hipMemsetAsync(d_total, 0, 8, st)); return 0; }
+    if (n == 0) { HIPCHK(hipMemsetAsync(d_total, 0, 8, st)); return 0; }
     unsigned long long *bs = sc.get<unsigned long long>(nb, err);
     if (!bs) return -4;
     hipLaunchKernelGGL(k_scan_local, dim3((unsigned)nb), dim3(SCAN_T), 0, st, a, n, bs);
-    if (nb == 1) { FQCHK(hipMemcpyAsync(d_total, bs, 8, hipMemcpyDeviceToDevice, st)); return 0; }
+    if (nb == 1) { HIPCHK(hipMemcpyAsync(d_total, bs, 8, hipMemcpyDeviceToDevice, st)); return 0; }
     if (int rc = exclusive_scan(bs, nb, d_total, st, sc, err)) return rc;
     hipLaunchKernelGGL(k_scan_add, dim3((unsigned)nb), dim3(SCAN_T), 0, st, a, n, bs);
-    FQCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -447,7 +418,7 @@ int gpu_pack_fastq(const uint8_t *t1, size_t n1, const uint8_t *t2, size_t n2, u
                    const GpuText *uploaded) {
     hipStream_t st = (hipStream_t)stream_v;
     out = GpuPacked();
-    Scratch sc; sc.bind(st);
+    PoolScope sc(st, "FASTQ parser");
     if (uploaded && t2) { err = "an uploaded text cannot be combined with a second file"; return -1; }
     // ---- framing that can be decided on the host: trailing blank lines are ignored, the last line of a
     // file may lack its newline (one is supplied between the files)
@@ -458,8 +429,8 @@ int gpu_pack_fastq(const uint8_t *t1, size_t n1, const uint8_t *t2, size_t n2, u
     if (e == 0) {                                        // no records at all
         uint32_t *so = sc.get<uint32_t>(2, err), *bs = sc.get<uint32_t>(2, err);
         if (!so || !bs) return -4;
-        FQCHK(hipMemsetAsync(so, 0, 8, st)); FQCHK(hipMemsetAsync(bs, 0, 8, st));
-        FQCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemsetAsync(so, 0, 8, st)); HIPCHK(hipMemsetAsync(bs, 0, 8, st));
+        HIPCHK(hipStreamSynchronize(st));
         out.bases_bytes = sc.keep(bs); out.seg_off_bytes = sc.keep(so);
         out.d_bases = bs; out.d_seg_off = so; return 0;
     }
@@ -467,27 +438,27 @@ int gpu_pack_fastq(const uint8_t *t1, size_t n1, const uint8_t *t2, size_t n2, u
     uint8_t *text = uploaded ? uploaded->d : sc.get<uint8_t>(e + 32, err);
     if (!text) return -4;
     hipEvent_t ev0, ev1, ev2;
-    FQCHK(hipEventCreate(&ev0)); FQCHK(hipEventCreate(&ev1)); FQCHK(hipEventCreate(&ev2));
+    HIPCHK(hipEventCreate(&ev0)); HIPCHK(hipEventCreate(&ev1)); HIPCHK(hipEventCreate(&ev2));
     struct EvGuard { hipEvent_t a, b, c; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); (void)hipEventDestroy(c); } } evg{ev0, ev1, ev2};
-    FQCHK(hipEventRecord(ev0, st));
+    HIPCHK(hipEventRecord(ev0, st));
     if (!uploaded) {
-        if (e1) FQCHK(hipMemcpyAsync(text, t1, e1, hipMemcpyHostToDevice, st));
-        if (off2 > e1) FQCHK(hipMemsetAsync(text + e1, '\n', 1, st));
-        if (e2) FQCHK(hipMemcpyAsync(text + off2, t2, e2, hipMemcpyHostToDevice, st));
-        FQCHK(hipMemsetAsync(text + e, 0, 32, st));
+        if (e1) HIPCHK(hipMemcpyAsync(text, t1, e1, hipMemcpyHostToDevice, st));
+        if (off2 > e1) HIPCHK(hipMemsetAsync(text + e1, '\n', 1, st));
+        if (e2) HIPCHK(hipMemcpyAsync(text + off2, t2, e2, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(text + e, 0, 32, st));
     }
-    FQCHK(hipEventRecord(ev1, st));
+    HIPCHK(hipEventRecord(ev1, st));
 
     const uint64_t n_chunks = (e + NL_CHUNK - 1) / NL_CHUNK;
     unsigned long long *chunk_cnt = sc.get<unsigned long long>(n_chunks, err);
     unsigned long long *d_tot = sc.get<unsigned long long>(8 + 64, err);     // [8..72): partial sums of the input bases
     if (!chunk_cnt || !d_tot) return -4;
-    FQCHK(hipMemsetAsync(d_tot, 0, (8 + 64) * 8, st));
+    HIPCHK(hipMemsetAsync(d_tot, 0, (8 + 64) * 8, st));
     hipLaunchKernelGGL(k_nl_count, dim3((unsigned)n_chunks), dim3(256), 0, st, text, (uint64_t)e, chunk_cnt);
     if (int rc = exclusive_scan(chunk_cnt, n_chunks, d_tot, st, sc, err)) return rc;
     unsigned long long n_nl = 0;
-    FQCHK(hipMemcpyAsync(&n_nl, d_tot, 8, hipMemcpyDeviceToHost, st));
-    FQCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(&n_nl, d_tot, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     FqParams fp; fp.n = e; fp.n_nl = n_nl; fp.n_lines = n_nl + (unterminated ? 1 : 0); fp.k = k; fp.min_qual = min_qual;
     fp.part2_off = off2; fp.part1_len = e1; fp.part1_reads = 0;
     if (fp.n_lines % 4 != 0) return 1;                    // irregular framing: the host parser decides
@@ -495,8 +466,8 @@ int gpu_pack_fastq(const uint8_t *t1, size_t n1, const uint8_t *t2, size_t n2, u
     if (e2) {                                             // the first file must hold whole records too
         hipLaunchKernelGGL(k_nl_total, dim3(grid1(off2, 256, 4096)), dim3(256), 0, st, text, (uint64_t)off2, d_tot + 6);
         unsigned long long l1 = 0;
-        FQCHK(hipMemcpyAsync(&l1, d_tot + 6, 8, hipMemcpyDeviceToHost, st));
-        FQCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpyAsync(&l1, d_tot + 6, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
         if (l1 % 4 != 0) return 1;
         fp.part1_reads = l1 / 4;
     } else fp.part1_reads = n_reads;
@@ -512,8 +483,8 @@ int gpu_pack_fastq(const uint8_t *t1, size_t n1, const uint8_t *t2, size_t n2, u
     if (int rc = exclusive_scan(seg_cnt, n_reads, d_tot + 4, st, sc, err)) return rc;
     if (int rc = exclusive_scan(base_cnt, n_reads, d_tot + 5, st, sc, err)) return rc;
     unsigned long long h[8 + 64];
-    FQCHK(hipMemcpyAsync(h, d_tot, sizeof h, hipMemcpyDeviceToHost, st));
-    FQCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(h, d_tot, sizeof h, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     h[3] = 0;
     for (int i = 0; i < 64; i++) h[3] += h[8 + i];
     if (h[2]) return 1;                                   // a malformed record: the host parser reports it
@@ -524,13 +495,13 @@ int gpu_pack_fastq(const uint8_t *t1, size_t n1, const uint8_t *t2, size_t n2, u
     uint32_t *bases = sc.get<uint32_t>(n_words, err);
     uint2 *edge = sc.get<uint2>(n_seg + 1, err);
     if (!seg_off || !bases || !edge) return -4;
-    FQCHK(hipMemsetAsync(bases, 0, n_words * 4, st));
+    HIPCHK(hipMemsetAsync(bases, 0, n_words * 4, st));
     if (n_seg)
         hipLaunchKernelGGL(k_read_wave<1>, dim3(grid1(n_reads * 64)), dim3(256), 0, st, text, line_end, fp, n_reads, seg_cnt, base_cnt,
                            d_tot + 2, seg_off, bases, edge);
     hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, st, seg_off + n_seg, (uint32_t)n_bases);
     if (n_seg) hipLaunchKernelGGL(k_merge_edges, dim3(grid1(n_seg)), dim3(256), 0, st, seg_off, edge, n_seg, bases);
-    FQCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     // progress marks
     if (every) {
         const uint64_t first_mark = read_base / every;
@@ -541,11 +512,11 @@ int gpu_pack_fastq(const uint8_t *t1, size_t n1, const uint8_t *t2, size_t n2, u
             if (!marks) return -4;
             hipLaunchKernelGGL(k_progress_marks, dim3(grid1(n_marks)), dim3(256), 0, st, line_end, fp, every, n_marks, marks, first_mark, read_base);
             out.progress_bytes.resize(n_marks);
-            FQCHK(hipMemcpyAsync(out.progress_bytes.data(), marks, n_marks * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(out.progress_bytes.data(), marks, n_marks * 8, hipMemcpyDeviceToHost, st));
         }
     }
-    FQCHK(hipEventRecord(ev2, st));
-    FQCHK(hipStreamSynchronize(st));
+    HIPCHK(hipEventRecord(ev2, st));
+    HIPCHK(hipStreamSynchronize(st));
     { float a = 0, b = 0; (void)hipEventElapsedTime(&a, ev0, ev1); (void)hipEventElapsedTime(&b, ev1, ev2); out.h2d_ms = uploaded ? uploaded->h2d_ms : a; out.kernels_ms = b; }
     out.bases_bytes = sc.keep(bases); out.seg_off_bytes = sc.keep(seg_off);
     out.d_bases = bases; out.d_seg_off = seg_off;
@@ -558,10 +529,9 @@ int gpu_upload_text(const uint8_t *t, size_t n, int device, GpuText &out, std::s
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); err = "hipSetDevice failed"; return -5; }
     out.e = trimmed_len(t, n);
     out.unterminated = out.e && t[out.e - 1] != '\n';
-    size_t bytes = out.e + 32;
-    out.d = (uint8_t *)device_pool_alloc(bytes);
-    if (!out.d) { err = "out of device memory for the FASTQ text"; return -4; }
-    out.pool_bytes = bytes;
+    PoolBlock blk;
+    if (!blk.get(out.e + 32)) { err = "out of device memory for the FASTQ text"; return -4; }
+    out.pool_bytes = blk.bytes; out.d = (uint8_t *)blk.take();
     // (creating and destroying a stream costs ~0.4 ms each: one upload stream per device is kept for the process;
     // uploads are issued by one thread at a time per handle, and two handles sharing the stream merely queue up)
     static std::mutex mu;

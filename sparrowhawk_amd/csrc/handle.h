@@ -9,6 +9,7 @@
 
 #include "fastq.h"
 #include "outputs.h"
+#include "device_mem.h"
 #include "pipeline.h"
 #include "shard_comm.h"
 
@@ -35,7 +36,7 @@ struct shk_handle {
     uint64_t batches_started = 0;      // batches handed to the pipeline (a failure after the first one poisons the handle)
     shk::ShardComm *shard_comm = nullptr;   // sharded assembly: the communicator shk_shard_preprocess ran on (shk_assemble is collective over it)
     shk::AssemblyText text;
-    std::shared_ptr<void> mem = shk::mem_acct_new();   // device bytes this handle holds / held at most (pipeline.h: mem_acct_*)
+    std::shared_ptr<void> mem = shk::mem_acct_new();   // device bytes this handle holds / held at most (device_mem.h: mem_acct_*)
 
     const char *mode() const { return do_bloom ? "bloom" : (chunk_size > 0 ? "chunked" : "bulk"); }
     void post(const std::string &s) { if (cb) cb(s.c_str(), cb_user); }

@@ -11,8 +11,8 @@
 #include <string>
 #include <thread>
 #include <vector>
+#include "device_mem.h"
 #include "fastq_gpu.h"
-#include "pipeline.h"
 
 namespace shk {
 
@@ -63,17 +63,6 @@ int bgzf_cut_windows(BgzfChain &c, uint64_t budget);
 struct BgzfWindowKnob { bool set; uint64_t bytes; };
 BgzfWindowKnob bgzf_window_knob(uint64_t max_bytes);
 
-struct Blk {                                               // a device block of the process-wide pool
-    void *p = nullptr; size_t bytes = 0;
-    Blk() = default;
-    Blk(const Blk &) = delete;
-    Blk &operator=(const Blk &) = delete;
-    ~Blk() { put(); }
-    bool get(size_t b) { bytes = b ? b : 8; p = device_pool_alloc(bytes); return p != nullptr; }      // (the pool may hand out more: bytes says what)
-    void put() { if (p) device_pool_release(p, bytes); p = nullptr; }
-    void *take() { void *q = p; p = nullptr; return q; }
-};
-
 // The device side of one file's windows: two input buffers (window w + 1 is uploaded, from a helper thread, while window w
 // is worked on) and two text buffers (window w's text starts with the carry: the partial record left over from window w - 1).
 //     if (bw.open(gz, &chain, device, stream, err)) ...
@@ -103,7 +92,7 @@ class BgzfWindows {
     void upload(size_t w);                                // blocking, on a stream of its own: -> up_[w & 1]
     const uint8_t *gz_ = nullptr; const BgzfChain *chain_ = nullptr;
     int device_ = 0; void *st_ = nullptr;
-    Blk d_in_[2], d_text_[2], d_desc_, d_status_, d_bad_;
+    PoolBlock d_in_[2], d_text_[2], d_desc_, d_status_, d_bad_;
     struct Upload { int rc = 0; std::string err; double ms = 0; } up_[2];
     std::thread prefetch_;                                // uploads window w + 1 during step(w); joined by step(w + 1) and close()
 };
@@ -116,7 +105,7 @@ int gpu_first_record_start(const uint8_t *t, size_t n, uint64_t from, int device
 // ---- one rank's slice of a file, for the sharded FASTQ entry point (preprocess.cpp: read_fastq_share) --------------------
 // The slice rule is stated in fastq.h (first_record_start, fastq_slice_bounds, plan_fastq_slices); here it is applied to text
 // that is born on the device.  A span is a run of text inside a device block it owns.
-struct DevSpan { Blk blk; uint64_t off = 0, len = 0; bool unterminated = false; };
+struct DevSpan { PoolBlock blk; uint64_t off = 0, len = 0; bool unterminated = false; };
 // A walked BGZF chain: rank r uploads and inflates the blocks of run r only (plan_fastq_slices), the non-empty block in front
 // of the run (whether the run's first byte begins a line is written there) and the follow-on blocks of run r + 1 in which its
 // slice ends — 2 first, then twice as many while the boundary is undecided, up to BgzfWindows::CARRY_MAX of text — with

@@ -44,7 +44,6 @@
 #include <vector>
 
 #include "inflate_gpu.h"
-#include "pipeline.h"
 #include "fastq.h"
 
 namespace shk {
@@ -811,11 +810,8 @@ double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::
 
 }  // namespace
 
-#define GZCHK(call)                                                                         \
-    do {                                                                                    \
-        const hipError_t _e = (call);                                                       \
-        if (_e != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(_e); (void)hipStreamSynchronize(st); return -5; } \
-    } while (0)
+// (a failed call leaves the stream drained: the blocks of the function that returns go back to the pool idle)
+#define GZCHK(call) HIPCHK_AS(#call, call, (void)hipStreamSynchronize(st))
 
 namespace {
 // the last bytes of a text on the device, for trim_text_end: fetch_tail enqueues the copy, the caller waits (with whatever
@@ -847,11 +843,11 @@ int trim_text_end(uint8_t *d_text, uint64_t n, const Tail &t, bool raw, hipStrea
 
 // The inflated text (d_text: `total` bytes and 64 more, tail: its last bytes, arrived) becomes out's, made ready for the
 // parser unless raw (trim_text_end).  0: out owns the block; 1: not taken (*why); -5.
-int hand_on_text(Blk &d_text, uint64_t total, const Tail &tail, bool raw, hipStream_t st, GpuText &out, const char *&why, std::string &err) {
+int hand_on_text(PoolBlock &d_text, uint64_t total, const Tail &tail, bool raw, hipStream_t st, GpuText &out, const char *&why, std::string &err) {
     uint64_t e = 0; bool unterminated = false;
     if (const int rc = trim_text_end((uint8_t *)d_text.p, total, tail, raw, st, e, unterminated, why, err)) return rc;
     if (e == 0) { why = "empty text"; return 1; }
-    out.pool_bytes = d_text.bytes; out.d = (uint8_t *)d_text.take();
+    out.pool_bytes = d_text.bytes; out.d = (uint8_t *)d_text.take();      // (out is a plain record: gpu_text_free)
     out.e = (size_t)e; out.unterminated = unterminated;
     return 0;
 }
@@ -863,7 +859,7 @@ int hand_on_text(Blk &d_text, uint64_t total, const Tail &tail, bool raw, hipStr
 // the run's text, which come back in the verdict's wait.
 // 0; 1: a block is not what its trailer says (*why); -5.
 int inflate_block_run(const BgzfChain &chain, size_t b0, size_t b1, const void *d_in, uint64_t in_base, uint8_t *d_text, uint64_t text_at,
-                      Blk &d_desc, Blk &d_status, Blk &d_bad, hipStream_t st, double &ms, double *crc_ms, Tail *tail, const char *&why, std::string &err) {
+                      PoolBlock &d_desc, PoolBlock &d_status, PoolBlock &d_bad, hipStream_t st, double &ms, double *crc_ms, Tail *tail, const char *&why, std::string &err) {
     std::vector<BgzfDesc> desc;
     for (size_t b = b0; b < b1; b++) {
         const BgzfChain::Block &k = chain.blocks[b];
@@ -916,7 +912,7 @@ int gpu_inflate_bgzf(const uint8_t *gz, size_t n, int device, hipStream_t st, Gp
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); err = "hipSetDevice failed"; return -5; }
     const double t_begin = now_ms();
     // ---- upload: the file as it is (26 bytes of header and trailer per block are not worth a repack), zero padding behind
-    Blk d_in, d_desc, d_status, d_bad, d_text;
+    PoolBlock d_in, d_desc, d_status, d_bad, d_text;
     const size_t in_words = (n + 3) / 4 + 2048 + 256;        // (the same padding as for a plain member: see gpu_inflate_member)
     if (!d_in.get(in_words * 4) || !d_desc.get((size_t)nb * sizeof(BgzfDesc)) || !d_status.get((size_t)nb * 4) || !d_bad.get(64) ||
         !d_text.get((size_t)total + 64))
@@ -987,7 +983,7 @@ int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, Gp
     const uint32_t C0 = (uint32_t)((dn + chunk_bytes - 1) / chunk_bytes);
     if (C0 < 2) return not_taken("small member");
     // ---- upload (the compressed bytes are all that crosses PCIe), zero padding behind
-    Blk d_in, d_start;
+    PoolBlock d_in, d_start;
     const size_t in_words = (dn + 3) / 4 + 2048 + 256;      // (8 KB of zero padding: the decoder checks for the end of the input once per 512 symbols; + the 128 dwords its reader keeps in flight)
     if (!d_in.get(in_words * 4) || !d_start.get((size_t)(C0 + 1) * 8)) { err = "out of device memory (gzip input)"; return -4; }
     GZCHK(hipMemsetAsync((char *)d_in.p + (dn & ~(size_t)3), 0, in_words * 4 - (dn & ~(size_t)3), st));
@@ -1018,7 +1014,7 @@ int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, Gp
         const uint64_t room = (comp * ratio + 8192 + 511) & ~511ull;
         sym_off[c + 1] = sym_off[c] + room;
     }
-    Blk d_syms, d_soff, d_res, d_bad;
+    PoolBlock d_syms, d_soff, d_res, d_bad;
     if (!d_syms.get((size_t)sym_off[C] * 2 + 64) || !d_soff.get((size_t)(C + 1) * 8) || !d_res.get((size_t)C * sizeof(ChunkOut)) || !d_bad.get(64)) {
         err = "out of device memory (gzip symbols)"; return -4;
     }
@@ -1046,7 +1042,7 @@ int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, Gp
     if ((uint32_t)total != want_len) return not_taken("ISIZE mismatch");
     if (total == 0 || total >= ((uint64_t)1 << 32)) return not_taken("empty or beyond 4 GiB");
     // ---- 3. windows front to back, 4. markers -> bytes, CRC
-    Blk d_ma, d_mb, d_ooff, d_text, d_crc;
+    PoolBlock d_ma, d_mb, d_ooff, d_text, d_crc;
     const uint32_t SLICE = 65536;
     const uint32_t n_slices = (uint32_t)((total + SLICE - 1) / SLICE);
     if (!d_ma.get((size_t)C * GZ_WSIZE * 2) || !d_mb.get((size_t)C * GZ_WSIZE * 2) || !d_ooff.get((size_t)(C + 1) * 8) || !d_text.get((size_t)total + 64) ||
@@ -1205,7 +1201,7 @@ BgzfWindowKnob bgzf_window_knob(uint64_t max_bytes) {
 void BgzfWindows::close() {
     if (prefetch_.joinable()) prefetch_.join();
     if (st_ || d_in_[0].p) (void)hipStreamSynchronize((hipStream_t)st_);      // the blocks go back to the pool idle
-    for (Blk *b : {&d_in_[0], &d_in_[1], &d_text_[0], &d_text_[1], &d_desc_, &d_status_, &d_bad_}) b->put();
+    for (PoolBlock *b : {&d_in_[0], &d_in_[1], &d_text_[0], &d_text_[1], &d_desc_, &d_status_, &d_bad_}) b->put();
 }
 
 int BgzfWindows::open(const uint8_t *gz, const BgzfChain *chain, int device, void *stream, std::string &err) {
@@ -1218,7 +1214,7 @@ int BgzfWindows::open(const uint8_t *gz, const BgzfChain *chain, int device, voi
     for (const BgzfChain::Window &w : chain->windows) {
         max_in = std::max(max_in, w.in_end - w.in_off); max_text = std::max(max_text, w.text); max_nb = std::max(max_nb, w.nonempty);
     }
-    // (the pool rounds a size up, or hands out a cached block that is larger: every Blk keeps the size it came with)
+    // (the pool rounds a size up, or hands out a cached block that is larger: every PoolBlock keeps the size it came with)
     bool ok = true;
     for (int i = 0; i < (chain->windows.size() > 1 ? 2 : 1) && ok; i++)
         ok = d_in_[i].get((size_t)((max_in + 3) & ~3ull) + WIN_IN_PAD) && d_text_[i].get((size_t)(CARRY_MAX + max_text + 64));
@@ -1293,7 +1289,7 @@ int BgzfWindows::step(size_t w, bool raw, uint64_t &carry, uint64_t &cut, bool &
 int gpu_last_record_start(const uint8_t *t, size_t n, int device, uint64_t &at, std::string &err) {
     hipStream_t st = nullptr;
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); err = "hipSetDevice failed"; return -5; }
-    Blk d_text, d_out;
+    PoolBlock d_text, d_out;
     if (!d_text.get(n + 64) || !d_out.get(64)) { err = "out of device memory"; return -4; }
     if (n) GZCHK(hipMemcpyAsync(d_text.p, t, n, hipMemcpyHostToDevice, st));
     const int rc = device_last_start((const uint8_t *)d_text.p, n, (unsigned long long *)d_out.p, st, at, err);
@@ -1304,7 +1300,7 @@ int gpu_last_record_start(const uint8_t *t, size_t n, int device, uint64_t &at, 
 int gpu_first_record_start(const uint8_t *t, size_t n, uint64_t from, int device, uint64_t &at, std::string &err) {
     hipStream_t st = nullptr;
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); err = "hipSetDevice failed"; return -5; }
-    Blk d_text, d_out;
+    PoolBlock d_text, d_out;
     if (!d_text.get(n + 64) || !d_out.get(64)) { err = "out of device memory"; return -4; }
     if (n) GZCHK(hipMemcpyAsync(d_text.p, t, n, hipMemcpyHostToDevice, st));
     const int rc = device_first_start((const uint8_t *)d_text.p, n, from, (unsigned long long *)d_out.p, st, at, err);
@@ -1348,7 +1344,7 @@ int gpu_bgzf_slice(const uint8_t *gz, const BgzfChain &chain, uint32_t rank, uin
         const uint64_t in_base = chain.blocks[pb].in_off;
         const size_t in_n = (size_t)(chain.blocks[ve - 1].in_off + chain.blocks[ve - 1].bsize - in_base);
         if (n_view >= (1ull << 32) - 64 || in_n >= ((size_t)1 << 34)) { why = "a slice beyond 4 GiB of text"; return 1; }
-        Blk d_in, d_desc, d_status, d_bad, d_text;
+        PoolBlock d_in, d_desc, d_status, d_bad, d_text;
         if (!d_in.get(((in_n + 3) & ~(size_t)3) + WIN_IN_PAD) || !d_desc.get((size_t)nb * sizeof(BgzfDesc)) || !d_status.get((size_t)nb * 4) ||
             !d_bad.get(128) || !d_text.get((size_t)n_view + 64)) { why = "out of device memory"; return 1; }
         // (on every way out of this attempt the stream is idle before the blocks go back to the pool: GZCHK waits)
@@ -1381,7 +1377,7 @@ int gpu_bgzf_slice(const uint8_t *gz, const BgzfChain &chain, uint32_t rank, uin
         if (s[0] > s[1]) s[0] = s[1];
         out.off = s[0]; out.len = s[1] - s[0];
         out.unterminated = at_end && s[1] == e && unterminated && out.len != 0;
-        out.blk.bytes = d_text.bytes; out.blk.p = d_text.take();
+        out.blk = std::move(d_text);
         GZCHK(hipStreamSynchronize(st));
         return 0;
     }
@@ -1392,7 +1388,7 @@ int gpu_text_slice(GpuText &text, uint32_t rank, uint32_t world, void *stream, D
     out.blk.put(); out.off = out.len = 0; out.unterminated = false;
     if (rank >= world) { err = "rank beyond world"; return -1; }
     const uint64_t e = text.e;
-    Blk d_out;
+    PoolBlock d_out;
     if (!d_out.get(64)) { err = "out of device memory"; return -4; }
     uint64_t s[2] = {0, e};
     for (int i = 0; i < 2; i++) {
@@ -1404,7 +1400,7 @@ int gpu_text_slice(GpuText &text, uint32_t rank, uint32_t world, void *stream, D
     }
     out.off = s[0]; out.len = s[1] - s[0];
     out.unterminated = s[1] == e && text.unterminated && out.len != 0;
-    out.blk.bytes = text.pool_bytes; out.blk.p = text.d;      // the text's block is the span's now
+    out.blk = PoolBlock(text.d, text.pool_bytes);             // the text's block is the span's now
     text = GpuText();
     return 0;
 }
@@ -1414,10 +1410,9 @@ int gpu_join_spans(const DevSpan *spans, int n_spans, void *stream, GpuText &out
     out = GpuText();
     uint64_t total = 0;
     for (int i = 0; i < n_spans; i++) total += spans[i].len + 1;
-    size_t bytes = (size_t)total + 32;
-    out.d = (uint8_t *)device_pool_alloc(bytes);
-    if (!out.d) { err = "out of device memory for the FASTQ text"; return -4; }
-    out.pool_bytes = bytes;
+    PoolBlock blk;
+    if (!blk.get((size_t)total + 32)) { err = "out of device memory for the FASTQ text"; return -4; }
+    out.pool_bytes = blk.bytes; out.d = (uint8_t *)blk.take();
     uint64_t at = 0;
     for (int i = 0; i < n_spans; i++) {
         if (!spans[i].len) continue;

@@ -5,7 +5,6 @@
 #include <string>
 #include <vector>
 #include <map>
-#include <memory>
 
 namespace shk {
 
@@ -125,48 +124,14 @@ public:
     virtual int device() const = 0;                  // the HIP device this pipeline's stream and buffers live on
 };
 
-// Device buffers that go out of scope on the calling thread while this object lives are kept until it dies; then the
-// pipeline's stream is drained and they go back to the pool (see DevBuf in pipeline.hip).  One per entry point of the C ABI.
-class DeferScope {
-public:
-    explicit DeferScope(IPipeline *pipe);
-    ~DeferScope();
-    DeferScope(const DeferScope &) = delete;
-    DeferScope &operator=(const DeferScope &) = delete;
-private:
-    IPipeline *pipe_; void *list_; void *prev_;
-};
-
 // returns nullptr (and err) if no device / bad k
 IPipeline *make_pipeline(int k, std::string &err);
-int device_count();
-int current_device();          // the calling thread's current HIP device
-int set_device(int dev);       // makes `dev` current for the calling thread, returns the previous one
 
 // host-side helpers implemented with the same kmer.h arithmetic as the kernels
 int host_canonical(const char *seq, uint32_t k, uint64_t *out_words, int *orient);
 uint64_t host_nthash(const char *seq, uint32_t k);
 
-// upload helper used by the host-buffer entry points
-int device_upload(const void *host, size_t bytes, void **dptr, std::string &err);
-void device_free(void *dptr);
-void device_pool_trim();
-// the process-wide device block cache (pipeline.hip): bytes is rounded up to the block actually handed out
-void *device_pool_alloc(size_t &bytes);
 // best rate (GB/s) of `iters` pure streaming reads of a `bytes` buffer on the current device
 int stream_read_gbs(size_t bytes, int iters, double *gbs, std::string &err);
-void device_pool_release(void *p, size_t bytes);
-// peak device memory per handle (Assembler.ts:69-71,137 reports peak wasm memory with every assembly): an accounting context
-// is made per handle, carried by the thread that serves it (mem_acct_set returns the previous one), and every block the pool
-// hands out meanwhile is charged to it until it goes back
-std::shared_ptr<void> mem_acct_new();
-std::shared_ptr<void> mem_acct_set(std::shared_ptr<void> a);
-uint64_t mem_acct_peak(const std::shared_ptr<void> &a);
-uint64_t mem_acct_current(const std::shared_ptr<void> &a);
-// the counter alone, on the host (tests): applies signed byte deltas, returns the high-water mark and what is left
-void mem_acct_replay(const int64_t *deltas, size_t n, uint64_t *peak, uint64_t *current);
-int device_stream_sync(void *stream, std::string &err);      // waits for a hipStream_t
-int device_copy_h2d_async(void *dst, const void *src, size_t bytes, void *stream, std::string &err);
-int device_download(void *host, const void *dptr, size_t bytes, std::string &err);      // blocking device -> host copy
 
 }  // namespace shk

@@ -1,5 +1,5 @@
 // pipeline.hip — the device pipeline of the assembly path (gfx950, wave64): device-side views, the
-// kernel headers, the device/pinned memory pools and the per-handle Pipeline<W> that sequences them.
+// kernel headers and the per-handle Pipeline<W> that sequences them.  (Its device and pinned memory: device_mem.h.)
 //
 // Reference rows replaced (the Rust lives in rust/sparrowhawk-asm, NOT IN TREE,
 // so citations are to the observable phases in www/src/components/pages/AssemblyPage.vue):
@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "ctl_words.h"
+#include "device_mem.h"
 #include "kmer.h"
 #include "pipeline.h"
 #include "shard_comm.h"
@@ -36,14 +37,6 @@
 
 namespace shk {
 
-#define HIPCHK(call)                                                                      \
-    do {                                                                                  \
-        hipError_t _e = (call);                                                           \
-        if (_e != hipSuccess) {                                                           \
-            err = std::string(#call) + ": " + hipGetErrorString(_e);                      \
-            return -5;                                                                    \
-        }                                                                                 \
-    } while (0)
 // host wait on the pipeline's stream (inside Pipeline<W> methods with `err` in scope): during a collective call of more
 // than one rank the wait is the shard layer's watchdog (shard_comm.h: comm_stream_wait) — a peer that left or died cannot
 // hold this rank for ever
@@ -126,178 +119,6 @@ namespace shk {
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-// Process-wide cache of device allocations: a handle lives for one preprocess+assemble, and
-// hipMalloc/hipFree of its multi-GB buffers cost more than the kernels (measured ~10 ms/step).
-// Blocks are returned here on release and reused by the next handle; shk_release_cached_memory()
-// gives them back to the driver.
-// Peak device memory of a handle (the reference reports peak wasm memory with every assembly: Assembler.ts:69-71,137).
-// Every block the pool hands out is charged to the accounting context the calling thread carries (set by the C ABI's entry
-// points for the handle they serve) and released from the context it was charged to, whichever thread gives it back.
-struct MemAcct {
-    std::atomic<uint64_t> cur{0}, peak{0};
-    void add(uint64_t b) { const uint64_t c = cur.fetch_add(b) + b; uint64_t p = peak.load(); while (c > p && !peak.compare_exchange_weak(p, c)) {} }
-    void sub(uint64_t b) { cur.fetch_sub(b); }
-};
-static thread_local std::shared_ptr<MemAcct> tls_mem_acct;
-std::shared_ptr<void> mem_acct_new() { return std::static_pointer_cast<void>(std::make_shared<MemAcct>()); }
-std::shared_ptr<void> mem_acct_set(std::shared_ptr<void> a) {
-    std::shared_ptr<void> prev = std::static_pointer_cast<void>(tls_mem_acct);
-    tls_mem_acct = std::static_pointer_cast<MemAcct>(a);
-    return prev;
-}
-uint64_t mem_acct_peak(const std::shared_ptr<void> &a) { return a ? std::static_pointer_cast<MemAcct>(a)->peak.load() : 0; }
-uint64_t mem_acct_current(const std::shared_ptr<void> &a) { return a ? std::static_pointer_cast<MemAcct>(a)->cur.load() : 0; }
-void mem_acct_replay(const int64_t *deltas, size_t n, uint64_t *peak, uint64_t *current) {
-    MemAcct a;
-    for (size_t i = 0; i < n; i++) { if (deltas[i] >= 0) a.add((uint64_t)deltas[i]); else a.sub((uint64_t)(-deltas[i])); }
-    if (peak) *peak = a.peak.load();
-    if (current) *current = a.cur.load();
-}
-
-struct DevPool {
-    std::mutex mu;
-    std::multimap<std::pair<int, size_t>, void *> free_blocks;     // (device, bytes) -> block
-    struct Out { int dev; std::shared_ptr<MemAcct> acct; };
-    std::map<void *, Out> owner_dev;                               // every block handed out -> the device it lives on, who pays for it
-    bool enabled = true;
-    DevPool() { const char *v = getenv("SHK_NO_POOL"); enabled = !(v && *v == '1'); }
-    static int cur_dev() { int d = 0; (void)hipGetDevice(&d); return d; }
-    void *get(size_t &bytes, hipError_t &e) {
-        bytes = (bytes + 4095) & ~(size_t)4095;
-        // big scratch buffers vary a little from handle to handle: round them up so the cached block fits again
-        if (bytes > ((size_t)256 << 20)) bytes = (bytes + ((size_t)256 << 20) - 1) & ~(((size_t)256 << 20) - 1);
-        const int dev = cur_dev();
-        const std::shared_ptr<MemAcct> &acct = tls_mem_acct;
-        if (enabled) {
-            std::lock_guard<std::mutex> lk(mu);
-            auto it = free_blocks.lower_bound(std::make_pair(dev, bytes));
-            if (it != free_blocks.end() && it->first.first == dev && it->first.second <= bytes + bytes / 2 + (1u << 20)) {
-                void *p = it->second; bytes = it->first.second; free_blocks.erase(it); owner_dev[p] = Out{dev, acct}; e = hipSuccess;
-                if (acct) acct->add(bytes);
-                return p;
-            }
-        }
-        void *p = nullptr;
-        e = hipMalloc(&p, bytes);
-        if (e != hipSuccess && enabled) {              // out of memory: drop the cache and retry once
-            trim();
-            e = hipMalloc(&p, bytes);
-        }
-        if (e == hipSuccess) { std::lock_guard<std::mutex> lk(mu); owner_dev[p] = Out{dev, acct}; if (acct) acct->add(bytes); }
-        return e == hipSuccess ? p : nullptr;
-    }
-    // a block goes back under the device it was allocated on, whatever device the calling thread has current
-    // (an FFI consumer may free a handle from another thread: the HIP current device is per thread)
-    void put(void *p, size_t bytes) {
-        if (!p) return;
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = owner_dev.find(p);
-        const int dev = it != owner_dev.end() ? it->second.dev : cur_dev();
-        if (it != owner_dev.end()) { if (it->second.acct) it->second.acct->sub(bytes); owner_dev.erase(it); }
-        if (!enabled) { (void)hipFree(p); return; }
-        free_blocks.emplace(std::make_pair(dev, bytes), p);
-    }
-    void trim() {
-        std::lock_guard<std::mutex> lk(mu);
-        for (auto &kv : free_blocks) (void)hipFree(kv.second);
-        free_blocks.clear();
-    }
-};
-static DevPool &dev_pool() { static DevPool *p = new DevPool(); return *p; }   // never destroyed (HIP teardown order)
-void device_pool_trim() { dev_pool().trim(); }
-void *device_pool_alloc(size_t &bytes) { hipError_t e; return dev_pool().get(bytes, e); }
-void device_pool_release(void *p, size_t bytes) { dev_pool().put(p, bytes); }
-
-// A DevBuf that goes out of scope while an entry point of the C ABI runs is parked until that entry point has drained the
-// handle's stream (DeferScope, pipeline.h): an early `return rc` may destroy buffers that kernels, collectives or copies
-// still in flight use, and the pool hands a freed block to whichever handle asks next (two handles in flight: batch.py).
-// Explicit release() calls — made where the code knows the stream is idle — go to the pool at once.
-static thread_local std::vector<std::pair<void *, size_t>> *tls_defer = nullptr;
-template <typename T> struct DevBuf {
-    T *p = nullptr; size_t n = 0; size_t bytes = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() {
-        if (p && tls_defer) {
-            try { tls_defer->push_back(std::make_pair((void *)p, bytes)); p = nullptr; n = 0; bytes = 0; return; }
-            catch (...) {}                                 // (no room for the note: give the block back now)
-        }
-        release();
-    }
-    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(bytes, o.bytes); }
-    void release() { if (p) { dev_pool().put(p, bytes); p = nullptr; n = 0; bytes = 0; } }
-    int alloc(size_t count, std::string &err) {
-        release();
-        if (count == 0) count = 1;
-        size_t b = count * sizeof(T);
-        hipError_t e;
-        p = (T *)dev_pool().get(b, e);
-        if (!p) { err = std::string("hipMalloc: ") + hipGetErrorString(e); return -4; }
-        n = count; bytes = b; return 0;
-    }
-};
-
-// pinned host staging buffer (D2H of contigs at full PCIe rate), cached the same way
-struct PinnedBuf {
-    char *p = nullptr; size_t bytes = 0;
-    static std::mutex &mu() { static std::mutex m; return m; }
-    static std::multimap<size_t, void *> &cache() { static auto *c = new std::multimap<size_t, void *>(); return *c; }
-    ~PinnedBuf() { if (p) { std::lock_guard<std::mutex> lk(mu()); cache().emplace(bytes, p); } }
-    int alloc(size_t b, std::string &err) {
-        b = (b + 4095) & ~(size_t)4095; if (!b) b = 4096;
-        if (p && bytes >= b) return 0;
-        if (p) { std::lock_guard<std::mutex> lk(mu()); cache().emplace(bytes, p); p = nullptr; bytes = 0; }
-        {
-            std::lock_guard<std::mutex> lk(mu());
-            auto it = cache().lower_bound(b);
-            if (it != cache().end() && it->first <= 2 * b + (1u << 20)) { p = (char *)it->second; bytes = it->first; cache().erase(it); return 0; }
-        }
-        hipError_t e = hipHostMalloc((void **)&p, b, hipHostMallocDefault);
-        if (e != hipSuccess) { p = nullptr; err = std::string("hipHostMalloc: ") + hipGetErrorString(e); return -4; }
-        bytes = b; return 0;
-    }
-};
-
-DeferScope::DeferScope(IPipeline *pipe) : pipe_(pipe) {
-    auto *v = new (std::nothrow) std::vector<std::pair<void *, size_t>>();
-    if (v) { try { v->reserve(256); } catch (...) {} }
-    list_ = v; prev_ = tls_defer; tls_defer = v;
-}
-DeferScope::~DeferScope() {
-    auto *v = (std::vector<std::pair<void *, size_t>> *)list_;
-    tls_defer = (std::vector<std::pair<void *, size_t>> *)prev_;
-    if (!v) return;
-    if (!v->empty()) {
-        if (pipe_) pipe_->drain();                        // nothing in flight reads or writes the parked blocks any more
-        else (void)hipDeviceSynchronize();
-        for (auto &b : *v) dev_pool().put(b.first, b.second);
-    }
-    delete v;
-}
-
-// streams of freed handles are reused too (create + destroy cost ~0.2 ms per handle); every use of a
-// handle's stream ends in a synchronize, so a pooled stream is idle
-static std::mutex g_stream_mu;
-static std::multimap<int, hipStream_t> &stream_cache() { static auto *c = new std::multimap<int, hipStream_t>(); return *c; }
-// (key: device, or device + 1000 for the copy streams of the host-buffer entry points — creating and destroying one per
-// handle cost ~1 ms of the 5.7 ms a step from host pinned memory took: profiles/r04)
-static hipStream_t stream_pool_get(int dev) {
-    std::lock_guard<std::mutex> lk(g_stream_mu);
-    auto it = stream_cache().find(dev);
-    if (it == stream_cache().end()) return nullptr;
-    hipStream_t s = it->second; stream_cache().erase(it); return s;
-}
-static void stream_pool_put(int dev, hipStream_t s) {
-    {
-        std::lock_guard<std::mutex> lk(g_stream_mu);
-        if (stream_cache().size() < 32) { stream_cache().emplace(dev, s); return; }
-    }
-    (void)hipStreamDestroy(s);
-}
-
-static std::mutex &upload_token(int dev) { static std::mutex m[16]; return m[(unsigned)dev % 16u]; }
-
 static inline int grid_for(uint64_t work, int block = 256, int max_blocks = 256 * 16) {
     uint64_t b = (work + block - 1) / block;
     if (b < 1) b = 1;
@@ -2814,19 +2635,6 @@ private:
     uint64_t rt_extra_host_ = 0;
 };
 
-int current_device() { int d = 0; (void)hipGetDevice(&d); return d; }
-int set_device(int dev) { int prev = 0; (void)hipGetDevice(&prev); if (prev != dev) (void)hipSetDevice(dev); return prev; }
-int device_download(void *host, const void *dptr, size_t bytes, std::string &err) {
-    HIPCHK(hipMemcpy(host, dptr, bytes, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int device_count() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
 IPipeline *make_pipeline(int k, std::string &err) {
     if (device_count() <= 0) { err = "no HIP device available (libshk_hip has no CPU fallback)"; return nullptr; }
     const int W = (2 * k + 63) / 64;
@@ -2843,22 +2651,6 @@ IPipeline *make_pipeline(int k, std::string &err) {
     else { err = "k too large for the compiled key widths"; return nullptr; }
     if (rc != 0) { delete p; return nullptr; }
     return p;
-}
-
-int device_upload(const void *host, size_t bytes, void **dptr, std::string &err) {
-    *dptr = nullptr;
-    HIPCHK(hipMalloc(dptr, bytes ? bytes : 4));
-    if (bytes) {
-        hipError_t e = hipMemcpy(*dptr, host, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(*dptr); *dptr = nullptr; err = hipGetErrorString(e); return -5; }
-    }
-    return 0;
-}
-void device_free(void *dptr) { if (dptr) (void)hipFree(dptr); }
-int device_stream_sync(void *stream, std::string &err) { HIPCHK(hipStreamSynchronize((hipStream_t)stream)); return 0; }
-int device_copy_h2d_async(void *dst, const void *src, size_t bytes, void *stream, std::string &err) {
-    if (bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
-    return 0;
 }
 
 // ---- host-side self-test helpers (same arithmetic as the kernels) ---------------------------

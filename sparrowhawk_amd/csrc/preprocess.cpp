@@ -629,24 +629,26 @@ int preprocess_packed_host_impl(shk_handle *h, const uint32_t *bases, const uint
     if (!bases || !seg_off) return fail(h, SHK_E_PARAM, "null host pointer");
     if (n_bases >= 0xFFFFFFFFull || n_seg >= 0xFFFFFFFFull) return fail(h, SHK_E_PARAM, "batch too large (>= 2^32 bases)");
     std::string err;
-    struct Block { void *p = nullptr; size_t bytes = 0; ~Block() { if (p) device_pool_release(p, bytes); } } db, ds;
-    db.bytes = (size_t)((n_bases + 15) / 16 + 1) * 4; ds.bytes = (size_t)(n_seg + 1) * 4;
-    const size_t want_b = db.bytes, want_s = ds.bytes;
-    db.p = device_pool_alloc(db.bytes); ds.p = device_pool_alloc(ds.bytes);
-    if (!db.p || !ds.p) return fail(h, SHK_E_OOM, "preprocess: device memory for the packed reads");
-    const double t0 = now_ms();
+    const size_t want_b = (size_t)((n_bases + 15) / 16 + 1) * 4, want_s = (size_t)(n_seg + 1) * 4;
     void *st = h->pipe->stream();
-    h->post_start();
-    h->n_reads = n_reads;
-    h->post_mode(("loop:" + std::to_string(n_reads) + ":100").c_str());
-    // upload and pass 1 overlap piece by piece (Pipeline::count_batch_host), then histogram / fit / filter as usual
-    h->batches_started++;
-    h->pipe->single_batch_resident(true);
-    int rc = h->pipe->count_batch_host((uint32_t *)db.p, (uint32_t *)ds.p, bases, seg_off, n_seg, n_bases, err);
-    if (rc) rc = fail_rc(h, Rc::Device, rc, err);
-    else rc = finish_counting(h);
-    h->pipe->single_batch_resident(false);
-    { std::string e2; (void)device_stream_sync(st, e2); }      // the blocks go back to the pool idle, also after a failure
+    double t0 = 0;
+    int rc = 0;
+    {   // (the scope ends in front of the host-clock total: its drain is part of the figure)
+        PoolScope sc(st);                                      // the blocks go back to the pool idle, also after a failure
+        uint32_t *db = sc.get<uint32_t>(want_b / 4, err), *ds = sc.get<uint32_t>(want_s / 4, err);
+        if (!db || !ds) return fail(h, SHK_E_OOM, "preprocess: device memory for the packed reads");
+        t0 = now_ms();
+        h->post_start();
+        h->n_reads = n_reads;
+        h->post_mode(("loop:" + std::to_string(n_reads) + ":100").c_str());
+        // upload and pass 1 overlap piece by piece (Pipeline::count_batch_host), then histogram / fit / filter as usual
+        h->batches_started++;
+        h->pipe->single_batch_resident(true);
+        rc = h->pipe->count_batch_host(db, ds, bases, seg_off, n_seg, n_bases, err);
+        if (rc) rc = fail_rc(h, Rc::Device, rc, err);
+        else rc = finish_counting(h);
+        h->pipe->single_batch_resident(false);
+    }
     h->pipe->times().add("h2d_packed_reads_MB", (double)(want_b + want_s) / 1e6);
     h->pipe->times().add("preprocess_from_host_total_host_clock", now_ms() - t0);
     return rc;
@@ -751,7 +753,7 @@ int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n
             if (int rc = gpu_upload_text(F.t + F.s0, (size_t)(F.s1 - F.s0), device, text, err)) return code_of(Rc::DeviceNoParam, rc);
             out.uploaded_bytes += text.e;
             spans[i].len = text.e; spans[i].unterminated = text.unterminated;
-            spans[i].blk.bytes = text.pool_bytes; spans[i].blk.p = text.d;
+            spans[i].blk = PoolBlock(text.d, text.pool_bytes);
             static_cast<GpuText &>(text) = GpuText();      // (the block is the span's now)
             F.route = F.gz ? Host : TextSlice;
         }

@@ -14,7 +14,7 @@
 #include <string.h>
 
 #include "shard_comm.h"
-#include "pipeline.h"
+#include "device_mem.h"
 
 namespace shk {
 
@@ -317,19 +317,14 @@ int comm_allgatherv(ShardComm *c, const void *d_send, void *d_recv, const uint64
 }
 
 // ---- small host-side collectives ---------------------------------------------------------------------
-namespace {
-struct PoolBlock {
-    void *p = nullptr; size_t bytes = 0;
-    explicit PoolBlock(size_t b, bool unused = false) : bytes(b ? b : 8) { if (!unused) p = device_pool_alloc(bytes); }
-    ~PoolBlock() { if (p) device_pool_release(p, bytes); }
-};
-}  // namespace
 
 int comm_allreduce_host_u64(ShardComm *c, uint64_t *host_inout, size_t n, void *stream, std::string &err) {
     if (!n) return 0;
     if (!c) { err = "comm: not initialised"; return -1; }
-    PoolBlock b(n * 8 <= c->stage_bytes ? 0 : n * 8, n * 8 <= c->stage_bytes);
-    void *buf = n * 8 <= c->stage_bytes ? c->stage : b.p;
+    const bool fits = n * 8 <= c->stage_bytes;
+    PoolBlock b;                                          // (what does not fit the communicator's staging block)
+    if (!fits) b.get(n * 8);
+    void *buf = fits ? c->stage : b.p;
     if (!buf) { err = "device allocation failed (all-reduce staging)"; return -4; }
     hipStream_t st = (hipStream_t)stream;
     if (hipMemcpyAsync(buf, host_inout, n * 8, hipMemcpyHostToDevice, st) != hipSuccess) { err = "hipMemcpyAsync failed"; return -5; }
@@ -345,7 +340,8 @@ int comm_allgather_host_u64(ShardComm *c, const uint64_t *host_in, size_t n, uin
     if (!c) { err = "comm: not initialised"; return -1; }
     const size_t world = (size_t)comm_world(c);
     const bool fits = n * 8 * (world + 1) <= c->stage_bytes;
-    PoolBlock blk(fits ? 0 : n * 8 * (world + 1), fits);
+    PoolBlock blk;
+    if (!fits) blk.get(n * 8 * (world + 1));
     char *base = fits ? (char *)c->stage : (char *)blk.p;
     if (!base) { err = "device allocation failed (all-gather staging)"; return -4; }
     void *in = base, *out = base + n * 8;

@@ -24,9 +24,8 @@
 #include <thread>
 #include <vector>
 
-#include "inflate_gpu.h"
+#include "device_mem.h"
 #include "kmer.h"
-#include "pipeline.h"
 #include "unitig_graph_gpu.h"
 
 namespace shk {
@@ -566,14 +565,7 @@ __global__ __launch_bounds__(256) void k_uc_place(UChainIn g, const uint32_t *__
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-#define UGCHK(call)                                                                                \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            err = std::string("unitig graph on the device: " #call ": ") + hipGetErrorString(e_);    \
-            return -5;                                                                               \
-        }                                                                                            \
-    } while (0)
+#define UGCHK(call) HIPCHK_AS("unitig graph on the device: " #call, call, (void)0)
 
 // workgroups per launch: two per CU of a 256-CU card (8 waves per CU keep the dependent reads of the probes and walks in
 // flight), the rest of the records by the grid stride — from 131 072 records on every thread takes more than one
@@ -581,9 +573,6 @@ unsigned ug_grid(uint64_t n) {
     const uint64_t b = (n + 255) / 256;
     return (unsigned)(b < 1 ? 1 : (b > 512 ? 512 : b));
 }
-
-// the blocks go back to the pool when the caller returns: nothing may still be running on them then
-struct DrainOnExit { hipStream_t st; ~DrainOnExit() { (void)hipStreamSynchronize(st); } };
 
 // SHK_UNITIG_CHAINS_DEVICE=0: the chains are walked by the host's unitig_chains, from alive / mirror / succ copied home
 bool chains_on_device() { const char *e = getenv("SHK_UNITIG_CHAINS_DEVICE"); return !(e && *e == '0'); }
@@ -603,34 +592,40 @@ hipError_t uc_scans(void *tmp, size_t &bytes, const uint32_t *h_cnt, const unsig
     return e;
 }
 
-// The device blocks of the walk.  Taken by the caller together with its own, before any work.
+// The device blocks of the walk, out of the caller's scope (taken together with its own, before any work), and the host ends
+// of the walk's copies: the caller declares this in front of its PoolScope, so that they outlive the scope's drain.
 struct ChainBlocks {
-    Blk pred, up[2], idx[2], nodes[2], kc[2], h_text, c_idx, rec_off, text_off, lin, place, flat, rings, tmp, ctl;
-    size_t tmp_bytes = 0;
-    bool get(size_t n) {
+    uint32_t *pred = nullptr, *c_idx = nullptr, *rec_off = nullptr, *flat = nullptr;
+    URank rk[2];
+    unsigned long long *h_text = nullptr, *text_off = nullptr, *ctl = nullptr;
+    UnitigFlatContig *lin = nullptr; UnitigPlace *place = nullptr; UnitigRingRec *rings = nullptr;
+    void *tmp = nullptr; size_t tmp_bytes = 0;
+    unsigned long long h_ctl[UC_WORDS];
+    std::vector<UnitigRingRec> h_rings;
+    bool get(PoolScope &sc, size_t n) {
+        std::string oom;
         if (uc_scans(nullptr, tmp_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, (int)(n + 1), nullptr) != hipSuccess) return false;
         for (int i = 0; i < 2; i++)
-            if (!up[i].get(n * 4) || !idx[i].get((n + 1) * 4) || !nodes[i].get(n * 8) || !kc[i].get(n * 8)) return false;
-        return pred.get(n * 4) && h_text.get((n + 1) * 8) && c_idx.get((n + 1) * 4) && rec_off.get((n + 1) * 4) && text_off.get((n + 1) * 8) &&
-               lin.get(n * sizeof(UnitigFlatContig)) && place.get(n * sizeof(UnitigPlace)) && flat.get(n * 4) &&
-               rings.get(n * sizeof(UnitigRingRec)) && tmp.get(tmp_bytes) && ctl.get(UC_WORDS * 8);
+            if (!(rk[i].up = sc.get<uint32_t>(n, oom)) || !(rk[i].idx = sc.get<uint32_t>(n + 1, oom)) ||
+                !(rk[i].nodes = sc.get<unsigned long long>(n, oom)) || !(rk[i].kc = sc.get<unsigned long long>(n, oom))) return false;
+        return (pred = sc.get<uint32_t>(n, oom)) && (h_text = sc.get<unsigned long long>(n + 1, oom)) && (c_idx = sc.get<uint32_t>(n + 1, oom)) &&
+               (rec_off = sc.get<uint32_t>(n + 1, oom)) && (text_off = sc.get<unsigned long long>(n + 1, oom)) && (lin = sc.get<UnitigFlatContig>(n, oom)) &&
+               (place = sc.get<UnitigPlace>(n, oom)) && (flat = sc.get<uint32_t>(n, oom)) && (rings = sc.get<UnitigRingRec>(n, oom)) &&
+               (tmp = sc.get<uint8_t>(tmp_bytes, oom)) && (ctl = sc.get<unsigned long long>(UC_WORDS, oom));
     }
 };
 
 // The walk: out.lin / recs_flat / place / lin_text from the device, the rings through unitig_ring_chains.  The caller holds
-// the blocks and drains the stream on its way out.  One host read per jumping round (the count of unfinished records), one
-// of the totals, then the results.
+// the blocks, and its scope drains the stream on the way out.  One host read per jumping round (the count of unfinished
+// records), one of the totals, then the results.
 template <int W> int chains_walk_t(const UChainIn &g, const std::vector<UnitigRec> &recs, ChainBlocks &b, hipStream_t st,
                                    UnitigGraphResult &out, std::string &err) {
     const size_t n = g.n;
     const dim3 grid(ug_grid(n)), block(256);
-    unsigned long long *ctl = (unsigned long long *)b.ctl.p;
-    uint32_t *pred = (uint32_t *)b.pred.p;
-    URank rk[2];
-    for (int i = 0; i < 2; i++) rk[i] = URank{(uint32_t *)b.up[i].p, (uint32_t *)b.idx[i].p, (unsigned long long *)b.nodes[i].p, (unsigned long long *)b.kc[i].p};
-    unsigned long long h_ctl[UC_WORDS];
-    std::vector<UnitigRingRec> rings;
-    DrainOnExit drain{st};                                        // (behind the host ends of the copies: they outlive it)
+    unsigned long long *ctl = b.ctl, *h_ctl = b.h_ctl;
+    uint32_t *pred = b.pred;
+    const URank *rk = b.rk;
+    std::vector<UnitigRingRec> &rings = b.h_rings;
     UGCHK(hipMemsetAsync(ctl, 0, UC_WORDS * 8, st));
     UGCHK(hipMemsetAsync(pred, 0xFF, n * 4, st));
     hipLaunchKernelGGL(k_uc_pred, grid, block, 0, st, g, pred);
@@ -657,19 +652,19 @@ template <int W> int chains_walk_t(const UChainIn &g, const std::vector<UnitigRe
     }
     // the other set of arrays is free from here on: the totals by head go there
     const URank a = rk[cur], o = rk[cur ^ 1];
-    uint32_t *h_cnt = o.idx, *c_idx = (uint32_t *)b.c_idx.p, *rec_off = (uint32_t *)b.rec_off.p;
-    unsigned long long *h_nodes = o.nodes, *h_kc = o.kc, *h_text = (unsigned long long *)b.h_text.p, *text_off = (unsigned long long *)b.text_off.p;
+    uint32_t *h_cnt = o.idx, *c_idx = b.c_idx, *rec_off = b.rec_off;
+    unsigned long long *h_nodes = o.nodes, *h_kc = o.kc, *h_text = b.h_text, *text_off = b.text_off;
     UGCHK(hipMemsetAsync(h_cnt, 0, (n + 1) * 4, st));
     UGCHK(hipMemsetAsync(h_text, 0, (n + 1) * 8, st));
     hipLaunchKernelGGL(k_uc_tails<W>, grid, block, 0, st, g, (const uint32_t *)pred, a, h_cnt, h_nodes, h_kc, h_text);
     UGCHK(hipGetLastError());
     size_t tmp_bytes = b.tmp_bytes;
-    UGCHK(uc_scans(b.tmp.p, tmp_bytes, h_cnt, h_text, c_idx, rec_off, text_off, (int)(n + 1), st));
+    UGCHK(uc_scans(b.tmp, tmp_bytes, h_cnt, h_text, c_idx, rec_off, text_off, (int)(n + 1), st));
     hipLaunchKernelGGL(k_uc_totals, dim3(1), dim3(64), 0, st, (uint32_t)n, (const uint32_t *)c_idx, (const uint32_t *)rec_off, (const unsigned long long *)text_off, ctl);
     hipLaunchKernelGGL(k_uc_contigs, grid, block, 0, st, (uint32_t)n, (const uint32_t *)h_cnt, (const unsigned long long *)h_nodes, (const unsigned long long *)h_kc,
-                       (const uint32_t *)c_idx, (const uint32_t *)rec_off, (const unsigned long long *)text_off, (UnitigFlatContig *)b.lin.p);
+                       (const uint32_t *)c_idx, (const uint32_t *)rec_off, (const unsigned long long *)text_off, b.lin);
     hipLaunchKernelGGL(k_uc_place, grid, block, 0, st, g, (const uint32_t *)pred, a, (const uint32_t *)h_cnt, (const uint32_t *)rec_off,
-                       (const unsigned long long *)text_off, (UnitigPlace *)b.place.p, (uint32_t *)b.flat.p, (UnitigRingRec *)b.rings.p, ctl + UC_NRING);
+                       (const unsigned long long *)text_off, b.place, b.flat, b.rings, ctl + UC_NRING);
     UGCHK(hipGetLastError());
     UGCHK(hipMemcpyAsync(h_ctl, ctl, 4 * 8, hipMemcpyDeviceToHost, st));
     UGCHK(hipStreamSynchronize(st));
@@ -679,10 +674,10 @@ template <int W> int chains_walk_t(const UChainIn &g, const std::vector<UnitigRe
     out.lin_text = h_ctl[UC_NTEXT];
     out.lin.resize(n_contig); out.recs_flat.resize(n_rec); out.place.resize(n);
     rings.resize(n_ring);
-    if (n_contig) UGCHK(hipMemcpyAsync(out.lin.data(), b.lin.p, n_contig * sizeof(UnitigFlatContig), hipMemcpyDeviceToHost, st));
-    if (n_rec) UGCHK(hipMemcpyAsync(out.recs_flat.data(), b.flat.p, n_rec * 4, hipMemcpyDeviceToHost, st));
-    UGCHK(hipMemcpyAsync(out.place.data(), b.place.p, n * sizeof(UnitigPlace), hipMemcpyDeviceToHost, st));
-    if (n_ring) UGCHK(hipMemcpyAsync(rings.data(), b.rings.p, n_ring * sizeof(UnitigRingRec), hipMemcpyDeviceToHost, st));
+    if (n_contig) UGCHK(hipMemcpyAsync(out.lin.data(), b.lin, n_contig * sizeof(UnitigFlatContig), hipMemcpyDeviceToHost, st));
+    if (n_rec) UGCHK(hipMemcpyAsync(out.recs_flat.data(), b.flat, n_rec * 4, hipMemcpyDeviceToHost, st));
+    UGCHK(hipMemcpyAsync(out.place.data(), b.place, n * sizeof(UnitigPlace), hipMemcpyDeviceToHost, st));
+    if (n_ring) UGCHK(hipMemcpyAsync(rings.data(), b.rings, n_ring * sizeof(UnitigRingRec), hipMemcpyDeviceToHost, st));
     UGCHK(hipStreamSynchronize(st));
     return unitig_ring_chains(recs, std::move(rings), out, err);
 }
@@ -714,17 +709,21 @@ template <int W> int assemble_device_t(int k, const std::vector<UnitigRec> &recs
     std::vector<uint8_t> h_circ, alive;
     std::vector<uint32_t> mirror, succ;
     unsigned long long h_ctl[CTL_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // ---- device blocks: all of them before any work, so that "no memory" leaves nothing behind
-    const size_t rec_words = (size_t)(2 * W + 2) * n;             // first[W][n], last[W][n], len[n], kc[n]
-    Blk d_rec, d_circ, d_slot, d_mirror, d_outn, d_alive, d_mark, d_succ, d_cand, d_tips, d_kill, d_head, d_ctl;
     ChainBlocks cb;
-    if (!d_rec.get(rec_words * 8) || !d_circ.get(n) || !d_slot.get((size_t)cap * 8) || !d_mirror.get(n * 4) || !d_outn.get(n * 16) ||
-        !d_alive.get(n) || !d_mark.get(n) || !d_succ.get(n * 4) || !d_cand.get(n * 4) || !d_tips.get(n * sizeof(UTip)) ||
-        !d_kill.get(n) || !d_head.get(n * 4) || !d_ctl.get(CTL_WORDS * 8) || (walk && !cb.get(n))) {
+    // ---- device blocks: all of them before any work, so that "no memory" leaves nothing behind.  They go back to the pool
+    // when this function returns, behind the scope's drain: nothing may still be running on them then
+    const size_t rec_words = (size_t)(2 * W + 2) * n;             // first[W][n], last[W][n], len[n], kc[n]
+    PoolScope sc(st);
+    std::string oom;
+    uint64_t *d_rec; uint8_t *d_circ, *d_alive, *d_mark, *d_kill; unsigned long long *d_slot, *d_ctl; uint32_t *d_mirror, *d_outn, *d_succ, *d_cand, *d_head; UTip *d_tips;
+    if (!(d_rec = sc.get<uint64_t>(rec_words, oom)) || !(d_circ = sc.get<uint8_t>(n, oom)) || !(d_slot = sc.get<unsigned long long>((size_t)cap, oom)) ||
+        !(d_mirror = sc.get<uint32_t>(n, oom)) || !(d_outn = sc.get<uint32_t>(n * 4, oom)) || !(d_alive = sc.get<uint8_t>(n, oom)) ||
+        !(d_mark = sc.get<uint8_t>(n, oom)) || !(d_succ = sc.get<uint32_t>(n, oom)) || !(d_cand = sc.get<uint32_t>(n, oom)) ||
+        !(d_tips = sc.get<UTip>(n, oom)) || !(d_kill = sc.get<uint8_t>(n, oom)) || !(d_head = sc.get<uint32_t>(n, oom)) ||
+        !(d_ctl = sc.get<unsigned long long>(CTL_WORDS, oom)) || (walk && !cb.get(sc, n))) {
         (void)hipGetLastError();
         return 1;
     }
-    DrainOnExit drain{st};
     // ---- records as structure-of-arrays (several host threads from the size on at which the host code uses them)
     h_rec.resize(rec_words); h_circ.resize(n);
     {
@@ -744,26 +743,26 @@ template <int W> int assemble_device_t(int k, const std::vector<UnitigRec> &recs
         for (auto &t : ts) t.join();
     }
     lap("transpose");
-    UGCHK(hipMemcpyAsync(d_rec.p, h_rec.data(), rec_words * 8, hipMemcpyHostToDevice, st));
-    UGCHK(hipMemcpyAsync(d_circ.p, h_circ.data(), n, hipMemcpyHostToDevice, st));
-    UGCHK(hipMemsetAsync(d_slot.p, 0xFF, (size_t)cap * 8, st));
-    UGCHK(hipMemsetAsync(d_mirror.p, 0xFF, n * 4, st));
-    UGCHK(hipMemsetAsync(d_outn.p, 0xFF, n * 16, st));
-    UGCHK(hipMemsetAsync(d_mark.p, 0, n, st));
-    UGCHK(hipMemsetAsync(d_ctl.p, 0, CTL_WORDS * 8, st));
+    UGCHK(hipMemcpyAsync(d_rec, h_rec.data(), rec_words * 8, hipMemcpyHostToDevice, st));
+    UGCHK(hipMemcpyAsync(d_circ, h_circ.data(), n, hipMemcpyHostToDevice, st));
+    UGCHK(hipMemsetAsync(d_slot, 0xFF, (size_t)cap * 8, st));
+    UGCHK(hipMemsetAsync(d_mirror, 0xFF, n * 4, st));
+    UGCHK(hipMemsetAsync(d_outn, 0xFF, n * 16, st));
+    UGCHK(hipMemsetAsync(d_mark, 0, n, st));
+    UGCHK(hipMemsetAsync(d_ctl, 0, CTL_WORDS * 8, st));
     lap("upload");
     UGraph<W> g;
-    g.F = (const uint64_t *)d_rec.p; g.T = g.F + (size_t)W * n; g.len = g.T + (size_t)W * n; g.kc = g.len + n;
-    g.circ = (const uint8_t *)d_circ.p; g.mirror = (uint32_t *)d_mirror.p; g.outn = (uint32_t *)d_outn.p; g.alive = (uint8_t *)d_alive.p;
+    g.F = d_rec; g.T = g.F + (size_t)W * n; g.len = g.T + (size_t)W * n; g.kc = g.len + n;
+    g.circ = d_circ; g.mirror = d_mirror; g.outn = d_outn; g.alive = d_alive;
     g.n = (uint32_t)n; g.k = k;
-    unsigned long long *ctl = (unsigned long long *)d_ctl.p;
+    unsigned long long *ctl = d_ctl;
     unsigned int *flags = (unsigned int *)(ctl + CTL_FLAGS);
     unsigned int *n_cand = (unsigned int *)(ctl + CTL_NCAND), *n_tips = (unsigned int *)(ctl + CTL_NTIPS), *n_fork = (unsigned int *)(ctl + CTL_NFORK);
-    uint8_t *mark = (uint8_t *)d_mark.p;
+    uint8_t *mark = d_mark;
     const dim3 grid(ug_grid(n)), block(256);
     // ---- index and links; one read of the flags
-    hipLaunchKernelGGL(k_ug_insert<W>, grid, block, 0, st, g, (unsigned long long *)d_slot.p, cap, flags);
-    hipLaunchKernelGGL(k_ug_links<W>, grid, block, 0, st, g, (const unsigned long long *)d_slot.p, cap, flags);
+    hipLaunchKernelGGL(k_ug_insert<W>, grid, block, 0, st, g, d_slot, cap, flags);
+    hipLaunchKernelGGL(k_ug_links<W>, grid, block, 0, st, g, d_slot, cap, flags);
     hipLaunchKernelGGL(k_ug_pairs<W>, grid, block, 0, st, g, flags);
     UGCHK(hipGetLastError());
     UGCHK(hipMemcpyAsync(h_ctl, ctl, 8, hipMemcpyDeviceToHost, st));
@@ -781,16 +780,16 @@ template <int W> int assemble_device_t(int k, const std::vector<UnitigRec> &recs
         for (int round = 0; round < 32; round++) {                // MAX_ROUNDS (S9)
             UGCHK(hipMemsetAsync(ctl + 1, 0, (CTL_WORDS - 1) * 8, st));
             if (tips) {
-                UGCHK(hipMemsetAsync(d_head.p, 0xFF, n * 4, st));
-                hipLaunchKernelGGL(k_ug_tip_candidates<W>, grid, block, 0, st, g, (uint32_t *)d_cand.p, n_cand);
-                hipLaunchKernelGGL(k_ug_tip_walk<W>, grid, block, 0, st, g, (const uint32_t *)d_cand.p, n_cand, (UTip *)d_tips.p, n_tips, (uint32_t *)d_head.p);
-                hipLaunchKernelGGL(k_ug_tip_decide<W>, grid, block, 0, st, g, (const UTip *)d_tips.p, n_tips, (const uint32_t *)d_head.p, (uint8_t *)d_kill.p);
-                hipLaunchKernelGGL(k_ug_tip_remove<W>, grid, block, 0, st, g, (const UTip *)d_tips.p, n_tips, (const uint8_t *)d_kill.p, mark);
+                UGCHK(hipMemsetAsync(d_head, 0xFF, n * 4, st));
+                hipLaunchKernelGGL(k_ug_tip_candidates<W>, grid, block, 0, st, g, d_cand, n_cand);
+                hipLaunchKernelGGL(k_ug_tip_walk<W>, grid, block, 0, st, g, d_cand, n_cand, d_tips, n_tips, d_head);
+                hipLaunchKernelGGL(k_ug_tip_decide<W>, grid, block, 0, st, g, d_tips, n_tips, d_head, d_kill);
+                hipLaunchKernelGGL(k_ug_tip_remove<W>, grid, block, 0, st, g, d_tips, n_tips, d_kill, mark);
                 hipLaunchKernelGGL(k_ug_apply<W>, grid, block, 0, st, g, mark, ctl + CTL_TIP_NODES);
             }
             if (bubbles) {                                        // on the graph the tip round left
-                hipLaunchKernelGGL(k_ug_fork_candidates<W>, grid, block, 0, st, g, (uint32_t *)d_cand.p, n_fork);
-                hipLaunchKernelGGL(k_ug_bubble<W>, grid, block, 0, st, g, (const uint32_t *)d_cand.p, n_fork, mark);
+                hipLaunchKernelGGL(k_ug_fork_candidates<W>, grid, block, 0, st, g, d_cand, n_fork);
+                hipLaunchKernelGGL(k_ug_bubble<W>, grid, block, 0, st, g, d_cand, n_fork, mark);
                 hipLaunchKernelGGL(k_ug_apply<W>, grid, block, 0, st, g, mark, ctl + CTL_BUB_NODES);
             }
             UGCHK(hipGetLastError());
@@ -803,12 +802,12 @@ template <int W> int assemble_device_t(int k, const std::vector<UnitigRec> &recs
     }
     lap("rounds");
     // ---- simple successors; then the walk of the chains, here —
-    hipLaunchKernelGGL(k_ug_succ<W>, grid, block, 0, st, g, (uint32_t *)d_succ.p);
+    hipLaunchKernelGGL(k_ug_succ<W>, grid, block, 0, st, g, d_succ);
     UGCHK(hipGetLastError());
     if (walk) {
         lap("succ");
         UChainIn in;
-        in.F = g.F; in.len = g.len; in.kc = g.kc; in.circ = g.circ; in.alive = g.alive; in.mirror = g.mirror; in.succ = (const uint32_t *)d_succ.p;
+        in.F = g.F; in.len = g.len; in.kc = g.kc; in.circ = g.circ; in.alive = g.alive; in.mirror = g.mirror; in.succ = d_succ;
         in.n = g.n; in.k = k;
         const int rc = chains_walk_t<W>(in, recs, cb, st, out, err);
         lap("chains");
@@ -816,9 +815,9 @@ template <int W> int assemble_device_t(int k, const std::vector<UnitigRec> &recs
     }
     // ---- or alive / mirror / succ go home, and the host's own walk makes the contigs
     alive.resize(n); mirror.resize(n); succ.resize(n);
-    UGCHK(hipMemcpyAsync(alive.data(), d_alive.p, n, hipMemcpyDeviceToHost, st));
-    UGCHK(hipMemcpyAsync(mirror.data(), d_mirror.p, n * 4, hipMemcpyDeviceToHost, st));
-    UGCHK(hipMemcpyAsync(succ.data(), d_succ.p, n * 4, hipMemcpyDeviceToHost, st));
+    UGCHK(hipMemcpyAsync(alive.data(), d_alive, n, hipMemcpyDeviceToHost, st));
+    UGCHK(hipMemcpyAsync(mirror.data(), d_mirror, n * 4, hipMemcpyDeviceToHost, st));
+    UGCHK(hipMemcpyAsync(succ.data(), d_succ, n * 4, hipMemcpyDeviceToHost, st));
     UGCHK(hipStreamSynchronize(st));
     lap("succ");
     const int rc = unitig_chains(k, recs, alive, std::move(mirror), succ, out, err);
@@ -837,13 +836,15 @@ template <int W> int chains_device_t(int k, const std::vector<UnitigRec> &recs, 
     std::vector<uint64_t> h_rec;                                  // (declared first: outlives the drain of the stream)
     std::vector<uint8_t> h_circ;
     const size_t rec_words = (size_t)(W + 2) * n;                 // first[W][n], len[n], kc[n]
-    Blk d_rec, d_circ, d_alive, d_mirror, d_succ;
     ChainBlocks cb;
-    if (!d_rec.get(rec_words * 8) || !d_circ.get(n) || !d_alive.get(n) || !d_mirror.get(n * 4) || !d_succ.get(n * 4) || !cb.get(n)) {
+    PoolScope sc(st);                                             // (drains the stream before the blocks go back)
+    std::string oom;
+    uint64_t *d_rec; uint8_t *d_circ, *d_alive; uint32_t *d_mirror, *d_succ;
+    if (!(d_rec = sc.get<uint64_t>(rec_words, oom)) || !(d_circ = sc.get<uint8_t>(n, oom)) || !(d_alive = sc.get<uint8_t>(n, oom)) ||
+        !(d_mirror = sc.get<uint32_t>(n, oom)) || !(d_succ = sc.get<uint32_t>(n, oom)) || !cb.get(sc, n)) {
         (void)hipGetLastError();
         return 1;
     }
-    DrainOnExit drain{st};
     h_rec.resize(rec_words); h_circ.resize(n);
     {
         uint64_t *F = h_rec.data(), *len = F + (size_t)W * n, *kc = len + n;
@@ -853,15 +854,15 @@ template <int W> int chains_device_t(int k, const std::vector<UnitigRec> &recs, 
             len[r] = R.len; kc[r] = R.kc; h_circ[r] = R.circ ? 1 : 0;
         }
     }
-    UGCHK(hipMemcpyAsync(d_rec.p, h_rec.data(), rec_words * 8, hipMemcpyHostToDevice, st));
-    UGCHK(hipMemcpyAsync(d_circ.p, h_circ.data(), n, hipMemcpyHostToDevice, st));
-    UGCHK(hipMemcpyAsync(d_alive.p, alive.data(), n, hipMemcpyHostToDevice, st));
-    UGCHK(hipMemcpyAsync(d_mirror.p, mirror.data(), n * 4, hipMemcpyHostToDevice, st));
-    UGCHK(hipMemcpyAsync(d_succ.p, succ.data(), n * 4, hipMemcpyHostToDevice, st));
+    UGCHK(hipMemcpyAsync(d_rec, h_rec.data(), rec_words * 8, hipMemcpyHostToDevice, st));
+    UGCHK(hipMemcpyAsync(d_circ, h_circ.data(), n, hipMemcpyHostToDevice, st));
+    UGCHK(hipMemcpyAsync(d_alive, alive.data(), n, hipMemcpyHostToDevice, st));
+    UGCHK(hipMemcpyAsync(d_mirror, mirror.data(), n * 4, hipMemcpyHostToDevice, st));
+    UGCHK(hipMemcpyAsync(d_succ, succ.data(), n * 4, hipMemcpyHostToDevice, st));
     UChainIn in;
-    in.F = (const uint64_t *)d_rec.p; in.len = in.F + (size_t)W * n; in.kc = in.len + n;
-    in.circ = (const uint8_t *)d_circ.p; in.alive = (const uint8_t *)d_alive.p;
-    in.mirror = (const uint32_t *)d_mirror.p; in.succ = (const uint32_t *)d_succ.p;
+    in.F = d_rec; in.len = in.F + (size_t)W * n; in.kc = in.len + n;
+    in.circ = d_circ; in.alive = d_alive;
+    in.mirror = d_mirror; in.succ = d_succ;
     in.n = (uint32_t)n; in.k = k;
     return chains_walk_t<W>(in, recs, cb, st, out, err);
 }
