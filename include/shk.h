@@ -152,7 +152,12 @@ int shk_shard_set_solid(shk_handle *h, const void *const *d_keys /* [W] */, cons
  * rank; keep the communicator until it has returned): adjacency with one pairwise exchange of neighbour queries and one
  * of answers, non-branching paths contracted per rank and stitched across ranks, tips / bubbles on the graph of unitigs,
  * every rank writing the bases of its own k-mers into the contigs (csrc/shard_graph.h).  Every rank ends with the same
- * get_assembly() text; the stage-inspection getters then describe the rank's own rows.  With SHK_SHARD_GRAPH=0 in the
+ * get_assembly() text; the stage-inspection getters then describe the rank's own rows.  From SHK_DEVICE_WRITER_MIN contigs
+ * on (default 20 000, the knob of the one-GPU path) every rank writes that text on its GPU from the all-reduced contig
+ * text, which is then never downloaded (csrc/writer_text_gpu.h, the writer behind shk_device_assembly_json;
+ * SHK_SHARD_DEVICE_WRITER=0 keeps the host writer).  shk_get_timings then has "shard_writer_device_x1" = 1, the
+ * "device_writer_*" entries and "outputs_host_clock" = 0; a rank whose device declines (no memory, a contig of 2^32 bases,
+ * 2^31 contigs) reports "shard_writer_device_declined_x1" = 1 and runs the host writer alone — the same bytes.  With SHK_SHARD_GRAPH=0 in the
  * environment the solid set is gathered instead (all-gather of the solid rows) and shk_assemble() runs locally, on the
  * whole graph, on every rank.  A Rust host binds these five functions and never writes a collective itself. */
 #define SHK_UNIQUE_ID_BYTES 128
@@ -272,6 +277,20 @@ int shk_host_fit(const uint64_t *histo500, uint32_t *used_min_count); /* 1 ok, 0
  * unitigs handed in as text, any strand, any order: seqs = the spellings back to back, offsets[n+1] their
  * bounds, kc[n] their k-mer count sums.  Returns a malloc'd NUL-terminated JSON (shk_host_free) or NULL. */
 char *shk_host_assembly_json(const char *seqs, const uint64_t *offsets, const uint64_t *kc, uint64_t n_contigs, uint32_t k);
+/* The device twin of shk_host_assembly_json (csrc/writer_text_gpu.h; needs a GPU): the same parameters, the same JSON byte
+ * for byte.  It uploads the text and the arrays, runs the device writer from contig text alone on the current HIP device —
+ * strand choice and reverse complement in place, order, links from a table of the contigs' end k-mers, records and
+ * sequences — and returns a malloc'd NUL-terminated JSON (shk_host_free).  This is the writer the sharded shk_assemble
+ * runs on the all-reduced contig text.  n_contigs == 0 gives the host twin's empty-assembly JSON.
+ * NULL: bad parameters (the host twin's refusals: offsets not ascending, a contig shorter than k), out of device memory,
+ * a contig of >= 2^32 bases, >= 2^31 contigs; *why (optional) says which. */
+char *shk_device_assembly_json(const char *seqs, const uint64_t *offsets, const uint64_t *kc, uint64_t n_contigs, uint32_t k,
+                               const char **why);
+/* host-only (tests): the end keys of that writer, in the code the kernels share with the host (csrc/end_keys.h).
+ * out_words[W] (W = ceil(2k/64), w[0] least significant) = seq[0..k) packed, reverse-complemented first if rc != 0;
+ * *entry = the table word for that key with the given orientation and sorted position.  Of two entries with one key the
+ * smaller word wins.  Returns SHK_OK or SHK_E_PARAM. */
+int shk_host_end_key(const char *seq, uint32_t k, int rc, uint32_t orientation, uint32_t pos, uint64_t *out_words, uint64_t *entry);
 /* the same on text that arrives while the writer works, piece_bytes at a time every delay_us microseconds (the device path
  * downloads the contigs in pieces and the writer copies what is there: csrc/pipeline.h TextArrival) — same JSON */
 char *shk_host_assembly_json_arriving(const char *seqs, const uint64_t *offsets, const uint64_t *kc, uint64_t n_contigs, uint32_t k,

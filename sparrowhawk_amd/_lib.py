@@ -76,7 +76,9 @@ SIGNATURES = {
     "shk_host_nthash": (_u64, [_cp, _u32]),
     "shk_host_fit": (_int, [_vp, C.POINTER(_u32)]),
     "shk_host_assembly_json": (_vp, [_cp, _vp, _vp, _u64, _u32]),
-    "shk_host_assembly_json_arriving": (_vp, [_cp, _vp, _vp, _u64, _u32, _u64, _u32]),
+    "shk_device_assembly_json": (_vp, [_cp, _vp, _vp, _u64, _u32, C.POINTER(C.c_char_p)]),
+    "shk_host_end_key": (_int, [_cp, _u32, _int, _u32, _u32, _vp, C.POINTER(_u64)]),
+    "shk_host_assembly_json_arriving":(_vp, [_cp, _vp, _vp, _u64, _u32, _u64, _u32]),
     "shk_host_free": (None, [_vp]),
     "shk_host_gunzip": (_int, [_cp, _sz, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_u64), C.POINTER(C.c_double)]),
     "shk_device_gunzip": (_int, [_cp, _sz, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(C.c_char_p), C.POINTER(C.c_double)]),

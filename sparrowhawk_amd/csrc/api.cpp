@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <set>
@@ -13,6 +14,7 @@
 #include <thread>
 #include <vector>
 
+#include "end_keys.h"
 #include "fastq_gpu.h"
 #include "inflate_gpu.h"
 #include "inflate_mt.h"
@@ -47,6 +49,13 @@ template <typename F> static int guarded(shk_handle *h, Poison poison, F &&body)
         (poison == Poison::Always || (poison == Poison::AfterFirstBatch && (h->batches_started > 0 || h->st == St::Sharding))))
         { h->st = St::Failed; h->first_err = h->err; }
     return rc;
+}
+
+// shk_host_end_key: the writer's end keys in the code the kernels share with the host (end_keys.h)
+template <int W> static void host_end_key_t(const char *seq, uint32_t k, int rc, uint32_t o, uint32_t pos, uint64_t *out, uint64_t *entry) {
+    const Kmer<W> x = rc ? ek_pack_rc<W>(seq, k) : ek_pack<W>(seq, k);
+    for (int j = 0; j < W; j++) out[j] = x.w[j];
+    if (entry) *entry = ek_entry(km_hash<W>(x), o, pos);
 }
 
 extern "C" {
@@ -199,13 +208,21 @@ static int assemble_impl(shk_handle *h) {
         h->post("assembly:create_graph");
         std::vector<RawContig> contigs;
         if (h->pipe->n_solid_global() >= (1u << 20)) writer_prewarm(3000);
-        int rc = h->pipe->shard_assemble(h->shard_comm, !h->no_deadend, !h->no_bubble, contigs, err);
+        const char *dev_json = nullptr; size_t dev_json_len = 0; uint64_t dev_nc = 0;
+        int rc = h->pipe->shard_assemble(h->shard_comm, !h->no_deadend, !h->no_bubble, contigs, err, &dev_json, &dev_json_len, &dev_nc);
         // (a failure the other ranks cannot know of has aborted the communicator already: Pipeline::shard_assemble)
         if (rc) return fail_rc(h, Rc::DeviceNoParam, rc, err);
         h->post("assembly:correct_graph");
         h->post("assembly:collapse_graph");
         h->pipe->times().add("assemble_device_total_host_clock", now_ms() - t0);
         h->post("assembly:saving");
+        if (dev_json) {                                    // a fragmented assembly: its text was written on the device (csrc/writer_text_gpu.h)
+            h->asm_json_dev = dev_json;
+            h->pipe->times().add("outputs_host_clock", 0.0);
+            h->st = St::Assembled;
+            h->post("assembly:end");
+            return SHK_OK;
+        }
         const double t1 = now_ms();
         build_assembly_text(contigs, h->k, h->text);
         h->asm_json.swap(h->text.json);
@@ -796,6 +813,21 @@ int shk_host_canonical(const char *seq, uint32_t k, uint64_t *out_words, int *or
     return host_canonical(seq, k, out_words, orient) == 0 ? SHK_OK : SHK_E_PARAM;
 }
 uint64_t shk_host_nthash(const char *seq, uint32_t k) { return host_nthash(seq, k); }
+int shk_host_end_key(const char *seq, uint32_t k, int rc, uint32_t orientation, uint32_t pos, uint64_t *out_words, uint64_t *entry) {
+    if (!seq || !out_words || k < 1 || k > SHK_K_MAX || orientation > 1 || pos > 0x7FFFFFFFu) return SHK_E_PARAM;
+    switch ((2 * k + 63) / 64) {
+        case 1: host_end_key_t<1>(seq, k, rc, orientation, pos, out_words, entry); break;
+        case 2: host_end_key_t<2>(seq, k, rc, orientation, pos, out_words, entry); break;
+        case 3: host_end_key_t<3>(seq, k, rc, orientation, pos, out_words, entry); break;
+        case 4: host_end_key_t<4>(seq, k, rc, orientation, pos, out_words, entry); break;
+        case 5: host_end_key_t<5>(seq, k, rc, orientation, pos, out_words, entry); break;
+        case 6: host_end_key_t<6>(seq, k, rc, orientation, pos, out_words, entry); break;
+        case 7: host_end_key_t<7>(seq, k, rc, orientation, pos, out_words, entry); break;
+        case 8: host_end_key_t<8>(seq, k, rc, orientation, pos, out_words, entry); break;
+        default: return SHK_E_PARAM;
+    }
+    return SHK_OK;
+}
 int shk_host_fit(const uint64_t *histo500, uint32_t *used) { return spectrum_fit(histo500, used) ? 1 : 0; }
 char *shk_host_assembly_json(const char *seqs, const uint64_t *offsets, const uint64_t *kc, uint64_t n_contigs, uint32_t k) {
     try {
@@ -856,6 +888,33 @@ char *shk_host_assembly_json_arriving(const char *seqs, const uint64_t *offsets,
         memcpy(out, text.json.data(), text.json.size());
         return out;
     } catch (...) { return nullptr; }
+}
+// the device twin of shk_host_assembly_json (csrc/writer_text_gpu.h): the same parameters, the same bytes; on the current device
+char *shk_device_assembly_json(const char *seqs, const uint64_t *offsets, const uint64_t *kc, uint64_t n_contigs, uint32_t k, const char **why) {
+    static thread_local std::string msg;
+    auto say = [&](const std::string &m) { if (why) { msg = m; *why = msg.c_str(); } };
+    try {
+        say("");
+        if ((!seqs && n_contigs) || !offsets || (!kc && n_contigs) || k < 1 || k > SHK_K_MAX) { say("bad parameters"); return nullptr; }
+        for (uint64_t i = 0; i < n_contigs; i++)
+            if (offsets[i + 1] < offsets[i] + k) { say("offsets not ascending, or a contig shorter than k"); return nullptr; }      // (the host twin's refusal)
+        if (n_contigs == 0) return shk_host_assembly_json(seqs, offsets, kc, 0, k);      // (no contig: the literals alone)
+        std::string err;
+        std::unique_ptr<IPipeline> pipe(make_pipeline((int)k, err));
+        if (!pipe) { say(err); return nullptr; }
+        const char *json = nullptr, *wn = ""; size_t len = 0;
+        char *out = nullptr;
+        {
+            DeferScope park(pipe.get());                   // (the writer's device buffers go back once its stream is idle)
+            const int rc = pipe->text_assembly_json(seqs, offsets, kc, n_contigs, &json, &len, &wn, err);
+            if (rc == 1) { say(wn); return nullptr; }
+            if (rc || !json) { say(err); return nullptr; }
+            out = (char *)malloc(len + 1);
+            if (!out) { say("out of host memory"); return nullptr; }
+            memcpy(out, json, len + 1);                    // (the JSON carries its terminator)
+        }
+        return out;
+    } catch (...) { say("out of host memory"); return nullptr; }
 }
 void shk_host_free(void *p) { free(p); }
 // the device inflater alone (csrc/inflate_gpu.hip): 0 = *out (malloc'd, shk_host_free) holds the bytes of the member or of

@@ -113,7 +113,17 @@ public:
                                  const uint64_t histo[500], uint64_t total_instances, std::string &err) = 0;
     virtual bool sharded_graph() const = 0;
     virtual uint64_t n_solid_global() const = 0;
-    virtual int shard_assemble(ShardComm *comm, bool tips, bool bubbles, std::vector<RawContig> &out, std::string &err) = 0;
+    // json (optional), as with collapse: from SHK_DEVICE_WRITER_MIN contigs on (unless SHK_SHARD_DEVICE_WRITER=0) the
+    // get_assembly() JSON is written on the device from the all-reduced contig text (writer_text_gpu.h) and `out` stays
+    // empty; a rank whose device declines (no memory, a size limit) downloads the text and fills `out` as below the threshold
+    // — both writers give the same bytes, so no agreement round is needed
+    virtual int shard_assemble(ShardComm *comm, bool tips, bool bubbles, std::vector<RawContig> &out, std::string &err,
+                               const char **json = nullptr, size_t *json_len = nullptr, uint64_t *n_contigs = nullptr) = 0;
+    // The device writer from contig text alone, by itself (shk_device_assembly_json): seqs / offsets[n + 1] / kc[n] as the
+    // host writer takes them, every contig at least k bases.  0: *json points at the NUL-terminated JSON in pinned memory
+    // owned by the pipeline; 1: declined, *why says why (no contig, 2^31 contigs, a contig of 2^32 bases, no device memory)
+    virtual int text_assembly_json(const char *seqs, const uint64_t *offsets, const uint64_t *kc, uint64_t n_contigs,
+                                   const char **json, size_t *json_len, const char **why, std::string &err) = 0;
     virtual StageTimes &times() = 0;                 // (waits for the events of timers that were stopped without waiting)
     // a host-clock figure added without that wait: for callers with work still to launch behind what the stream holds
     virtual void add_time(const char *name, double ms) = 0;

@@ -29,6 +29,7 @@
 
 #include "ctl_words.h"
 #include "device_mem.h"
+#include "end_keys.h"
 #include "kmer.h"
 #include "pipeline.h"
 #include "shard_comm.h"
@@ -115,6 +116,7 @@ namespace shk {
 #include "collapse.h"
 #include "shard_graph.h"
 #include "writer_gpu.h"
+#include "writer_text_gpu.h"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -1910,11 +1912,38 @@ public:
         HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp.p, bytes, in.p, out.p, (int)n, stream_));
         return 0;
     }
+    // The two device writers — from the graph (device_write_json) and from the contig text alone (device_write_text_json:
+    // writer_text_gpu.h) — share the order in front of the links and everything behind them; they differ in who fills
+    // `links` and counts them.
+    struct WriterBufs {
+        DevBuf<unsigned long long> keys, keys2, slen, skc, links, links2;
+        DevBuf<uint32_t> vals, vals2, rank_of_slot, rank_of_contig;
+        DevBuf<unsigned int> d_cnt;              // [0] links found, [1] distinct links, [2] the graph writer's flags
+        DevBuf<char> tmp;
+        uint32_t link_cap = 0;
+    };
     int device_write_json(Graph<W> &g, ChainState &cs, DevBuf<WContig> &d_c, uint32_t nc, uint32_t n_slots, const char *d_text, uint64_t text_bytes,
                           const char **json, size_t *json_len, std::string &err) {
-        typedef unsigned long long u64;
         EvTimer tw(stream_, stage_timers_);
-        DevBuf<u64> keys, keys2, slen, skc; DevBuf<uint32_t> vals, vals2, rank_of_slot, rank_of_contig; DevBuf<char> tmp;
+        WriterBufs wb;
+        if (int rc = writer_order(wb, d_c, nc, n_slots, d_text, err)) return rc;
+        // ---- links
+        if (int rc = writer_links_alloc(wb, nc, err)) return rc;
+        hipLaunchKernelGGL(k_w_links<W>, dim3(grid_for(2ull * nc)), dim3(256), 0, stream_, g, cs.d_heads.p, cs.ol.p, d_c.p, nc, wb.vals2.p, wb.rank_of_slot.p,
+                           wb.links.p, wb.d_cnt.p, wb.link_cap, wb.d_cnt.p + 2);
+        HIPCHK(hipGetLastError());
+        unsigned int h_cnt[4] = {0, 0, 0, 0};
+        HIPCHK(hipMemcpyAsync(h_cnt, wb.d_cnt.p, 16, hipMemcpyDeviceToHost, stream_));
+        WAIT_STREAM();
+        if (h_cnt[2]) { err = "device writer: the graph and the chains disagree about a link (" + std::to_string(h_cnt[2]) + ")"; return -6; }
+        if (h_cnt[0] > wb.link_cap) { err = "device writer: more links than 8 per contig"; return -6; }
+        return writer_finish(wb, d_c, nc, h_cnt[0], d_text, text_bytes, tw, json, json_len, err);
+    }
+    // order: (length descending, sequence ascending); d_c[i].slot < n_slots
+    int writer_order(WriterBufs &wb, DevBuf<WContig> &d_c, uint32_t nc, uint32_t n_slots, const char *d_text, std::string &err) {
+        typedef unsigned long long u64;
+        DevBuf<u64> &keys = wb.keys, &keys2 = wb.keys2, &slen = wb.slen, &skc = wb.skc;
+        DevBuf<uint32_t> &vals = wb.vals, &vals2 = wb.vals2, &rank_of_slot = wb.rank_of_slot, &rank_of_contig = wb.rank_of_contig; DevBuf<char> &tmp = wb.tmp;
         if (int rc = keys.alloc(nc, err)) return rc;
         if (int rc = keys2.alloc(nc, err)) return rc;
         if (int rc = vals.alloc(nc, err)) return rc;
@@ -1935,22 +1964,24 @@ public:
         hipLaunchKernelGGL(k_w_ties, dim3(grid_for(nc)), dim3(256), 0, stream_, d_text, d_c.p, nc, keys2.p, vals2.p);
         hipLaunchKernelGGL(k_w_rank, dim3(grid_for(nc)), dim3(256), 0, stream_, d_c.p, nc, vals2.p, rank_of_slot.p, slen.p, skc.p, rank_of_contig.p);
         HIPCHK(hipGetLastError());
-        // ---- links
-        DevBuf<u64> links, links2; DevBuf<unsigned int> d_cnt;
-        const uint32_t link_cap = 8u * nc + 64u;
-        if (int rc = links.alloc(link_cap, err)) return rc;
-        if (int rc = links2.alloc(link_cap, err)) return rc;
-        if (int rc = d_cnt.alloc(4, err)) return rc;
-        HIPCHK(hipMemsetAsync(d_cnt.p, 0, 16, stream_));
-        hipLaunchKernelGGL(k_w_links<W>, dim3(grid_for(2ull * nc)), dim3(256), 0, stream_, g, cs.d_heads.p, cs.ol.p, d_c.p, nc, vals2.p, rank_of_slot.p,
-                           links.p, d_cnt.p, link_cap, d_cnt.p + 2);
-        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    // room for the links (at most four from each end of a contig) and their zeroed counters
+    int writer_links_alloc(WriterBufs &wb, uint32_t nc, std::string &err) {
+        wb.link_cap = 8u * nc + 64u;
+        if (int rc = wb.links.alloc(wb.link_cap, err)) return rc;
+        if (int rc = wb.links2.alloc(wb.link_cap, err)) return rc;
+        if (int rc = wb.d_cnt.alloc(4, err)) return rc;
+        HIPCHK(hipMemsetAsync(wb.d_cnt.p, 0, 16, stream_));
+        return 0;
+    }
+    // behind the links: wb.links holds nl link words in any order, a link possibly more than once
+    int writer_finish(WriterBufs &wb, DevBuf<WContig> &d_c, uint32_t nc, uint32_t nl, const char *d_text, uint64_t text_bytes, EvTimer &tw,
+                      const char **json, size_t *json_len, std::string &err) {
+        typedef unsigned long long u64;
+        DevBuf<u64> &slen = wb.slen, &skc = wb.skc, &links = wb.links, &links2 = wb.links2;
+        DevBuf<uint32_t> &rank_of_contig = wb.rank_of_contig; DevBuf<unsigned int> &d_cnt = wb.d_cnt; DevBuf<char> &tmp = wb.tmp;
         unsigned int h_cnt[4] = {0, 0, 0, 0};
-        HIPCHK(hipMemcpyAsync(h_cnt, d_cnt.p, 16, hipMemcpyDeviceToHost, stream_));
-        WAIT_STREAM();
-        if (h_cnt[2]) { err = "device writer: the graph and the chains disagree about a link (" + std::to_string(h_cnt[2]) + ")"; return -6; }
-        if (h_cnt[0] > link_cap) { err = "device writer: more links than 8 per contig"; return -6; }
-        uint32_t nl = h_cnt[0];
         if (nl) {
             size_t bytes = 0;
             HIPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, links.p, links2.p, (int)nl, 0, 64, stream_));
@@ -2020,6 +2051,67 @@ public:
         times_.add("device_writer_links_x1e-3", nl * 1e-3);
         *json = hjson_.p; if (json_len) *json_len = (size_t)total;
         return 0;
+    }
+
+    // ---- the writer from contig text alone (writer_text_gpu.h) --------------------------------------------------
+    // d_c: nc >= 1 contigs in text order, back to back from offset 0 (d_c[i].slot = i), on any strand; d_text is turned in
+    // place.  0: *json points at the text (hjson_); 1: declined, *why says why — the text may have been turned by then, which
+    // the host writer does not mind; < 0: a HIP error.
+    int device_write_text_json(DevBuf<WContig> &d_c, uint64_t n_contigs, char *d_text, uint64_t text_bytes, const char **json, size_t *json_len,
+                               const char **why, std::string &err) {
+        *json = nullptr; *why = "";
+        if (n_contigs == 0 || n_contigs >= 0x7FFFFFF0ull) { *why = "no contig, or 2^31 contigs or more"; return 1; }
+        const uint32_t nc = (uint32_t)n_contigs;
+        const int rc = device_write_text_json_impl(d_c, nc, d_text, text_bytes, json, json_len, err);
+        if (rc == -4) { *why = "out of device memory"; *json = nullptr; return 1; }
+        return rc;
+    }
+    int device_write_text_json_impl(DevBuf<WContig> &d_c, uint32_t nc, char *d_text, uint64_t text_bytes, const char **json, size_t *json_len, std::string &err) {
+        EvTimer tw(stream_, stage_timers_);
+        // ---- canonical strand
+        DevBuf<uint8_t> flip;
+        if (int rc = flip.alloc(nc, err)) return rc;
+        hipLaunchKernelGGL(k_t_strand, dim3(grid_for(64ull * nc)), dim3(256), 0, stream_, (const char *)d_text, d_c.p, nc, flip.p);
+        hipLaunchKernelGGL(k_t_revcomp, dim3(grid_for((text_bytes + 7) / 8)), dim3(256), 0, stream_, d_text, (unsigned long long)text_bytes, d_c.p, nc, flip.p);
+        HIPCHK(hipGetLastError());
+        // ---- order
+        WriterBufs wb;
+        if (int rc = writer_order(wb, d_c, nc, nc, d_text, err)) return rc;
+        // ---- links
+        if (int rc = writer_links_alloc(wb, nc, err)) return rc;
+        DevBuf<unsigned long long> table;
+        const uint64_t slots = ek_table_slots(nc);
+        if (int rc = table.alloc(slots, err)) return rc;
+        HIPCHK(hipMemsetAsync(table.p, 0xFF, slots * 8, stream_));
+        hipLaunchKernelGGL(k_t_table_fill<W>, dim3(grid_for(2ull * nc)), dim3(256), 0, stream_, (const char *)d_text, d_c.p, nc, wb.vals2.p, (uint32_t)k_,
+                           table.p, (unsigned long long)(slots - 1));
+        hipLaunchKernelGGL(k_t_links<W>, dim3(grid_for(2ull * nc)), dim3(256), 0, stream_, (const char *)d_text, d_c.p, nc, wb.vals2.p, (uint32_t)k_,
+                           (const unsigned long long *)table.p, (unsigned long long)(slots - 1), wb.links.p, wb.d_cnt.p, wb.link_cap);
+        HIPCHK(hipGetLastError());
+        unsigned int h_cnt[4] = {0, 0, 0, 0};
+        HIPCHK(hipMemcpyAsync(h_cnt, wb.d_cnt.p, 16, hipMemcpyDeviceToHost, stream_));
+        WAIT_STREAM();
+        if (h_cnt[0] > wb.link_cap) { err = "device writer: more links than 8 per contig"; return -6; }
+        return writer_finish(wb, d_c, nc, h_cnt[0], d_text, text_bytes, tw, json, json_len, err);
+    }
+    int text_assembly_json(const char *seqs, const uint64_t *offsets, const uint64_t *kc, uint64_t n_contigs, const char **json, size_t *json_len,
+                           const char **why, std::string &err) override {
+        *json = nullptr; *why = "";
+        if (n_contigs == 0 || n_contigs >= 0x7FFFFFF0ull) { *why = "no contig, or 2^31 contigs or more"; return 1; }
+        const uint64_t t0 = offsets[0], text_bytes = offsets[n_contigs] - t0;
+        std::vector<WContig> hc((size_t)n_contigs);
+        for (uint64_t i = 0; i < n_contigs; i++) {
+            const uint64_t len = offsets[i + 1] - offsets[i];
+            if (len > 0xFFFFFFFFull) { *why = "a contig of 2^32 bases or more"; return 1; }
+            hc[i].off = offsets[i] - t0; hc[i].kc = kc[i]; hc[i].len = (uint32_t)len; hc[i].slot = (uint32_t)i;
+        }
+        DevBuf<WContig> d_c; DevBuf<char> d_text;
+        if (d_c.alloc(n_contigs + 1, err) || d_text.alloc(text_bytes + 16, err)) { *why = "out of device memory"; return 1; }
+        HIPCHK(hipMemcpyAsync(d_c.p, hc.data(), (size_t)n_contigs * sizeof(WContig), hipMemcpyHostToDevice, stream_));
+        HIPCHK(hipMemcpyAsync(d_text.p, seqs + t0, text_bytes, hipMemcpyHostToDevice, stream_));
+        const int rc = device_write_text_json(d_c, n_contigs, d_text.p, text_bytes, json, json_len, why, err);
+        drain();                                            // (the uploads read pageable host memory of this frame)
+        return rc;
     }
 
     // ---- sharded assembly (shard_graph.h) ---------------------------------------------------------------------
@@ -2119,11 +2211,13 @@ public:
     // round and all ranks return an error together (sh_agreed_); a failure nobody else can know of (device memory that runs
     // out after the sizes were agreed, a HIP error, a collective that fails) aborts the communicator at once, so that the
     // peers' watchdogs (comm_stream_wait) end their waits instead of blocking for ever, and shk_comm_free does not block.
-    int shard_assemble(ShardComm *c, bool tips, bool bubbles, std::vector<RawContig> &out, std::string &err) override {
+    int shard_assemble(ShardComm *c, bool tips, bool bubbles, std::vector<RawContig> &out, std::string &err,
+                       const char **json, size_t *json_len, uint64_t *n_contigs) override {
+        if (json) *json = nullptr;
         sh_agreed_ = false;
         wd_comm_ = (c && comm_world(c) > 1) ? c : nullptr;
         const uint64_t waits0 = n_host_waits_;
-        const int rc = shard_assemble_impl(c, tips, bubbles, out, err);
+        const int rc = shard_assemble_impl(c, tips, bubbles, out, err, json, json_len, n_contigs);
         times_.add("shard_host_waits_x1", (double)(n_host_waits_ - waits0));     // stream waits + host-side collectives of this call
         if (rc && wd_comm_ && !sh_agreed_) comm_abort_now(c);
         drain();                                           // (through the watchdog: the stream may hold collectives of a call that failed)
@@ -2133,7 +2227,8 @@ public:
     // (the host-side collectives wait for the stream: counted like the stream waits)
     int counted_allreduce_host_u64(ShardComm *c, uint64_t *v, size_t n, void *st, std::string &e) { n_host_waits_++; return comm_allreduce_host_u64(c, v, n, st, e); }
     int counted_allgather_host_u64(ShardComm *c, const uint64_t *in, size_t n, uint64_t *out, void *st, std::string &e) { n_host_waits_++; return comm_allgather_host_u64(c, in, n, out, st, e); }
-    int shard_assemble_impl(ShardComm *c, bool tips, bool bubbles, std::vector<RawContig> &out, std::string &err) {
+    int shard_assemble_impl(ShardComm *c, bool tips, bool bubbles, std::vector<RawContig> &out, std::string &err,
+                            const char **json, size_t *json_len, uint64_t *n_contigs_out) {
         // SHK_STAGE_LOG=1: after every step the stream is drained and the step's name goes to stderr (which step a fault belongs to)
         const bool stage_log = getenv("SHK_STAGE_LOG") != nullptr;
         auto stage = [&](const char *what) {
@@ -2493,7 +2588,11 @@ public:
         if (int rc = d_lay.alloc(n_u + 1, err)) return rc;
         if (int rc = d_text.alloc(text_w32 * 16 + 16, err)) return rc;
         if (int rc = d_pack.alloc(text_w32 + 2, err)) return rc;
-        if (int rc = hout_.alloc(text_w32 * 16 + 16, err)) return rc;
+        // a fragmented assembly: its get_assembly() text is written on the device from the all-reduced text (writer_text_gpu.h),
+        // as collapse() does on one GPU — the text is then never downloaded
+        const bool dev_writer = json && text_bytes && (uint64_t)n_contigs >= env_u64("SHK_DEVICE_WRITER_MIN", 20000) &&
+                                env_u64("SHK_SHARD_DEVICE_WRITER", 1) != 0;
+        if (!dev_writer) if (int rc = hout_.alloc(text_w32 * 16 + 16, err)) return rc;
         if (text_bytes) {
             HIPCHK(hipMemsetAsync(d_text.p, 0, text_w32 * 16, stream_));
             HIPCHK(hipMemcpyAsync(d_lay.p, lay.data(), (size_t)(n_u + 1) * sizeof(ULayout), hipMemcpyHostToDevice, stream_));
@@ -2510,11 +2609,48 @@ public:
                 HIPCHK(hipGetLastError());
                 times_.add("shard_graph_text_allreduce_MB", (double)(text_w32 * 4) / 1e6);
             }
-            HIPCHK(hipMemcpyAsync(hout_.p, d_text.p, text_bytes, hipMemcpyDeviceToHost, stream_));
+            if (!dev_writer) HIPCHK(hipMemcpyAsync(hout_.p, d_text.p, text_bytes, hipMemcpyDeviceToHost, stream_));
         }
         stage("6 emission kernels");
+        if (dev_writer) {
+            if (te.on()) times_.add("shard_graph_emit", te.stop());
+            // the contigs in text order: the linear ones, then the rings (24 bytes each to upload)
+            const char *why = "";
+            int rc_w = 0;
+            std::vector<WContig> hc(n_contigs);
+            std::atomic<int> bad{0};
+            auto put = [&](size_t i, uint64_t nodes, uint64_t kc) {
+                const uint64_t bases = nodes + (uint64_t)(k_ - 1);
+                if (bases > 0xFFFFFFFFull) bad.store(1);
+                else if (c_off[i] + bases != (i + 1 < n_contigs ? c_off[i + 1] : text_bytes)) bad.store(2);
+                hc[i].off = c_off[i]; hc[i].kc = kc; hc[i].len = (uint32_t)bases; hc[i].slot = (uint32_t)i;
+            };
+            host_par_ranges(n_lin, [&](size_t a, size_t b) { for (size_t i = a; i < b; i++) put(i, res.lin[i].len_nodes, res.lin[i].kc); });
+            for (size_t i = 0; i < res.contigs.size(); i++) put(n_lin + i, res.contigs[i].len_nodes, res.contigs[i].kc);
+            DevBuf<WContig> d_c;
+            if (bad.load()) { why = bad.load() == 1 ? "a contig of 2^32 bases or more" : "the contigs do not lie back to back in the text"; rc_w = 1; }
+            else if (n_contigs >= 0x7FFFFFF0ull) { why = "2^31 contigs or more"; rc_w = 1; }
+            else if (d_c.alloc(n_contigs + 1, err)) { why = "out of device memory"; rc_w = 1; }
+            if (!rc_w) {
+                HIPCHK(hipMemcpyAsync(d_c.p, hc.data(), n_contigs * sizeof(WContig), hipMemcpyHostToDevice, stream_));
+                rc_w = device_write_text_json(d_c, n_contigs, d_text.p, text_bytes, json, json_len, &why, err);
+                if (rc_w < 0) return rc_w;
+            }
+            if (rc_w == 0) {
+                if (n_contigs_out) *n_contigs_out = n_contigs;
+                times_.add("shard_writer_device_x1", 1.0);
+                times_.add("shard_assemble_host_clock", now_ms_() - t_all0);
+                return 0;
+            }
+            // declined (rank-local; the host writer gives the same bytes from the text, turned or not): download it as below the threshold
+            if (stage_log) { fprintf(stderr, "[shard_assemble rank %d] device writer declined: %s\n", comm_rank(c), why); fflush(stderr); }
+            times_.add("shard_writer_device_declined_x1", 1.0);
+            *json = nullptr; err.clear();
+            if (int rc = hout_.alloc(text_w32 * 16 + 16, err)) return rc;
+            HIPCHK(hipMemcpyAsync(hout_.p, d_text.p, text_bytes, hipMemcpyDeviceToHost, stream_));
+        }
         WAIT_STREAM();
-        if (te.on()) times_.add("shard_graph_emit", te.stop());
+        if (te.on() && !dev_writer) times_.add("shard_graph_emit", te.stop());
         out.resize(n_contigs);
         host_par_ranges(n_lin, [&](size_t a, size_t b) {
             for (size_t i = a; i < b; i++) {
