@@ -10,7 +10,9 @@
 //   k_read_wave<1>           the same walk again: segment table + the 2-bit stream (gather + encode per output word)
 // Only REGULAR input is handled (fixed 4-line framing, no blank lines between records); anything
 // else — and every malformed record — is left to the host parser, which owns the error messages.
-// The result is the same packed layout bit for bit (tests/test_gpu_parity.py compares both).
+// The result is the same packed layout bit for bit: tests/test_gpu_fastq_pack.py compares the counts, seg_off and every word
+// with a reference packer (tests/fastq_cases.py), which tests/test_fastq_cases.py holds against fastq.cpp in the same way;
+// tests/test_gpu_parity.py compares the k-mer tables of both parsers.
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <stdint.h>

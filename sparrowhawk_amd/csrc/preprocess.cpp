@@ -778,7 +778,10 @@ int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n
     PackedReads pr;
     for (int i = 0; i < nf; i++) {
         if (int rc = host_slice(i)) return rc;
-        if (int rc = pack_fastq(f[i].t + f[i].s0, (size_t)(f[i].s1 - f[i].s0), k, min_qual, pr, err)) return code_of(Rc::Parser, rc);
+        // A slice that reaches the end of the text takes the blank lines behind it along: trimmed_len cannot tell a blank line
+        // from the line end that closes the empty quality line of a last record without bases, and the parser skips the others.
+        const uint64_t end = f[i].s1 == f[i].e ? f[i].l : f[i].s1;
+        if (int rc = pack_fastq(f[i].t + f[i].s0, (size_t)(end - f[i].s0), k, min_qual, pr, err)) return code_of(Rc::Parser, rc);
     }
     if (too_large(pr.n_bases)) return SHK_E_PARAM;
     out.n_reads = pr.n_reads; out.n_input_bases = pr.n_input_bases;
