@@ -33,6 +33,7 @@
 #include "kmer.h"
 #include "pipeline.h"
 #include "shard_comm.h"
+#include "shard_plan.h"
 #include "unitig_graph.h"
 #include "unitig_graph_gpu.h"
 
@@ -1455,8 +1456,6 @@ public:
                 WAIT_STREAM();
                 if (int rc = check_graph_flags(err)) return rc;
             }
-            // (the big scratch of this phase goes back to the pool now, not when the entry point ends: see DeferScope)
-            if (!sh_active_ || sh_world_ <= 1) { /* the stream is busy: parked until the call ends, or reused below */ }
         }
         graph_ready_ = true;
         return 0;
@@ -1613,18 +1612,21 @@ public:
     // (plan: an assembly with few chains has its emission planned on the device — k_plan_emit —, its text written and sent to
     // the host behind the ranking, inside the same launch sequence: the host's ONE wait brings the counters, the chain records
     // and the text.  planned = the device did it; otherwise the caller plans as before.)
+    // SHK_STAGE_LOG=1 (read once per call, by the callers): after every step the stream is drained and the step's name goes to
+    // stderr (which step a fault belongs to)
+    void stage_done(const char *who, unsigned id, const char *what) {
+        const hipError_t e = hipStreamSynchronize(stream_);
+        fprintf(stderr, "[%s%u] %s done%s\n", who, id, what, e == hipSuccess ? "" : " (stream error)");
+        fflush(stderr);
+    }
     struct EmitPlan { EmitRec *d_off; char *d_out; char *h_out; uint32_t max_heads; unsigned long long out_cap; bool planned; unsigned long long out_bytes; uint32_t n_emit; };
     int rank_chains(ChainState &cs, bool rings, std::string &err, uint32_t keep_on_device_from = 0xFFFFFFFFu, EmitPlan *plan = nullptr) {
         const uint32_t n = (uint32_t)n_solid_;
         const uint32_t total = 2 * n;
         Graph<W> g = graph_view();
         if (plan) plan->planned = false;
-        const bool stage_log = getenv("SHK_STAGE_LOG") != nullptr;          // (see shard_assemble)
-        auto stage = [&](const char *what) {
-            if (!stage_log) return;
-            const hipError_t e = hipStreamSynchronize(stream_);
-            fprintf(stderr, "[rank_chains n=%u] %s done%s\n", n, what, e == hipSuccess ? "" : " (stream error)"); fflush(stderr);
-        };
+        const bool stage_log = getenv("SHK_STAGE_LOG") != nullptr;
+        auto stage = [&](const char *what) { if (stage_log) stage_done("rank_chains n=", n, what); };
         if (int rc = cs.winfo.alloc(total, err)) return rc;
         if (int rc = cs.frag.alloc(total, err)) return rc;
         if (int rc = cs.spl.alloc(total, err)) return rc;
@@ -2140,6 +2142,15 @@ public:
         DevBuf<uint64_t> send, recv; DevBuf<uint32_t> sidx;
         std::vector<uint64_t> send_cnt, recv_cnt; uint64_t n_send = 0, n_recv = 0;
     };
+    // what comm_alltoallv wants of a pairwise exchange: per peer the offset and the size in bytes, sending and receiving
+    struct PairwiseBytes {
+        std::vector<uint64_t> so, sb, ro, rb;
+        PairwiseBytes(const std::vector<uint64_t> &send_cnt, const std::vector<uint64_t> &recv_cnt, uint64_t rec_bytes)
+            : so(send_cnt.size()), sb(send_cnt.size()), ro(send_cnt.size()), rb(send_cnt.size()) {
+            uint64_t a = 0, b = 0;
+            for (size_t q = 0; q < send_cnt.size(); q++) { so[q] = a; sb[q] = send_cnt[q] * rec_bytes; a += sb[q]; ro[q] = b; rb[q] = recv_cnt[q] * rec_bytes; b += rb[q]; }
+        }
+    };
     // (the size exchange happens on the device: the row of counts is gathered by RCCL and read back ONCE, world x (world + 1)
     // words; `extra` rides along — a word of the caller's, e.g. "my local step failed" — and comes back as extra_all[world])
     template <int PW>
@@ -2189,23 +2200,89 @@ public:
                                rt_cur_.p, r.send.p, r.sidx.p);
             HIPCHK(hipGetLastError());
         }
-        std::vector<uint64_t> so(world), sb(world), ro(world), rb(world);
-        uint64_t a = 0, b = 0;
-        for (uint32_t q = 0; q < world; q++) { so[q] = a; sb[q] = r.send_cnt[q] * PW * 8; a += sb[q]; ro[q] = b; rb[q] = r.recv_cnt[q] * PW * 8; b += rb[q]; }
-        if (int rc = comm_alltoallv(c, r.send.p, so.data(), sb.data(), r.recv.p, ro.data(), rb.data(), stream_, err)) return rc;
+        const PairwiseBytes x(r.send_cnt, r.recv_cnt, PW * 8);
+        if (int rc = comm_alltoallv(c, r.send.p, x.so.data(), x.sb.data(), r.recv.p, x.ro.data(), x.rb.data(), stream_, err)) return rc;
         // (no wait: what follows is ordered on the same stream, and every buffer involved outlives the call)
         times_.add("shard_graph_exchanged_MB", (double)(r.n_send * PW * 8) / 1e6);
         return 0;
     }
     // the answers to what was received (one u64 per received record, in r.recv's order) travel back: back[i] = answer to r.send[i]
     int reply_exchange(ShardComm *c, const Routed &r, const unsigned long long *ans, DevBuf<unsigned long long> &back, std::string &err) {
-        const uint32_t world = sh_world_;
         if (int rc = back.alloc(r.n_send + 1, err)) return rc;
-        std::vector<uint64_t> so(world), sb(world), ro(world), rb(world);
-        uint64_t a = 0, b = 0;
-        for (uint32_t q = 0; q < world; q++) { so[q] = a; sb[q] = r.recv_cnt[q] * 8; a += sb[q]; ro[q] = b; rb[q] = r.send_cnt[q] * 8; b += rb[q]; }
-        return comm_alltoallv(c, ans, so.data(), sb.data(), back.p, ro.data(), rb.data(), stream_, err);
+        const PairwiseBytes x(r.recv_cnt, r.send_cnt, 8);
+        return comm_alltoallv(c, ans, x.so.data(), x.sb.data(), back.p, x.ro.data(), x.rb.data(), stream_, err);
     }
+    // (the host-side collectives wait for the stream: counted like the stream waits)
+    int counted_allreduce_host_u64(ShardComm *c, uint64_t *v, size_t n, void *st, std::string &e) { n_host_waits_++; return comm_allreduce_host_u64(c, v, n, st, e); }
+    int counted_allgather_host_u64(ShardComm *c, const uint64_t *in, size_t n, uint64_t *out, void *st, std::string &e) { n_host_waits_++; return comm_allgather_host_u64(c, in, n, out, st, e); }
+    // every local step's result travels with the next collective: all ranks leave together (as in shk_shard_preprocess)
+    int agree(ShardComm *c, int local_rc, const char *stage, std::string &err) {
+        uint64_t f = local_rc ? 1u : 0u;
+        std::string e2;
+        if (int rc = counted_allreduce_host_u64(c, &f, 1, stream_, e2)) { if (local_rc) return local_rc; err = e2; return rc; }
+        if (f) sh_agreed_ = true;                        // (every rank has seen the flag and leaves)
+        if (local_rc) return local_rc;
+        if (f) { err = std::string("sharded assembly: another rank failed during ") + stage; return -5; }
+        return 0;
+    }
+
+    // Everything one shard_assemble call owns, alive until that call's last wait (shard_assemble drains the stream before it
+    // lets go of it): no wait is needed for a buffer's sake, the waits that remain are the ones whose RESULT the host needs.
+    // THE RULE: host memory handed to hipMemcpyAsync lives here or in a member of the pipeline (rt_extra_host_, rt_cur_host_,
+    // sh_gbase_) — never in a step's frame, which an early `return rc` unwinds under the copy.  The one exception: the same
+    // function waits on the stream after the copy and before it returns (hM2 / h_fl in sh_stitch_rank, `all` in route_exchange).
+    struct ShardRun {
+        ShardComm *c = nullptr; bool tips = true, bubbles = true;
+        uint32_t world = 1, rank = 0;
+        uint32_t n = 0;                                  // this rank's solid k-mers
+        unsigned long long gbase = 0;                    // the global id of its first
+        uint32_t n_lch = 0; int rc_chain = 0;            // its local chains; what ranking them returned (travels with their count)
+        uint64_t M = 0;                                  // local chains of all ranks
+        unsigned int n_u = 0;                            // unitigs
+        double t_all0 = 0, t_host0 = 0, t_lap = 0;
+        const bool stage_log = getenv("SHK_STAGE_LOG") != nullptr;      // (see stage_done)
+        const bool ug_dbg = getenv("SHK_UG_DEBUG") != nullptr;          // stage times of the host section on stderr (sh_lap)
+        Graph<W> g;
+        // 1. adjacency, 2. half links
+        DevBuf<unsigned long long> xnb;                  // per cross query: the neighbour's oriented global id (~0: not a solid k-mer)
+        Routed rq, hl;
+        DevBuf<unsigned long long> xans, xback;
+        DevBuf<uint32_t> hdest; DevBuf<uint64_t> hpay;
+        DevBuf<uint32_t> xpred;                          // per local oriented node: record of hl.recv that names its simple predecessor on another rank
+        // 3. local chains, 4. stitching
+        ChainState cs;
+        std::vector<uint64_t> lcnt, lbase;               // local chains per rank; lbase[r]: rank r's first in the gathered list
+        DevBuf<SegRec> lsegs, gsegs;
+        DevBuf<unsigned long long> d_gbases;
+        DevBuf<uint32_t> ldest; DevBuf<uint64_t> lpay; DevBuf<unsigned long long> lans, lback;
+        Routed ls;
+        DevBuf<RankRec> Ra, Rb; DevBuf<uint32_t> slot_of, uid_of_slot; DevBuf<FinRec> fin; DevBuf<UHead> d_uheads; DevBuf<unsigned int> d_M;
+        unsigned int hM[2] = {0, 0};
+        std::vector<UHead> uheads;
+        // 5. unitig graph
+        std::vector<uint32_t> order, h_uid_of_slot;
+        std::vector<EndReq> reqs;
+        DevBuf<EndReq> d_req; DevBuf<uint64_t> d_ends;
+        std::vector<uint64_t> h_ends;
+        std::vector<UnitigRec> recs;
+        UnitigGraphResult res;
+        // rings
+        std::vector<uint32_t> ring_of_uid;
+        DevBuf<uint32_t> d_ring_of_uid, ring_of, vmin; DevBuf<unsigned long long> pmin; DevBuf<uint64_t> rep;
+        std::vector<uint64_t> h_pmin, all_pmin, h_rep, all_rep;
+        // 6. emission, delivery
+        ContigLayout L;                                  // lay, c_off, text_bytes, n_lin, n_contigs
+        uint64_t text_w32 = 0;                           // 2-bit words (16 bases each), an even number: all-reduced as u64
+        bool dev_writer = false;
+        DevBuf<ULayout> d_lay; DevBuf<char> d_text; DevBuf<uint32_t> d_pack;
+        std::vector<WContig> hc; DevBuf<WContig> d_c;
+        uint32_t lchain0() const { return (uint32_t)lbase[rank]; }      // this rank's first chain in the gathered list
+    };
+    void sh_lap(ShardRun &s, const char *what) {
+        if (!s.ug_dbg) return;
+        const double t = now_ms_(); fprintf(stderr, "[shard_assemble host] %-14s %8.1f ms\n", what, t - s.t_lap); s.t_lap = t;
+    }
+    void sh_stage(ShardRun &s, const char *what) { if (s.stage_log) stage_done("shard_assemble rank ", (unsigned)comm_rank(s.c), what); }
 
     // Collective.  Every way out leaves the ranks in step: a local failure travels with the next size exchange or agreement
     // round and all ranks return an error together (sh_agreed_); a failure nobody else can know of (device memory that runs
@@ -2217,256 +2294,236 @@ public:
         sh_agreed_ = false;
         wd_comm_ = (c && comm_world(c) > 1) ? c : nullptr;
         const uint64_t waits0 = n_host_waits_;
-        const int rc = shard_assemble_impl(c, tips, bubbles, out, err, json, json_len, n_contigs);
+        ShardRun s;                                        // (outlives the drain below)
+        s.c = c; s.tips = tips; s.bubbles = bubbles;
+        const int rc = shard_assemble_impl(s, out, err, json, json_len, n_contigs);
         times_.add("shard_host_waits_x1", (double)(n_host_waits_ - waits0));     // stream waits + host-side collectives of this call
         if (rc && wd_comm_ && !sh_agreed_) comm_abort_now(c);
         drain();                                           // (through the watchdog: the stream may hold collectives of a call that failed)
         wd_comm_ = nullptr;
         return rc;
     }
-    // (the host-side collectives wait for the stream: counted like the stream waits)
-    int counted_allreduce_host_u64(ShardComm *c, uint64_t *v, size_t n, void *st, std::string &e) { n_host_waits_++; return comm_allreduce_host_u64(c, v, n, st, e); }
-    int counted_allgather_host_u64(ShardComm *c, const uint64_t *in, size_t n, uint64_t *out, void *st, std::string &e) { n_host_waits_++; return comm_allgather_host_u64(c, in, n, out, st, e); }
-    int shard_assemble_impl(ShardComm *c, bool tips, bool bubbles, std::vector<RawContig> &out, std::string &err,
-                            const char **json, size_t *json_len, uint64_t *n_contigs_out) {
-        // SHK_STAGE_LOG=1: after every step the stream is drained and the step's name goes to stderr (which step a fault belongs to)
-        const bool stage_log = getenv("SHK_STAGE_LOG") != nullptr;
-        auto stage = [&](const char *what) {
-            if (!stage_log) return;
-            const hipError_t e = hipStreamSynchronize(stream_);
-            fprintf(stderr, "[shard_assemble rank %d] %s done%s\n", comm_rank(c), what, e == hipSuccess ? "" : " (stream error)");
-            fflush(stderr);
-        };
+    // the six steps of shard_graph.h, one function each (the unitig graph in four: records, graph, rings, layout)
+    int shard_assemble_impl(ShardRun &s, std::vector<RawContig> &out, std::string &err, const char **json, size_t *json_len, uint64_t *n_contigs_out) {
         out.clear();
         if (!sh_active_) { err = "shard_assemble: the handle was not preprocessed by the sharded path"; return -2; }
-        const uint32_t world = sh_world_, rank = sh_rank_;
-        const uint32_t n = (uint32_t)n_solid_;
-        const unsigned long long gbase = sh_gbase_[rank];
-        // every local step's result travels with the next collective: all ranks leave together (as in shk_shard_preprocess)
-        auto agree = [&](int local_rc, const char *stage) -> int {
-            uint64_t f = local_rc ? 1u : 0u;
-            std::string e2;
-            if (int rc = counted_allreduce_host_u64(c, &f, 1, stream_, e2)) { if (local_rc) return local_rc; err = e2; return rc; }
-            if (f) sh_agreed_ = true;                        // (every rank has seen the flag and leaves)
-            if (local_rc) return local_rc;
-            if (f) { err = std::string("sharded assembly: another rank failed during ") + stage; return -5; }
-            return 0;
-        };
-        const double t_all0 = now_ms_();
-        // ---- 1. adjacency: local tables, local candidates, then the candidates of other ranks
-        // (every buffer a collective or a kernel of this call touches lives until the call's last wait: no wait is needed for
-        // a buffer's sake; the waits that remain are the ones whose RESULT the host needs)
+        s.world = sh_world_; s.rank = sh_rank_;
+        s.n = (uint32_t)n_solid_;
+        s.gbase = sh_gbase_[s.rank];
+        s.t_all0 = now_ms_();
+        if (int rc = sh_adjacency(s, err)) return rc;
+        if (int rc = sh_half_links(s, err)) return rc;
+        sh_local_chains(s, err);                           // (what it returned travels with the chain counts: sh_stitch_counts)
+        if (int rc = sh_stitch(s, err)) return rc;
+        s.t_host0 = s.t_lap = now_ms_();
+        if (int rc = sh_unitig_records(s, err)) return rc;
+        if (int rc = sh_unitig_graph(s, err)) return rc;
+        if (int rc = sh_rings(s, err)) return rc;
+        if (int rc = sh_layout(s, err)) return rc;
+        EvTimer te(stream_, stage_timers_);
+        if (int rc = sh_emit(s, json != nullptr, err)) return rc;
+        return sh_deliver(s, te, out, err, json, json_len, n_contigs_out);
+    }
+    // ---- 1. adjacency: local tables, local candidates, then the candidates of other ranks
+    int sh_adjacency(ShardRun &s, std::string &err) {
+        ShardComm *c = s.c;
         xq_n_ = 0;
         EvTimer tg(stream_, stage_timers_);
         const int rc_local = build_graph(err);
-        if (world == 1 && rc_local) return rc_local;
-        Graph<W> g = graph_view();
-        DevBuf<unsigned long long> xnb;                  // per cross query: the neighbour's oriented global id (~0: not a solid k-mer)
-        Routed rq, hl;
-        DevBuf<unsigned long long> xans, xback;
-        DevBuf<uint32_t> hdest; DevBuf<uint64_t> hpay;
-        if (world > 1) {
+        if (s.world == 1 && rc_local) return rc_local;
+        s.g = graph_view();
+        if (s.world > 1) {
             // (the result of the local build travels with the size exchange of the first routed exchange)
             std::vector<uint64_t> flags;
             const int rc_x = rc_local ? rc_local : 0;
-            if (int rc = route_exchange<W + 1>(c, xq_dest_.p, xq_pay_.p, rc_x ? 0u : xq_n_, rq, err, rc_x ? 1u : 0u, &flags)) { if (rc_x) return rc_x; return rc; }
+            if (int rc = route_exchange<W + 1>(c, xq_dest_.p, xq_pay_.p, rc_x ? 0u : xq_n_, s.rq, err, rc_x ? 1u : 0u, &flags)) { if (rc_x) return rc_x; return rc; }
             if (rc_x) { sh_agreed_ = true; return rc_x; }
             for (uint64_t f : flags) if (f) { sh_agreed_ = true; err = "sharded assembly: another rank failed during the local graph build"; return -5; }
-            if (int rc = xans.alloc(rq.n_recv + 1, err)) return rc;
-            if (rq.n_recv) {
-                hipLaunchKernelGGL(k_xq_answer<W>, dim3(grid_for(rq.n_recv)), dim3(256), 0, stream_, g.keys, g.gt, rq.recv.p, rq.n_recv, gbase, xans.p);
+            if (int rc = s.xans.alloc(s.rq.n_recv + 1, err)) return rc;
+            if (s.rq.n_recv) {
+                hipLaunchKernelGGL(k_xq_answer<W>, dim3(grid_for(s.rq.n_recv)), dim3(256), 0, stream_, s.g.keys, s.g.gt, s.rq.recv.p, s.rq.n_recv, s.gbase, s.xans.p);
                 HIPCHK(hipGetLastError());
             }
-            if (int rc = reply_exchange(c, rq, xans.p, xback, err)) return rc;
-            if (int rc = xnb.alloc(xq_n_ + 1, err)) return rc;
+            if (int rc = reply_exchange(c, s.rq, s.xans.p, s.xback, err)) return rc;
+            if (int rc = s.xnb.alloc(xq_n_ + 1, err)) return rc;
             if (xq_n_) {
-                hipLaunchKernelGGL(k_xq_apply, dim3(grid_for(xq_n_)), dim3(256), 0, stream_, xq_meta_.p, rq.sidx.p, xback.p, xq_n_, adj_.p, nb_.p, xnb.p);
+                hipLaunchKernelGGL(k_xq_apply, dim3(grid_for(xq_n_)), dim3(256), 0, stream_, xq_meta_.p, s.rq.sidx.p, s.xback.p, xq_n_, adj_.p, nb_.p, s.xnb.p);
                 HIPCHK(hipGetLastError());
-                if (keep_stages_) HIPCHK(hipMemcpyAsync(adj0_.p, adj_.p, n, hipMemcpyDeviceToDevice, stream_));    // (stage inspection: the complete initial adjacency)
+                if (keep_stages_) HIPCHK(hipMemcpyAsync(adj0_.p, adj_.p, s.n, hipMemcpyDeviceToDevice, stream_));    // (stage inspection: the complete initial adjacency)
             }
-        } else if (int rc = xnb.alloc(1, err)) return rc;
+        } else if (int rc = s.xnb.alloc(1, err)) return rc;
         tg.stop_later("shard_graph_adjacency_total", pending_timers_);
         times_.add("shard_graph_cross_queries_x1e-3", xq_n_ * 1e-3);
-        stage("1 adjacency");
-        // ---- 2. half links: which links across ranks are simple
+        sh_stage(s, "1 adjacency");
+        return 0;
+    }
+    // ---- 2. half links: which links across ranks are simple
+    int sh_half_links(ShardRun &s, std::string &err) {
+        const uint32_t n = s.n;
         EvTimer th(stream_, stage_timers_);
-        DevBuf<uint32_t> xpred;                          // per local oriented node: record of hl.recv that names its simple predecessor on another rank
-        if (int rc = xpred.alloc(2ull * n + 2, err)) return rc;
-        HIPCHK(hipMemsetAsync(xpred.p, 0xFF, (2ull * n + 2) * 4, stream_));
+        if (int rc = s.xpred.alloc(2ull * n + 2, err)) return rc;
+        HIPCHK(hipMemsetAsync(s.xpred.p, 0xFF, (2ull * n + 2) * 4, stream_));
         HIPCHK(fill2_async(ctl(&GraphWords::halflink_flags), ctl_span(&GraphWords::halflink_flags), 0u, nullptr, 0, 0u, stream_));
-        if (world > 1) {
-            if (int rc = hdest.alloc(2ull * n + 1, err)) return rc;
-            if (int rc = hpay.alloc(4ull * n + 2, err)) return rc;
+        if (s.world > 1) {
+            if (int rc = s.hdest.alloc(2ull * n + 1, err)) return rc;
+            if (int rc = s.hpay.alloc(4ull * n + 2, err)) return rc;
             if (n) {
-                hipLaunchKernelGGL(k_hl_stage, dim3(grid_for(2ull * n)), dim3(256), 0, stream_, adj_.p, nb_.p, n, xnb.p, xq_meta_.p, gbase, hdest.p, hpay.p);
+                hipLaunchKernelGGL(k_hl_stage, dim3(grid_for(2ull * n)), dim3(256), 0, stream_, adj_.p, nb_.p, n, s.xnb.p, xq_meta_.p, s.gbase, s.hdest.p, s.hpay.p);
                 HIPCHK(hipGetLastError());
             }
-            if (int rc = route_exchange<2>(c, hdest.p, hpay.p, 2u * n, hl, err)) return rc;
-            if (hl.n_recv) {
-                hipLaunchKernelGGL(k_hl_apply, dim3(grid_for(hl.n_recv)), dim3(256), 0, stream_, hl.recv.p, hl.n_recv, gbase, n, adj_.p, xpred.p, (uint32_t *)ctl(&GraphWords::halflink_flags));
+            if (int rc = route_exchange<2>(s.c, s.hdest.p, s.hpay.p, 2u * n, s.hl, err)) return rc;
+            if (s.hl.n_recv) {
+                hipLaunchKernelGGL(k_hl_apply, dim3(grid_for(s.hl.n_recv)), dim3(256), 0, stream_, s.hl.recv.p, s.hl.n_recv, s.gbase, n, adj_.p, s.xpred.p, (uint32_t *)ctl(&GraphWords::halflink_flags));
                 HIPCHK(hipGetLastError());
             }
-        } else if (int rc = hl.recv.alloc(2, err)) return rc;
+        } else if (int rc = s.hl.recv.alloc(2, err)) return rc;
         th.stop_later("shard_graph_half_links", pending_timers_);
-        stage("2 half links");
-        // ---- 3. the chains of simple links that stay on this rank (the single-GPU contraction)
-        ChainState cs;
-        int rc_chain = 0;
-        if (n) rc_chain = rank_chains(cs, false, err);
-        const uint32_t n_lch = n ? (uint32_t)cs.n_heads : 0u;
-        stage("3 local chains");
-        // ---- 4. stitching: the local chains of all ranks, ranked by every rank
+        sh_stage(s, "2 half links");
+        return 0;
+    }
+    // ---- 3. the chains of simple links that stay on this rank (the single-GPU contraction)
+    void sh_local_chains(ShardRun &s, std::string &err) {
+        if (s.n) s.rc_chain = rank_chains(s.cs, false, err);
+        s.n_lch = s.n ? (uint32_t)s.cs.n_heads : 0u;
+        sh_stage(s, "3 local chains");
+    }
+    // ---- 4. stitching: the local chains of all ranks, ranked by every rank
+    int sh_stitch(ShardRun &s, std::string &err) {
         EvTimer ts(stream_, stage_timers_);
-        std::vector<uint64_t> lcnt(world, 0), lbase(world + 1, 0);
-        {
-            uint64_t mine[2] = {rc_chain ? 0u : n_lch, rc_chain ? 1u : 0u};
-            std::vector<uint64_t> all2((size_t)world * 2);
-            if (int rc = counted_allgather_host_u64(c, mine, 2, all2.data(), stream_, err)) { if (rc_chain) return rc_chain; return rc; }
-            if (rc_chain) { sh_agreed_ = true; return rc_chain; }
-            for (uint32_t r = 0; r < world; r++) { if (all2[2 * r + 1]) { sh_agreed_ = true; err = "sharded assembly: another rank failed during the local contraction"; return -5; } lcnt[r] = all2[2 * r]; }
-            for (uint32_t r = 0; r < world; r++) lbase[r + 1] = lbase[r] + lcnt[r];
-        }
-        const uint64_t M = lbase[world];
-        if (M >= 0xFFFFFFF0ull) { sh_agreed_ = true; err = "sharded assembly: more than 2^32 local chains"; return -1; }      // (the same sum on every rank)
-        DevBuf<SegRec> lsegs, gsegs;
-        DevBuf<unsigned long long> d_gbases;
-        if (int rc = lsegs.alloc(n_lch + 1, err)) return rc;
-        if (int rc = gsegs.alloc(M + 1, err)) return rc;
-        if (int rc = d_gbases.alloc(world + 1, err)) return rc;
-        HIPCHK(hipMemcpyAsync(d_gbases.p, sh_gbase_.data(), (size_t)(world + 1) * 8, hipMemcpyHostToDevice, stream_));
-        DevBuf<uint32_t> ldest; DevBuf<uint64_t> lpay; DevBuf<unsigned long long> lans, lback;
-        Routed ls;
-        {
-            if (int rc = ldest.alloc(n_lch + 1, err)) return rc;
-            if (int rc = lpay.alloc(n_lch + 1, err)) return rc;
-            if (n_lch) {
-                hipLaunchKernelGGL(k_lchain_stage, dim3(grid_for(n_lch)), dim3(256), 0, stream_, cs.d_heads.p, n_lch, xpred.p, hl.recv.p,
-                                   d_gbases.p, world, lsegs.p, ldest.p, lpay.p);
-                HIPCHK(hipGetLastError());
-            }
-            if (world > 1) {
-                if (int rc = route_exchange<1>(c, ldest.p, lpay.p, n_lch, ls, err)) return rc;
-                if (int rc = lans.alloc(ls.n_recv + 1, err)) return rc;
-                if (ls.n_recv) {
-                    hipLaunchKernelGGL(k_ls_answer, dim3(grid_for(ls.n_recv)), dim3(256), 0, stream_, ls.recv.p, ls.n_recv, gbase, n, cs.ol.p,
-                                       (uint32_t)lbase[rank], lans.p, (uint32_t *)ctl(&GraphWords::halflink_flags));
-                    HIPCHK(hipGetLastError());
-                }
-                if (int rc = reply_exchange(c, ls, lans.p, lback, err)) return rc;
-            } else { if (int rc = lback.alloc(1, err)) return rc; if (int rc = ls.sidx.alloc(n_lch + 1, err)) return rc; }
-            if (n_lch) {
-                hipLaunchKernelGGL(k_ls_apply, dim3(grid_for(n_lch)), dim3(256), 0, stream_, ldest.p, ls.sidx.p, lback.p, n_lch, (uint32_t)lbase[rank], lsegs.p);
-                HIPCHK(hipGetLastError());
-            }
-            // gather the chain records of all ranks (32 bytes each)
-            std::vector<uint64_t> off(world), len(world);
-            for (uint32_t r = 0; r < world; r++) { off[r] = lbase[r] * sizeof(SegRec); len[r] = lcnt[r] * sizeof(SegRec); }
-            if (int rc = comm_allgatherv(c, lsegs.p, gsegs.p, off.data(), len.data(), stream_, err)) return rc;
-        }
-        // rank the gathered list: unitigs (rings across ranks in the same pass: collapse.h)
-        DevBuf<RankRec> Ra, Rb; DevBuf<uint32_t> slot_of, uid_of_slot; DevBuf<FinRec> fin; DevBuf<UHead> d_uheads; DevBuf<unsigned int> d_M;
-        const uint32_t Mu = (uint32_t)M;
-        if (int rc = Ra.alloc(M + 1, err)) return rc;
-        if (int rc = Rb.alloc(M + 1, err)) return rc;
-        if (int rc = slot_of.alloc(M + 1, err)) return rc;
-        if (int rc = fin.alloc(M + 1, err)) return rc;
-        if (int rc = d_uheads.alloc(M + 1, err)) return rc;
-        if (int rc = d_M.alloc(2, err)) return rc;
-        unsigned int n_u = 0;
-        std::vector<UHead> uheads;
-        if (Mu) {
-            const unsigned int hM[2] = {Mu, 0u};
-            HIPCHK(hipMemcpyAsync(d_M.p, hM, 8, hipMemcpyHostToDevice, stream_));
-            HIPCHK(hipMemsetAsync(slot_of.p, 0xFF, (size_t)M * 4, stream_));
-            const int gr = grid_for(M);
-            int rounds = 1; { uint64_t reach = RANK_HOPS; while (reach < M + 1u) { reach *= RANK_HOPS; rounds++; } }
-            hipLaunchKernelGGL(k_rank_init, dim3(gr), dim3(256), 0, stream_, gsegs.p, (const unsigned int *)d_M.p, Ra.p);
-            RankRec *Ri = Ra.p, *Ro = Rb.p;
-            for (int r = 0; r < rounds; r++) { hipLaunchKernelGGL(k_rank_jump, dim3(gr), dim3(256), 0, stream_, (const unsigned int *)d_M.p, Ri, Ro); std::swap(Ri, Ro); }
-            hipLaunchKernelGGL(k_stitch_tails, dim3(gr), dim3(256), 0, stream_, gsegs.p, (const unsigned int *)d_M.p, Ri, d_uheads.p, slot_of.p, d_M.p + 1);
-            hipLaunchKernelGGL(k_rank_fin, dim3(gr), dim3(256), 0, stream_, gsegs.p, (const unsigned int *)d_M.p, Ri, slot_of.p, fin.p);
-            HIPCHK(hipGetLastError());
-            unsigned int hM2[2] = {0, 0};
-            unsigned long long h_fl = 0;
-            HIPCHK(hipMemcpyAsync(hM2, d_M.p, 8, hipMemcpyDeviceToHost, stream_));
-            HIPCHK(hipMemcpyAsync(&h_fl, ctl(&GraphWords::halflink_flags), ctl_span(&GraphWords::halflink_flags), hipMemcpyDeviceToHost, stream_));      // (flags of k_hl_apply / k_ls_answer, read with the counts)
-            WAIT_STREAM();
-            // (these flags are LOCAL: the verdict must be every rank's — a rank that left alone would leave the others in the
-            // next collective and itself one collective ahead for the rest of the process)
-            int rc_fl = 0;
-            if ((uint32_t)h_fl) {
-                err = (uint32_t)h_fl == 1 ? "sharded assembly: a record reached a rank that does not own its k-mer (ownership rules disagree)"
-                                         : "sharded assembly: the two sides of a link across ranks disagree";
-                rc_fl = -6;
-            }
-            if (world > 1) { if (int rc = agree(rc_fl, "the stitching of the chains")) return rc; }
-            else if (rc_fl) return rc_fl;
-            n_u = hM2[1];
-            uheads.resize(n_u);
-            if (n_u) HIPCHK(hipMemcpy(uheads.data(), d_uheads.p, (size_t)n_u * sizeof(UHead), hipMemcpyDeviceToHost));
-        }
+        if (int rc = sh_stitch_counts(s, err)) return rc;
+        if (int rc = sh_stitch_exchange(s, err)) return rc;
+        if (int rc = sh_stitch_rank(s, err)) return rc;
         if (ts.on()) times_.add("shard_graph_stitch", ts.stop());
-        times_.add("shard_graph_local_chains_x1e-3", n_lch * 1e-3);
-        times_.add("shard_graph_unitigs_x1", (double)n_u);
-        stage("4 stitching");
-        // ---- 5. the unitig graph on the host (identical on every rank: the records are put in the order of their first chain)
-        const double t_host0 = now_ms_();
-        const bool ug_dbg = getenv("SHK_UG_DEBUG") != nullptr;     // stage times of this host section on stderr
-        double t_lap = t_host0;
-        auto lap = [&](const char *what) { if (ug_dbg) { const double t = now_ms_(); fprintf(stderr, "[shard_assemble host] %-14s %8.1f ms\n", what, t - t_lap); t_lap = t; } };
-        // (the first chains are distinct numbers below M: a table instead of a sort — a metagenome has millions of unitigs)
-        std::vector<uint32_t> order(n_u);
-        {
-            std::vector<uint32_t> slot_at((size_t)M + 1, 0xFFFFFFFFu);
-            for (uint32_t i = 0; i < n_u; i++) {
-                // (the gathered records and their ranking are the same on every rank: so is this verdict)
-                if (uheads[i].root >= M || slot_at[uheads[i].root] != 0xFFFFFFFFu) { sh_agreed_ = true; err = "sharded assembly: two unitigs with one first chain"; return -6; }
-                slot_at[uheads[i].root] = i;
-            }
-            uint32_t at = 0;
-            for (uint32_t c0 = 0; c0 < M; c0++) if (slot_at[c0] != 0xFFFFFFFFu) order[at++] = slot_at[c0];
+        times_.add("shard_graph_local_chains_x1e-3", s.n_lch * 1e-3);
+        times_.add("shard_graph_unitigs_x1", (double)s.n_u);
+        sh_stage(s, "4 stitching");
+        return 0;
+    }
+    int sh_stitch_counts(ShardRun &s, std::string &err) {
+        const uint32_t world = s.world;
+        s.lcnt.assign(world, 0); s.lbase.assign(world + 1, 0);
+        uint64_t mine[2] = {s.rc_chain ? 0u : s.n_lch, s.rc_chain ? 1u : 0u};
+        std::vector<uint64_t> all2((size_t)world * 2);
+        if (int rc = counted_allgather_host_u64(s.c, mine, 2, all2.data(), stream_, err)) { if (s.rc_chain) return s.rc_chain; return rc; }
+        if (s.rc_chain) { sh_agreed_ = true; return s.rc_chain; }
+        for (uint32_t r = 0; r < world; r++) { if (all2[2 * r + 1]) { sh_agreed_ = true; err = "sharded assembly: another rank failed during the local contraction"; return -5; } s.lcnt[r] = all2[2 * r]; }
+        for (uint32_t r = 0; r < world; r++) s.lbase[r + 1] = s.lbase[r] + s.lcnt[r];
+        s.M = s.lbase[world];
+        if (s.M >= 0xFFFFFFF0ull) { sh_agreed_ = true; err = "sharded assembly: more than 2^32 local chains"; return -1; }      // (the same sum on every rank)
+        return 0;
+    }
+    // the chain records: who continues a chain on another rank is asked of that rank, then all ranks' records are gathered
+    int sh_stitch_exchange(ShardRun &s, std::string &err) {
+        ShardComm *c = s.c;
+        const uint32_t world = s.world, n_lch = s.n_lch;
+        if (int rc = s.lsegs.alloc(n_lch + 1, err)) return rc;
+        if (int rc = s.gsegs.alloc(s.M + 1, err)) return rc;
+        if (int rc = s.d_gbases.alloc(world + 1, err)) return rc;
+        HIPCHK(hipMemcpyAsync(s.d_gbases.p, sh_gbase_.data(), (size_t)(world + 1) * 8, hipMemcpyHostToDevice, stream_));
+        if (int rc = s.ldest.alloc(n_lch + 1, err)) return rc;
+        if (int rc = s.lpay.alloc(n_lch + 1, err)) return rc;
+        if (n_lch) {
+            hipLaunchKernelGGL(k_lchain_stage, dim3(grid_for(n_lch)), dim3(256), 0, stream_, s.cs.d_heads.p, n_lch, s.xpred.p, s.hl.recv.p,
+                               s.d_gbases.p, world, s.lsegs.p, s.ldest.p, s.lpay.p);
+            HIPCHK(hipGetLastError());
         }
-        lap("order");
-        std::vector<uint32_t> h_uid_of_slot(n_u);
-        for (uint32_t u = 0; u < n_u; u++) h_uid_of_slot[order[u]] = u;
-        // first / last k-mer of every unitig: asked of the rank that holds that chain
-        std::vector<EndReq> reqs;
-        reqs.reserve(world == 1 ? 2 * (size_t)n_u : 2 * (size_t)n_u / world + 1024);
-        for (uint32_t u = 0; u < n_u; u++) {
-            const UHead &h = uheads[order[u]];
-            if (h.root >= lbase[rank] && h.root < lbase[rank + 1]) reqs.push_back(EndReq{u, 0u, (uint32_t)(h.root - lbase[rank]), 0u});
-            if (h.tail >= lbase[rank] && h.tail < lbase[rank + 1]) reqs.push_back(EndReq{u, 1u, (uint32_t)(h.tail - lbase[rank]), 0u});
-        }
-        lap("requests");
-        DevBuf<EndReq> d_req; DevBuf<uint64_t> d_ends;
-        const size_t ends_words = (size_t)n_u * 2 * W;
-        if (int rc = d_req.alloc(reqs.size() + 1, err)) return rc;
-        if (int rc = d_ends.alloc(ends_words + 1, err)) return rc;
-        if (int rc = uid_of_slot.alloc(n_u + 1, err)) return rc;
-        std::vector<uint64_t> h_ends(ends_words + 1, 0);
-        if (n_u) {
-            HIPCHK(hipMemsetAsync(d_ends.p, 0, ends_words * 8, stream_));
-            HIPCHK(hipMemcpyAsync(uid_of_slot.p, h_uid_of_slot.data(), (size_t)n_u * 4, hipMemcpyHostToDevice, stream_));
-            if (!reqs.empty()) {
-                HIPCHK(hipMemcpyAsync(d_req.p, reqs.data(), reqs.size() * sizeof(EndReq), hipMemcpyHostToDevice, stream_));
-                hipLaunchKernelGGL(k_fill_ends<W>, dim3(grid_for(reqs.size())), dim3(256), 0, stream_, g, cs.d_heads.p, d_req.p, (uint32_t)reqs.size(), d_ends.p);
+        if (world > 1) {
+            if (int rc = route_exchange<1>(c, s.ldest.p, s.lpay.p, n_lch, s.ls, err)) return rc;
+            if (int rc = s.lans.alloc(s.ls.n_recv + 1, err)) return rc;
+            if (s.ls.n_recv) {
+                hipLaunchKernelGGL(k_ls_answer, dim3(grid_for(s.ls.n_recv)), dim3(256), 0, stream_, s.ls.recv.p, s.ls.n_recv, s.gbase, s.n, s.cs.ol.p,
+                                   s.lchain0(), s.lans.p, (uint32_t *)ctl(&GraphWords::halflink_flags));
                 HIPCHK(hipGetLastError());
             }
-            if (int rc = comm_allreduce_u64(c, d_ends.p, ends_words, stream_, err)) return rc;     // (every word is written by exactly one rank)
-            HIPCHK(hipMemcpyAsync(h_ends.data(), d_ends.p, ends_words * 8, hipMemcpyDeviceToHost, stream_));
+            if (int rc = reply_exchange(c, s.ls, s.lans.p, s.lback, err)) return rc;
+        } else { if (int rc = s.lback.alloc(1, err)) return rc; if (int rc = s.ls.sidx.alloc(n_lch + 1, err)) return rc; }
+        if (n_lch) {
+            hipLaunchKernelGGL(k_ls_apply, dim3(grid_for(n_lch)), dim3(256), 0, stream_, s.ldest.p, s.ls.sidx.p, s.lback.p, n_lch, s.lchain0(), s.lsegs.p);
+            HIPCHK(hipGetLastError());
+        }
+        // gather the chain records of all ranks (32 bytes each)
+        std::vector<uint64_t> off(world), len(world);
+        for (uint32_t r = 0; r < world; r++) { off[r] = s.lbase[r] * sizeof(SegRec); len[r] = s.lcnt[r] * sizeof(SegRec); }
+        return comm_allgatherv(c, s.lsegs.p, s.gsegs.p, off.data(), len.data(), stream_, err);
+    }
+    // rank the gathered list: unitigs (rings across ranks in the same pass: collapse.h)
+    int sh_stitch_rank(ShardRun &s, std::string &err) {
+        const uint64_t M = s.M;
+        const uint32_t Mu = (uint32_t)M;
+        if (int rc = s.Ra.alloc(M + 1, err)) return rc;
+        if (int rc = s.Rb.alloc(M + 1, err)) return rc;
+        if (int rc = s.slot_of.alloc(M + 1, err)) return rc;
+        if (int rc = s.fin.alloc(M + 1, err)) return rc;
+        if (int rc = s.d_uheads.alloc(M + 1, err)) return rc;
+        if (int rc = s.d_M.alloc(2, err)) return rc;
+        if (!Mu) return 0;
+        s.hM[0] = Mu; s.hM[1] = 0u;
+        HIPCHK(hipMemcpyAsync(s.d_M.p, s.hM, 8, hipMemcpyHostToDevice, stream_));
+        HIPCHK(hipMemsetAsync(s.slot_of.p, 0xFF, (size_t)M * 4, stream_));
+        const int gr = grid_for(M);
+        int rounds = 1; { uint64_t reach = RANK_HOPS; while (reach < M + 1u) { reach *= RANK_HOPS; rounds++; } }
+        hipLaunchKernelGGL(k_rank_init, dim3(gr), dim3(256), 0, stream_, s.gsegs.p, (const unsigned int *)s.d_M.p, s.Ra.p);
+        RankRec *Ri = s.Ra.p, *Ro = s.Rb.p;
+        for (int r = 0; r < rounds; r++) { hipLaunchKernelGGL(k_rank_jump, dim3(gr), dim3(256), 0, stream_, (const unsigned int *)s.d_M.p, Ri, Ro); std::swap(Ri, Ro); }
+        hipLaunchKernelGGL(k_stitch_tails, dim3(gr), dim3(256), 0, stream_, s.gsegs.p, (const unsigned int *)s.d_M.p, Ri, s.d_uheads.p, s.slot_of.p, s.d_M.p + 1);
+        hipLaunchKernelGGL(k_rank_fin, dim3(gr), dim3(256), 0, stream_, s.gsegs.p, (const unsigned int *)s.d_M.p, Ri, s.slot_of.p, s.fin.p);
+        HIPCHK(hipGetLastError());
+        unsigned int hM2[2] = {0, 0};
+        unsigned long long h_fl = 0;
+        HIPCHK(hipMemcpyAsync(hM2, s.d_M.p, 8, hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipMemcpyAsync(&h_fl, ctl(&GraphWords::halflink_flags), ctl_span(&GraphWords::halflink_flags), hipMemcpyDeviceToHost, stream_));      // (flags of k_hl_apply / k_ls_answer, read with the counts)
+        WAIT_STREAM();
+        // (these flags are LOCAL: the verdict must be every rank's — a rank that left alone would leave the others in the
+        // next collective and itself one collective ahead for the rest of the process)
+        int rc_fl = 0;
+        if ((uint32_t)h_fl) {
+            err = (uint32_t)h_fl == 1 ? "sharded assembly: a record reached a rank that does not own its k-mer (ownership rules disagree)"
+                                     : "sharded assembly: the two sides of a link across ranks disagree";
+            rc_fl = -6;
+        }
+        if (s.world > 1) { if (int rc = agree(s.c, rc_fl, "the stitching of the chains", err)) return rc; }
+        else if (rc_fl) return rc_fl;
+        s.n_u = hM2[1];
+        s.uheads.resize(s.n_u);
+        if (s.n_u) HIPCHK(hipMemcpy(s.uheads.data(), s.d_uheads.p, (size_t)s.n_u * sizeof(UHead), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    // ---- 5. the unitig graph on the host (identical on every rank: the records are put in the order of their first chain)
+    // first / last k-mer of every unitig: asked of the rank that holds that chain
+    int sh_unitig_records(ShardRun &s, std::string &err) {
+        const unsigned int n_u = s.n_u;
+        // (the gathered records and their ranking are the same on every rank: so is this verdict)
+        if (plan_order(s.uheads, s.M, s.order, s.h_uid_of_slot)) { sh_agreed_ = true; err = "sharded assembly: two unitigs with one first chain"; return -6; }
+        sh_lap(s, "order");
+        plan_end_requests(s.uheads, s.order, s.lbase[s.rank], s.lbase[s.rank + 1], s.world, s.reqs);
+        sh_lap(s, "requests");
+        const std::vector<EndReq> &reqs = s.reqs;
+        const size_t ends_words = (size_t)n_u * 2 * W;
+        if (int rc = s.d_req.alloc(reqs.size() + 1, err)) return rc;
+        if (int rc = s.d_ends.alloc(ends_words + 1, err)) return rc;
+        if (int rc = s.uid_of_slot.alloc(n_u + 1, err)) return rc;
+        s.h_ends.assign(ends_words + 1, 0);
+        if (n_u) {
+            HIPCHK(hipMemsetAsync(s.d_ends.p, 0, ends_words * 8, stream_));
+            HIPCHK(hipMemcpyAsync(s.uid_of_slot.p, s.h_uid_of_slot.data(), (size_t)n_u * 4, hipMemcpyHostToDevice, stream_));
+            if (!reqs.empty()) {
+                HIPCHK(hipMemcpyAsync(s.d_req.p, reqs.data(), reqs.size() * sizeof(EndReq), hipMemcpyHostToDevice, stream_));
+                hipLaunchKernelGGL(k_fill_ends<W>, dim3(grid_for(reqs.size())), dim3(256), 0, stream_, s.g, s.cs.d_heads.p, s.d_req.p, (uint32_t)reqs.size(), s.d_ends.p);
+                HIPCHK(hipGetLastError());
+            }
+            if (int rc = comm_allreduce_u64(s.c, s.d_ends.p, ends_words, stream_, err)) return rc;     // (every word is written by exactly one rank)
+            HIPCHK(hipMemcpyAsync(s.h_ends.data(), s.d_ends.p, ends_words * 8, hipMemcpyDeviceToHost, stream_));
             WAIT_STREAM();
         }
-        lap("ends");
-        std::vector<UnitigRec> recs(n_u);
-        host_par_ranges(n_u, [&](size_t a, size_t b) {
-            for (size_t u = a; u < b; u++) {
-                const UHead &h = uheads[order[u]];
-                for (int w = 0; w < W; w++) { recs[u].first[w] = h_ends[(u * 2 + 0) * W + w]; recs[u].last[w] = h_ends[(u * 2 + 1) * W + w]; }
-                recs[u].len = h.len; recs[u].kc = h.kc; recs[u].circ = h.circ;
-            }
-        });
-        lap("records");
-        UnitigGraphResult res;
+        sh_lap(s, "ends");
+        plan_records<W>(s.uheads, s.order, s.h_ends, s.recs);
+        sh_lap(s, "records");
+        return 0;
+    }
+    // tips, bubbles and the final chains: on the device or on the host
+    int sh_unitig_graph(ShardRun &s, std::string &err) {
+        const unsigned int n_u = s.n_u;
+        UnitigGraphResult &res = s.res;
         // SHK_UNITIG_DEVICE: 1 — the device twin (unitig_graph_gpu.h), 0 — the host code; unset: the device from
         // SHK_UNITIG_DEVICE_MIN records on (UNITIG_DEVICE_MIN_DEFAULT: DESIGN.md §5 says where the figure comes from).  The
         // two compute the same result from the same records, so a rank whose device has no room falls back alone.
@@ -2479,201 +2536,149 @@ public:
         }
         int rc_ug = 1;
         if (ug_device) {
-            rc_ug = unitig_assemble_device(k_, recs, tips, bubbles, stream_dev_, stream_, res, err);
+            rc_ug = unitig_assemble_device(k_, s.recs, s.tips, s.bubbles, stream_dev_, stream_, res, err);
             if (rc_ug == 1) times_.add("shard_graph_unitig_device_declined_x1", 1.0);
             else times_.add("shard_graph_unitig_device_x1", 1.0);
         }
-        if (rc_ug == 1) rc_ug = unitig_assemble(k_, recs, tips, bubbles, res, err);
+        if (rc_ug == 1) rc_ug = unitig_assemble(k_, s.recs, s.tips, s.bubbles, res, err);
         times_.add("shard_graph_unitig_graph", now_ms_() - t_ug0);
-        lap("unitig graph");
+        sh_lap(s, "unitig graph");
         // (the same code on the same records: inconsistent records fail on every rank or on none — an agreement round is only
         // paid where the graph is large enough for one host to run out of memory alone.  A HIP error of the device twin is
         // rank-local like that: below 2^20 records this rank leaves with -6 without a round, as it does after a host failure
         // of its own, and the others meet the communicator's time limit in their next collective)
-        if (n_u >= (1u << 20)) { if (int rc = agree(rc_ug ? -6 : 0, "the unitig graph")) return rc; }
+        if (n_u >= (1u << 20)) { if (int rc = agree(s.c, rc_ug ? -6 : 0, "the unitig graph", err)) return rc; }
         else if (rc_ug) { sh_agreed_ = true; return -6; }
         tips_removed_ = res.tips_removed; bubbles_removed_ = res.bubbles_removed; rounds_ = res.rounds;
-        // rings: the smallest k-mer of their records — a pass over the nodes of the rings, on every rank, merged on the host
+        return 0;
+    }
+    // rings: the smallest k-mer of their records — a pass over the nodes of the rings, on every rank, merged on the host
+    int sh_rings(ShardRun &s, std::string &err) {
+        ShardComm *c = s.c;
+        const uint32_t world = s.world, n = s.n, n_lch = s.n_lch;
+        const unsigned int n_u = s.n_u;
+        UnitigGraphResult &res = s.res;
         if (!res.need_min.empty()) {
             const uint32_t n_rings = (uint32_t)res.need_min.size();
-            std::vector<uint32_t> ring_of_uid(n_u, NIL);
-            for (uint32_t i = 0; i < n_rings; i++) ring_of_uid[res.need_min[i]] = i;
-            DevBuf<uint32_t> d_ring_of_uid, ring_of, vmin; DevBuf<unsigned long long> pmin; DevBuf<uint64_t> rep;
-            if (int rc = d_ring_of_uid.alloc(n_u + 1, err)) return rc;
-            if (int rc = ring_of.alloc(n_lch + 1, err)) return rc;
-            if (int rc = vmin.alloc(n_rings + 1, err)) return rc;
-            if (int rc = pmin.alloc(n_rings + 1, err)) return rc;
-            if (int rc = rep.alloc((size_t)n_rings * (W + 2) + 1, err)) return rc;
-            HIPCHK(hipMemcpyAsync(d_ring_of_uid.p, ring_of_uid.data(), (size_t)n_u * 4, hipMemcpyHostToDevice, stream_));
-            HIPCHK(hipMemsetAsync(pmin.p, 0xFF, (size_t)n_rings * 8, stream_));
-            HIPCHK(hipMemsetAsync(vmin.p, 0xFF, (size_t)n_rings * 4, stream_));
-            std::vector<uint64_t> h_pmin(n_rings, ~0ull), all_pmin((size_t)world * n_rings);
+            s.ring_of_uid.assign(n_u, NIL);
+            for (uint32_t i = 0; i < n_rings; i++) s.ring_of_uid[res.need_min[i]] = i;
+            if (int rc = s.d_ring_of_uid.alloc(n_u + 1, err)) return rc;
+            if (int rc = s.ring_of.alloc(n_lch + 1, err)) return rc;
+            if (int rc = s.vmin.alloc(n_rings + 1, err)) return rc;
+            if (int rc = s.pmin.alloc(n_rings + 1, err)) return rc;
+            if (int rc = s.rep.alloc((size_t)n_rings * (W + 2) + 1, err)) return rc;
+            HIPCHK(hipMemcpyAsync(s.d_ring_of_uid.p, s.ring_of_uid.data(), (size_t)n_u * 4, hipMemcpyHostToDevice, stream_));
+            HIPCHK(hipMemsetAsync(s.pmin.p, 0xFF, (size_t)n_rings * 8, stream_));
+            HIPCHK(hipMemsetAsync(s.vmin.p, 0xFF, (size_t)n_rings * 4, stream_));
+            std::vector<uint64_t> &h_pmin = s.h_pmin, &all_pmin = s.all_pmin, &h_rep = s.h_rep, &all_rep = s.all_rep;
+            h_pmin.assign(n_rings, ~0ull); all_pmin.assign((size_t)world * n_rings, 0);
             if (n_lch) {
-                hipLaunchKernelGGL(k_ring_of, dim3(grid_for(n_lch)), dim3(256), 0, stream_, fin.p, (uint32_t)lbase[rank], n_lch, uid_of_slot.p, d_ring_of_uid.p, ring_of.p);
-                hipLaunchKernelGGL(k_sring_min1<W>, dim3(grid_for(2ull * n)), dim3(256), 0, stream_, g, cs.ol.p, ring_of.p, pmin.p);
+                hipLaunchKernelGGL(k_ring_of, dim3(grid_for(n_lch)), dim3(256), 0, stream_, s.fin.p, s.lchain0(), n_lch, s.uid_of_slot.p, s.d_ring_of_uid.p, s.ring_of.p);
+                hipLaunchKernelGGL(k_sring_min1<W>, dim3(grid_for(2ull * n)), dim3(256), 0, stream_, s.g, s.cs.ol.p, s.ring_of.p, s.pmin.p);
                 HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpyAsync(h_pmin.data(), pmin.p, (size_t)n_rings * 8, hipMemcpyDeviceToHost, stream_));
+                HIPCHK(hipMemcpyAsync(h_pmin.data(), s.pmin.p, (size_t)n_rings * 8, hipMemcpyDeviceToHost, stream_));
                 WAIT_STREAM();
             }
             if (int rc = counted_allgather_host_u64(c, h_pmin.data(), n_rings, all_pmin.data(), stream_, err)) return rc;
             for (uint32_t i = 0; i < n_rings; i++) for (uint32_t r = 0; r < world; r++) h_pmin[i] = std::min(h_pmin[i], all_pmin[(size_t)r * n_rings + i]);
-            std::vector<uint64_t> h_rep((size_t)n_rings * (W + 2), ~0ull), all_rep((size_t)world * n_rings * (W + 2));
+            h_rep.assign((size_t)n_rings * (W + 2), ~0ull); all_rep.assign((size_t)world * n_rings * (W + 2), 0);
             if (n_lch) {
-                HIPCHK(hipMemcpyAsync(pmin.p, h_pmin.data(), (size_t)n_rings * 8, hipMemcpyHostToDevice, stream_));
-                hipLaunchKernelGGL(k_sring_min2<W>, dim3(grid_for(2ull * n)), dim3(256), 0, stream_, g, cs.ol.p, ring_of.p, pmin.p, vmin.p);
-                hipLaunchKernelGGL(k_sring_report<W>, dim3(grid_for(n_rings)), dim3(256), 0, stream_, g, cs.ol.p, fin.p, (uint32_t)lbase[rank], vmin.p, n_rings, rep.p);
+                HIPCHK(hipMemcpyAsync(s.pmin.p, h_pmin.data(), (size_t)n_rings * 8, hipMemcpyHostToDevice, stream_));
+                hipLaunchKernelGGL(k_sring_min2<W>, dim3(grid_for(2ull * n)), dim3(256), 0, stream_, s.g, s.cs.ol.p, s.ring_of.p, s.pmin.p, s.vmin.p);
+                hipLaunchKernelGGL(k_sring_report<W>, dim3(grid_for(n_rings)), dim3(256), 0, stream_, s.g, s.cs.ol.p, s.fin.p, s.lchain0(), s.vmin.p, n_rings, s.rep.p);
                 HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpyAsync(h_rep.data(), rep.p, h_rep.size() * 8, hipMemcpyDeviceToHost, stream_));
+                HIPCHK(hipMemcpyAsync(h_rep.data(), s.rep.p, h_rep.size() * 8, hipMemcpyDeviceToHost, stream_));
                 WAIT_STREAM();
             }
             if (int rc = counted_allgather_host_u64(c, h_rep.data(), h_rep.size(), all_rep.data(), stream_, err)) return rc;
             std::vector<UnitigMinKey> mk(n_u);
-            for (uint32_t i = 0; i < n_rings; i++) {
-                UnitigMinKey best;
-                for (uint32_t r = 0; r < world; r++) {
-                    const uint64_t *o = &all_rep[((size_t)r * n_rings + i) * (W + 2)];
-                    if (o[W] == ~0ull) continue;
-                    UnitigMinKey cand; cand.valid = true; cand.o = (uint32_t)o[W]; cand.pos = o[W + 1];
-                    for (int w = 0; w < W; w++) cand.key[w] = o[w];
-                    bool less = !best.valid;
-                    if (!less) {
-                        bool decided = false;
-                        for (int w = W - 1; w >= 0 && !decided; w--) if (cand.key[w] != best.key[w]) { less = cand.key[w] < best.key[w]; decided = true; }
-                        if (!decided) less = cand.o < best.o;
-                    }
-                    if (less) best = cand;
-                }
-                mk[res.need_min[i]] = best;
-            }
-            int rc_rr = unitig_resolve_rings(k_, recs, mk, res, err);
+            plan_ring_min_keys<W>(all_rep, world, res.need_min, mk);
+            int rc_rr = unitig_resolve_rings(k_, s.recs, mk, res, err);
             if (rc_rr) { sh_agreed_ = true; return -6; }      // (deterministic on identical input: every rank takes the same way out)
         }
-        lap("rings");
-        // layout: contig text offsets, and for every unitig record where its nodes go
-        // (the walk on the device hands over the linear contigs flat, with every record's placement: the linear contigs
-        // come first, the rings — res.contigs — behind them, their text from the linear contigs' total on)
-        const size_t n_lin = res.flat ? res.lin.size() : 0, n_contigs = n_lin + res.contigs.size();
-        if (res.flat && (res.place.size() != (size_t)n_u || res.recs_flat.size() > (size_t)n_u)) { sh_agreed_ = true; err = "sharded assembly: the flat form of the unitig graph does not fit the records"; return -6; }
-        std::vector<ULayout> lay(n_u + 1);
-        uint64_t text_bytes = 0;
-        std::vector<uint64_t> c_off(n_contigs);
-        if (res.flat) {
-            host_par_ranges(n_u, [&](size_t a, size_t b) {
-                for (size_t r = a; r < b; r++) { ULayout &L = lay[r]; L.off = res.place[r].off; L.node_off = res.place[r].node_off; L.ring_len = 0; L.rot = 0; }
-            });
-            { ULayout &L = lay[n_u]; L.off = ~0ull; L.node_off = 0; L.ring_len = 0; L.rot = 0; }
-            host_par_ranges(n_lin, [&](size_t a, size_t b) { for (size_t i = a; i < b; i++) c_off[i] = res.lin[i].text_off; });
-            text_bytes = res.lin_text;
-        } else
-            for (auto &L : lay) { L.off = ~0ull; L.node_off = 0; L.ring_len = 0; L.rot = 0; }
-        if (res.flat) times_.add("shard_graph_unitig_chains_device_x1", 1.0);
-        times_.add("shard_graph_unitig_contigs_x1", (double)n_contigs);
-        for (size_t i = 0; i < res.contigs.size(); i++) {
-            const UnitigContig &ct = res.contigs[i];
-            c_off[n_lin + i] = text_bytes;
-            uint64_t node_off = 0;
-            for (uint32_t r : ct.recs) {
-                lay[r].off = text_bytes; lay[r].node_off = node_off; lay[r].ring_len = ct.ring ? ct.len_nodes : 0; lay[r].rot = ct.ring ? ct.rot : 0;
-                node_off += recs[r].len;
-            }
-            text_bytes += ct.len_nodes + (uint64_t)(k_ - 1);
-        }
-        lap("layout");
-        times_.add("shard_graph_unitig_host_clock", now_ms_() - t_host0);
-        stage("5 unitig graph");
-        // ---- 6. emission
-        EvTimer te(stream_, stage_timers_);
-        const uint64_t text_w32 = ((text_bytes + 15) / 16 + 1) & ~1ull;           // 2-bit words (16 bases each), an even number: all-reduced as u64
-        DevBuf<ULayout> d_lay; DevBuf<char> d_text; DevBuf<uint32_t> d_pack;
-        if (int rc = d_lay.alloc(n_u + 1, err)) return rc;
-        if (int rc = d_text.alloc(text_w32 * 16 + 16, err)) return rc;
-        if (int rc = d_pack.alloc(text_w32 + 2, err)) return rc;
+        sh_lap(s, "rings");
+        return 0;
+    }
+    // layout: contig text offsets, and for every unitig record where its nodes go
+    int sh_layout(ShardRun &s, std::string &err) {
+        // (the records and the unitig graph are the same on every rank: so is this verdict)
+        if (plan_layout(k_, s.res, s.recs, s.L)) { sh_agreed_ = true; err = "sharded assembly: the flat form of the unitig graph does not fit the records"; return -6; }
+        if (s.res.flat) times_.add("shard_graph_unitig_chains_device_x1", 1.0);
+        times_.add("shard_graph_unitig_contigs_x1", (double)s.L.n_contigs);
+        sh_lap(s, "layout");
+        times_.add("shard_graph_unitig_host_clock", now_ms_() - s.t_host0);
+        sh_stage(s, "5 unitig graph");
+        return 0;
+    }
+    // ---- 6. emission: emit, pack, all-reduce, unpack
+    int sh_emit(ShardRun &s, bool want_json, std::string &err) {
+        const uint64_t text_bytes = s.L.text_bytes;
+        const uint64_t text_w32 = s.text_w32 = ((text_bytes + 15) / 16 + 1) & ~1ull;
+        if (int rc = s.d_lay.alloc(s.n_u + 1, err)) return rc;
+        if (int rc = s.d_text.alloc(text_w32 * 16 + 16, err)) return rc;
+        if (int rc = s.d_pack.alloc(text_w32 + 2, err)) return rc;
         // a fragmented assembly: its get_assembly() text is written on the device from the all-reduced text (writer_text_gpu.h),
         // as collapse() does on one GPU — the text is then never downloaded
-        const bool dev_writer = json && text_bytes && (uint64_t)n_contigs >= env_u64("SHK_DEVICE_WRITER_MIN", 20000) &&
-                                env_u64("SHK_SHARD_DEVICE_WRITER", 1) != 0;
-        if (!dev_writer) if (int rc = hout_.alloc(text_w32 * 16 + 16, err)) return rc;
+        s.dev_writer = want_json && text_bytes && (uint64_t)s.L.n_contigs >= env_u64("SHK_DEVICE_WRITER_MIN", 20000) &&
+                       env_u64("SHK_SHARD_DEVICE_WRITER", 1) != 0;
+        if (!s.dev_writer) if (int rc = hout_.alloc(text_w32 * 16 + 16, err)) return rc;
         if (text_bytes) {
-            HIPCHK(hipMemsetAsync(d_text.p, 0, text_w32 * 16, stream_));
-            HIPCHK(hipMemcpyAsync(d_lay.p, lay.data(), (size_t)(n_u + 1) * sizeof(ULayout), hipMemcpyHostToDevice, stream_));
-            if (n) {
-                hipLaunchKernelGGL(k_shard_emit<W>, dim3(grid_for(n)), dim3(256), 0, stream_, g, cs.ol.p, fin.p, (uint32_t)lbase[rank], uid_of_slot.p, d_lay.p, d_text.p);
+            HIPCHK(hipMemsetAsync(s.d_text.p, 0, text_w32 * 16, stream_));
+            HIPCHK(hipMemcpyAsync(s.d_lay.p, s.L.lay.data(), (size_t)(s.n_u + 1) * sizeof(ULayout), hipMemcpyHostToDevice, stream_));
+            if (s.n) {
+                hipLaunchKernelGGL(k_shard_emit<W>, dim3(grid_for(s.n)), dim3(256), 0, stream_, s.g, s.cs.ol.p, s.fin.p, s.lchain0(), s.uid_of_slot.p, s.d_lay.p, s.d_text.p);
                 HIPCHK(hipGetLastError());
             }
-            if (world > 1) {
+            if (s.world > 1) {
                 // every base is written by exactly one rank: packed 2 bits per base (A = 0 = "not mine") the ranks' words add up
-                hipLaunchKernelGGL(k_text_pack2, dim3(grid_for(text_w32)), dim3(256), 0, stream_, d_text.p, text_bytes, d_pack.p, text_w32);
+                hipLaunchKernelGGL(k_text_pack2, dim3(grid_for(text_w32)), dim3(256), 0, stream_, s.d_text.p, text_bytes, s.d_pack.p, text_w32);
                 HIPCHK(hipGetLastError());
-                if (int rc = comm_allreduce_u64(c, d_pack.p, text_w32 / 2, stream_, err)) return rc;
-                hipLaunchKernelGGL(k_text_unpack2, dim3(grid_for(text_w32)), dim3(256), 0, stream_, d_pack.p, text_w32, d_text.p);
+                if (int rc = comm_allreduce_u64(s.c, s.d_pack.p, text_w32 / 2, stream_, err)) return rc;
+                hipLaunchKernelGGL(k_text_unpack2, dim3(grid_for(text_w32)), dim3(256), 0, stream_, s.d_pack.p, text_w32, s.d_text.p);
                 HIPCHK(hipGetLastError());
                 times_.add("shard_graph_text_allreduce_MB", (double)(text_w32 * 4) / 1e6);
             }
-            if (!dev_writer) HIPCHK(hipMemcpyAsync(hout_.p, d_text.p, text_bytes, hipMemcpyDeviceToHost, stream_));
+            if (!s.dev_writer) HIPCHK(hipMemcpyAsync(hout_.p, s.d_text.p, text_bytes, hipMemcpyDeviceToHost, stream_));
         }
-        stage("6 emission kernels");
-        if (dev_writer) {
+        sh_stage(s, "6 emission kernels");
+        return 0;
+    }
+    // delivery: the device writer, or the text's download (also when the writer declines)
+    int sh_deliver(ShardRun &s, EvTimer &te, std::vector<RawContig> &out, std::string &err, const char **json, size_t *json_len, uint64_t *n_contigs_out) {
+        const size_t n_contigs = s.L.n_contigs;
+        const uint64_t text_bytes = s.L.text_bytes;
+        if (s.dev_writer) {
             if (te.on()) times_.add("shard_graph_emit", te.stop());
             // the contigs in text order: the linear ones, then the rings (24 bytes each to upload)
             const char *why = "";
             int rc_w = 0;
-            std::vector<WContig> hc(n_contigs);
-            std::atomic<int> bad{0};
-            auto put = [&](size_t i, uint64_t nodes, uint64_t kc) {
-                const uint64_t bases = nodes + (uint64_t)(k_ - 1);
-                if (bases > 0xFFFFFFFFull) bad.store(1);
-                else if (c_off[i] + bases != (i + 1 < n_contigs ? c_off[i + 1] : text_bytes)) bad.store(2);
-                hc[i].off = c_off[i]; hc[i].kc = kc; hc[i].len = (uint32_t)bases; hc[i].slot = (uint32_t)i;
-            };
-            host_par_ranges(n_lin, [&](size_t a, size_t b) { for (size_t i = a; i < b; i++) put(i, res.lin[i].len_nodes, res.lin[i].kc); });
-            for (size_t i = 0; i < res.contigs.size(); i++) put(n_lin + i, res.contigs[i].len_nodes, res.contigs[i].kc);
-            DevBuf<WContig> d_c;
-            if (bad.load()) { why = bad.load() == 1 ? "a contig of 2^32 bases or more" : "the contigs do not lie back to back in the text"; rc_w = 1; }
+            const int bad = plan_writer_contigs(k_, s.res, s.L, s.hc);
+            if (bad) { why = bad == 1 ? "a contig of 2^32 bases or more" : "the contigs do not lie back to back in the text"; rc_w = 1; }
             else if (n_contigs >= 0x7FFFFFF0ull) { why = "2^31 contigs or more"; rc_w = 1; }
-            else if (d_c.alloc(n_contigs + 1, err)) { why = "out of device memory"; rc_w = 1; }
+            else if (s.d_c.alloc(n_contigs + 1, err)) { why = "out of device memory"; rc_w = 1; }
             if (!rc_w) {
-                HIPCHK(hipMemcpyAsync(d_c.p, hc.data(), n_contigs * sizeof(WContig), hipMemcpyHostToDevice, stream_));
-                rc_w = device_write_text_json(d_c, n_contigs, d_text.p, text_bytes, json, json_len, &why, err);
+                HIPCHK(hipMemcpyAsync(s.d_c.p, s.hc.data(), n_contigs * sizeof(WContig), hipMemcpyHostToDevice, stream_));
+                rc_w = device_write_text_json(s.d_c, n_contigs, s.d_text.p, text_bytes, json, json_len, &why, err);
                 if (rc_w < 0) return rc_w;
             }
             if (rc_w == 0) {
                 if (n_contigs_out) *n_contigs_out = n_contigs;
                 times_.add("shard_writer_device_x1", 1.0);
-                times_.add("shard_assemble_host_clock", now_ms_() - t_all0);
+                times_.add("shard_assemble_host_clock", now_ms_() - s.t_all0);
                 return 0;
             }
             // declined (rank-local; the host writer gives the same bytes from the text, turned or not): download it as below the threshold
-            if (stage_log) { fprintf(stderr, "[shard_assemble rank %d] device writer declined: %s\n", comm_rank(c), why); fflush(stderr); }
+            if (s.stage_log) { fprintf(stderr, "[shard_assemble rank %d] device writer declined: %s\n", comm_rank(s.c), why); fflush(stderr); }
             times_.add("shard_writer_device_declined_x1", 1.0);
             *json = nullptr; err.clear();
-            if (int rc = hout_.alloc(text_w32 * 16 + 16, err)) return rc;
-            HIPCHK(hipMemcpyAsync(hout_.p, d_text.p, text_bytes, hipMemcpyDeviceToHost, stream_));
+            if (int rc = hout_.alloc(s.text_w32 * 16 + 16, err)) return rc;
+            HIPCHK(hipMemcpyAsync(hout_.p, s.d_text.p, text_bytes, hipMemcpyDeviceToHost, stream_));
         }
         WAIT_STREAM();
-        if (te.on() && !dev_writer) times_.add("shard_graph_emit", te.stop());
-        out.resize(n_contigs);
-        host_par_ranges(n_lin, [&](size_t a, size_t b) {
-            for (size_t i = a; i < b; i++) {
-                RawContig &rcg = out[i]; rcg.kc = res.lin[i].kc;
-                rcg.ext = hout_.p + c_off[i]; rcg.ext_n = res.lin[i].len_nodes + (uint64_t)(k_ - 1);
-            }
-        });
-        for (size_t i = 0; i < res.contigs.size(); i++) {
-            RawContig &rcg = out[n_lin + i]; rcg.kc = res.contigs[i].kc;
-            rcg.ext = hout_.p + c_off[n_lin + i]; rcg.ext_n = res.contigs[i].len_nodes + (uint64_t)(k_ - 1);
-        }
-        times_.add("shard_assemble_host_clock", now_ms_() - t_all0);
+        if (te.on() && !s.dev_writer) times_.add("shard_graph_emit", te.stop());
+        plan_raw_contigs(k_, s.res, s.L, hout_.p, out);
+        times_.add("shard_assemble_host_clock", now_ms_() - s.t_all0);
         return 0;
-    }
-    // a loop over millions of host records (the unitigs of a metagenome) on several threads
-    template <typename F> static void host_par_ranges(size_t n, F &&fn) {
-        const unsigned hw = std::thread::hardware_concurrency();
-        const unsigned T = n < 262144 ? 1u : std::min(16u, std::max(1u, hw));
-        if (T == 1) { fn((size_t)0, n); return; }
-        std::vector<std::thread> ts;
-        for (unsigned t = 1; t < T; t++) ts.emplace_back([&fn, n, t, T] { fn(n * t / T, n * (t + 1) / T); });
-        fn((size_t)0, n / T);
-        for (auto &t : ts) t.join();
     }
     static double now_ms_() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 

@@ -23,6 +23,7 @@
 //                  (the ranks' bytes are disjoint) puts the text together
 // All integer work, no MFMA.
 #pragma once
+#include "shard_plan.h"     // UHead, EndReq, ULayout (pipeline.hip includes it first, in front of the namespace)
 
 static constexpr uint32_t XREF = 0x80000000u;              // nb[] entry: the neighbour lives on another rank; low bits = cross query index
 static constexpr int ROUTE_CH = 4096;                      // items per workgroup of the router
@@ -229,7 +230,6 @@ __global__ __launch_bounds__(256) void k_ls_apply(const uint32_t *__restrict__ d
 
 // per unitig (a chain of local chains): reported by its last record — the tail of a linear one, the record in front of the
 // smallest index of a ring (collapse.h: k_rank_tails without the strand decision, which the host takes from the k-mers)
-struct UHead { uint32_t root, tail, circ, pad; unsigned long long len, kc; };
 __global__ __launch_bounds__(256) void k_stitch_tails(const SegRec *__restrict__ segs, const unsigned int *__restrict__ n_p, const RankRec *__restrict__ R,
                                                       UHead *__restrict__ heads, uint32_t *__restrict__ slot_of, unsigned int *__restrict__ n_heads) {
     const uint32_t n = *n_p;
@@ -253,7 +253,6 @@ __global__ __launch_bounds__(256) void k_stitch_tails(const SegRec *__restrict__
 }
 
 // ---- 5. first / last k-mer of the unitigs this rank holds an end of -----------------------------------------------
-struct EndReq { uint32_t uid, which /* 0 first, 1 last */, chain /* local chain */, pad; };
 template <int W>
 __global__ __launch_bounds__(256) void k_fill_ends(Graph<W> g, const HeadRec *__restrict__ heads, const EndReq *__restrict__ req, uint32_t n_req,
                                                    uint64_t *__restrict__ ends /* [uid][2][W] */) {
@@ -337,7 +336,6 @@ __global__ __launch_bounds__(256) void k_sring_report(Graph<W> g, const uint2 *_
 }
 
 // ---- 6. emission: every rank writes the bases of its own nodes ---------------------------------------------------
-struct ULayout { unsigned long long off /* byte offset of the contig text; ~0: not emitted */, node_off, ring_len /* 0: linear */, rot; };
 template <int W>
 __global__ __launch_bounds__(256) void k_shard_emit(Graph<W> g, const uint2 *__restrict__ ol, const FinRec *__restrict__ fin, uint32_t lbase,
                                                     const uint32_t *__restrict__ uid_of_slot, const ULayout *__restrict__ lay,

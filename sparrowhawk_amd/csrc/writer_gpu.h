@@ -10,8 +10,7 @@
 // of hashing contig ends, every record's size computed from its numbers, exclusive scans for the offsets, records and
 // sequences written in place — the host copies one buffer.
 #pragma once
-
-struct WContig { unsigned long long off, kc; uint32_t len /* bases */, slot /* chain record */; };
+#include "shard_plan.h"     // WContig (pipeline.hip includes it first, in front of the namespace)
 
 __device__ __forceinline__ uint32_t w_ndig(unsigned long long v) { uint32_t n = 1; while (v >= 10ull) { v /= 10ull; n++; } return n; }
 // the two sinks of the host writer (outputs.cpp): one measures, one writes; NL / TAB / QUOTE are JSON-escaped (two characters)
