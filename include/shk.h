@@ -171,6 +171,14 @@ int shk_comm_world(const shk_comm *c);
 void shk_comm_free(shk_comm *c);
 int shk_shard_preprocess(shk_handle *h, shk_comm *c, const void *d_bases, const void *d_seg_off, uint64_t n_seg,
                          uint64_t n_bases, uint64_t n_reads, uint32_t n_partitions);
+/* The same call for a rank whose packed reads lie in HBM in SEVERAL batches (callers who stage reads themselves and hold 2^32
+ * bases or more; the layer on which the file route below sits): batch b is d_bases[b] / d_seg_off[b] with n_seg[b] segments
+ * and n_bases[b] < 2^32 bases, in the layout of shk_preprocess_packed_device; n_reads counts the reads of all of them.  Pass 1
+ * runs on every batch into the same partitions, then everything goes on as in shk_shard_preprocess, which is this call with
+ * one batch.  n_batches == 0: this rank has none.  The ranks need not hold the same number of batches.  Results do not depend
+ * on how the reads were cut into batches.  The batches are not retained. */
+int shk_shard_preprocess_batches(shk_handle *h, shk_comm *c, uint32_t n_batches, const void *const *d_bases, const void *const *d_seg_off,
+                                 const uint64_t *n_seg, const uint64_t *n_bases, uint64_t n_reads, uint32_t n_partitions);
 /* The same call from FASTQ FILES: every rank reads its share into ONE packed batch in HBM — inflated (csrc/inflate_gpu.hip)
  * and parsed (csrc/fastq_gpu.hip) on the device, so the compressed bytes are what crosses PCIe — and the batch goes through
  * shk_shard_preprocess as it is: the same progress strings, the same SHK_E_STATE rules, the handle ends "preprocessed", the
@@ -189,11 +197,25 @@ int shk_shard_preprocess(shk_handle *h, shk_comm *c, const void *d_bases, const 
  * ranks are many.  What the device declines (several members, a damaged block, text that is not regular 4-line FASTQ) is
  * read on the host, whole, and cut by the same rule; the host reader and the host parser own those messages, and the RECORD
  * NUMBERS in them count from the start of the rank's SLICE, not of the file.
- * A share of more than one batch (SHK_BATCH_BASES, default 2^31 packed bases) is SHK_E_PARAM: several batches per rank are
- * not supported.  A rank whose reading fails (a parse error, a damaged stream, memory, an oversized share) still enters the
- * first collective: it returns its own code and message, every other rank SHK_E_DEVICE "another rank failed during
- * reading", and nobody hangs.  The environment switches that choose a route (SHK_GUNZIP_DEVICE_MIN, ...) must be the same on
- * every rank.  The buffers are not retained. */
+ * A share of ANY size: one that fits one batch (SHK_BATCH_BASES, default 2^31 packed bases, at most 3 * 2^30) is read whole,
+ * as described; a larger one goes through pass 1 batch by batch — a window is inflated and parsed, counted into the rank's
+ * partitions, and let go — and everything behind pass 1 is the same (ONE record exchange).  Results do not depend on how a share
+ * was cut.  Whether a share goes in batches is decided before anything is uploaded where the host can tell (the ISIZE sums of
+ * the rank's run of BGZF blocks, the slice bounds of plain text).  In batches: a BGZF run is cut into windows of at most
+ * SHK_GUNZIP_DEVICE_WINDOW (default 1 GiB, at most 2 * SHK_BATCH_BASES) bytes of text (shk_plan_share_windows), every window
+ * but the last is cut at its last record start and the rest is carried, window w + 1 travels while window w is worked on;
+ * plain text is cut on the host, at record starts, into pieces of about 2 * SHK_BATCH_BASES bytes; a plain gzip member is
+ * inflated whole (on the host above 4 GiB of text) and the rank's slice of it is cut into such pieces on the device; the files
+ * of a pair go one after the other.  A window that is not regular 4-line FASTQ goes to the host parser, from that window to the
+ * end of the slice; its record numbers still count from the start of the slice.  One progress string
+ * preprocess:<mode>:loop:<reads so far>:<pct> per batch (pct: the part of the share's text that is consumed; the last says 100).
+ * The ranks need not agree: one may take several batches, another one, another none.
+ * A rank whose reading fails (a parse error, a damaged stream, memory) still enters the next collective — the first one for a
+ * share of one batch, the size exchange behind pass 1 for a failure in a later window: it returns its own code and message,
+ * every other rank SHK_E_DEVICE "another rank failed during ...", and nobody hangs.  The environment switches that choose a
+ * route (SHK_GUNZIP_DEVICE_MIN, ...) must be the same on every rank.  The buffers are not retained.
+ * Timings: shard_fastq_batches_x1 (batches pass 1 took on this rank), shard_fastq_windows_x1 (windows and pieces of text they
+ * were parsed from). */
 int shk_shard_preprocess_fastq(shk_handle *h, shk_comm *c, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2,
                                uint32_t n_partitions, int split);
 /* The routes of split = 1 without a communicator (tests, staging; needs a GPU): slice `rank` of `world` of the file(s) as one
@@ -226,6 +248,13 @@ uint32_t shk_choose_partitions(uint64_t total_instances_ub, uint32_t world, uint
  * window holds at most `budget` bytes of text and, unless the file has none, some.  Returns the number of windows (of
  * which the first `cap` are written), or SHK_E_PARAM when a block alone exceeds the budget. */
 int64_t shk_plan_bgzf_windows(const uint32_t *isize, uint64_t n_blocks, uint64_t budget, uint64_t *first_block, uint64_t cap);
+/* host-only: the windows ONE rank's run of blocks is cut into where its share exceeds one batch (shk_shard_preprocess_fastq):
+ * shk_plan_fastq_slices, then shk_plan_bgzf_windows on the blocks of run `rank` alone.  first_block[w] counts blocks of the
+ * FILE; the last window ends where the run ends (first_block[rank + 1] of shk_plan_fastq_slices); an empty run has no window.
+ * Returns the number of windows (of which the first `cap` are written), or SHK_E_PARAM: rank >= world, an ISIZE beyond 65536,
+ * a block of the run that alone exceeds the budget. */
+int64_t shk_plan_share_windows(const uint32_t *isize, uint64_t n_blocks, uint32_t world, uint32_t rank, uint64_t budget,
+                               uint64_t *first_block, uint64_t cap);
 /* host-only: where such a window is cut — the start of the last FASTQ record of text[0..n) that is known to be one: a
  * line that begins with '@' and whose line after next begins with '+' (a quality line may begin with '@' too); a line
  * whose line after next has not begun inside the text is undecided and passed over.  UINT64_MAX: none.

@@ -40,6 +40,14 @@ public:
         check(shk_shard_preprocess_fastq(h_, comm, file1 ? file1->data() : nullptr, file1 ? file1->size() : 0,
                                          file2 ? file2->data() : nullptr, file2 ? file2->size() : 0, n_partitions, split ? 1 : 0));
     }
+    // the same for a rank that staged its packed reads in HBM itself, in several batches of < 2^32 bases each (shk.h:
+    // shk_shard_preprocess_batches; no batch: this rank has none)
+    struct PackedBatch { const void *d_bases, *d_seg_off; uint64_t n_seg, n_bases; };
+    void sharded_preprocess_batches(shk_comm *comm, const std::vector<PackedBatch> &batches, uint64_t n_reads, uint32_t n_partitions = 0) {
+        std::vector<const void *> b, s; std::vector<uint64_t> ns, nb;
+        for (const PackedBatch &x : batches) { b.push_back(x.d_bases); s.push_back(x.d_seg_off); ns.push_back(x.n_seg); nb.push_back(x.n_bases); }
+        check(shk_shard_preprocess_batches(h_, comm, (uint32_t)batches.size(), b.data(), s.data(), ns.data(), nb.data(), n_reads, n_partitions));
+    }
     std::string get_preprocessing_info() {
         const char *s = shk_get_preprocessing_info(h_);
         if (!s) throw std::runtime_error(shk_last_error(h_));

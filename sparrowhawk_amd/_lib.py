@@ -48,6 +48,7 @@ SIGNATURES = {
     "shk_comm_world": (_int, [_vp]),
     "shk_comm_free": (None, [_vp]),
     "shk_shard_preprocess": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u64, _u32]),
+    "shk_shard_preprocess_batches": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u64, _u32]),
     "shk_shard_preprocess_fastq": (_int, [_vp, _vp, _cp, _sz, _cp, _sz, _u32, _int]),
     "shk_device_pack_fastq_slice": (_int, [_cp, _sz, _cp, _sz, _u32, _u32, _u32, _u32, C.POINTER(ShkPacked), C.POINTER(_u64), C.POINTER(_cp)]),
     "shk_host_first_record_start": (_u64, [_cp, _sz, _u64]),
@@ -56,6 +57,7 @@ SIGNATURES = {
     "shk_plan_exchange": (_int, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "shk_choose_partitions": (_u32, [_u64, _u32, _u32]),
     "shk_plan_bgzf_windows": (C.c_int64, [_vp, _u64, _u64, _vp, _u64]),
+    "shk_plan_share_windows": (C.c_int64, [_vp, _u64, _u32, _u32, _u64, _vp, _u64]),
     "shk_host_last_record_start": (_u64, [_cp, _sz]),
     "shk_device_last_record_start": (_int, [_cp, _sz, C.POINTER(_u64)]),
     "shk_pack_fastq": (_int, [_cp, _sz, _u32, _u32, C.POINTER(ShkPacked), C.POINTER(_cp)]),

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -351,8 +352,20 @@ void shk_host_mem_counter(const int64_t *deltas, size_t n, uint64_t *peak, uint6
 struct shk_comm { ShardComm *c = nullptr; };
 static thread_local std::string g_comm_err;
 
-static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_bases, const void *d_seg_off, uint64_t n_seg,
-                                 uint64_t n_bases, uint64_t n_reads, uint32_t n_partitions) {
+// This rank's reads as shard_preprocess_impl takes them: a step that hands over any number of batches (none, one, several: the
+// ranks need not agree), each of which goes through pass 1 at once and is the step's again afterwards.
+//   inst_ub   the k-mer instances of all the batches — n_bases - n_seg * (k - 1) summed — where the rank knows them before it
+//             starts (packed reads), else an upper bound (files read window by window: text bytes / 2).  What the rank adds to
+//             the instance all-reduce from which P is chosen (n_partitions == 0): pass 1 of the FIRST batch needs P.
+//   feed      calls sink.batch once per batch; SHK_OK, or the code of an error that is set in the handle (a failure in a later
+//             batch travels with the size exchange, as every failure of pass 1 does)
+//   n_reads   where feed does not count them itself (it then leaves h->n_reads to the sink's last batch)
+struct ShardReads {
+    uint64_t inst_ub = 0, n_reads = 0;
+    std::function<int(ShardBatchSink &)> feed;
+};
+
+static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const ShardReads &reads, uint32_t n_partitions) {
     if (!cm || !cm->c) return fail(h, SHK_E_PARAM, "shard_preprocess: null communicator");
     if (h->st != St::Fresh) return fail(h, SHK_E_STATE, "shard_preprocess: handle already used");
     if (comm_device(cm->c) != h->pipe->device()) return fail(h, SHK_E_PARAM, "shard_preprocess: communicator and handle live on different devices");
@@ -392,7 +405,7 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
     };
     // ---- the partition count must be the same everywhere: from the global instance count
     if (n_partitions == 0) {
-        uint64_t inst = n_bases > n_seg * (uint64_t)(h->k - 1) ? n_bases - n_seg * (uint64_t)(h->k - 1) : 0;
+        uint64_t inst = reads.inst_ub;
         if (int rc = comm_allreduce_host_u64(c, &inst, 1, st, err)) return fail_rc(h, Rc::Device, rc, err);
         n_partitions = choose_partitions(inst, world, W == 1 ? 100000 : 40000);
     }
@@ -404,7 +417,37 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
     // ones (error-rich reads do not deduplicate, and their partitions need the k-mer-level repartition, which counts
     // unweighted records).  Bloom mode counts raw records too.  The decision is taken from the gathered rows: same everywhere.
     std::vector<uint64_t> part(2 * (size_t)P + 2, 0);      // [0,P) records to send, [P,2P) raw records, [2P] = this rank failed, [2P+1] = 0 raw / 1 auto / 2 always
-    int rc_p1 = shard_partition_impl(h, d_bases, d_seg_off, n_seg, n_bases, n_reads, P, part.data());
+    // pass 1 batch by batch: every batch into the same P partitions (Pipeline::shard_add_batch), one progress string each
+    struct Sink : ShardBatchSink {
+        shk_handle *h; uint64_t n_batches = 0, inst = 0, last_pct = 0;
+        explicit Sink(shk_handle *hh) : h(hh) {}
+        int batch(const uint32_t *d_bases, const uint32_t *d_seg_off, uint64_t n_seg, uint64_t n_bases, uint64_t n_reads, uint64_t text_done,
+                  uint64_t text_total) override {
+            std::string e2;
+            if (int rc = h->pipe->shard_add_batch(d_bases, d_seg_off, n_seg, n_bases, e2)) return fail_rc(h, Rc::Device, rc, e2);
+            n_batches++;
+            inst += n_bases > n_seg * (uint64_t)(h->k - 1) ? n_bases - n_seg * (uint64_t)(h->k - 1) : 0;
+            h->n_reads = n_reads;
+            last_pct = text_total ? std::min<uint64_t>(100, std::max<uint64_t>(last_pct, (uint64_t)((unsigned __int128)100 * text_done / text_total))) : 100;
+            h->post_mode(("loop:" + std::to_string(n_reads) + ":" + std::to_string(last_pct)).c_str());
+            return SHK_OK;
+        }
+    } sink(h);
+    int rc_p1 = SHK_OK;
+    h->post_start();
+    h->n_reads = reads.n_reads;
+    { std::string e2; if (int r2 = h->pipe->shard_begin(P, e2)) rc_p1 = fail_rc(h, Rc::Device, r2, e2); }
+    if (!rc_p1) rc_p1 = reads.feed(sink);
+    if (!rc_p1) {
+        std::vector<uint64_t> pr; std::string e2;
+        if (int r2 = h->pipe->shard_totals(pr, e2)) rc_p1 = fail_rc(h, Rc::Device, r2, e2);
+        else memcpy(part.data(), pr.data(), (size_t)P * 8);
+    }
+    if (!rc_p1) {
+        if (sink.n_batches == 0 || sink.last_pct != 100) h->post_mode(("loop:" + std::to_string(h->n_reads) + ":100").c_str());
+        h->post_loop_edge("loop:end");
+        h->st = St::Sharding;
+    }
     if (!rc_p1) rc_p1 = injected("pass1");
     if (!rc_p1) {
         memcpy(&part[P], &part[0], (size_t)P * 8);
@@ -501,7 +544,7 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
     // ([500] k-mer instances counted, [501] ranks that failed, [502] k-mer instances this rank's READS hold: after the
     // all-reduce [500] must equal [502] — a record exchange that lost or duplicated data cannot pass unnoticed)
     uint64_t red[SHK_HISTO_BINS + 3] = {0};
-    const uint64_t inst_in_reads = n_bases > n_seg * (uint64_t)(h->k - 1) ? n_bases - n_seg * (uint64_t)(h->k - 1) : 0;
+    const uint64_t inst_in_reads = sink.inst;             // (summed over this rank's batches)
     int rc_cnt = shard_count_impl(h, recv, plan.run_off.data(), plan.run_cnt.data(), (uint32_t)plan.owned.size(), world, red,
                                   &red[SHK_HISTO_BINS], weighted ? recv_w : nullptr);
     stage("pass 2");
@@ -591,9 +634,45 @@ static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const void *d_base
     return SHK_OK;
 }
 
-// shk_shard_preprocess from FASTQ files: this rank's share is read into ONE packed batch in HBM (preprocess.cpp:
+// one batch that lies in HBM already
+static ShardReads one_batch(shk_handle *h, const void *d_bases, const void *d_seg_off, uint64_t n_seg, uint64_t n_bases, uint64_t n_reads) {
+    ShardReads r;
+    r.inst_ub = n_bases > n_seg * (uint64_t)(h->k - 1) ? n_bases - n_seg * (uint64_t)(h->k - 1) : 0;
+    r.n_reads = n_reads;
+    r.feed = [=](ShardBatchSink &sink) { return sink.batch((const uint32_t *)d_bases, (const uint32_t *)d_seg_off, n_seg, n_bases, n_reads, 1, 1); };
+    return r;
+}
+
+// several (shk_shard_preprocess_batches): the reads posted with a batch are n_reads in proportion to the bases so far
+static int shard_preprocess_batches_impl(shk_handle *h, shk_comm *cm, uint32_t n_batches, const void *const *d_bases, const void *const *d_seg_off,
+                                         const uint64_t *n_seg, const uint64_t *n_bases, uint64_t n_reads, uint32_t n_partitions) {
+    if (n_batches && (!d_bases || !d_seg_off || !n_seg || !n_bases)) return fail(h, SHK_E_PARAM, "shard_preprocess_batches: null batch arrays");
+    if (n_batches == 1) return shard_preprocess_impl(h, cm, one_batch(h, d_bases[0], d_seg_off[0], n_seg[0], n_bases[0], n_reads), n_partitions);
+    ShardReads r;
+    uint64_t total_bases = 0;
+    for (uint32_t b = 0; b < n_batches; b++) {
+        if (n_seg[b] && (!d_bases[b] || !d_seg_off[b])) return fail(h, SHK_E_PARAM, "shard_preprocess_batches: a batch with segments and no memory");
+        r.inst_ub += n_bases[b] > n_seg[b] * (uint64_t)(h->k - 1) ? n_bases[b] - n_seg[b] * (uint64_t)(h->k - 1) : 0;
+        total_bases += n_bases[b];
+    }
+    r.n_reads = n_reads;
+    r.feed = [=](ShardBatchSink &sink) {
+        uint64_t bases = 0;
+        for (uint32_t b = 0; b < n_batches; b++) {
+            bases += n_bases[b];
+            const uint64_t so_far = b + 1 == n_batches || !total_bases ? n_reads : (uint64_t)((unsigned __int128)n_reads * bases / total_bases);
+            if (int rc = sink.batch((const uint32_t *)d_bases[b], (const uint32_t *)d_seg_off[b], n_seg[b], n_bases[b], so_far, b + 1, n_batches)) return rc;
+        }
+        return (int)SHK_OK;
+    };
+    return shard_preprocess_impl(h, cm, r, n_partitions);
+}
+
+// shk_shard_preprocess from FASTQ files.  A share that fits one batch is read into ONE packed batch in HBM (preprocess.cpp:
 // read_fastq_share — split: slice `rank` of `world` of the same files on every rank; else the rank's own files, whole), the
-// ranks agree that all of them have their reads, and the batch goes through shard_preprocess_impl as it is.
+// ranks agree that all of them have their reads, and the batch goes through shard_preprocess_impl as it is.  A larger share is
+// only looked at in front of that agreement (read_fastq_share says in_batches before it uploads anything, where it can) and is
+// read inside pass 1, window by window (read_fastq_share_batches): its failures travel with the size exchange.
 static int shard_preprocess_fastq_impl(shk_handle *h, shk_comm *cm, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2,
                                        uint32_t n_partitions, int split) {
     if (!cm || !cm->c) return fail(h, SHK_E_PARAM, "shard_preprocess_fastq: null communicator");
@@ -605,11 +684,11 @@ static int shard_preprocess_fastq_impl(shk_handle *h, shk_comm *cm, const uint8_
     FastqShare sh;
     // (declared after the share: its blocks go back to the pool with the stream idle, on every way out)
     struct DrainOnExit { void *st; ~DrainOnExit() { std::string e; (void)device_stream_sync(st, e); } } drain{st};
-    // A rank whose reading fails (a parse error, a damaged stream, memory, an oversized share) enters the first collective all
-    // the same, with "I failed": it returns its own code and message, every other rank "another rank failed during reading".
+    // A rank whose reading fails (a parse error, a damaged stream, memory) enters the first collective all the same, with
+    // "I failed": it returns its own code and message, every other rank "another rank failed during reading".
     std::string err;
-    int rc_read = read_fastq_share(fq1, n1, fq2, n2, h->k, h->min_qual, split ? (uint32_t)comm_rank(c) : 0u, split ? (uint32_t)comm_world(c) : 1u,
-                                   h->pipe->device(), st, sh, err);
+    const uint32_t s_rank = split ? (uint32_t)comm_rank(c) : 0u, s_world = split ? (uint32_t)comm_world(c) : 1u;
+    int rc_read = read_fastq_share(fq1, n1, fq2, n2, h->k, h->min_qual, s_rank, s_world, h->pipe->device(), st, sh, err, true);
     if (rc_read) rc_read = fail(h, rc_read, err);
     const char *inject = getenv("SHK_FAULT_INJECT");      // (step `read`: see shard_preprocess_impl)
     if (!rc_read && inject && !strcmp(inject, "read")) rc_read = fail(h, SHK_E_INTERNAL, "injected fault (SHK_FAULT_INJECT=read)");
@@ -618,14 +697,36 @@ static int shard_preprocess_fastq_impl(shk_handle *h, shk_comm *cm, const uint8_
     if (int rc = comm_allreduce_host_u64(c, &failed, 1, st, e2)) return rc_read ? rc_read : fail_rc(h, Rc::Device, rc, e2);
     if (rc_read) return rc_read;
     if (failed) return fail(h, SHK_E_DEVICE, "shard_preprocess_fastq: another rank failed during reading (this rank's handle is untouched; free it)");
-    auto &t = h->pipe->times();
-    if (sh.n_bgzf_slice) t.add("shard_fastq_bgzf_slice_x1", (double)sh.n_bgzf_slice);
-    if (sh.n_member_whole) t.add("shard_fastq_member_whole_x1", (double)sh.n_member_whole);
-    if (sh.n_text_slice) t.add("shard_fastq_text_slice_x1", (double)sh.n_text_slice);
-    if (sh.n_host) t.add("shard_fastq_host_x1", (double)sh.n_host);
-    t.add("shard_fastq_uploaded_bytes", (double)sh.uploaded_bytes);
-    t.add("shard_fastq_read_host_clock", now_ms() - t0);
-    return shard_preprocess_impl(h, cm, sh.n_seg ? sh.d_bases : nullptr, sh.n_seg ? sh.d_seg_off : nullptr, sh.n_seg, sh.n_bases, sh.n_reads, n_partitions);
+    auto book = [h, t0](const FastqShare &s, uint64_t batches, uint64_t windows) {
+        auto &t = h->pipe->times();
+        if (s.n_bgzf_slice) t.add("shard_fastq_bgzf_slice_x1", (double)s.n_bgzf_slice);
+        if (s.n_member_whole) t.add("shard_fastq_member_whole_x1", (double)s.n_member_whole);
+        if (s.n_text_slice) t.add("shard_fastq_text_slice_x1", (double)s.n_text_slice);
+        if (s.n_host) t.add("shard_fastq_host_x1", (double)s.n_host);
+        t.add("shard_fastq_uploaded_bytes", (double)s.uploaded_bytes);
+        t.add("shard_fastq_batches_x1", (double)batches);
+        t.add("shard_fastq_windows_x1", (double)windows);
+        t.add("shard_fastq_read_host_clock", now_ms() - t0);
+    };
+    if (!sh.in_batches) {
+        book(sh, 1, 1);
+        return shard_preprocess_impl(h, cm, one_batch(h, sh.n_seg ? sh.d_bases : nullptr, sh.n_seg ? sh.d_seg_off : nullptr, sh.n_seg, sh.n_bases, sh.n_reads), n_partitions);
+    }
+    // several batches: reading and pass 1 take turns (shard_fastq_read_host_clock then holds both)
+    ShardReads r;
+    r.inst_ub = sh.text_ub / 2;
+    const uint64_t uploaded_before = sh.uploaded_bytes;
+    r.feed = [&](ShardBatchSink &sink) -> int {
+        FastqShare got;
+        std::string e3;
+        int rc = read_fastq_share_batches(fq1, n1, fq2, n2, h->k, h->min_qual, s_rank, s_world, h->pipe->device(), st, sink, got, e3);
+        if (rc && !e3.empty()) rc = fail(h, rc, e3);
+        got.uploaded_bytes += uploaded_before;
+        book(got, got.n_batches, got.n_windows);
+        if (!rc) h->n_reads = got.n_reads;
+        return rc;
+    };
+    return shard_preprocess_impl(h, cm, r, n_partitions);
 }
 
 int shk_comm_unique_id(uint8_t id[SHK_UNIQUE_ID_BYTES]) {
@@ -657,8 +758,16 @@ void shk_comm_free(shk_comm *c) {
 int shk_shard_preprocess(shk_handle *h, shk_comm *c, const void *d_bases, const void *d_seg_off, uint64_t n_seg,
                          uint64_t n_bases, uint64_t n_reads, uint32_t n_partitions) {
     return guarded(h, Poison::AfterFirstBatch, [&] {
-        const int rc = shard_preprocess_impl(h, c, d_bases, d_seg_off, n_seg, n_bases, n_reads, n_partitions);
+        const int rc = shard_preprocess_impl(h, c, one_batch(h, d_bases, d_seg_off, n_seg, n_bases, n_reads), n_partitions);
         // a collective that failed on this rank alone: abort now, so that the peers' waits end (shard_comm.h: comm_stream_wait)
+        if (rc != SHK_OK && c && c->c && comm_broken(c->c)) comm_abort_now(c->c);
+        return rc;
+    });
+}
+int shk_shard_preprocess_batches(shk_handle *h, shk_comm *c, uint32_t n_batches, const void *const *d_bases, const void *const *d_seg_off,
+                                 const uint64_t *n_seg, const uint64_t *n_bases, uint64_t n_reads, uint32_t n_partitions) {
+    return guarded(h, Poison::AfterFirstBatch, [&] {
+        const int rc = shard_preprocess_batches_impl(h, c, n_batches, d_bases, d_seg_off, n_seg, n_bases, n_reads, n_partitions);
         if (rc != SHK_OK && c && c->c && comm_broken(c->c)) comm_abort_now(c->c);
         return rc;
     });
@@ -690,6 +799,17 @@ int64_t shk_plan_bgzf_windows(const uint32_t *isize, uint64_t n_blocks, uint64_t
         if ((!isize && n_blocks) || (!first_block && cap)) return SHK_E_PARAM;
         std::vector<uint64_t> first;
         if (plan_bgzf_windows(isize, (size_t)n_blocks, budget, first)) return SHK_E_PARAM;
+        for (size_t i = 0; i < first.size() && i < cap; i++) first_block[i] = first[i];
+        return (int64_t)first.size();
+    } catch (...) { return SHK_E_OOM; }
+}
+int64_t shk_plan_share_windows(const uint32_t *isize, uint64_t n_blocks, uint32_t world, uint32_t rank, uint64_t budget, uint64_t *first_block,
+                               uint64_t cap) {
+    try {
+        if ((!isize && n_blocks) || (!first_block && cap) || !world || rank >= world) return SHK_E_PARAM;
+        for (uint64_t i = 0; i < n_blocks; i++) if (isize[i] > 65536) return SHK_E_PARAM;
+        std::vector<uint64_t> first; uint64_t run_end = 0;
+        if (plan_share_windows(isize, (size_t)n_blocks, world, rank, budget, first, run_end)) return SHK_E_PARAM;
         for (size_t i = 0; i < first.size() && i < cap; i++) first_block[i] = first[i];
         return (int64_t)first.size();
     } catch (...) { return SHK_E_OOM; }

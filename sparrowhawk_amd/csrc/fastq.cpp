@@ -155,17 +155,6 @@ bool bgzf_block(const uint8_t *b, size_t n, size_t &bsize) {
     return false;
 }
 
-int plan_bgzf_windows(const uint32_t *isize, size_t n_blocks, uint64_t budget, std::vector<uint64_t> &first) {
-    first.clear();
-    uint64_t sum = 0;
-    for (size_t i = 0; i < n_blocks; i++) {
-        if (isize[i] > budget) return -1;
-        if (first.empty() || sum + isize[i] > budget) { first.push_back(i); sum = 0; }      // (an empty block never opens a window but the first)
-        sum += isize[i];
-    }
-    return 0;
-}
-
 uint64_t last_record_start(const uint8_t *t, size_t n) {
     // line starts from the back; s1 / s2: the starts of the next line and of the line after next (n: not inside t)
     size_t s1 = n, s2 = n;
@@ -213,18 +202,6 @@ void fastq_slice_bounds(const uint8_t *t, size_t e, uint32_t rank, uint32_t worl
         return p == UINT64_MAX ? e : p;                   // (the whole text is in view: undecided = none)
     };
     s0 = bound(rank, cut0); s1 = bound(rank + 1, cut1);
-}
-
-void plan_fastq_slices(const uint32_t *isize, size_t n_blocks, uint32_t world, std::vector<uint64_t> &first) {
-    uint64_t text = 0;
-    for (size_t i = 0; i < n_blocks; i++) text += isize[i];
-    first.assign((size_t)world + 1, n_blocks);
-    size_t b = 0; uint64_t off = 0;                       // off: the text offset of block b
-    for (uint32_t r = 0; r < world; r++) {
-        const uint64_t want = r ? slice_cut(text, r, world) : 0;
-        while (b < n_blocks && off < want) off += isize[b++];
-        first[r] = b;
-    }
 }
 
 static int inflate_bgzf(const uint8_t *in, size_t n, ByteVec &out, std::string &err, bool &is_bgzf) {

@@ -2,6 +2,7 @@
 // Replaces the reader the reference's crate builds over web_sys::File + gz sniff + seq_io
 // (/root/reference/AGENTS.md:180-183; sibling in tree: rust/orphos-bridge/src/fastx_wasm.rs:53-70).
 #pragma once
+#include "share_windows.h"
 #include <stdint.h>
 #include <stddef.h>
 #include <functional>
@@ -40,12 +41,8 @@ int pack_fastq(const uint8_t *buf, size_t n, uint32_t k, uint32_t min_qual, Pack
 // b[0..n) starts with a whole BGZF block (SAM spec 4.1: a gzip member with a 'BC' extra subfield that holds its size - 1):
 // bsize = that size.  The one rule by which both the host reader and the device inflater (inflate_gpu.hip) walk a chain.
 bool bgzf_block(const uint8_t *b, size_t n, size_t &bsize);
-// The windows of a BGZF chain (preprocess.cpp, route 2): runs of consecutive blocks whose text (the sum of their ISIZE
-// fields) is at most `budget` bytes.  first[w] = the first block of window w; window w ends where window w + 1 begins, the
-// last one at n_blocks.  Every block lies in exactly one window and no window is without text, unless the file has none
-// (then there is one window, or none for a file of no blocks).  Empty blocks ride with the window in front of them.
-// Returns 0, or -1 when a block alone exceeds the budget.
-int plan_bgzf_windows(const uint32_t *isize, size_t n_blocks, uint64_t budget, std::vector<uint64_t> &first);
+// (the windows of a BGZF chain and the ranks' runs of its blocks — plan_bgzf_windows, plan_fastq_slices, plan_share_windows —
+// and slice_cut: share_windows.h, which a host compiler takes alone)
 // Where the last FASTQ record of t[0..n) starts that is known to be one: a line that begins with '@' and whose line after
 // next begins with '+' (the rule of next_record_start in preprocess.cpp; a quality line may begin with '@', but its line
 // after next is a sequence).  A line whose line after next has not begun inside t is undecided and is passed over.  Byte 0
@@ -61,12 +58,7 @@ uint64_t first_record_start(const uint8_t *t, size_t n, size_t from);
 // between s_r = the first record start at or after the nominal cut c_r (e where there is none).  cut0 / cut1: c_rank and
 // c_(rank + 1) — floor(r * e / world) for plain text and the text of a plain gzip member (slice_cut), for a BGZF chain the
 // text offset at which block first_block[r] of plan_fastq_slices begins.
-inline uint64_t slice_cut(uint64_t e, uint32_t r, uint32_t world) { return (uint64_t)((unsigned __int128)e * r / world); }
 void fastq_slice_bounds(const uint8_t *t, size_t e, uint32_t rank, uint32_t world, uint64_t cut0, uint64_t cut1, uint64_t &s0, uint64_t &s1);
-// The runs of a BGZF chain that the ranks of the sharded FASTQ entry point inflate: world runs of consecutive blocks,
-// first[r] = the first block whose text offset (the sum of the ISIZE fields in front of it) is >= r * text / world, first[0]
-// = 0, first[world] = n_blocks.  Empty blocks may sit anywhere; more ranks than blocks gives empty runs.
-void plan_fastq_slices(const uint32_t *isize, size_t n_blocks, uint32_t world, std::vector<uint64_t> &first);
 // gzip sniff (1F 8B) + multi-member inflate; plain input is passed through (p/n point at buf or at `storage`)
 int maybe_inflate(const uint8_t *buf, size_t n, ByteVec &storage, const uint8_t *&p, size_t &pn,
                   std::string &err);

@@ -88,13 +88,66 @@ class BgzfWindows {
     int step(size_t w, bool raw, uint64_t &carry, uint64_t &cut, bool &unterminated, const char *&why, std::string &err);
     uint8_t *text(size_t w) const { return (uint8_t *)d_text_[w & 1].p; }
     double h2d_ms = 0, decode_ms = 0;                      // summed over the windows
+    uint64_t uploaded = 0;                                 // compressed bytes of the windows worked on so far
+    // The parts step() is made of, for a caller that cuts its windows elsewhere (BgzfShareWindows below: a rank's run begins
+    // and ends inside a window).  inflate: window w behind `carry` bytes in text(w), n = carry + its text; window w + 1 is sent
+    // ahead where asked for (a window nobody sent ahead travels when its turn comes).  first_start / last_start: the record
+    // starts of text(w)[0..n) by the kernels' rules (UINT64_MAX: none / undecided).  trim_end: the end-of-text rule on
+    // text(w)[0..n).  carry_on: text(w)[cut..n) to the front of text(w + 1), 32 zero bytes behind the cut.
+    // Each 0; 1 (*why) where step() returns 1; -5.
+    int inflate(size_t w, bool prefetch_next, uint64_t carry, uint64_t &n, const char *&why, std::string &err);
+    int first_start(size_t w, uint64_t n, uint64_t from, uint64_t &at, std::string &err);
+    int last_start(size_t w, uint64_t n, uint64_t &at, std::string &err);
+    int trim_end(size_t w, uint64_t n, uint64_t &e, bool &unterminated, const char *&why, std::string &err);
+    int carry_on(size_t w, uint64_t n, uint64_t cut, std::string &err);
+    void *stream() const { return st_; }
   private:
     void upload(size_t w);                                // blocking, on a stream of its own: -> up_[w & 1]
+    size_t up_w_[2] = {SIZE_MAX, SIZE_MAX};                // the window whose bytes d_in_[i] holds
     const uint8_t *gz_ = nullptr; const BgzfChain *chain_ = nullptr;
     int device_ = 0; void *st_ = nullptr;
     PoolBlock d_in_[2], d_text_[2], d_desc_, d_status_, d_bad_;
     struct Upload { int rc = 0; std::string err; double ms = 0; } up_[2];
     std::thread prefetch_;                                // uploads window w + 1 during step(w); joined by step(w + 1) and close()
+};
+
+// One rank's run of a walked BGZF chain, of any size, window by window: the slice gpu_bgzf_slice hands over in one piece, in
+// pieces of whole records.  The run (fastq.h: plan_fastq_slices) is cut into windows of at most `budget` bytes of text
+// (share_windows.h: plan_share_windows); the non-empty block in front of the run rides with window 0 (k_first_record_start
+// finds s_rank there), every window but the last is cut at its last record start and the rest is carried (BgzfWindows), and
+// s_(rank + 1) is looked for in small windows of follow-on blocks of run rank + 1 — 2 non-empty blocks, then twice as many
+// while it is undecided, up to BgzfWindows::CARRY_MAX of text.  Window w + 1 is uploaded while the caller works on window w;
+// only the rank's blocks and these few neighbours cross PCIe.
+//     if (sw.open(gz, chain, rank, world, budget, device, stream, why, err)) ...          // 1: declined, nothing was uploaded
+//     for (;;) { if (sw.next(piece, at, done, why, err)) ...; if (done) break; parse piece; }
+// A piece is text in the parser's form (16-byte aligned, 32 zero bytes behind) that stays the object's: it is good until the
+// next call.  at: where the piece begins in the file's text.  next() returns 1 (*why) where a window is the host reader's: the
+// host reads the file, cuts the same slice and goes on at consumed() (everything in front of it has been handed over).
+class BgzfShareWindows {
+  public:
+    BgzfShareWindows() = default;
+    ~BgzfShareWindows() { close(); }
+    BgzfShareWindows(const BgzfShareWindows &) = delete;
+    BgzfShareWindows &operator=(const BgzfShareWindows &) = delete;
+    int open(const uint8_t *gz, const BgzfChain &chain, uint32_t rank, uint32_t world, uint64_t budget, int device, void *stream,
+             const char *&why, std::string &err);
+    int next(GpuText &piece, uint64_t &at, bool &done, const char *&why, std::string &err);
+    void close();
+    uint64_t run_text() const { return c1_ - c0_; }        // bytes of text of the rank's run (the sum of its ISIZE fields)
+    uint64_t run_begin() const { return c0_; }
+    uint64_t consumed() const { return consumed_; }        // the file's text in front of this offset is done with
+    uint64_t uploaded() const { return bw_.uploaded; }
+    uint64_t windows() const { return windows_; }          // windows inflated so far
+    double h2d_ms() const { return bw_.h2d_ms; }
+    double decode_ms() const { return bw_.decode_ms; }
+  private:
+    BgzfChain view_;                                       // the chain's blocks with the windows of THIS rank
+    BgzfWindows bw_;
+    PoolBlock first_;                                      // a piece that does not begin where its window's buffer begins
+    size_t B_ = 0, n_own_ = 0, w_ = 0;
+    uint32_t rank_ = 0;
+    uint64_t c0_ = 0, c1_ = 0, carry_ = 0, consumed_ = 0, windows_ = 0;
+    bool started_ = false, done_ = false;
 };
 
 // k_last_record_start alone on n bytes of host text (the tests compare it with last_record_start)
@@ -117,6 +170,11 @@ int gpu_bgzf_slice(const uint8_t *gz, const BgzfChain &chain, uint32_t rank, uin
 // A whole text on the device (a plain gzip member inflated by gpu_inflate_member; nominal cuts floor(r * e / world)): its
 // block becomes the span's.  0; -4; -5.
 int gpu_text_slice(GpuText &text, uint32_t rank, uint32_t world, void *stream, DevSpan &out, std::string &err);
+// A piece of a span for the parser, where the span is more than one batch takes: span text [from, from + want) cut back to
+// its last record start — or all that is left, where that is no more than `want` — copied into a text of its own (16-byte
+// aligned, 32 zero bytes behind).  next: where the following piece begins (span.len: this was the last; out.e == 0: nothing was
+// left).  0; 1: no record starts inside the piece (not regular FASTQ: the host parser's); -4; -5.
+int gpu_span_piece(const DevSpan &span, uint64_t from, uint64_t want, void *stream, GpuText &out, uint64_t &next, std::string &err);
 // The spans back to back in one text as the parser wants it (16-byte aligned start, 32 zero bytes behind, a newline between
 // two files where the first ends without one).  0; -4; -5.
 int gpu_join_spans(const DevSpan *spans, int n_spans, void *stream, GpuText &out, std::string &err);

@@ -1207,8 +1207,8 @@ void BgzfWindows::close() {
 int BgzfWindows::open(const uint8_t *gz, const BgzfChain *chain, int device, void *stream, std::string &err) {
     close();
     gz_ = gz; chain_ = chain; device_ = device; st_ = stream;
-    h2d_ms = decode_ms = 0;
-    up_[0] = up_[1] = Upload();
+    h2d_ms = decode_ms = 0; uploaded = 0;
+    up_[0] = up_[1] = Upload(); up_w_[0] = up_w_[1] = SIZE_MAX;
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); err = "hipSetDevice failed"; return -5; }
     uint64_t max_in = 0, max_text = 0; uint32_t max_nb = 1;
     for (const BgzfChain::Window &w : chain->windows) {
@@ -1238,52 +1238,202 @@ void BgzfWindows::upload(size_t w) {
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     up.ms = now_ms() - t0;
     if (e != hipSuccess) { up.err = std::string("upload of a BGZF window: ") + hipGetErrorString(e); up.rc = -5; }
+    up_w_[w & 1] = w;
 }
 
-int BgzfWindows::step(size_t w, bool raw, uint64_t &carry, uint64_t &cut, bool &unterminated, const char *&why, std::string &err) {
+int BgzfWindows::inflate(size_t w, bool prefetch_next, uint64_t carry, uint64_t &n, const char *&why, std::string &err) {
     hipStream_t st = (hipStream_t)st_;
     const BgzfChain::Window &win = chain_->windows[w];
-    const bool last = w + 1 == chain_->windows.size();
-    // this window's compressed bytes have arrived (window 0: they travel now); the next window's travel while this one is worked on
-    if (w == 0) upload(0);
-    else if (prefetch_.joinable()) prefetch_.join();
+    // this window's compressed bytes have arrived (they travel now where nobody sent them ahead); the next window's travel while this one is worked on
+    if (prefetch_.joinable()) prefetch_.join();
+    if (up_w_[w & 1] != w) upload(w);
     if (up_[w & 1].rc) { err = up_[w & 1].err; return up_[w & 1].rc; }
     h2d_ms += up_[w & 1].ms;
-    if (!last)
+    uploaded += win.in_end - win.in_off;
+    if (prefetch_next)
         prefetch_ = std::thread([this, w]() {
             try { upload(w + 1); }
             catch (...) { up_[(w + 1) & 1].rc = -4; up_[(w + 1) & 1].err = "out of host memory (uploader)"; }
         });
     if (carry > CARRY_MAX) { why = "a partial record beyond the room for it"; return 1; }
     double ms = 0;
-    int rc = inflate_block_run(*chain_, win.b0, win.b1, d_in_[w & 1].p, win.in_off, text(w), carry, d_desc_, d_status_, d_bad_, st, ms, nullptr, nullptr, why, err);
+    const int rc = inflate_block_run(*chain_, win.b0, win.b1, d_in_[w & 1].p, win.in_off, text(w), carry, d_desc_, d_status_, d_bad_, st, ms, nullptr, nullptr, why, err);
     decode_ms += ms;
+    n = carry + win.text;
+    return rc;
+}
+
+int BgzfWindows::trim_end(size_t w, uint64_t n, uint64_t &e, bool &unterminated, const char *&why, std::string &err) {
+    hipStream_t st = (hipStream_t)st_;
+    Tail tail;
+    GZCHK(fetch_tail(text(w), n, tail, st));
+    GZCHK(hipStreamSynchronize(st));
+    return trim_text_end(text(w), n, tail, false, st, e, unterminated, why, err);
+}
+
+int BgzfWindows::last_start(size_t w, uint64_t n, uint64_t &at, std::string &err) {
+    // the last record start in reach: a start further front leaves more to carry than there is room for
+    return device_last_start(text(w), n, (unsigned long long *)d_bad_.p + 4, (hipStream_t)st_, at, err, CARRY_MAX + 64);
+}
+
+int BgzfWindows::first_start(size_t w, uint64_t n, uint64_t from, uint64_t &at, std::string &err) {
+    return device_first_start(text(w), n, from, (unsigned long long *)d_bad_.p + 4, (hipStream_t)st_, at, err);
+}
+
+int BgzfWindows::carry_on(size_t w, uint64_t n, uint64_t cut, std::string &err) {
+    hipStream_t st = (hipStream_t)st_;
+    // the carry goes to the next window's buffer first: the parser wants 32 zero bytes behind the cut
+    if (n > cut) GZCHK(hipMemcpyAsync(text(w + 1), text(w) + cut, (size_t)(n - cut), hipMemcpyDeviceToDevice, st));
+    GZCHK(hipMemsetAsync(text(w) + cut, 0, 32, st));
+    GZCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int BgzfWindows::step(size_t w, bool raw, uint64_t &carry, uint64_t &cut, bool &unterminated, const char *&why, std::string &err) {
+    const bool last = w + 1 == chain_->windows.size();
+    uint64_t n = 0;
+    int rc = inflate(w, !last, carry, n, why, err);
     if (rc) return rc;
-    const uint64_t n = carry + win.text;
     cut = n; unterminated = false;
     if (last) {
-        if (!raw) {
-            Tail tail;
-            GZCHK(fetch_tail(text(w), n, tail, st));
-            GZCHK(hipStreamSynchronize(st));
-            if ((rc = trim_text_end(text(w), n, tail, false, st, cut, unterminated, why, err))) return rc;
-        }
+        if (!raw) if ((rc = trim_end(w, n, cut, unterminated, why, err))) return rc;
         carry = 0;
         return 0;
     }
-    // the last record start in reach: a start further front leaves more to carry than there is room for
-    if ((rc = device_last_start(text(w), n, (unsigned long long *)d_bad_.p + 4, st, cut, err, CARRY_MAX + 64))) return rc;
+    if ((rc = last_start(w, n, cut, err))) return rc;
     if (cut == UINT64_MAX) cut = raw ? n : 0;             // (none.  One record's middle: all of it is carried on, if there is room)
     if (n - cut > CARRY_MAX) {
         if (!raw) { why = "a partial record beyond the room for it"; return 1; }
         cut = n;
     }
-    // the carry goes to the next window's buffer first: the parser wants 32 zero bytes behind the cut
-    if (n > cut) GZCHK(hipMemcpyAsync(text(w + 1), text(w) + cut, (size_t)(n - cut), hipMemcpyDeviceToDevice, st));
-    GZCHK(hipMemsetAsync(text(w) + cut, 0, 32, st));
-    GZCHK(hipStreamSynchronize(st));
+    if ((rc = carry_on(w, n, cut, err))) return rc;
     carry = n - cut;
     return 0;
+}
+
+// ---- one rank's run of a walked chain, window by window (inflate_gpu.h) ---------------------------------------------------
+int BgzfShareWindows::open(const uint8_t *gz, const BgzfChain &chain, uint32_t rank, uint32_t world, uint64_t budget, int device, void *stream,
+                           const char *&why, std::string &err) {
+    close();
+    rank_ = rank; B_ = chain.blocks.size();
+    if (rank >= world) { err = "rank beyond world"; return -1; }
+    std::vector<uint32_t> isize(B_);
+    std::vector<uint64_t> off(B_ + 1, 0);                   // off[b]: the text offset at which block b begins
+    for (size_t i = 0; i < B_; i++) { isize[i] = chain.blocks[i].isize; off[i + 1] = off[i] + isize[i]; }
+    std::vector<uint64_t> first; uint64_t run_end = 0;
+    if (plan_share_windows(isize.data(), B_, world, rank, budget, first, run_end)) { why = "a BGZF block beyond the window budget"; return 1; }
+    const size_t b1 = (size_t)run_end, b0 = first.empty() ? b1 : (size_t)first[0];
+    c0_ = off[b0]; c1_ = off[b1];
+    if (c0_ == c1_) { done_ = true; return 0; }             // (a run without text: s_rank == s_(rank + 1))
+    view_.blocks = chain.blocks; view_.text = chain.text; view_.nonempty = chain.nonempty;
+    auto window = [&](size_t wb0, size_t wb1) {
+        BgzfChain::Window win{wb0, wb1, chain.blocks[wb0].in_off, chain.blocks[wb1 - 1].in_off + chain.blocks[wb1 - 1].bsize, off[wb1] - off[wb0], off[wb0], 0};
+        for (size_t b = wb0; b < wb1; b++) win.nonempty += isize[b] != 0;
+        view_.windows.push_back(win);
+    };
+    // the block in front of the run rides with window 0: whether the run's first byte begins a line is written there
+    size_t pb = b0;
+    while (rank > 0 && pb > 0) { pb--; if (isize[pb]) break; }
+    const bool follow = rank + 1 != world && off[B_] > c1_;      // text behind the run: the slice ends in it
+    n_own_ = first.size();
+    for (size_t w = 0; w < n_own_; w++)
+        window(w == 0 ? pb : (size_t)first[w], w + 1 < n_own_ ? (size_t)first[w + 1] : (follow ? b1 : B_ /* empty blocks ride along */));
+    // the follow-on blocks of run rank + 1: 2 non-empty ones first, then twice as many while the boundary is undecided, up to
+    // CARRY_MAX of text (gpu_bgzf_slice widens its view the same way; here every widening is a small window of its own)
+    if (follow) {
+        uint64_t text = 0;
+        for (size_t tb = b1, extra = 2; tb < B_ && text < BgzfWindows::CARRY_MAX; extra *= 2) {
+            size_t te = tb;
+            for (size_t got = 0; te < B_ && got < extra && text < BgzfWindows::CARRY_MAX; te++) { text += isize[te]; got += isize[te] != 0; }
+            while (te < B_ && !isize[te]) te++;
+            window(tb, te);
+            tb = te;
+        }
+    }
+    const int rc = bw_.open(gz, &view_, device, stream, err);
+    if (rc == 1) why = "out of device memory";
+    if (rc) close();
+    return rc;
+}
+
+void BgzfShareWindows::close() {
+    bw_.close(); first_.put();
+    view_ = BgzfChain(); n_own_ = w_ = 0; carry_ = consumed_ = windows_ = 0; started_ = done_ = false;
+}
+
+int BgzfShareWindows::next(GpuText &piece, uint64_t &at_out, bool &done, const char *&why, std::string &err) {
+    hipStream_t st = (hipStream_t)bw_.stream();
+    piece = GpuText(); done = false;
+    const uint64_t NONE = UINT64_MAX;
+    while (true) {
+        if (done_ || w_ >= view_.windows.size()) { done_ = done = true; return 0; }
+        const size_t w = w_;
+        const BgzfChain::Window &win = view_.windows[w];
+        const bool is_tail = w >= n_own_, last_in_list = w + 1 == view_.windows.size(), at_end = win.b1 == B_;
+        uint64_t n = 0;
+        if (const int rc = bw_.inflate(w, !last_in_list && w + 1 <= n_own_, carry_, n, why, err)) return rc;
+        windows_++;
+        const uint64_t base = win.text_before - carry_;     // where text(w)[0] lies in the file's text
+        uint64_t lim = n; bool unterm = false;
+        if (last_in_list && at_end) if (const int rc = bw_.trim_end(w, n, lim, unterm, why, err)) return rc;
+        // all that is left of this window goes to the front of the next one (nothing could be decided in it)
+        auto carry_all = [&](uint64_t from, const char *too_much) -> int {
+            if (n - from > BgzfWindows::CARRY_MAX) { why = too_much; return 1; }
+            if (const int rc = bw_.carry_on(w, n, from, err)) return rc;
+            carry_ = n - from; w_++;
+            return 0;
+        };
+        uint64_t lo = 0;
+        if (!started_) {                                    // s_rank: the first record start at or after the run's first byte
+            if (rank_ > 0) {
+                uint64_t at = NONE;
+                if (const int rc = bw_.first_start(w, lim, c0_ - base, at, err)) return rc;
+                if (at == NONE) {
+                    if (last_in_list && at_end) { done_ = done = true; return 0; }      // (no record begins in the run or behind it)
+                    if (last_in_list) { why = "no record start within reach"; return 1; }
+                    if (const int rc = carry_all(0, "no record start in a whole window")) return rc;
+                    continue;
+                }
+                lo = at;
+            }
+            started_ = true;
+        }
+        uint64_t hi = lim; bool fin = true, unt = unterm;
+        if (is_tail) {                                      // s_(rank + 1): the first record start at or after the next run's first byte
+            uint64_t at = NONE;
+            if (const int rc = bw_.first_start(w, lim, std::max(c1_ - base, lo), at, err)) return rc;
+            if (at == NONE && !(last_in_list && at_end)) {
+                if (last_in_list) { why = "no record start within reach behind the run"; return 1; }
+                if (const int rc = carry_all(lo, "no record start within reach behind the run")) return rc;
+                consumed_ = base + lo;
+                continue;
+            }
+            if (at != NONE) { hi = at; unt = false; }
+        } else if (!last_in_list) {                         // a window of the run with more behind it: cut at its last record start
+            uint64_t cut = NONE;
+            if (const int rc = bw_.last_start(w, n, cut, err)) return rc;
+            if (cut == NONE || cut < lo) cut = lo;
+            if (const int rc = carry_all(cut, "a partial record beyond the room for it")) return rc;
+            hi = cut; fin = false; unt = false;
+        }
+        if (fin) w_ = view_.windows.size();
+        if (hi < lo) hi = lo;
+        consumed_ = base + hi;
+        if (hi == lo) continue;
+        at_out = base + lo;
+        piece.e = (size_t)(hi - lo); piece.unterminated = fin && unt;
+        if (lo == 0) {
+            piece.d = bw_.text(w);
+            if (fin) GZCHK(hipMemsetAsync(piece.d + hi, 0, 32, st));
+        } else {                                            // (the parser wants its text at a 16-byte boundary)
+            if (!first_.get((size_t)(hi - lo) + 64)) { why = "out of device memory"; return 1; }
+            GZCHK(hipMemcpyAsync(first_.p, bw_.text(w) + lo, (size_t)(hi - lo), hipMemcpyDeviceToDevice, st));
+            GZCHK(hipMemsetAsync((uint8_t *)first_.p + (hi - lo), 0, 32, st));
+            piece.d = (uint8_t *)first_.p;
+        }
+        GZCHK(hipStreamSynchronize(st));
+        return 0;
+    }
 }
 
 int gpu_last_record_start(const uint8_t *t, size_t n, int device, uint64_t &at, std::string &err) {
@@ -1402,6 +1552,31 @@ int gpu_text_slice(GpuText &text, uint32_t rank, uint32_t world, void *stream, D
     out.unterminated = s[1] == e && text.unterminated && out.len != 0;
     out.blk = PoolBlock(text.d, text.pool_bytes);             // the text's block is the span's now
     text = GpuText();
+    return 0;
+}
+
+int gpu_span_piece(const DevSpan &span, uint64_t from, uint64_t want, void *stream, GpuText &out, uint64_t &next, std::string &err) {
+    hipStream_t st = (hipStream_t)stream;
+    out = GpuText();
+    next = span.len;
+    if (from >= span.len) return 0;
+    if (span.len - from > want) {
+        PoolBlock d_out;
+        if (!d_out.get(64)) { err = "out of device memory"; return -4; }
+        uint64_t at = UINT64_MAX;
+        // (the search stays inside the piece: it never looks further front than `want` bytes)
+        if (const int rc = device_last_start((const uint8_t *)span.blk.p, span.off + from + want, (unsigned long long *)d_out.p, st, at, err, want)) return rc;
+        if (at == UINT64_MAX || at <= span.off + from) return 1;
+        next = at - span.off;
+    }
+    const uint64_t len = next - from;
+    PoolBlock blk;
+    if (!blk.get((size_t)len + 64)) { err = "out of device memory for the FASTQ text"; return -4; }
+    GZCHK(hipMemcpyAsync(blk.p, (const uint8_t *)span.blk.p + span.off + from, (size_t)len, hipMemcpyDeviceToDevice, st));
+    GZCHK(hipMemsetAsync((uint8_t *)blk.p + len, 0, 32, st));
+    GZCHK(hipStreamSynchronize(st));
+    out.pool_bytes = blk.bytes; out.d = (uint8_t *)blk.take();
+    out.e = (size_t)len; out.unterminated = next == span.len && span.unterminated;
     return 0;
 }
 

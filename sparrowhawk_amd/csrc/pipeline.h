@@ -92,6 +92,11 @@ public:
     // [all-gather] -> set_solid -> build_graph/correct/collapse as usual
     virtual int shard_partition(const uint32_t *d_bases, const uint32_t *d_seg_off, uint64_t n_seg, uint64_t n_bases,
                                 uint32_t n_partitions, std::vector<uint64_t> &part_records, std::string &err) = 0;
+    // the same in steps, for a rank whose reads come in several batches: begin, one shard_add_batch per batch (each < 2^32
+    // bases), then the totals over all of them.  shard_partition is the three with one batch.
+    virtual int shard_begin(uint32_t n_partitions, std::string &err) = 0;
+    virtual int shard_add_batch(const uint32_t *d_bases, const uint32_t *d_seg_off, uint64_t n_seg, uint64_t n_bases, std::string &err) = 0;
+    virtual int shard_totals(std::vector<uint64_t> &part_records, std::string &err) = 0;
     virtual uint32_t rec_words() const = 0;
     virtual int shard_pack(void *d_send, const uint64_t *base_records, uint32_t n_partitions, std::string &err) = 0;
     // records deduplicated by their SOURCE before the exchange (count_part.h: k_dedupe_partitions): part_records in = raw

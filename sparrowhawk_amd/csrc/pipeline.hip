@@ -1125,16 +1125,33 @@ public:
     }
 
     // ---- shard layer (one process per GPU; DESIGN.md "Multi-GPU") --------------------------------
-    int shard_partition(const uint32_t *d_bases, const uint32_t *d_seg_off, uint64_t n_seg, uint64_t n_bases,
-                        uint32_t n_partitions, std::vector<uint64_t> &part_records, std::string &err) override {
+    // Pass 1 of the shard layer: shard_begin fixes P, shard_add_batch runs pass 1 on one batch (any number of them, as the one-GPU
+    // path takes them: count_batch_impl packs the batch before into a dense buffer of its own), shard_totals closes pass 1 and
+    // says what every partition holds.  ONE batch: the records stay in their slices (run_view_ with S = G), as they always did.
+    // Several: the last batch is packed too and run_view_ has one run per batch and partition (make_batch_run_view) —
+    // shard_dedupe reads either view, shard_pack copies from either.
+    int shard_begin(uint32_t n_partitions, std::string &err) override {
         if (global_mode_) { err = "shard layer needs the partitioned counting mode"; return -1; }
         if (n_partitions < 1 || n_partitions > (uint32_t)PART_MAX_P || (n_partitions & (n_partitions - 1))) {
             err = "n_partitions must be a power of two <= 16384"; return -1;
         }
         forced_P_ = n_partitions;
-        part_records.assign(n_partitions, 0);
-        if (int rc = count_batch(d_bases, d_seg_off, n_seg, n_bases, err)) return rc;
-        if (!have_parts_) return 0;                       // no segments on this rank
+        return 0;
+    }
+    int shard_add_batch(const uint32_t *d_bases, const uint32_t *d_seg_off, uint64_t n_seg, uint64_t n_bases, std::string &err) override {
+        if (!forced_P_) { err = "shard_add_batch before shard_begin"; return -1; }
+        return count_batch(d_bases, d_seg_off, n_seg, n_bases, err);
+    }
+    int shard_totals(std::vector<uint64_t> &part_records, std::string &err) override {
+        part_records.assign(forced_P_, 0);
+        if (!have_parts_ && batches_.empty()) return 0;   // no segments on this rank
+        if (!batches_.empty()) {
+            if (have_parts_ && recs_.p) if (int rc = pack_current_batch(err)) return rc;
+            if (int rc = make_batch_run_view(err)) return rc;
+            for (auto &b : batches_)
+                for (uint32_t p = 0; p < pp_.P; p++) part_records[p] += b->part_off[p + 1] - b->part_off[p];
+            return 0;
+        }
         DevBuf<unsigned long long> tot;
         if (int rc = tot.alloc(pp_.P, err)) return rc;
         hipLaunchKernelGGL(k_part_totals, dim3(pp_.P), dim3(256), 0, stream_, fill_.p, pp_, tot.p);
@@ -1145,6 +1162,13 @@ public:
         for (uint32_t p = 0; p < pp_.P; p++) part_records[p] = h[p];
         return 0;
     }
+    int shard_partition(const uint32_t *d_bases, const uint32_t *d_seg_off, uint64_t n_seg, uint64_t n_bases,
+                        uint32_t n_partitions, std::vector<uint64_t> &part_records, std::string &err) override {
+        if (int rc = shard_begin(n_partitions, err)) return rc;
+        part_records.assign(n_partitions, 0);
+        if (int rc = shard_add_batch(d_bases, d_seg_off, n_seg, n_bases, err)) return rc;
+        return shard_totals(part_records, err);
+    }
     uint32_t rec_words() const override { return 2 * W; }
 
     int shard_pack(void *d_send, const uint64_t *base_records, uint32_t n_partitions, std::string &err) override {
@@ -1154,13 +1178,16 @@ public:
         if (int rc = base.alloc(pp_.P, err)) return rc;
         HIPCHK(hipMemcpyAsync(base.p, base_records, (size_t)pp_.P * 8, hipMemcpyHostToDevice, stream_));
         EvTimer t(stream_, stage_timers_);
-        hipLaunchKernelGGL((k_pack_partition<2 * W>), dim3(pp_.P), dim3(256), 0, stream_, recs_.p, fill_.p, pp_, base.p,
-                           (uint64_t *)d_send);
+        if (batches_.empty())
+            hipLaunchKernelGGL((k_pack_partition<2 * W>), dim3(pp_.P), dim3(256), 0, stream_, recs_.p, fill_.p, pp_, base.p,
+                               (uint64_t *)d_send);
+        else                                              // several batches: one run per batch, partition p's runs back to back at base[p]
+            hipLaunchKernelGGL((k_merge_runs<2 * W>), dim3(pp_.P), dim3(256), 0, stream_, run_view_, base.p, (uint64_t *)d_send);
         HIPCHK(hipGetLastError());
         if (t.on()) times_.add("shard_pack_kernel", t.stop());
         WAIT_STREAM();
-        // the local slices are no longer needed once packed
-        recs_.release(); fill_.release(); run_off_.release(); run_cnt_.release(); have_parts_ = false;
+        // the local slices (or the batches' buffers) are no longer needed once packed
+        recs_.release(); fill_.release(); run_off_.release(); run_cnt_.release(); batches_.clear(); have_parts_ = false;
         return 0;
     }
 
@@ -1212,7 +1239,7 @@ public:
         if (t.on()) times_.add("shard_pack_kernel", t.stop());
         WAIT_STREAM();
         shard_drop_dedup();
-        recs_.release(); fill_.release(); run_off_.release(); run_cnt_.release(); have_parts_ = false;
+        recs_.release(); fill_.release(); run_off_.release(); run_cnt_.release(); batches_.clear(); have_parts_ = false;
         return 0;
     }
 

@@ -21,6 +21,8 @@
 //   8 read_fastq_share           the sharded entry point from files (shk_shard_preprocess_fastq): one rank's slice of every file
 //                                as ONE packed batch — per file a BGZF slice, a whole member or a text slice on the device, the
 //                                host reader and the host parser for what the device declines (preprocess.h)
+//   9 read_fastq_share_batches   the same slices where they exceed one batch: window by window (a BGZF run) or piece by piece
+//                                into pass 1 of the shard layer, one batch each
 // The device parser (fastq_gpu.hip) takes regular 4-line FASTQ only; irregular framing and every malformed record go to
 // the host parser (fastq.cpp), which owns the error messages.
 #include "preprocess.h"
@@ -678,7 +680,7 @@ void bgzf_slice_cuts(const BgzfChain &chain, uint32_t rank, uint32_t world, uint
 }  // namespace
 
 int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual, uint32_t rank,
-                     uint32_t world, int device, void *stream, FastqShare &out, std::string &err) {
+                     uint32_t world, int device, void *stream, FastqShare &out, std::string &err, bool allow_batches) {
     if ((!fq1 && (n1 || fq2)) || (!fq2 && n2)) { err = "shard_preprocess_fastq: a null file with a size, or a second file without a first"; return SHK_E_PARAM; }
     if (world == 0 || rank >= world) { err = "shard_preprocess_fastq: rank beyond world"; return SHK_E_PARAM; }
     const Knobs kn;
@@ -715,6 +717,24 @@ int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n
               " packed bases); several batches per rank are not supported: use more ranks or split the input";
         return true;
     };
+    // beyond one batch, for the caller that takes batches: nothing is held, read_fastq_share_batches reads the share (again)
+    auto in_batches = [&](uint64_t text_ub) -> int {
+        err.clear();
+        gpu_packed_free(out.gp); out.gp = GpuPacked();
+        out.in_batches = true; out.text_ub = text_ub;
+        return SHK_OK;
+    };
+    if (allow_batches) {
+        // decided before anything is uploaded, where the host can tell: the ISIZE sums of the rank's run, the slice bounds of plain
+        // text, a plain member's ISIZE field over the ranks (a guess: what it misses is found after the inflation, below)
+        uint64_t text = 0;
+        for (int i = 0; i < nf; i++) {
+            if (f[i].walked) { uint64_t c0 = 0, c1 = 0; bgzf_slice_cuts(f[i].chain, rank, world, c0, c1); text += c1 - c0; }
+            else if (f[i].gz) { const uint8_t *t = fq[i] + fn[i] - 4; text += (t[0] | ((uint64_t)t[1] << 8) | ((uint64_t)t[2] << 16) | ((uint64_t)t[3] << 24)) / world; }
+            else { if (int rc = host_slice(i)) return rc; text += f[i].s1 - f[i].s0; }
+        }
+        if (text / 2 > kn.batch_bases) return in_batches(text);
+    }
     auto finish = [&](bool host_parsed) -> int {
         for (int i = 0; i < nf; i++) {
             const Route r = host_parsed ? Host : f[i].route;
@@ -759,14 +779,14 @@ int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n
         }
         uint64_t bytes = 0;
         for (int i = 0; i < nf; i++) bytes += spans[i].len;
-        if (too_large(bytes / 2)) return SHK_E_PARAM;
+        if (too_large(bytes / 2)) return allow_batches ? in_batches(bytes) : SHK_E_PARAM;
         Text joined;
         if (int rc = gpu_join_spans(spans, nf, stream, joined, err)) return code_of(Rc::DeviceNoParam, rc);
         for (int i = 0; i < nf; i++) spans[i].blk.put();
         const int rc = gpu_pack_fastq(nullptr, 0, nullptr, 0, k, min_qual, 0, stream, out.gp, err, 0, &joined);
         if (rc < 0) { gpu_packed_free(out.gp); out.gp = GpuPacked(); return code_of(Rc::Device, rc); }
         if (rc == 0) {
-            if (too_large(out.gp.n_bases)) return SHK_E_PARAM;
+            if (too_large(out.gp.n_bases)) return allow_batches ? in_batches(bytes) : SHK_E_PARAM;
             out.d_bases = out.gp.d_bases; out.d_seg_off = out.gp.d_seg_off;
             out.n_seg = out.gp.n_seg; out.n_bases = out.gp.n_bases; out.n_reads = out.gp.n_reads; out.n_input_bases = out.gp.n_input_bases;
             return finish(false);
@@ -783,7 +803,12 @@ int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n
         const uint64_t end = f[i].s1 == f[i].e ? f[i].l : f[i].s1;
         if (int rc = pack_fastq(f[i].t + f[i].s0, (size_t)(end - f[i].s0), k, min_qual, pr, err)) return code_of(Rc::Parser, rc);
     }
-    if (too_large(pr.n_bases)) return SHK_E_PARAM;
+    if (too_large(pr.n_bases)) {
+        if (!allow_batches) return SHK_E_PARAM;
+        uint64_t text = 0;
+        for (int i = 0; i < nf; i++) text += f[i].s1 - f[i].s0;
+        return in_batches(text);
+    }
     out.n_reads = pr.n_reads; out.n_input_bases = pr.n_input_bases;
     if (pr.n_seg()) {
         pr.finish();
@@ -795,4 +820,173 @@ int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n
         out.n_seg = pr.n_seg(); out.n_bases = pr.n_bases;
     }
     return finish(true);
+}
+
+// ---- the same share, beyond one batch: batch by batch into pass 1 of the shard layer (preprocess.h) --------------------------
+int read_fastq_share_batches(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual, uint32_t rank,
+                             uint32_t world, int device, void *stream, ShardBatchSink &sink, FastqShare &out, std::string &err) {
+    if ((!fq1 && (n1 || fq2)) || (!fq2 && n2)) { err = "shard_preprocess_fastq: a null file with a size, or a second file without a first"; return SHK_E_PARAM; }
+    if (world == 0 || rank >= world) { err = "shard_preprocess_fastq: rank beyond world"; return SHK_E_PARAM; }
+    const Knobs kn;
+    const uint8_t *const fq[2] = {fq1, fq2}; const size_t fn[2] = {n1, fq2 ? n2 : 0};
+    const int nf = fq2 ? 2 : (fq1 ? 1 : 0);
+    const uint64_t piece_bytes = 2 * kn.batch_bases;      // text per piece: its bases fit one batch
+    enum Route { None, BgzfSlice, MemberWhole, TextSlice, Host };
+    static const char *const route_name[] = {"", "bgzf_slice", "member_whole", "text_slice", "host"};
+    struct File {
+        BgzfChain chain; bool walked = false, gz = false;
+        ByteVec st; const uint8_t *t = nullptr; size_t l = 0, e = 0; bool host_text = false;
+        uint64_t s0 = 0, s1 = 0;                           // the slice inside the host text
+        uint64_t est = 0;                                  // bytes of text of the slice, as far as known beforehand (progress)
+    } f[2];
+    auto host_slice = [&](int i) -> int {                  // the host's text of file i (read once) and the slice in it
+        File &F = f[i];
+        if (F.host_text) return SHK_OK;
+        if (int ri = maybe_inflate(fq[i], fn[i], F.st, F.t, F.l, err)) return code_of(Rc::Inflater, ri);
+        F.e = trimmed_len(F.t, F.l);
+        uint64_t c0 = slice_cut(F.e, rank, world), c1 = slice_cut(F.e, rank + 1, world);
+        if (F.walked) bgzf_slice_cuts(F.chain, rank, world, c0, c1);
+        fastq_slice_bounds(F.t, F.e, rank, world, c0, c1, F.s0, F.s1);
+        F.host_text = true;
+        return SHK_OK;
+    };
+    uint64_t total = 0;
+    for (int i = 0; i < nf; i++) {
+        File &F = f[i];
+        F.gz = fn[i] >= 18 && fq[i][0] == 0x1F && fq[i][1] == 0x8B;
+        size_t bs = 0; const char *why = "";
+        F.walked = F.gz && bgzf_block(fq[i], fn[i], bs) && bgzf_walk(fq[i], fn[i], F.chain, why) == 0;
+        if (F.walked) { uint64_t c0 = 0, c1 = 0; bgzf_slice_cuts(F.chain, rank, world, c0, c1); F.est = c1 - c0; }
+        else if (F.gz) { const uint8_t *t = fq[i] + fn[i] - 4; F.est = (t[0] | ((uint64_t)t[1] << 8) | ((uint64_t)t[2] << 16) | ((uint64_t)t[3] << 24)) / world; }
+        else { if (int rc = host_slice(i)) return rc; F.est = F.s1 - F.s0; }
+        total += F.est;
+    }
+    uint64_t reads = 0, before = 0;                        // the rank's reads so far; the text of the files that are done
+    int at_file = 0;
+    auto hand = [&](const uint32_t *d_bases, const uint32_t *d_seg_off, uint64_t n_seg, uint64_t n_bases, uint64_t file_done) -> int {
+        out.n_batches++; out.n_seg += n_seg; out.n_bases += n_bases;
+        const int rc = sink.batch(n_seg ? d_bases : nullptr, n_seg ? d_seg_off : nullptr, n_seg, n_bases, reads, before + std::min(file_done, f[at_file].est), total);
+        if (rc) err.clear();
+        return rc;
+    };
+    // a piece of regular text on the device -> parser -> one batch.  DECLINED: not regular 4-line FASTQ (nothing was counted)
+    auto device_piece = [&](const GpuText &text, uint64_t file_done) -> int {
+        Packed gp;
+        const int rc = gpu_pack_fastq(nullptr, 0, nullptr, 0, k, min_qual, 0, stream, gp, err, 0, &text);
+        if (rc < 0) return code_of(Rc::Device, rc);
+        if (rc) return DECLINED;
+        out.n_windows++;
+        reads += gp.n_reads; out.n_reads += gp.n_reads; out.n_input_bases += gp.n_input_bases;
+        return hand(gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases, file_done);
+    };
+    // the host parser from `from` to the end of the slice (its messages count the slice's records: file_reads came before),
+    // a batch every SHK_BATCH_BASES bases
+    auto host_from = [&](int i, uint64_t from, uint64_t file_reads) -> int {
+        File &F = f[i];
+        // (a slice that reaches the end of the text takes the blank lines behind it along: read_fastq_share says why)
+        const uint64_t end = F.s1 == F.e ? F.l : F.s1;
+        if (from >= end) return SHK_OK;
+        PackedReads pr;
+        int flush_rc = SHK_OK;
+        uint64_t counted = 0, counted_in = 0;              // reads and input bases of pr that are in the totals already
+        auto flush = [&](PackedReads &p, uint64_t file_done) -> int {
+            if (p.n_seg() == 0 && p.n_reads == counted) return 0;      // (nothing new)
+            reads += p.n_reads - counted; out.n_reads += p.n_reads - counted; counted = p.n_reads;
+            out.n_input_bases += p.n_input_bases - counted_in; counted_in = p.n_input_bases;
+            void *d_bases = nullptr, *d_off = nullptr;
+            if (p.n_seg()) {
+                p.finish();
+                int rc = device_upload(p.bases.data(), p.bases.size() * 4, &d_bases, err);
+                if (!rc) rc = device_upload(p.seg_off.data(), p.seg_off.size() * 4, &d_off, err);
+                if (rc) { device_free(d_bases); device_free(d_off); flush_rc = SHK_E_OOM; return -7; }
+                out.uploaded_bytes += (p.bases.size() + p.seg_off.size()) * 4;
+            }
+            flush_rc = hand((const uint32_t *)d_bases, (const uint32_t *)d_off, p.n_seg(), p.n_bases, file_done);
+            device_free(d_bases); device_free(d_off);
+            p.reset_stream();
+            return flush_rc ? -7 : 0;
+        };
+        const int rc = pack_fastq(F.t + from, (size_t)(end - from), k, min_qual, pr, err, 0, nullptr, 0, kn.batch_bases,
+                                  [&](PackedReads &p) { return flush(p, from - F.s0); }, file_reads);
+        if (rc == -7) return flush_rc;
+        if (rc) return code_of(Rc::Parser, rc);
+        return flush(pr, F.s1 - F.s0) ? flush_rc : SHK_OK;
+    };
+    for (int i = 0; i < nf; i++) {
+        File &F = f[i];
+        at_file = i;
+        Route route = None;
+        uint64_t resume = 0;                               // the file's text in front of this offset has been handed over
+        bool host_parser = kn.host_parser, through = false;
+        const uint64_t reads0 = reads;
+        if (!kn.host_parser && F.gz && kn.gunzip_device) {
+            if (F.walked) {
+                BgzfShareWindows sw;
+                const char *why = "";
+                int rc = sw.open(fq[i], F.chain, rank, world, kn.window.bytes, device, stream, why, err);
+                if (rc < 0) return code_of(Rc::DeviceNoParam, rc);
+                while (!rc) {
+                    GpuText piece; uint64_t at = 0; bool done = false;
+                    rc = sw.next(piece, at, done, why, err);
+                    if (rc < 0) return code_of(Rc::DeviceNoParam, rc);
+                    if (rc) { resume = sw.consumed(); break; }              // this window is the host reader's, and what follows it
+                    route = BgzfSlice;
+                    if (done) { through = true; break; }
+                    const int prc = device_piece(piece, at + piece.e - sw.run_begin());
+                    if (prc == DECLINED) { resume = at; host_parser = true; break; }
+                    if (prc) return prc;
+                }
+                out.uploaded_bytes += sw.uploaded();
+            } else {
+                Text text;
+                int rc = gpu_inflate_member(fq[i], fn[i], device, stream, text, err);
+                if (rc < 0) return code_of(Rc::DeviceNoParam, rc);
+                if (!rc) {
+                    out.uploaded_bytes += fn[i];
+                    DevSpan span;
+                    if ((rc = gpu_text_slice(text, rank, world, stream, span, err)) < 0) return code_of(Rc::DeviceNoParam, rc);
+                    route = MemberWhole;
+                    through = true;
+                    for (uint64_t from = 0; from < span.len;) {
+                        Text piece; uint64_t next = 0;
+                        rc = gpu_span_piece(span, from, piece_bytes, stream, piece, next, err);
+                        if (rc < 0) return code_of(Rc::DeviceNoParam, rc);
+                        const int prc = rc ? DECLINED : device_piece(piece, next);
+                        if (prc == DECLINED) { resume = span.off + from; host_parser = true; through = false; break; }
+                        if (prc) return prc;
+                        from = next;
+                    }
+                }
+            }
+        }
+        if (!through) {
+            // plain text, what the device declined, SHK_HOST_PARSER=1: the host's text, cut on the host
+            if (int rc = host_slice(i)) return rc;
+            route = F.gz ? Host : TextSlice;
+            uint64_t from = std::max(F.s0, resume);
+            while (!host_parser && from < F.s1) {
+                uint64_t end = F.s1;
+                if (F.s1 - from > piece_bytes) {
+                    const uint64_t at = last_record_start(F.t + from, (size_t)piece_bytes);
+                    if (at == UINT64_MAX || at == 0) { host_parser = true; break; }      // (no record starts inside the piece)
+                    end = from + at;
+                }
+                Text text;
+                if (int rc = gpu_upload_text(F.t + from, (size_t)(end - from), device, text, err)) return code_of(Rc::DeviceNoParam, rc);
+                out.uploaded_bytes += text.e;
+                const int prc = device_piece(text, end - F.s0);
+                if (prc == DECLINED) { host_parser = true; break; }
+                if (prc) return prc;
+                from = end;
+            }
+            if (host_parser) {
+                route = Host;
+                if (int rc = host_from(i, from, reads - reads0)) return rc;
+            }
+        }
+        before += F.est;
+        out.n_bgzf_slice += route == BgzfSlice; out.n_member_whole += route == MemberWhole; out.n_text_slice += route == TextSlice; out.n_host += route == Host;
+        if (out.route.find(route_name[route]) == std::string::npos) out.route += (out.route.empty() ? "" : "+") + std::string(route_name[route]);
+    }
+    return SHK_OK;
 }

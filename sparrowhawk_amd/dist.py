@@ -185,6 +185,21 @@ def sharded_preprocess_rccl(helper: AssemblyHelper, d_bases_ptr, d_seg_off_ptr, 
                                                  int(n_reads), int(n_partitions or 0)))
 
 
+def sharded_preprocess_batches(helper: AssemblyHelper, comm: LibComm, batches, n_reads, n_partitions=0):
+    """Collective over `comm`: this rank's packed reads in SEVERAL batches in HBM (shk_shard_preprocess_batches).  batches: a
+    sequence of (d_bases_ptr, d_seg_off_ptr, n_seg, n_bases), each below 2^32 bases; an empty one: this rank has no reads.
+    The ranks need not hold the same number.  sharded_preprocess_rccl is this call with one batch."""
+    n = len(batches)
+    pb = (C.c_void_p * max(n, 1))(*[int(b[0]) if b[2] else None for b in batches])
+    ps = (C.c_void_p * max(n, 1))(*[int(b[1]) if b[2] else None for b in batches])
+    ns = np.array([int(b[2]) for b in batches], dtype=np.uint64)
+    nb = np.array([int(b[3]) for b in batches], dtype=np.uint64)
+    helper._check(helper._L.shk_shard_preprocess_batches(helper._h, comm._c, n, C.cast(pb, C.c_void_p) if n else None,
+                                                         C.cast(ps, C.c_void_p) if n else None,
+                                                         ns.ctypes.data if n else None, nb.ctypes.data if n else None,
+                                                         int(n_reads), int(n_partitions or 0)))
+
+
 def sharded_preprocess_fastq(helper: AssemblyHelper, comm: LibComm, file1, file2=None, split=True, n_partitions=0):
     """Collective over `comm`: the sharded preprocess straight from FASTQ files (plain, .gz or BGZF; bytes, a path or a
     file object).  split=True: every rank passes the SAME file(s) and takes slice `rank` of `world` of each — of a BGZF

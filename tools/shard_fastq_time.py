@@ -8,6 +8,11 @@ alternated in one process, every call ending with the counts on the host (the de
     one_gpu   shk_preprocess(file1, file2), for scale
 
     python tools/shard_fastq_time.py [n_reads] [reps] [warmup] [level]      one JSON line per way, then a summary line
+    python tools/shard_fastq_time.py n_reads reps warmup level 1,4,16       the batch knob: `fastq` alone, the same input as it
+                                                                            fits (1) and forced into about N batches through
+                                                                            SHK_BATCH_BASES — one JSON line per N with the wall
+                                                                            time and, per repeat, where the time and the memory go
+                                                                            (verbose handles: batch_pack_kernel is a stage timer)
 
 One rank says what the call costs, not how it scales: with N ranks each uploads and inflates 1 / N of the compressed bytes
 (shard_fastq_uploaded_bytes, pinned by tests/test_gpu_shard_fastq.py), which a single GPU cannot show as a time."""
@@ -24,6 +29,7 @@ n_reads = int(sys.argv[1]) if len(sys.argv) > 1 else 3_333_334
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 warmup = int(sys.argv[3]) if len(sys.argv) > 3 else 2
 level = int(sys.argv[4]) if len(sys.argv) > 4 else 6
+forced = [int(x) for x in sys.argv[5].split(",")] if len(sys.argv) > 5 else []
 K, MIN_COUNT, MIN_QUAL = 31, 5, 20
 dev = torch.device("cuda", 0)
 lib = _lib.load()
@@ -93,6 +99,34 @@ t0 = time.perf_counter()
 z1, z2, text_bytes = make_pair()
 print("# %.3f GB of text in %d reads -> %.3f + %.3f GB of BGZF at level %d (%.1f s)" % (text_bytes / 1e9, n_reads, len(z1) / 1e9, len(z2) / 1e9, level, time.perf_counter() - t0), flush=True)
 comm = LibComm(0, 1)
+if forced:
+    KEYS = ("shard_fastq_read_host_clock", "shard_preprocess_host_clock", "shard_dedupe_kernel", "batch_pack_kernel", "batch_merge_kernel",
+            "partition_kernel", "shard_pack_kernel", "shard_fastq_batches_x1", "shard_fastq_windows_x1", "shard_fastq_uploaded_bytes")
+    infos = []
+    for nb in forced:
+        if nb > 1:
+            os.environ["SHK_BATCH_BASES"] = str(text_bytes // (2 * nb) + 1)
+        else:
+            os.environ.pop("SHK_BATCH_BASES", None)
+        wall, rows = [], []
+        for rep in range(warmup + reps):
+            h = AssemblyHelper.new(K, True, MIN_COUNT, MIN_QUAL, 0, False, False, False, False)
+            t1 = time.perf_counter()
+            sharded_preprocess_fastq(h, comm, z1, z2, split=True)
+            dt = time.perf_counter() - t1
+            if rep >= warmup:
+                t = h.timings()
+                wall.append(round(dt * 1e3, 2))
+                rows.append({**{k: round(t[k], 3) for k in KEYS if k in t}, "peak_device_bytes": h.peak_device_bytes})
+            info = h.get_preprocessing_info()
+            h.free()
+        infos.append(info)
+        print(json.dumps({"way": "fastq", "asked_batches": nb, "SHK_BATCH_BASES": os.environ.get("SHK_BATCH_BASES"), "wall_ms": wall, "repeats": rows}), flush=True)
+    os.environ.pop("SHK_BATCH_BASES", None)
+    comm.free()
+    assert all(i == infos[0] for i in infos), "the batch counts disagree"
+    print(json.dumps({"summary": "same preprocessing info for every batch count", "asked_batches": forced}), flush=True)
+    sys.exit(0)
 ways = {"fastq": way_fastq, "packed": way_packed, "one_gpu": way_one_gpu}
 ms = {w: [] for w in ways}
 last, info = {}, {}
