@@ -73,6 +73,21 @@ void shk_set_progress_cb(shk_handle *h, shk_progress_cb cb, void *user);
  * The buffers are not retained. */
 int shk_preprocess(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2);
 
+/* The same for FASTA input (SPEC S1a): whole files, plain text or gzip; fa2 may be NULL, two files are pooled, file 1 first.
+ * A record is a header line ('>') and the lines behind it, joined; its segments are the maximal runs of ACGTacgt, a run of
+ * more than 16384 + k - 1 bases goes in as overlapping pieces; min_qual is not used.  The results are those of shk_preprocess
+ * on the FASTQ text in which every record stands with its joined sequence and a quality that passes.  State rules, progress
+ * strings (loop:<records>:<pct>), bulk / chunked / Bloom modes (chunk_size counts records) as shk_preprocess.
+ * Routes: a plain gzip member or a BGZF file the device inflater takes (>= SHK_GUNZIP_DEVICE_MIN) is inflated and packed on
+ * the device; other gzip input is inflated on the host; text of >= SHK_FASTA_DEVICE_MIN bytes (default 1 MiB, the smallest size measured and already ahead there: DESIGN.md §5)
+ * is uploaded and packed on the device by a byte-parallel packer (records of any length), smaller text and whatever the
+ * device packer declines on the host, which owns the messages: a non-blank line in front of the first header of a file is
+ * SHK_E_PARSE ("FASTA: ...").  SHK_HOST_PARSER=1: always the host packer.
+ * Text beyond one batch (SHK_BATCH_BASES bytes) is cut on the host at header lines, a batch per piece; a single record beyond
+ * one batch is SHK_E_PARAM.  shk_preprocess itself does not sniff FASTA and refuses it as before.
+ * Timings: fasta_device_x1 / fasta_host_x1 (texts each packer took), fasta_batches_x1, fasta_device_parse_pack_host_clock. */
+int shk_preprocess_fasta(shk_handle *h, const uint8_t *fa1, size_t n1, const uint8_t *fa2, size_t n2);
+
 /* Streaming form of preprocess for inputs that do not fit host memory at once (modelled on the
  * reference's chunked bridge, rust/deacon-bridge/src/lib.rs:112,158).  Each chunk must hold
  * whole FASTQ records (plain text); shk_finish_reads() completes preprocessing. */
@@ -272,6 +287,14 @@ typedef struct shk_packed {
 /* returns SHK_OK or SHK_E_PARSE / SHK_E_OOM; *err (optional) receives a static message */
 int shk_pack_fastq(const uint8_t *fq, size_t n, uint32_t k, uint32_t min_qual, shk_packed *out,
                    const char **err);
+/* the host FASTA packer (SPEC S1a; plain or gzip): SHK_OK, SHK_E_PARSE (message with "FASTA") / SHK_E_OOM; SHK_E_PARAM
+ * where k is not odd and within [15, 255] */
+int shk_pack_fasta(const uint8_t *fa, size_t n, uint32_t k, shk_packed *out, const char **err);
+/* the device FASTA packer alone (tests; needs a GPU), whatever the size of the text: the batch is copied back to the host.
+ * *route (optional): "device", "host" (the device packer declined, the host packer took the text) — on failure, the message
+ * ("host: <message>" where the host packer, having taken the text over, refused it). */
+int shk_device_pack_fasta(const uint8_t *fa1, size_t n1, const uint8_t *fa2, size_t n2, uint32_t k, struct shk_packed *out,
+                          const char **route);
 void shk_packed_free(shk_packed *p);
 
 /* ---- stage inspection (used by the parity tests; SURVEY.md §7 step 1 stages a-f).

@@ -32,6 +32,11 @@ public:
         check(shk_preprocess(h_, file1.data(), file1.size(), file2 ? file2->data() : nullptr,
                              file2 ? file2->size() : 0));
     }
+    // the same for FASTA files, plain or gzip (shk.h: shk_preprocess_fasta; SPEC S1a)
+    void preprocess_fasta(const std::vector<uint8_t> &file1, const std::vector<uint8_t> *file2 = nullptr) {
+        check(shk_preprocess_fasta(h_, file1.data(), file1.size(), file2 ? file2->data() : nullptr,
+                                   file2 ? file2->size() : 0));
+    }
     // preprocess(file1, file2 | null) across the ranks of a communicator (shk.h: shk_shard_preprocess_fastq; collective, and
     // so is assemble() after it).  split: every rank passes the same file(s) and takes its slice; otherwise the files are
     // this rank's own reads (file1 == nullptr: it has none).

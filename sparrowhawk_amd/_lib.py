@@ -28,6 +28,7 @@ SIGNATURES = {
     "shk_last_error": (_cp, [_vp]),
     "shk_set_progress_cb": (None, [_vp, PROGRESS_CB, _vp]),
     "shk_preprocess": (_int, [_vp, _cp, _sz, _cp, _sz]),
+    "shk_preprocess_fasta": (_int, [_vp, _cp, _sz, _cp, _sz]),
     "shk_push_reads": (_int, [_vp, _cp, _sz]),
     "shk_finish_reads": (_int, [_vp]),
     "shk_preprocess_packed_device": (_int, [_vp, _vp, _vp, _u64, _u64, _u64]),
@@ -61,6 +62,8 @@ SIGNATURES = {
     "shk_host_last_record_start": (_u64, [_cp, _sz]),
     "shk_device_last_record_start": (_int, [_cp, _sz, C.POINTER(_u64)]),
     "shk_pack_fastq": (_int, [_cp, _sz, _u32, _u32, C.POINTER(ShkPacked), C.POINTER(_cp)]),
+    "shk_pack_fasta": (_int, [_cp, _sz, _u32, C.POINTER(ShkPacked), C.POINTER(_cp)]),
+    "shk_device_pack_fasta": (_int, [_cp, _sz, _cp, _sz, _u32, C.POINTER(ShkPacked), C.POINTER(_cp)]),
     "shk_packed_free": (None, [C.POINTER(ShkPacked)]),
     "shk_key_words": (_u32, [_vp]),
     "shk_total_instances": (_u64, [_vp]),

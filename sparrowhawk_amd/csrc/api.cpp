@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "end_keys.h"
+#include "fasta_gpu.h"
 #include "fastq_gpu.h"
 #include "inflate_gpu.h"
 #include "inflate_mt.h"
@@ -276,12 +277,64 @@ const char *shk_get_assembly(shk_handle *h) {
 }
 
 // ---- packer ------------------------------------------------------------------------------
+static int packed_to_caller(PackedReads &pr, shk_packed *out);      // a finished copy in malloc'ed memory (shk_packed_free)
 int shk_pack_fastq(const uint8_t *fq, size_t n, uint32_t k, uint32_t min_qual, shk_packed *out, const char **errp) {
     static thread_local std::string msg;
     if (!out) return SHK_E_PARAM;
     PackedReads pr;
     int rc = pack_fastq(fq, n, k, min_qual, pr, msg);
     if (rc) { if (errp) *errp = msg.c_str(); return code_of(Rc::Parser, rc); }
+    return packed_to_caller(pr, out);
+}
+int shk_pack_fasta(const uint8_t *fa, size_t n, uint32_t k, shk_packed *out, const char **errp) {
+    static thread_local std::string msg;
+    if (!out || (!fa && n)) return SHK_E_PARAM;
+    if ((k & 1u) == 0 || k < SHK_K_MIN || k > SHK_K_MAX) { msg = "k must be odd and within [15, 255]"; if (errp) *errp = msg.c_str(); return SHK_E_PARAM; }
+    try {
+        PackedReads pr;
+        int rc = pack_fasta(fa, n, k, pr, msg);
+        if (rc) { if (errp) *errp = msg.c_str(); return code_of(Rc::Parser, rc); }
+        return packed_to_caller(pr, out);
+    } catch (...) { return SHK_E_OOM; }
+}
+// the device FASTA packer alone (tests): the batch comes back to the host (shk_packed_free); *route: "device", "host" (the
+// device packer declined and the host packer took the text), or the message of a failure
+int shk_device_pack_fasta(const uint8_t *fa1, size_t n1, const uint8_t *fa2, size_t n2, uint32_t k, shk_packed *out, const char **route) {
+    static thread_local std::string msg;
+    try {
+        if (!out || (!fa1 && n1) || (!fa2 && n2)) return SHK_E_PARAM;
+        *out = shk_packed();
+        if (route) *route = "";
+        if ((k & 1u) == 0 || k < SHK_K_MIN || k > SHK_K_MAX) { msg = "k must be odd and within [15, 255]"; if (route) *route = msg.c_str(); return SHK_E_PARAM; }
+        ByteVec st1, st2; const uint8_t *t1 = nullptr, *t2 = nullptr; size_t l1 = 0, l2 = 0;
+        if (int ri = maybe_inflate_pair(fa1, n1, fa2, n2, st1, st2, t1, l1, t2, l2, msg)) { if (route) *route = msg.c_str(); return code_of(Rc::Inflater, ri); }
+        GpuPacked gp;
+        struct Free { GpuPacked &g; ~Free() { gpu_packed_free(g); } } free_gp{gp};
+        const int rc = gpu_pack_fasta(t1, l1, fa2 ? t2 : nullptr, l2, k, 0, nullptr, gp, msg);
+        if (rc < 0) { if (route) *route = msg.c_str(); return code_of(Rc::Device, rc); }
+        if (rc == 1) {
+            PackedReads pr;
+            int rh = pack_fasta(t1, l1, k, pr, msg);
+            if (!rh && fa2) rh = pack_fasta(t2, l2, k, pr, msg);
+            if (rh) msg = "host: " + msg;                  // (the route, then the host packer's message)
+            if (route) *route = rh ? msg.c_str() : "host";
+            return rh ? code_of(Rc::Parser, rh) : packed_to_caller(pr, out);
+        }
+        const size_t nw = (size_t)(gp.n_bases >> 4) + 2;
+        out->bases = (uint32_t *)calloc(nw, 4);
+        out->seg_off = (uint32_t *)calloc((size_t)gp.n_seg + 1, 4);
+        if (!out->bases || !out->seg_off) { shk_packed_free(out); return SHK_E_OOM; }
+        if (device_download(out->bases, gp.d_bases, nw * 4, msg) || device_download(out->seg_off, gp.d_seg_off, ((size_t)gp.n_seg + 1) * 4, msg)) {
+            shk_packed_free(out);
+            if (route) *route = msg.c_str();
+            return SHK_E_DEVICE;
+        }
+        out->n_seg = gp.n_seg; out->n_bases = gp.n_bases; out->n_reads = gp.n_reads; out->n_input_bases = gp.n_input_bases;
+        if (route) *route = "device";
+        return SHK_OK;
+    } catch (...) { return SHK_E_OOM; }
+}
+static int packed_to_caller(PackedReads &pr, shk_packed *out) {
     pr.finish();
     out->n_seg = pr.n_seg(); out->n_bases = pr.n_bases; out->n_reads = pr.n_reads; out->n_input_bases = pr.n_input_bases;
     out->bases = (uint32_t *)malloc(pr.bases.size() * 4);
@@ -880,6 +933,9 @@ uint32_t shk_choose_partitions(uint64_t total_instances_ub, uint32_t world, uint
 // ---- the guarded entry points (device guard, no exception across the ABI, failed-handle state) ----
 int shk_preprocess(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2) {
     return guarded(h, Poison::AfterFirstBatch, [&] { return preprocess_impl(h, fq1, n1, fq2, n2); });
+}
+int shk_preprocess_fasta(shk_handle *h, const uint8_t *fa1, size_t n1, const uint8_t *fa2, size_t n2) {
+    return guarded(h, Poison::AfterFirstBatch, [&] { return preprocess_fasta_impl(h, fa1, n1, fa2, n2); });
 }
 int shk_push_reads(shk_handle *h, const uint8_t *chunk, size_t n) {
     return guarded(h, Poison::AfterFirstBatch, [&] { return push_reads_impl(h, chunk, n); });

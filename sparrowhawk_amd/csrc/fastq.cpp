@@ -364,4 +364,63 @@ int pack_fastq(const uint8_t *buf, size_t n, uint32_t k, uint32_t min_qual, Pack
     return 0;
 }
 
+// SPEC S1a.  One walk over the lines; the run in hand lives across line breaks and ends at an invalid byte, a header or the
+// end of the text.  A record is complete — counted, progress, flush — when the next header or the end of the text is met.
+int pack_fasta(const uint8_t *buf, size_t n, uint32_t k, PackedReads &out, std::string &err, uint64_t every,
+               const ProgressFn &progress, uint64_t flush_reads, uint64_t flush_bases, const FlushFn &flush, uint64_t rec_base) {
+    ByteVec inflated;
+    if (n >= 2 && buf[0] == 0x1F && buf[1] == 0x8B) {
+        const uint8_t *q = nullptr; size_t qn = 0;
+        if (int rc = maybe_inflate(buf, n, inflated, q, qn, err)) return rc;
+        buf = q; n = qn;
+    }
+    if (out.seg_off.empty()) out.seg_off.push_back(0);
+    std::vector<uint8_t> run;
+    const size_t kPiece = 16384;                          // (the piece rule of pack_fastq)
+    auto close_run = [&]() -> int {
+        if (run.size() >= k) {
+            const size_t pieces = (run.size() - k + 1 + kPiece - 1) / kPiece;
+            if (out.n_bases + run.size() + pieces * (size_t)k >= 0xFFFFFFF0ull) { err = "input exceeds 2^32 bases per batch"; return -1; }
+            for (size_t p0 = 0; p0 + k - 1 < run.size(); p0 += kPiece)
+                append_run(out, run.data() + p0, std::min(run.size() - p0, kPiece + k - 1));
+        }
+        run.clear();
+        return 0;
+    };
+    bool in_record = false;
+    auto close_record = [&](size_t at) -> int {          // at: where the next record begins, or n
+        if (!in_record) return 0;
+        if (int rc = close_run()) return rc;
+        out.n_reads++;
+        if (every && progress && (out.n_reads % every) == 0) progress(out.n_reads, at, n);
+        if (flush && ((flush_reads && (out.n_reads % flush_reads) == 0) || (flush_bases && out.n_bases >= flush_bases))) {
+            if (int rc = flush(out)) { err = "batch hand-over failed"; return rc; }
+            if (out.seg_off.empty()) out.seg_off.push_back(0);
+        }
+        return 0;
+    };
+    size_t p = 0;
+    while (p < n) {
+        const uint8_t *nl = (const uint8_t *)memchr(buf + p, '\n', n - p);
+        const size_t next = nl ? (size_t)(nl - buf) + 1 : n;
+        size_t e = nl ? (size_t)(nl - buf) : n;
+        if (e > p && buf[e - 1] == '\r') e--;             // (in front of '\n', or the last byte of the text)
+        if (e == p) { p = next; continue; }               // a blank line
+        if (buf[p] == '>') {
+            if (int rc = close_record(p)) return rc;
+            in_record = true;
+        } else {
+            if (!in_record) { err = "FASTA: sequence line in front of the first header (record " + std::to_string(rec_base) + ")"; return -3; }
+            for (size_t i = p; i < e; i++) {
+                const uint8_t c = LUT.code[buf[i]];
+                if (c < 4) run.push_back(c);
+                else if (int rc = close_run()) return rc;
+            }
+            out.n_input_bases += e - p;
+        }
+        p = next;
+    }
+    return close_record(n);
+}
+
 }  // namespace shk

@@ -38,6 +38,15 @@ int pack_fastq(const uint8_t *buf, size_t n, uint32_t k, uint32_t min_qual, Pack
                uint64_t flush_reads = 0, uint64_t flush_bases = 0, const FlushFn &flush = nullptr,
                uint64_t rec_base = 0 /* records of this file that came before buf: numbering of the error messages */);
 
+// The same for one FASTA buffer (plain or gzip; SPEC S1a): a record per header line, its lines joined, the maximal runs of
+// ACGTacgt of the joined sequence as segments, a long run in pieces by the rule of pack_fastq.  There are no qualities.
+// progress / flush: after a record, i.e. when the next header or the end of the text is met (bytes_consumed: where that
+// header begins).  A non-blank line in front of the first header is -3, "FASTA: ..." (rec_base: records of this file that
+// came before buf — a piece that begins at a header).  The device states the same rule in fasta_gpu.hip.
+int pack_fasta(const uint8_t *buf, size_t n, uint32_t k, PackedReads &out, std::string &err, uint64_t every = 0,
+               const ProgressFn &progress = nullptr, uint64_t flush_reads = 0, uint64_t flush_bases = 0,
+               const FlushFn &flush = nullptr, uint64_t rec_base = 0);
+
 // b[0..n) starts with a whole BGZF block (SAM spec 4.1: a gzip member with a 'BC' extra subfield that holds its size - 1):
 // bsize = that size.  The one rule by which both the host reader and the device inflater (inflate_gpu.hip) walk a chain.
 bool bgzf_block(const uint8_t *b, size_t n, size_t &bsize);

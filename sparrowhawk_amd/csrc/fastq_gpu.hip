@@ -22,6 +22,7 @@
 
 #include "device_mem.h"
 #include "fastq_gpu.h"
+#include "scan_gpu.h"
 
 namespace shk {
 
@@ -56,12 +57,8 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_add(unsigned long long *__restr
     for (int i = 0; i < SCAN_I; i++) if (base + i < n) a[base + i] += o;
 }
 
-static inline unsigned grid1(uint64_t work, unsigned block = 256, unsigned cap = 65536) {
-    uint64_t b = (work + block - 1) / block; if (b < 1) b = 1; if (b > cap) b = cap; return (unsigned)b;
-}
-
-// in-place exclusive scan of a[0..n); *total (device) receives the sum
-static int exclusive_scan(unsigned long long *a, uint64_t n, unsigned long long *d_total, hipStream_t st, PoolScope &sc,
+// in-place exclusive scan of a[0..n); *total (device) receives the sum (scan_gpu.h: the FASTA packer uses it too)
+int exclusive_scan(unsigned long long *a, uint64_t n, unsigned long long *d_total, hipStream_t st, PoolScope &sc,
                           std::string &err) {
     const uint64_t per = SCAN_T * SCAN_I;
     const uint64_t nb = (n + per - 1) / per;

@@ -34,6 +34,7 @@
 #include <utility>
 #include <vector>
 
+#include "fasta_gpu.h"
 #include "fastq_gpu.h"
 #include "inflate_gpu.h"
 #include "inflate_mt.h"
@@ -49,6 +50,7 @@ uint32_t emit_threshold_of(const shk_handle *h) {
 
 namespace {
 
+const size_t FASTA_DEVICE_MIN_DEFAULT = (size_t)1 << 20;
 const int DECLINED = 1;                 // what a route returns when the next one is to be tried (SHK_E_* are <= 0)
 
 // the environment's switches, read once per call (the tests change them between handles of one process)
@@ -58,6 +60,8 @@ struct Knobs {
     const bool host_parser = is(getenv("SHK_HOST_PARSER"), '1'), gunzip_device = !is(getenv("SHK_GUNZIP_DEVICE"), '0');
     const size_t pipeline_min = num(getenv("SHK_FASTQ_PIPELINE_MIN"), 64ull << 20), stream_device_min = num(getenv("SHK_STREAM_DEVICE_MIN"), 8ull << 20);
     const size_t pieces = (size_t)std::max<long long>(1, (long long)num(getenv("SHK_FASTQ_PIECES"), 4));
+    // FASTA texts below this many bytes go to the host packer (shk_preprocess_fasta; the default: DESIGN.md §5, profiles/fasta)
+    const size_t fasta_device_min = num(getenv("SHK_FASTA_DEVICE_MIN"), FASTA_DEVICE_MIN_DEFAULT);
     // bases per batch of the host-parsed paths (a batch is limited to 2^32 packed bases by its 32-bit offsets)
     const uint64_t batch_bases = std::min<uint64_t>(std::max<uint64_t>(num(getenv("SHK_BATCH_BASES"), 1ull << 31), 1024), 3ull << 30);
     // text per window of route 2 (bytes; default 1 GiB — unmeasured so far): a window and its carry fit one batch.  Set: a BGZF
@@ -570,6 +574,202 @@ int preprocess_impl(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t 
     if (rc == DECLINED && device && one_batch && !pipelined) rc = route_device_single(h, kn, in);
     if (rc == DECLINED && device && !one_batch) rc = route_device_pieces(h, kn, in, false);
     return rc == DECLINED ? route_host(h, kn, in) : rc;
+}
+
+// ---- FASTA (shk_preprocess_fasta; SPEC S1a) ----------------------------------------------------------------------------------
+// Whole files, plain or gzip, through the routes shk_preprocess has for one batch:
+//   F1 fasta_device_gzip   every file is what the device inflater takes (a plain member or a BGZF chain of >= SHK_GUNZIP_DEVICE_MIN)
+//                          and the text fits one batch: inflated on the device, packed there (gpu_pack_fasta), one batch
+//      (what is gzip is inflated on the host here, once)
+//   F2 one batch, >= SHK_FASTA_DEVICE_MIN of text: one upload, one pack on the device
+//   F3 host                SHK_HOST_PARSER=1, a small text, or the device packer declined (the host packer owns the messages)
+//   F4 fasta_batches       the text exceeds one batch (SHK_BATCH_BASES bytes: a FASTA byte is a base): cut on the host at header
+//                          lines, each piece a batch of its own through either packer
+namespace {
+
+struct FastaBook {                                       // the counters, on every way out
+    shk_handle *h; uint64_t batches0; double device = 0, host = 0;
+    explicit FastaBook(shk_handle *hh) : h(hh), batches0(hh->batches_started) {}
+    ~FastaBook() {
+        auto &t = h->pipe->times();
+        if (device) t.add("fasta_device_x1", device);
+        if (host) t.add("fasta_host_x1", host);
+        t.add("fasta_batches_x1", (double)(h->batches_started - batches0));
+    }
+};
+
+int fasta_host_parse(shk_handle *h, const Knobs &kn, const uint8_t *t, size_t n, PackedReads &pr, const Span &sp, uint64_t flush_reads, uint64_t rec_base = 0) {
+    std::string err;
+    auto prog = [&](uint64_t reads, uint64_t bytes, uint64_t) { post_loop(h, reads, sp, bytes); };
+    int flush_rc = SHK_OK;
+    auto flush = [&](PackedReads &p) -> int { flush_rc = flush_host_batch(h, p); return flush_rc ? -7 : 0; };
+    const int rc = pack_fasta(t, n, h->k, pr, err, h->progress_every(), prog, flush_reads, kn.batch_bases, flush, rec_base);
+    if (rc == -7) return flush_rc;
+    return rc ? fail_rc(h, Rc::Parser, rc, err) : SHK_OK;
+}
+
+int fasta_device_gzip(shk_handle *h, const Knobs &kn, const Input &in, FastaBook &book) {
+    const uint8_t *gz[2] = {in.fq1, in.fq2}; const size_t gn[2] = {in.n1, in.fq2 ? in.n2 : 0};
+    const int nf = in.fq2 ? 2 : 1;
+    for (int f = 0; f < nf; f++) if (gn[f] < 18 || gz[f][0] != 0x1F || gz[f][1] != 0x8B) return DECLINED;
+    std::string err;
+    const double t0 = now_ms();
+    Text text[2]; Packed packed[2];
+    double ms_h2d = 0, ms_search = 0, ms_decode = 0, ms_resolve = 0;
+    uint64_t bgzf_blocks = 0;
+    for (int f = 0; f < nf; f++) {
+        GpuInflateStats st;
+        const int rc = gpu_inflate_member(gz[f], gn[f], h->pipe->device(), h->pipe->stream(), text[f], err, &st);
+        if (rc == 1) { h->pipe->times().add("gunzip_device_not_taken_x1", 1.0); return DECLINED; }
+        if (rc) return fail_rc(h, Rc::DeviceNoParam, rc, err);
+        ms_h2d += st.h2d_ms; ms_search += st.search_ms; ms_decode += st.decode_ms; ms_resolve += st.resolve_ms;
+        bgzf_blocks += st.blocks;
+    }
+    const double t1 = now_ms();
+    Span sp;
+    for (int f = 0; f < nf; f++) sp.total += text[f].e;
+    if (sp.total > kn.batch_bases) return DECLINED;      // (several batches: cut on the host)
+    uint64_t reads_done = 0;
+    for (int f = 0; f < nf; f++) {
+        const int rc = gpu_pack_fasta(nullptr, 0, nullptr, 0, h->k, h->progress_every(), h->pipe->stream(), packed[f], err, reads_done, &text[f]);
+        if (rc < 0) return fail_rc(h, Rc::Device, rc, err);
+        if (rc == 1) { h->pipe->times().add("fasta_device_declined_x1", 1.0); return DECLINED; }      // (inflated, but not packed: the host packer owns the message)
+        reads_done += packed[f].n_reads;
+        h->pipe->times().add("fasta_device_kernels", packed[f].kernels_ms);
+    }
+    // (marks only now that both files are packed: a decline over file 2 leaves none behind for the host route to post again)
+    for (int f = 0; f < nf; f++) {
+        post_device_progress(h, packed[f], sp);
+        sp.base += text[f].e;
+        text[f].reset();
+    }
+    h->pipe->times().add("gunzip_device_host_clock", t1 - t0);
+    h->pipe->times().add("gunzip_device_h2d", ms_h2d);
+    h->pipe->times().add("gunzip_device_search", ms_search);
+    h->pipe->times().add("gunzip_device_decode", ms_decode);
+    h->pipe->times().add("gunzip_device_windows_resolve_crc", ms_resolve);
+    h->pipe->times().add("gunzip_device_members_x1", (double)nf);
+    if (bgzf_blocks) h->pipe->times().add("gunzip_device_bgzf_blocks_x1", (double)bgzf_blocks);
+    h->pipe->times().add("fasta_device_parse_pack_host_clock", now_ms() - t1);
+    book.device += nf;
+    h->n_reads = reads_done;
+    std::vector<DevPiece> pcs;
+    for (int f = 0; f < nf; f++) if (packed[f].n_seg) pcs.push_back(DevPiece{packed[f].d_bases, packed[f].d_seg_off, packed[f].n_seg, packed[f].n_bases});
+    const int rc = count_pieces(h, pcs);
+    return rc ? rc : finish_counting(h);
+}
+
+// F4.  Pieces of at most batch_bases bytes that begin at a header line (the first one: at the start of its file).
+int fasta_batches(shk_handle *h, const Knobs &kn, const Input &in, bool device, FastaBook &book) {
+    std::string err;
+    const uint8_t *const text[2] = {in.t1, in.t2}; const size_t len[2] = {in.l1, in.l2};
+    struct Piece { int file; size_t off, end; };
+    std::vector<Piece> pieces;
+    const size_t room = (size_t)kn.batch_bases;
+    for (int f = 0; f < 2; f++)
+        for (size_t off = 0, end; text[f] && off < len[f]; off = end) {
+            end = len[f];
+            if (len[f] - off > room) {
+                // the last header line that begins inside (off, off + room]
+                const uint8_t *t = text[f];
+                size_t q = off + room + 1;                 // search t[off + 1 .. q) for a '>' behind a '\n'
+                end = 0;
+                while (q > off + 1) {
+                    const void *g = memrchr(t + off + 1, '>', q - (off + 1));
+                    if (!g) break;
+                    const size_t p = (size_t)((const uint8_t *)g - t);
+                    if (t[p - 1] == '\n') { end = p; break; }
+                    q = p;
+                }
+                if (!end) {
+                    const void *nx = memmem(t + off + 1, len[f] - off - 1, "\n>", 2);
+                    const size_t rec_end = nx ? (size_t)((const uint8_t *)nx - t) + 1 : len[f];
+                    return fail(h, SHK_E_PARAM, "preprocess_fasta: a single FASTA record of " + std::to_string(rec_end - off) +
+                                " bytes exceeds one batch (SHK_BATCH_BASES = " + std::to_string(kn.batch_bases) + "): a record is never split");
+                }
+            }
+            pieces.push_back(Piece{f, off, end});
+        }
+    h->pipe->expect_more_batches();
+    uint64_t reads_done = 0, file_reads = 0;
+    const double t0 = now_ms();
+    for (size_t i = 0; i < pieces.size(); i++) {
+        const Piece pc = pieces[i];
+        if (i == 0 || pieces[i - 1].file != pc.file) file_reads = 0;
+        const Span sp{(pc.file ? in.n1 : 0) + pc.off, in.total};
+        bool on_host = !device;
+        if (!on_host) {
+            Packed gp;
+            const int rc = gpu_pack_fasta(text[pc.file] + pc.off, pc.end - pc.off, nullptr, 0, h->k, h->progress_every(), h->pipe->stream(), gp, err, reads_done);
+            if (rc < 0) return fail_rc(h, Rc::Device, rc, err);
+            if (rc == 0) {
+                book.device += 1;
+                h->pipe->times().add("fasta_h2d_text", gp.h2d_ms);
+                h->pipe->times().add("fasta_device_kernels", gp.kernels_ms);
+                if (int rc2 = device_batch_in(h, gp, sp, reads_done, &file_reads)) return rc2;
+            } else on_host = true;                        // declined: the host packer owns the message
+        }
+        if (on_host) {
+            book.host += 1;
+            PackedReads pr;
+            pr.n_reads = reads_done;
+            if (int rc = fasta_host_parse(h, kn, text[pc.file] + pc.off, pc.end - pc.off, pr, sp, flush_every_reads(h), file_reads)) return rc;
+            if (int rc = flush_host_batch(h, pr)) return rc;
+            file_reads += pr.n_reads - reads_done;
+            reads_done = pr.n_reads;
+        }
+    }
+    h->pipe->times().add(device ? "fasta_device_parse_pack_host_clock" : "fasta_parse_pack_host_clock", now_ms() - t0);
+    h->n_reads = reads_done;
+    return finish_counting(h);
+}
+
+}  // namespace
+
+int preprocess_fasta_impl(shk_handle *h, const uint8_t *fa1, size_t n1, const uint8_t *fa2, size_t n2) {
+    if (!h) return SHK_E_PARAM;
+    if (h->st != St::Fresh) return fail(h, SHK_E_STATE, "preprocess_fasta: handle already used (one preprocess per handle)");
+    if (!fa1) return fail(h, SHK_E_PARAM, "preprocess_fasta: file1 is required");
+    h->post_start();
+    const Knobs kn;
+    Input in{fa1, fa2, n1, n2, n1 + (fa2 ? n2 : 0), now_ms()};
+    FastaBook book(h);
+    const bool device = !kn.host_parser;
+    int rc = DECLINED;
+    if (device && kn.gunzip_device) rc = fasta_device_gzip(h, kn, in, book);
+    if (rc != DECLINED) return rc;
+    std::string err;
+    const uint64_t mt0 = inflate_mt_members();
+    if (int ri = maybe_inflate_pair(fa1, n1, fa2, n2, in.st1, in.st2, in.t1, in.l1, in.t2, in.l2, err)) return fail_rc(h, Rc::Inflater, ri, err);
+    h->pipe->times().add("gunzip_host_clock", now_ms() - in.t0);
+    h->pipe->times().add("gunzip_mt_members_x1", (double)(inflate_mt_members() - mt0));
+    const bool on_device = device && in.text_total() >= kn.fasta_device_min;
+    if (in.text_total() > kn.batch_bases) return fasta_batches(h, kn, in, on_device, book);
+    const int nf = fa2 ? 2 : 1;
+    if (on_device) {
+        const double t0 = now_ms();
+        Packed gp;
+        rc = gpu_pack_fasta(in.t1, in.l1, in.t2, in.l2, h->k, h->progress_every(), h->pipe->stream(), gp, err);
+        if (rc < 0) return fail_rc(h, Rc::Device, rc, err);
+        if (rc == 0) {
+            book.device += nf;
+            h->pipe->times().add("fasta_device_parse_pack_host_clock", now_ms() - t0);
+            h->pipe->times().add("fasta_h2d_text", gp.h2d_ms);
+            h->pipe->times().add("fasta_device_kernels", gp.kernels_ms);
+            post_device_progress(h, gp, Span{0, in.total}, in.n1);
+            h->n_reads = gp.n_reads;
+            return run_counting(h, gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases);
+        }
+    }
+    book.host += nf;
+    PackedReads pr;
+    if (flush_every_reads(h)) h->pipe->expect_more_batches();
+    if (int rc2 = fasta_host_parse(h, kn, in.t1, in.l1, pr, Span{0, in.total}, flush_every_reads(h))) return rc2;
+    if (fa2) if (int rc2 = fasta_host_parse(h, kn, in.t2, in.l2, pr, Span{in.n1, in.total}, flush_every_reads(h))) return rc2;
+    h->n_reads = pr.n_reads;
+    h->pipe->times().add("fasta_parse_pack_host_clock", now_ms() - in.t0);
+    rc = flush_host_batch(h, pr);
+    return rc ? rc : finish_counting(h);
 }
 
 int push_reads_impl(shk_handle *h, const uint8_t *chunk, size_t n) {

@@ -5,6 +5,8 @@
 #include "fastq_gpu.h"
 
 int preprocess_impl(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2);
+// shk_preprocess_fasta: whole FASTA files, plain or gzip (SPEC S1a), by the device packer (fasta_gpu.h) or the host packer
+int preprocess_fasta_impl(shk_handle *h, const uint8_t *fa1, size_t n1, const uint8_t *fa2, size_t n2);
 int push_reads_impl(shk_handle *h, const uint8_t *chunk, size_t n);
 int finish_reads_impl(shk_handle *h);
 int preprocess_packed_device_impl(shk_handle *h, const void *d_bases, const void *d_seg_off, uint64_t n_seg,

@@ -83,6 +83,11 @@ class AssemblyHelper:
         b1, b2 = _as_bytes(file1), _as_bytes(file2)
         self._check(self._L.shk_preprocess(self._h, b1, len(b1), b2, len(b2) if b2 is not None else 0))
 
+    def preprocess_fasta(self, file1, file2=None):
+        """preprocess() for FASTA files (plain or gzip; SPEC S1a): a record per header line, no qualities"""
+        b1, b2 = _as_bytes(file1), _as_bytes(file2)
+        self._check(self._L.shk_preprocess_fasta(self._h, b1, len(b1), b2, len(b2) if b2 is not None else 0))
+
     def get_preprocessing_info(self):
         s = self._L.shk_get_preprocessing_info(self._h)
         if s is None:
@@ -162,6 +167,21 @@ def pack_fastq(data, k, min_qual):
     rc = L.shk_pack_fastq(data, len(data), k, min_qual, C.byref(out), C.byref(err))
     if rc != 0:
         raise ShkError(rc, (err.value or b"").decode())
+    return _packed_arrays(L, out)
+
+
+def pack_fasta(data, k):
+    """Host FASTA packer (SPEC S1a): returns (bases u32[], seg_off u32[], n_bases, n_reads)."""
+    L = _lib.load()
+    out = _lib.ShkPacked()
+    err = C.c_char_p()
+    rc = L.shk_pack_fasta(data, len(data), k, C.byref(out), C.byref(err))
+    if rc != 0:
+        raise ShkError(rc, (err.value or b"").decode())
+    return _packed_arrays(L, out)
+
+
+def _packed_arrays(L, out):
     try:
         nw = (out.n_bases >> 4) + 2
         bases = np.ctypeslib.as_array(out.bases, shape=(nw,)).copy()
