@@ -245,6 +245,43 @@ int shk_device_pack_fastq_slice(const uint8_t *fq1, size_t n1, const uint8_t *fq
  * shk_device_first_record_start (needs a GPU): the device kernel that finds the same. */
 uint64_t shk_host_first_record_start(const uint8_t *text, size_t n, uint64_t from);
 int shk_device_first_record_start(const uint8_t *text, size_t n, uint64_t from, uint64_t *at);
+/* The same call from FASTA FILES (SPEC S1a; shk_preprocess_fasta across ranks): the contract of shk_shard_preprocess_fastq —
+ * collective over c, split = 0 (the rank's own files, or none) and split = 1 (slice r of the same files), the routes
+ * (bgzf_slice, member_whole, text_slice, host), the SHK_E_STATE rules, one progress string
+ * preprocess:<mode>:loop:<records so far>:<pct> per batch (the last says 100), the failure agreement (the failing rank returns
+ * its own code and message, every other rank SHK_E_DEVICE "another rank failed during ...", nobody hangs); afterwards the handle
+ * is "preprocessed", the graph stays sharded by default and shk_assemble is collective.  min_qual is not used; n_reads counts
+ * records.
+ * The slice rule: a record starts at p when text[p] == '>' and p begins a line (p == 0 or text[p - 1] == '\n'; a lone '\r'
+ * ends no line).  s_0 = 0, s_world = the end of the text, otherwise s_r = the first record start at or after the nominal cut
+ * c_r (the end where there is none), c_r as for FASTQ: floor(r * n / world) in plain text and in the text of a plain gzip
+ * member, the block starts of shk_plan_fastq_slices in a BGZF chain.  Slices may be empty and records are never split; a
+ * non-blank line in front of a file's first header lies in slice 0 and is SHK_E_PARSE ("FASTA: ...", the host packer's
+ * message) there.  On the device the starts are found by a grid-wide search (csrc/inflate_gpu.hip: k_fasta_header_search).
+ * What differs from FASTQ: a byte of text is a base, so a share goes in batches when its TEXT exceeds SHK_BATCH_BASES, and
+ * every piece of text that becomes a batch is at most SHK_BATCH_BASES bytes, cut at the last header behind its first byte; a
+ * single record beyond one batch is SHK_E_PARAM ("a single FASTA record of ... bytes exceeds one batch ...") on the rank that
+ * meets it.  In a BGZF run a record beyond 16 MiB of carry, or a slice end not found within 16 MiB of follow-on blocks, sends
+ * that file's slice from that window on to the host reader.  The two files of a pair are packed separately (the rule on the
+ * lines in front of the first header holds for each file) and go to pass 1 as batches of their own.  Text that is inflated on
+ * the device is packed there; host-resident text goes to the device packer from SHK_FASTA_DEVICE_MIN bytes of slice on and
+ * to the host packer below it; SHK_HOST_PARSER=1 always takes the host packer, which also takes what the device packer
+ * declines and owns the messages (record numbers count from the start of the slice).
+ * Timings: shard_fasta_bgzf_slice_x1, shard_fasta_member_whole_x1, shard_fasta_text_slice_x1, shard_fasta_host_x1 (files by
+ * route), shard_fasta_uploaded_bytes, shard_fasta_batches_x1, shard_fasta_windows_x1, shard_fasta_read_host_clock. */
+int shk_shard_preprocess_fasta(shk_handle *h, shk_comm *c, const uint8_t *fa1, size_t n1, const uint8_t *fa2, size_t n2,
+                               uint32_t n_partitions, int split);
+/* The routes of split = 1 without a communicator (tests; needs a GPU), as shk_device_pack_fastq_slice: slice `rank` of
+ * `world` of the file(s) as ONE packed batch on the host, the two files' batches concatenated.  A share beyond one batch is
+ * SHK_E_PARAM. */
+int shk_device_pack_fasta_slice(const uint8_t *fa1, size_t n1, const uint8_t *fa2, size_t n2, uint32_t k, uint32_t rank,
+                                uint32_t world, struct shk_packed *out, uint64_t *uploaded_bytes, const char **route);
+/* host-only: the FASTA record starts — first: the smallest p >= from with text[p] == '>' that begins a line; last: the
+ * largest such p < n; UINT64_MAX: none.  shk_device_*_fasta_record_start (need a GPU): the device kernel that finds the same. */
+uint64_t shk_host_first_fasta_record_start(const uint8_t *text, size_t n, uint64_t from);
+uint64_t shk_host_last_fasta_record_start(const uint8_t *text, size_t n);
+int shk_device_first_fasta_record_start(const uint8_t *text, size_t n, uint64_t from, uint64_t *at);
+int shk_device_last_fasta_record_start(const uint8_t *text, size_t n, uint64_t *at);
 /* host-only: the runs of blocks the ranks take of a BGZF chain.  isize[n_blocks] as for shk_plan_bgzf_windows; run r is the
  * blocks first_block[r] ... first_block[r + 1] - 1 and starts at the first block whose text offset is >= r * text / world;
  * first_block[0] = 0, first_block[world] = n_blocks; more ranks than blocks gives empty runs.  Returns world, or SHK_E_PARAM. */

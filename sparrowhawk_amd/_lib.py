@@ -52,6 +52,12 @@ SIGNATURES = {
     "shk_shard_preprocess_batches": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u64, _u32]),
     "shk_shard_preprocess_fastq": (_int, [_vp, _vp, _cp, _sz, _cp, _sz, _u32, _int]),
     "shk_device_pack_fastq_slice": (_int, [_cp, _sz, _cp, _sz, _u32, _u32, _u32, _u32, C.POINTER(ShkPacked), C.POINTER(_u64), C.POINTER(_cp)]),
+    "shk_shard_preprocess_fasta": (_int, [_vp, _vp, _cp, _sz, _cp, _sz, _u32, _int]),
+    "shk_device_pack_fasta_slice": (_int, [_cp, _sz, _cp, _sz, _u32, _u32, _u32, C.POINTER(ShkPacked), C.POINTER(_u64), C.POINTER(_cp)]),
+    "shk_host_first_fasta_record_start": (_u64, [_cp, _sz, _u64]),
+    "shk_host_last_fasta_record_start": (_u64, [_cp, _sz]),
+    "shk_device_first_fasta_record_start": (_int, [_cp, _sz, _u64, C.POINTER(_u64)]),
+    "shk_device_last_fasta_record_start": (_int, [_cp, _sz, C.POINTER(_u64)]),
     "shk_host_first_record_start": (_u64, [_cp, _sz, _u64]),
     "shk_device_first_record_start": (_int, [_cp, _sz, _u64, C.POINTER(_u64)]),
     "shk_plan_fastq_slices": (C.c_int64, [_vp, _u64, _u32, _vp]),

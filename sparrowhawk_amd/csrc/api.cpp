@@ -727,10 +727,13 @@ static int shard_preprocess_batches_impl(shk_handle *h, shk_comm *cm, uint32_t n
 // only looked at in front of that agreement (read_fastq_share says in_batches before it uploads anything, where it can) and is
 // read inside pass 1, window by window (read_fastq_share_batches): its failures travel with the size exchange.
 static int shard_preprocess_fastq_impl(shk_handle *h, shk_comm *cm, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2,
-                                       uint32_t n_partitions, int split) {
-    if (!cm || !cm->c) return fail(h, SHK_E_PARAM, "shard_preprocess_fastq: null communicator");
-    if (h->st != St::Fresh) return fail(h, SHK_E_STATE, "shard_preprocess_fastq: handle already used");
-    if (comm_device(cm->c) != h->pipe->device()) return fail(h, SHK_E_PARAM, "shard_preprocess_fastq: communicator and handle live on different devices");
+                                       uint32_t n_partitions, int split, RecFmt fmt = RecFmt::Fastq) {
+    // (FASTA, shk_shard_preprocess_fasta: the same steps — the readers take the format; its names in the messages and the timings)
+    const bool fasta = fmt == RecFmt::Fasta;
+    const std::string entry = fasta ? "shard_preprocess_fasta" : "shard_preprocess_fastq", tag = fasta ? "shard_fasta_" : "shard_fastq_";
+    if (!cm || !cm->c) return fail(h, SHK_E_PARAM, entry + ": null communicator");
+    if (h->st != St::Fresh) return fail(h, SHK_E_STATE, entry + ": handle already used");
+    if (comm_device(cm->c) != h->pipe->device()) return fail(h, SHK_E_PARAM, entry + ": communicator and handle live on different devices");
     ShardComm *c = cm->c;
     void *st = h->pipe->stream();
     const double t0 = now_ms();
@@ -741,7 +744,7 @@ static int shard_preprocess_fastq_impl(shk_handle *h, shk_comm *cm, const uint8_
     // "I failed": it returns its own code and message, every other rank "another rank failed during reading".
     std::string err;
     const uint32_t s_rank = split ? (uint32_t)comm_rank(c) : 0u, s_world = split ? (uint32_t)comm_world(c) : 1u;
-    int rc_read = read_fastq_share(fq1, n1, fq2, n2, h->k, h->min_qual, s_rank, s_world, h->pipe->device(), st, sh, err, true);
+    int rc_read = read_fastq_share(fq1, n1, fq2, n2, h->k, h->min_qual, s_rank, s_world, h->pipe->device(), st, sh, err, true, fmt);
     if (rc_read) rc_read = fail(h, rc_read, err);
     const char *inject = getenv("SHK_FAULT_INJECT");      // (step `read`: see shard_preprocess_impl)
     if (!rc_read && inject && !strcmp(inject, "read")) rc_read = fail(h, SHK_E_INTERNAL, "injected fault (SHK_FAULT_INJECT=read)");
@@ -749,30 +752,47 @@ static int shard_preprocess_fastq_impl(shk_handle *h, shk_comm *cm, const uint8_
     std::string e2;
     if (int rc = comm_allreduce_host_u64(c, &failed, 1, st, e2)) return rc_read ? rc_read : fail_rc(h, Rc::Device, rc, e2);
     if (rc_read) return rc_read;
-    if (failed) return fail(h, SHK_E_DEVICE, "shard_preprocess_fastq: another rank failed during reading (this rank's handle is untouched; free it)");
-    auto book = [h, t0](const FastqShare &s, uint64_t batches, uint64_t windows) {
+    if (failed) return fail(h, SHK_E_DEVICE, entry + ": another rank failed during reading (this rank's handle is untouched; free it)");
+    auto book = [h, t0, tag](const FastqShare &s, uint64_t batches, uint64_t windows) {
         auto &t = h->pipe->times();
-        if (s.n_bgzf_slice) t.add("shard_fastq_bgzf_slice_x1", (double)s.n_bgzf_slice);
-        if (s.n_member_whole) t.add("shard_fastq_member_whole_x1", (double)s.n_member_whole);
-        if (s.n_text_slice) t.add("shard_fastq_text_slice_x1", (double)s.n_text_slice);
-        if (s.n_host) t.add("shard_fastq_host_x1", (double)s.n_host);
-        t.add("shard_fastq_uploaded_bytes", (double)s.uploaded_bytes);
-        t.add("shard_fastq_batches_x1", (double)batches);
-        t.add("shard_fastq_windows_x1", (double)windows);
-        t.add("shard_fastq_read_host_clock", now_ms() - t0);
+        if (s.n_bgzf_slice) t.add((tag + "bgzf_slice_x1").c_str(), (double)s.n_bgzf_slice);
+        if (s.n_member_whole) t.add((tag + "member_whole_x1").c_str(), (double)s.n_member_whole);
+        if (s.n_text_slice) t.add((tag + "text_slice_x1").c_str(), (double)s.n_text_slice);
+        if (s.n_host) t.add((tag + "host_x1").c_str(), (double)s.n_host);
+        t.add((tag + "uploaded_bytes").c_str(), (double)s.uploaded_bytes);
+        t.add((tag + "batches_x1").c_str(), (double)batches);
+        t.add((tag + "windows_x1").c_str(), (double)windows);
+        t.add((tag + "read_host_clock").c_str(), now_ms() - t0);
     };
+    if (!sh.in_batches && fasta) {
+        // the files of a pair were packed separately: one batch per file (ShardReads takes any number)
+        book(sh, sh.batches.size(), sh.batches.size());
+        ShardReads r;
+        for (const FastqShare::Batch &b : sh.batches) r.inst_ub += b.n_bases > b.n_seg * (uint64_t)(h->k - 1) ? b.n_bases - b.n_seg * (uint64_t)(h->k - 1) : 0;
+        r.n_reads = sh.n_reads;
+        r.feed = [&sh](ShardBatchSink &sink) -> int {
+            uint64_t reads = 0;
+            for (size_t i = 0; i < sh.batches.size(); i++) {
+                const FastqShare::Batch &b = sh.batches[i];
+                reads += b.n_reads;
+                if (int rc = sink.batch(b.n_seg ? b.d_bases : nullptr, b.n_seg ? b.d_seg_off : nullptr, b.n_seg, b.n_bases, reads, i + 1, sh.batches.size())) return rc;
+            }
+            return (int)SHK_OK;
+        };
+        return shard_preprocess_impl(h, cm, r, n_partitions);
+    }
     if (!sh.in_batches) {
         book(sh, 1, 1);
         return shard_preprocess_impl(h, cm, one_batch(h, sh.n_seg ? sh.d_bases : nullptr, sh.n_seg ? sh.d_seg_off : nullptr, sh.n_seg, sh.n_bases, sh.n_reads), n_partitions);
     }
     // several batches: reading and pass 1 take turns (shard_fastq_read_host_clock then holds both)
     ShardReads r;
-    r.inst_ub = sh.text_ub / 2;
+    r.inst_ub = fasta ? sh.text_ub : sh.text_ub / 2;
     const uint64_t uploaded_before = sh.uploaded_bytes;
     r.feed = [&](ShardBatchSink &sink) -> int {
         FastqShare got;
         std::string e3;
-        int rc = read_fastq_share_batches(fq1, n1, fq2, n2, h->k, h->min_qual, s_rank, s_world, h->pipe->device(), st, sink, got, e3);
+        int rc = read_fastq_share_batches(fq1, n1, fq2, n2, h->k, h->min_qual, s_rank, s_world, h->pipe->device(), st, sink, got, e3, fmt);
         if (rc && !e3.empty()) rc = fail(h, rc, e3);
         got.uploaded_bytes += uploaded_before;
         book(got, got.n_batches, got.n_windows);
@@ -833,6 +853,14 @@ int shk_shard_preprocess_fastq(shk_handle *h, shk_comm *c, const uint8_t *fq1, s
         return rc;
     });
 }
+int shk_shard_preprocess_fasta(shk_handle *h, shk_comm *c, const uint8_t *fa1, size_t n1, const uint8_t *fa2, size_t n2,
+                               uint32_t n_partitions, int split) {
+    return guarded(h, Poison::AfterFirstBatch, [&] {
+        const int rc = shard_preprocess_fastq_impl(h, c, fa1, n1, fa2, n2, n_partitions, split, RecFmt::Fasta);
+        if (rc != SHK_OK && c && c->c && comm_broken(c->c)) comm_abort_now(c->c);
+        return rc;
+    });
+}
 int shk_plan_exchange(const uint64_t *part_records_all, uint32_t world, uint32_t n_partitions, uint32_t rank,
                       uint64_t *base, uint64_t *send_counts, uint64_t *recv_counts, uint64_t *run_off, uint32_t *run_cnt) {
     try {
@@ -885,6 +913,26 @@ int shk_device_first_record_start(const uint8_t *text, size_t n, uint64_t from, 
         return rc ? code_of(Rc::DeviceNoParam, rc) : SHK_OK;
     } catch (...) { return SHK_E_OOM; }
 }
+uint64_t shk_host_first_fasta_record_start(const uint8_t *text, size_t n, uint64_t from) {
+    return (text || !n) ? fasta_first_record_start(text, n, (size_t)std::min<uint64_t>(from, n)) : UINT64_MAX;
+}
+uint64_t shk_host_last_fasta_record_start(const uint8_t *text, size_t n) { return (text || !n) ? fasta_last_record_start(text, n) : UINT64_MAX; }
+int shk_device_first_fasta_record_start(const uint8_t *text, size_t n, uint64_t from, uint64_t *at) {
+    try {
+        if ((!text && n) || !at) return SHK_E_PARAM;
+        std::string err;
+        const int rc = gpu_fasta_record_start(text, n, false, from, current_device(), *at, err);
+        return rc ? code_of(Rc::DeviceNoParam, rc) : SHK_OK;
+    } catch (...) { return SHK_E_OOM; }
+}
+int shk_device_last_fasta_record_start(const uint8_t *text, size_t n, uint64_t *at) {
+    try {
+        if ((!text && n) || !at) return SHK_E_PARAM;
+        std::string err;
+        const int rc = gpu_fasta_record_start(text, n, true, 0, current_device(), *at, err);
+        return rc ? code_of(Rc::DeviceNoParam, rc) : SHK_OK;
+    } catch (...) { return SHK_E_OOM; }
+}
 int64_t shk_plan_fastq_slices(const uint32_t *isize, uint64_t n_blocks, uint32_t world, uint64_t *first_block) {
     try {
         if ((!isize && n_blocks) || !first_block || !world) return SHK_E_PARAM;
@@ -919,6 +967,45 @@ int shk_device_pack_fastq_slice(const uint8_t *fq1, size_t n1, const uint8_t *fq
                 if (route) *route = msg.c_str();
                 return SHK_E_DEVICE;
             }
+        }
+        out->n_seg = sh.n_seg; out->n_bases = sh.n_bases; out->n_reads = sh.n_reads; out->n_input_bases = sh.n_input_bases;
+        route_s = sh.route;
+        if (route) *route = route_s.c_str();
+        return SHK_OK;
+    } catch (...) { return SHK_E_OOM; }
+}
+// its FASTA twin: the files of a pair are packed separately, their batches come back as one (file 1's segments, then file 2's)
+int shk_device_pack_fasta_slice(const uint8_t *fa1, size_t n1, const uint8_t *fa2, size_t n2, uint32_t k, uint32_t rank, uint32_t world,
+                                shk_packed *out, uint64_t *uploaded_bytes, const char **route) {
+    static thread_local std::string msg, route_s;
+    try {
+        if (!out) return SHK_E_PARAM;
+        *out = shk_packed();
+        if (route) *route = "";
+        if ((k & 1u) == 0 || k < SHK_K_MIN || k > SHK_K_MAX) { msg = "k must be odd and within [15, 255]"; if (route) *route = msg.c_str(); return SHK_E_PARAM; }
+        FastqShare sh;
+        const int rc = read_fastq_share(fa1, n1, fa2, n2, k, 0, rank, world, current_device(), nullptr, sh, msg, false, RecFmt::Fasta);
+        if (uploaded_bytes) *uploaded_bytes = sh.uploaded_bytes;
+        if (rc) { if (route) *route = msg.c_str(); return rc; }      // (on failure *route carries the message)
+        const size_t nw = (size_t)(sh.n_bases >> 4) + 2;
+        out->bases = (uint32_t *)calloc(nw, 4);
+        out->seg_off = (uint32_t *)calloc((size_t)sh.n_seg + 1, 4);
+        if (!out->bases || !out->seg_off) { shk_packed_free(out); return SHK_E_OOM; }
+        uint64_t base_at = 0, seg_at = 0;
+        for (const FastqShare::Batch &b : sh.batches) {
+            if (!b.n_seg) continue;
+            std::vector<uint32_t> bases((size_t)(b.n_bases >> 4) + 2), seg((size_t)b.n_seg + 1);
+            if (device_download(bases.data(), b.d_bases, bases.size() * 4, msg) || device_download(seg.data(), b.d_seg_off, seg.size() * 4, msg)) {
+                shk_packed_free(out);
+                if (route) *route = msg.c_str();
+                return SHK_E_DEVICE;
+            }
+            for (uint64_t i = 0; i < b.n_bases; i++) {           // (a test entry: base by base behind what file 1 gave)
+                const uint32_t code = (bases[(size_t)(i >> 4)] >> (2 * (i & 15))) & 3u;
+                out->bases[(size_t)((base_at + i) >> 4)] |= code << (2 * ((base_at + i) & 15));
+            }
+            for (uint64_t j = 1; j <= b.n_seg; j++) out->seg_off[(size_t)(seg_at + j)] = (uint32_t)(base_at + seg[(size_t)j]);
+            base_at += b.n_bases; seg_at += b.n_seg;
         }
         out->n_seg = sh.n_seg; out->n_bases = sh.n_bases; out->n_reads = sh.n_reads; out->n_input_bases = sh.n_input_bases;
         route_s = sh.route;

@@ -204,6 +204,38 @@ void fastq_slice_bounds(const uint8_t *t, size_t e, uint32_t rank, uint32_t worl
     s0 = bound(rank, cut0); s1 = bound(rank + 1, cut1);
 }
 
+uint64_t fasta_first_record_start(const uint8_t *t, size_t n, size_t from) {
+    for (size_t p = from; p < n;) {
+        const void *g = memchr(t + p, '>', n - p);
+        if (!g) break;
+        p = (size_t)((const uint8_t *)g - t);
+        if (p == 0 || t[p - 1] == '\n') return p;
+        p++;
+    }
+    return UINT64_MAX;
+}
+
+uint64_t fasta_last_record_start(const uint8_t *t, size_t n) {
+    for (size_t q = n; q;) {
+        const void *g = memrchr(t, '>', q);
+        if (!g) break;
+        const size_t p = (size_t)((const uint8_t *)g - t);
+        if (p == 0 || t[p - 1] == '\n') return p;
+        q = p;
+    }
+    return UINT64_MAX;
+}
+
+void fasta_slice_bounds(const uint8_t *t, size_t e, uint32_t rank, uint32_t world, uint64_t cut0, uint64_t cut1, uint64_t &s0, uint64_t &s1) {
+    auto bound = [&](uint32_t r, uint64_t cut) -> uint64_t {
+        if (r == 0) return 0;
+        if (r >= world) return e;
+        const uint64_t p = fasta_first_record_start(t, e, (size_t)std::min<uint64_t>(cut, e));
+        return p == UINT64_MAX ? e : p;
+    };
+    s0 = bound(rank, cut0); s1 = bound(rank + 1, cut1);
+}
+
 static int inflate_bgzf(const uint8_t *in, size_t n, ByteVec &out, std::string &err, bool &is_bgzf) {
     struct Blk { size_t in_off, in_len, out_off, out_len, hdr; };
     std::vector<Blk> blocks;

@@ -68,6 +68,15 @@ uint64_t first_record_start(const uint8_t *t, size_t n, size_t from);
 // c_(rank + 1) — floor(r * e / world) for plain text and the text of a plain gzip member (slice_cut), for a BGZF chain the
 // text offset at which block first_block[r] of plan_fastq_slices begins.
 void fastq_slice_bounds(const uint8_t *t, size_t e, uint32_t rank, uint32_t world, uint64_t cut0, uint64_t cut1, uint64_t &s0, uint64_t &s1);
+// FASTA (RecFmt::Fasta, share_windows.h; SPEC S1a): a record starts at p when t[p] == '>' and p begins a line (p == 0 or t[p - 1] == '\n'; a lone '\r' ends
+// no line).  A line is decided by its own first byte, so a partial view leaves nothing open but whether its first byte begins
+// a line.  first: the smallest such p >= from; last: the largest such p < n; UINT64_MAX: none.  The device states the same rule
+// in k_fasta_header_search (inflate_gpu.hip).
+uint64_t fasta_first_record_start(const uint8_t *t, size_t n, size_t from);
+uint64_t fasta_last_record_start(const uint8_t *t, size_t n);
+// the twin of fastq_slice_bounds: s_0 = 0, s_world = e, in between s_r = the first FASTA record start at or after c_r (e where
+// there is none).  Slices may be empty; a non-blank line in front of the file's first header lies in slice 0.
+void fasta_slice_bounds(const uint8_t *t, size_t e, uint32_t rank, uint32_t world, uint64_t cut0, uint64_t cut1, uint64_t &s0, uint64_t &s1);
 // gzip sniff (1F 8B) + multi-member inflate; plain input is passed through (p/n point at buf or at `storage`)
 int maybe_inflate(const uint8_t *buf, size_t n, ByteVec &storage, const uint8_t *&p, size_t &pn,
                   std::string &err);

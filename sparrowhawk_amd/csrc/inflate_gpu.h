@@ -13,6 +13,7 @@
 #include <vector>
 #include "device_mem.h"
 #include "fastq_gpu.h"
+#include "share_windows.h"
 
 namespace shk {
 
@@ -96,8 +97,8 @@ class BgzfWindows {
     // text(w)[0..n).  carry_on: text(w)[cut..n) to the front of text(w + 1), 32 zero bytes behind the cut.
     // Each 0; 1 (*why) where step() returns 1; -5.
     int inflate(size_t w, bool prefetch_next, uint64_t carry, uint64_t &n, const char *&why, std::string &err);
-    int first_start(size_t w, uint64_t n, uint64_t from, uint64_t &at, std::string &err);
-    int last_start(size_t w, uint64_t n, uint64_t &at, std::string &err);
+    int first_start(size_t w, uint64_t n, uint64_t from, uint64_t &at, std::string &err, RecFmt fmt = RecFmt::Fastq);
+    int last_start(size_t w, uint64_t n, uint64_t &at, std::string &err, RecFmt fmt = RecFmt::Fastq);
     int trim_end(size_t w, uint64_t n, uint64_t &e, bool &unterminated, const char *&why, std::string &err);
     int carry_on(size_t w, uint64_t n, uint64_t cut, std::string &err);
     void *stream() const { return st_; }
@@ -130,7 +131,7 @@ class BgzfShareWindows {
     BgzfShareWindows(const BgzfShareWindows &) = delete;
     BgzfShareWindows &operator=(const BgzfShareWindows &) = delete;
     int open(const uint8_t *gz, const BgzfChain &chain, uint32_t rank, uint32_t world, uint64_t budget, int device, void *stream,
-             const char *&why, std::string &err);
+             const char *&why, std::string &err, RecFmt fmt = RecFmt::Fastq);
     int next(GpuText &piece, uint64_t &at, bool &done, const char *&why, std::string &err);
     void close();
     uint64_t run_text() const { return c1_ - c0_; }        // bytes of text of the rank's run (the sum of its ISIZE fields)
@@ -146,6 +147,7 @@ class BgzfShareWindows {
     PoolBlock first_;                                      // a piece that does not begin where its window's buffer begins
     size_t B_ = 0, n_own_ = 0, w_ = 0;
     uint32_t rank_ = 0;
+    RecFmt fmt_ = RecFmt::Fastq;                           // the format its windows and its slice are cut by
     uint64_t c0_ = 0, c1_ = 0, carry_ = 0, consumed_ = 0, windows_ = 0;
     bool started_ = false, done_ = false;
 };
@@ -155,9 +157,15 @@ int gpu_last_record_start(const uint8_t *t, size_t n, int device, uint64_t &at, 
 // its forward twin, k_first_record_start, alone (the tests compare it with first_record_start); at = UINT64_MAX: none / undecided
 int gpu_first_record_start(const uint8_t *t, size_t n, uint64_t from, int device, uint64_t &at, std::string &err);
 
-// ---- one rank's slice of a file, for the sharded FASTQ entry point (preprocess.cpp: read_fastq_share) --------------------
-// The slice rule is stated in fastq.h (first_record_start, fastq_slice_bounds, plan_fastq_slices); here it is applied to text
-// that is born on the device.  A span is a run of text inside a device block it owns.
+// k_fasta_header_search alone on n bytes of host text (the tests compare it with fasta_first_record_start / fasta_last_record_start;
+// last: `from` is not used)
+int gpu_fasta_record_start(const uint8_t *t, size_t n, bool last, uint64_t from, int device, uint64_t &at, std::string &err);
+
+// ---- one rank's slice of a file, for the sharded FASTQ and FASTA entry points (preprocess.cpp: read_fastq_share) ---------
+// The slice rule is stated in fastq.h (first_record_start, fastq_slice_bounds, plan_fastq_slices; FASTA: fasta_first_record_start,
+// fasta_slice_bounds); here it is applied to text that is born on the device.  fmt: the record format the cuts go by (FASTQ where
+// nothing is said: k_first_record_start / k_last_record_start; FASTA: k_fasta_header_search).  A span is a run of text inside a
+// device block it owns.
 struct DevSpan { PoolBlock blk; uint64_t off = 0, len = 0; bool unterminated = false; };
 // A walked BGZF chain: rank r uploads and inflates the blocks of run r only (plan_fastq_slices), the non-empty block in front
 // of the run (whether the run's first byte begins a line is written there) and the follow-on blocks of run r + 1 in which its
@@ -166,15 +174,17 @@ struct DevSpan { PoolBlock blk; uint64_t off = 0, len = 0; bool unterminated = f
 // 0: out is the slice (possibly empty); 1: declined (*why: a damaged block, no boundary within reach, out of device memory) —
 // the caller reads the file on the host and cuts the same slice there; -5.
 int gpu_bgzf_slice(const uint8_t *gz, const BgzfChain &chain, uint32_t rank, uint32_t world, int device, void *stream, DevSpan &out,
-                   uint64_t &uploaded, const char *&why, std::string &err);
+                   uint64_t &uploaded, const char *&why, std::string &err, RecFmt fmt = RecFmt::Fastq);
 // A whole text on the device (a plain gzip member inflated by gpu_inflate_member; nominal cuts floor(r * e / world)): its
 // block becomes the span's.  0; -4; -5.
-int gpu_text_slice(GpuText &text, uint32_t rank, uint32_t world, void *stream, DevSpan &out, std::string &err);
+int gpu_text_slice(GpuText &text, uint32_t rank, uint32_t world, void *stream, DevSpan &out, std::string &err, RecFmt fmt = RecFmt::Fastq);
 // A piece of a span for the parser, where the span is more than one batch takes: span text [from, from + want) cut back to
 // its last record start — or all that is left, where that is no more than `want` — copied into a text of its own (16-byte
 // aligned, 32 zero bytes behind).  next: where the following piece begins (span.len: this was the last; out.e == 0: nothing was
-// left).  0; 1: no record starts inside the piece (not regular FASTQ: the host parser's); -4; -5.
-int gpu_span_piece(const DevSpan &span, uint64_t from, uint64_t want, void *stream, GpuText &out, uint64_t &next, std::string &err);
+// left).  0; 1: no record starts inside the piece (not regular FASTQ: the host parser's; FASTA: one record beyond `want`, which
+// ends at span offset `next`); -4; -5.
+int gpu_span_piece(const DevSpan &span, uint64_t from, uint64_t want, void *stream, GpuText &out, uint64_t &next, std::string &err,
+                   RecFmt fmt = RecFmt::Fastq);
 // The spans back to back in one text as the parser wants it (16-byte aligned start, 32 zero bytes behind, a newline between
 // two files where the first ends without one).  0; -4; -5.
 int gpu_join_spans(const DevSpan *spans, int n_spans, void *stream, GpuText &out, std::string &err);

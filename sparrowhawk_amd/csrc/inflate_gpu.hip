@@ -29,6 +29,8 @@
 //   k_bgzf_crc         CRC-32 of every block's text against its trailer; one word comes back, not a checksum per block
 //   k_last_record_start  a BGZF file window by window (BgzfWindows): where the last whole FASTQ record of a window's text ends —
 //                      one wave walks the text's tail from the back, a ballot over the newlines of 64 bytes per step
+//   k_fasta_header_search  the FASTA twin of the two record-start kernels (RecFmt::Fasta): a grid over the text, 16 bytes a lane,
+//                      because a FASTA record is a contig or a chromosome and the search may cross megabytes
 // Everything that does not look as expected makes gpu_inflate_member return 1 and the caller inflates on the host: the
 // bytes handed on are always the bytes zlib would produce (CRC-32 and ISIZE of the trailer are checked here too).
 #include <hip/hip_runtime.h>
@@ -787,6 +789,57 @@ __global__ __launch_bounds__(64) void k_first_record_start(const uint8_t *__rest
     if (lane == 0) out[0] = found;
 }
 
+// The FASTA rule — fasta_first_record_start / fasta_last_record_start (fastq.cpp), which this kernel must agree with byte for
+// byte: a record starts at p where text[p] == '>' and p begins a line (p == 0 or text[p - 1] == '\n').  A record is a contig
+// or a chromosome, so the search may cross megabytes: it is byte-parallel, a grid over text[lo, hi) with 16 bytes per lane.
+// The groups of 16 lie at 16-byte aligned ADDRESSES (a span need not begin at one): a group that lies inside [lo, hi) whole is
+// one vector load, the head and the tail groups are read byte by byte and never outside [lo, hi).  The byte in front of a
+// lane's first byte is one extra load (text[lo - 1] is read where lo > 0: it belongs to the text).  Lanes lie in text order,
+// so the first lane of a wave's ballot holds the wave's first start and the last lane its last: one 64-bit atomic per wave
+// that found a start.  LAST false: out[0] = min(out[0], p), the host sets ~0 (none).  LAST true: out[0] = max(out[0], p + 1),
+// the host sets 0 (none).  hi <= n.
+template <bool LAST>
+__global__ __launch_bounds__(256) void k_fasta_header_search(const uint8_t *__restrict__ text, unsigned long long lo, unsigned long long hi,
+                                                             unsigned long long *__restrict__ out) {
+    const unsigned long long head = (unsigned long long)((uintptr_t)(text + lo) & 15u);      // bytes of the first group in front of lo
+    const unsigned long long g = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+    // the group [i0, i0 + 16) in text offsets, i0 + head counted from lo so that nothing goes below zero
+    const unsigned long long rel = g * 16ull;                 // the group begins rel - head bytes behind lo
+    const unsigned long long s = rel > head ? lo + (rel - head) : lo;
+    unsigned long long e = lo + (rel + 16ull - head);
+    if (e > hi) e = hi;
+    uint32_t hdr = 0;                                         // bit j: a record starts at s0 + j, s0 = the group's first byte
+    if (s < e) {
+        const unsigned shift = rel > head ? 0u : (unsigned)(head - rel);      // the bit of byte s (the head group alone begins in front of it)
+        uint32_t gt = 0, nl = 0;
+        if (e - s == 16ull) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(text + s);
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                const uint32_t c = (w[j >> 2] >> (8 * (j & 3))) & 0xFFu;
+                gt |= (uint32_t)(c == '>') << j; nl |= (uint32_t)(c == '\n') << j;
+            }
+        } else {
+            for (unsigned long long p = s; p < e; p++) {
+                const uint32_t c = text[p], j = shift + (uint32_t)(p - s);
+                gt |= (uint32_t)(c == '>') << j; nl |= (uint32_t)(c == '\n') << j;
+            }
+        }
+        const uint32_t before = (s == 0 || text[s - 1] == '\n') ? 1u << shift : 0u;
+        hdr = gt & ((nl << 1) | before);
+    }
+    const unsigned long long found = __ballot(hdr != 0);
+    if (!found) return;
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned shift = rel > head ? 0u : (unsigned)(head - rel);
+    if (!LAST) {
+        if (lane == (unsigned)(__ffsll((long long)found) - 1)) atomicMin(out, s - shift + (unsigned)(__ffs((int)hdr) - 1));
+    } else {
+        if (lane == 63u - (unsigned)__clzll((long long)found)) atomicMax(out, s - shift + (31u - (unsigned)__clz((int)hdr)) + 1ull);
+    }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 // CRC-32 of A || B from crc(A), crc(B): crc(A) advanced over len(B) zero bytes (a GF(2) matrix), XOR crc(B).  The slices
 // have one length, so the matrix is built once (zlib 1.2.11 has no crc32_combine_gen).
@@ -1160,8 +1213,37 @@ const size_t WIN_IN_PAD = (2048 + 256) * 4 + 8;           // zero bytes behind a
 
 // the last record start of d_text[0..n): the tail of 1 MiB first, a wider one while nothing is found — up to max_tail bytes
 // (one wave walks it: the windows' caller has no use for a start further front than it can carry)
-int device_last_start(const uint8_t *d_text, uint64_t n, unsigned long long *d_out, hipStream_t st, uint64_t &at, std::string &err, uint64_t max_tail = UINT64_MAX) {
+// k_fasta_header_search over d_text[lo, hi): the result word is set here.  got: the start, or UINT64_MAX
+template <bool LAST>
+int fasta_header_search(const uint8_t *d_text, uint64_t lo, uint64_t hi, unsigned long long *d_out, hipStream_t st, uint64_t &got, std::string &err) {
+    got = UINT64_MAX;
+    if (lo >= hi) return 0;
+    const uint64_t groups = (hi - lo + 15 + 15) / 16;        // (an unaligned head adds at most one group)
+    if (groups > 256ull * 0x7FFFFFFFull) { err = "a FASTA header search beyond the grid"; return -5; }
+    GZCHK(hipMemsetAsync(d_out, LAST ? 0 : 0xFF, 8, st));
+    hipLaunchKernelGGL(k_fasta_header_search<LAST>, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, d_text, (unsigned long long)lo, (unsigned long long)hi, d_out);
+    GZCHK(hipGetLastError());
+    unsigned long long w = 0;
+    GZCHK(hipMemcpyAsync(&w, d_out, 8, hipMemcpyDeviceToHost, st));
+    GZCHK(hipStreamSynchronize(st));
+    if (LAST) { if (w) got = w - 1; }
+    else if (w != ~0ull) got = w;
+    return 0;
+}
+
+int device_last_start(const uint8_t *d_text, uint64_t n, unsigned long long *d_out, hipStream_t st, uint64_t &at, std::string &err, uint64_t max_tail = UINT64_MAX,
+                      RecFmt fmt = RecFmt::Fastq) {
     at = UINT64_MAX;
+    if (fmt == RecFmt::Fasta) {
+        // the same tails; a line is decided by its own first byte, so what a tail has shown to hold no start is not searched again
+        uint64_t hi = n;
+        for (uint64_t tail = std::min<uint64_t>(1ull << 20, max_tail);; tail = tail > max_tail / 16 ? max_tail : tail * 16) {
+            const uint64_t from = n > tail ? n - tail : 0;
+            if (const int rc = fasta_header_search<true>(d_text, from, hi, d_out, st, at, err)) return rc;
+            if (at != UINT64_MAX || from == 0 || tail >= max_tail) return 0;
+            hi = from;
+        }
+    }
     for (uint64_t tail = std::min<uint64_t>(1ull << 20, max_tail);; tail = tail > max_tail / 16 ? max_tail : tail * 16) {
         const uint64_t from = n > tail ? n - tail : 0;
         hipLaunchKernelGGL(k_last_record_start, dim3(1), dim3(64), 0, st, d_text, (unsigned long long)n, (unsigned long long)from, d_out);
@@ -1176,9 +1258,20 @@ int device_last_start(const uint8_t *d_text, uint64_t n, unsigned long long *d_o
 
 // the first record start of d_text[0..n) at or after `from`: 1 MiB behind `from` first, a wider reach while nothing is
 // decided.  at = UINT64_MAX: undecided at the end of the text
-int device_first_start(const uint8_t *d_text, uint64_t n, uint64_t from, unsigned long long *d_out, hipStream_t st, uint64_t &at, std::string &err) {
+int device_first_start(const uint8_t *d_text, uint64_t n, uint64_t from, unsigned long long *d_out, hipStream_t st, uint64_t &at, std::string &err,
+                       RecFmt fmt = RecFmt::Fastq) {
     at = UINT64_MAX;
     if (from >= n) return 0;
+    if (fmt == RecFmt::Fasta) {
+        // the same reaches (a start near `from` stays cheap); each one begins where the one before it ended.  UINT64_MAX: none
+        uint64_t lo = from;
+        for (uint64_t reach = 1ull << 20;; reach *= 16) {
+            const uint64_t limit = n - from > reach ? from + reach : n;
+            if (const int rc = fasta_header_search<false>(d_text, lo, limit, d_out, st, at, err)) return rc;
+            if (at != UINT64_MAX || limit == n) return 0;
+            lo = limit;
+        }
+    }
     for (uint64_t reach = 1ull << 20;; reach *= 16) {
         const uint64_t limit = n - from > reach ? from + reach : n;
         hipLaunchKernelGGL(k_first_record_start, dim3(1), dim3(64), 0, st, d_text, (unsigned long long)n, (unsigned long long)from, (unsigned long long)limit, d_out);
@@ -1271,13 +1364,13 @@ int BgzfWindows::trim_end(size_t w, uint64_t n, uint64_t &e, bool &unterminated,
     return trim_text_end(text(w), n, tail, false, st, e, unterminated, why, err);
 }
 
-int BgzfWindows::last_start(size_t w, uint64_t n, uint64_t &at, std::string &err) {
+int BgzfWindows::last_start(size_t w, uint64_t n, uint64_t &at, std::string &err, RecFmt fmt) {
     // the last record start in reach: a start further front leaves more to carry than there is room for
-    return device_last_start(text(w), n, (unsigned long long *)d_bad_.p + 4, (hipStream_t)st_, at, err, CARRY_MAX + 64);
+    return device_last_start(text(w), n, (unsigned long long *)d_bad_.p + 4, (hipStream_t)st_, at, err, CARRY_MAX + 64, fmt);
 }
 
-int BgzfWindows::first_start(size_t w, uint64_t n, uint64_t from, uint64_t &at, std::string &err) {
-    return device_first_start(text(w), n, from, (unsigned long long *)d_bad_.p + 4, (hipStream_t)st_, at, err);
+int BgzfWindows::first_start(size_t w, uint64_t n, uint64_t from, uint64_t &at, std::string &err, RecFmt fmt) {
+    return device_first_start(text(w), n, from, (unsigned long long *)d_bad_.p + 4, (hipStream_t)st_, at, err, fmt);
 }
 
 int BgzfWindows::carry_on(size_t w, uint64_t n, uint64_t cut, std::string &err) {
@@ -1313,8 +1406,9 @@ int BgzfWindows::step(size_t w, bool raw, uint64_t &carry, uint64_t &cut, bool &
 
 // ---- one rank's run of a walked chain, window by window (inflate_gpu.h) ---------------------------------------------------
 int BgzfShareWindows::open(const uint8_t *gz, const BgzfChain &chain, uint32_t rank, uint32_t world, uint64_t budget, int device, void *stream,
-                           const char *&why, std::string &err) {
+                           const char *&why, std::string &err, RecFmt fmt) {
     close();
+    fmt_ = fmt;
     rank_ = rank; B_ = chain.blocks.size();
     if (rank >= world) { err = "rank beyond world"; return -1; }
     std::vector<uint32_t> isize(B_);
@@ -1387,7 +1481,7 @@ int BgzfShareWindows::next(GpuText &piece, uint64_t &at_out, bool &done, const c
         if (!started_) {                                    // s_rank: the first record start at or after the run's first byte
             if (rank_ > 0) {
                 uint64_t at = NONE;
-                if (const int rc = bw_.first_start(w, lim, c0_ - base, at, err)) return rc;
+                if (const int rc = bw_.first_start(w, lim, c0_ - base, at, err, fmt_)) return rc;
                 if (at == NONE) {
                     if (last_in_list && at_end) { done_ = done = true; return 0; }      // (no record begins in the run or behind it)
                     if (last_in_list) { why = "no record start within reach"; return 1; }
@@ -1401,7 +1495,7 @@ int BgzfShareWindows::next(GpuText &piece, uint64_t &at_out, bool &done, const c
         uint64_t hi = lim; bool fin = true, unt = unterm;
         if (is_tail) {                                      // s_(rank + 1): the first record start at or after the next run's first byte
             uint64_t at = NONE;
-            if (const int rc = bw_.first_start(w, lim, std::max(c1_ - base, lo), at, err)) return rc;
+            if (const int rc = bw_.first_start(w, lim, std::max(c1_ - base, lo), at, err, fmt_)) return rc;
             if (at == NONE && !(last_in_list && at_end)) {
                 if (last_in_list) { why = "no record start within reach behind the run"; return 1; }
                 if (const int rc = carry_all(lo, "no record start within reach behind the run")) return rc;
@@ -1411,7 +1505,7 @@ int BgzfShareWindows::next(GpuText &piece, uint64_t &at_out, bool &done, const c
             if (at != NONE) { hi = at; unt = false; }
         } else if (!last_in_list) {                         // a window of the run with more behind it: cut at its last record start
             uint64_t cut = NONE;
-            if (const int rc = bw_.last_start(w, n, cut, err)) return rc;
+            if (const int rc = bw_.last_start(w, n, cut, err, fmt_)) return rc;
             if (cut == NONE || cut < lo) cut = lo;
             if (const int rc = carry_all(cut, "a partial record beyond the room for it")) return rc;
             hi = cut; fin = false; unt = false;
@@ -1458,9 +1552,24 @@ int gpu_first_record_start(const uint8_t *t, size_t n, uint64_t from, int device
     return rc;
 }
 
+// (the text lies n % 16 bytes behind a 16-byte boundary: texts of every length mod 16 so meet every alignment of the kernel's
+// head and tail groups)
+int gpu_fasta_record_start(const uint8_t *t, size_t n, bool last, uint64_t from, int device, uint64_t &at, std::string &err) {
+    hipStream_t st = nullptr;
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); err = "hipSetDevice failed"; return -5; }
+    PoolBlock d_text, d_out;
+    if (!d_text.get(n + 64) || !d_out.get(64)) { err = "out of device memory"; return -4; }
+    uint8_t *d = (uint8_t *)d_text.p + (n & 15);
+    if (n) GZCHK(hipMemcpyAsync(d, t, n, hipMemcpyHostToDevice, st));
+    const int rc = last ? device_last_start(d, n, (unsigned long long *)d_out.p, st, at, err, UINT64_MAX, RecFmt::Fasta)
+                        : device_first_start(d, n, from, (unsigned long long *)d_out.p, st, at, err, RecFmt::Fasta);
+    (void)hipStreamSynchronize(st);
+    return rc;
+}
+
 // ---- slices for the sharded FASTQ entry point (inflate_gpu.h) -----------------------------------------------------------
 int gpu_bgzf_slice(const uint8_t *gz, const BgzfChain &chain, uint32_t rank, uint32_t world, int device, void *stream, DevSpan &out,
-                   uint64_t &uploaded, const char *&why, std::string &err) {
+                   uint64_t &uploaded, const char *&why, std::string &err, RecFmt fmt) {
     hipStream_t st = (hipStream_t)stream;
     out.blk.put(); out.off = out.len = 0; out.unterminated = false;
     uploaded = 0;
@@ -1514,7 +1623,7 @@ int gpu_bgzf_slice(const uint8_t *gz, const BgzfChain &chain, uint32_t rank, uin
             if (i == 0 ? rank == 0 : last_rank) continue;
             const uint64_t from = i == 0 ? lead : lead + own;
             uint64_t at = UINT64_MAX;
-            if (const int rc = device_first_start((const uint8_t *)d_text.p, e, from, (unsigned long long *)d_bad.p + 8, st, at, err)) return rc;
+            if (const int rc = device_first_start((const uint8_t *)d_text.p, e, from, (unsigned long long *)d_bad.p + 8, st, at, err, fmt)) return rc;
             if (at == UINT64_MAX && !at_end) { widen = true; break; }
             s[i] = at == UINT64_MAX ? e : at;
         }
@@ -1533,7 +1642,7 @@ int gpu_bgzf_slice(const uint8_t *gz, const BgzfChain &chain, uint32_t rank, uin
     }
 }
 
-int gpu_text_slice(GpuText &text, uint32_t rank, uint32_t world, void *stream, DevSpan &out, std::string &err) {
+int gpu_text_slice(GpuText &text, uint32_t rank, uint32_t world, void *stream, DevSpan &out, std::string &err, RecFmt fmt) {
     hipStream_t st = (hipStream_t)stream;
     out.blk.put(); out.off = out.len = 0; out.unterminated = false;
     if (rank >= world) { err = "rank beyond world"; return -1; }
@@ -1545,7 +1654,7 @@ int gpu_text_slice(GpuText &text, uint32_t rank, uint32_t world, void *stream, D
         const uint32_t r = rank + (uint32_t)i;
         if (r == 0 || r == world) continue;
         uint64_t at = UINT64_MAX;
-        if (const int rc = device_first_start(text.d, e, slice_cut(e, r, world), (unsigned long long *)d_out.p, st, at, err)) return rc;
+        if (const int rc = device_first_start(text.d, e, slice_cut(e, r, world), (unsigned long long *)d_out.p, st, at, err, fmt)) return rc;
         s[i] = at == UINT64_MAX ? e : at;
     }
     out.off = s[0]; out.len = s[1] - s[0];
@@ -1555,7 +1664,7 @@ int gpu_text_slice(GpuText &text, uint32_t rank, uint32_t world, void *stream, D
     return 0;
 }
 
-int gpu_span_piece(const DevSpan &span, uint64_t from, uint64_t want, void *stream, GpuText &out, uint64_t &next, std::string &err) {
+int gpu_span_piece(const DevSpan &span, uint64_t from, uint64_t want, void *stream, GpuText &out, uint64_t &next, std::string &err, RecFmt fmt) {
     hipStream_t st = (hipStream_t)stream;
     out = GpuText();
     next = span.len;
@@ -1565,8 +1674,14 @@ int gpu_span_piece(const DevSpan &span, uint64_t from, uint64_t want, void *stre
         if (!d_out.get(64)) { err = "out of device memory"; return -4; }
         uint64_t at = UINT64_MAX;
         // (the search stays inside the piece: it never looks further front than `want` bytes)
-        if (const int rc = device_last_start((const uint8_t *)span.blk.p, span.off + from + want, (unsigned long long *)d_out.p, st, at, err, want)) return rc;
-        if (at == UINT64_MAX || at <= span.off + from) return 1;
+        if (const int rc = device_last_start((const uint8_t *)span.blk.p, span.off + from + want, (unsigned long long *)d_out.p, st, at, err, want, fmt)) return rc;
+        if (at == UINT64_MAX || at <= span.off + from) {
+            if (fmt == RecFmt::Fasta) {                     // one record beyond `want`: next = where it ends, for the caller's message
+                if (const int rc = device_first_start((const uint8_t *)span.blk.p, span.off + span.len, span.off + from + 1, (unsigned long long *)d_out.p, st, at, err, fmt)) return rc;
+                next = at == UINT64_MAX ? span.len : at - span.off;
+            }
+            return 1;
+        }
         next = at - span.off;
     }
     const uint64_t len = next - from;

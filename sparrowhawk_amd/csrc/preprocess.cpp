@@ -23,6 +23,8 @@
 //                                host reader and the host parser for what the device declines (preprocess.h)
 //   9 read_fastq_share_batches   the same slices where they exceed one batch: window by window (a BGZF run) or piece by piece
 //                                into pass 1 of the shard layer, one batch each
+//     (8 and 9 take a record format, ShareFormat below: with RecFmt::Fasta they are shk_shard_preprocess_fasta — slices, windows
+//      and pieces cut at header lines, the FASTA packers, a byte of text a base, the files of a pair packed separately)
 // The device parser (fastq_gpu.hip) takes regular 4-line FASTQ only; irregular framing and every malformed record go to
 // the host parser (fastq.cpp), which owns the error messages.
 #include "preprocess.h"
@@ -860,6 +862,8 @@ int preprocess_packed_host_impl(shk_handle *h, const uint32_t *bases, const uint
 FastqShare::~FastqShare() {
     gpu_packed_free(gp);
     device_free(up_bases); device_free(up_seg_off);
+    for (shk::GpuPacked &g : held_gp) gpu_packed_free(g);
+    for (void *p : held_up) device_free(p);
 }
 
 namespace {
@@ -877,12 +881,39 @@ void bgzf_slice_cuts(const BgzfChain &chain, uint32_t rank, uint32_t world, uint
         if (b < isize.size()) off += isize[b];
     }
 }
+
+// What the record format decides for the two readers below: the name in the messages, the slice bounds, the packers, where
+// host pieces are cut, and how many bases a byte of text can hold (FASTQ: half of the text is bases; FASTA: a byte is a base).
+struct ShareFormat {
+    RecFmt fmt;
+    bool fasta() const { return fmt == RecFmt::Fasta; }
+    const char *entry() const { return fasta() ? "shard_preprocess_fasta" : "shard_preprocess_fastq"; }
+    uint64_t bases_ub(uint64_t text_bytes) const { return fasta() ? text_bytes : text_bytes / 2; }
+    uint64_t piece_bytes(const Knobs &kn) const { return fasta() ? kn.batch_bases : 2 * kn.batch_bases; }      // text per piece: its bases fit one batch
+    void bounds(const uint8_t *t, size_t e, uint32_t rank, uint32_t world, uint64_t c0, uint64_t c1, uint64_t &s0, uint64_t &s1) const {
+        if (fasta()) fasta_slice_bounds(t, e, rank, world, c0, c1, s0, s1); else fastq_slice_bounds(t, e, rank, world, c0, c1, s0, s1);
+    }
+    uint64_t last_start(const uint8_t *t, size_t n) const { return fasta() ? fasta_last_record_start(t, n) : last_record_start(t, n); }
+    // a text on the device -> one packed batch (0; 1 declined: the host packer owns the messages; < 0)
+    int device_pack(const GpuText &text, uint32_t k, uint32_t min_qual, void *stream, GpuPacked &gp, std::string &err) const {
+        return fasta() ? gpu_pack_fasta(nullptr, 0, nullptr, 0, k, 0, stream, gp, err, 0, &text) : gpu_pack_fastq(nullptr, 0, nullptr, 0, k, min_qual, 0, stream, gp, err, 0, &text);
+    }
+    int host_pack(const uint8_t *t, size_t n, uint32_t k, uint32_t min_qual, PackedReads &pr, std::string &err, uint64_t flush_bases = 0,
+                  const FlushFn &flush = nullptr, uint64_t rec_base = 0) const {
+        return fasta() ? pack_fasta(t, n, k, pr, err, 0, nullptr, 0, flush_bases, flush, rec_base) : pack_fastq(t, n, k, min_qual, pr, err, 0, nullptr, 0, flush_bases, flush, rec_base);
+    }
+    std::string one_record_too_long(uint64_t bytes, const Knobs &kn) const {
+        return std::string(entry()) + ": a single FASTA record of " + std::to_string(bytes) + " bytes exceeds one batch (SHK_BATCH_BASES = " +
+               std::to_string(kn.batch_bases) + "): a record is never split";
+    }
+};
 }  // namespace
 
 int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual, uint32_t rank,
-                     uint32_t world, int device, void *stream, FastqShare &out, std::string &err, bool allow_batches) {
-    if ((!fq1 && (n1 || fq2)) || (!fq2 && n2)) { err = "shard_preprocess_fastq: a null file with a size, or a second file without a first"; return SHK_E_PARAM; }
-    if (world == 0 || rank >= world) { err = "shard_preprocess_fastq: rank beyond world"; return SHK_E_PARAM; }
+                     uint32_t world, int device, void *stream, FastqShare &out, std::string &err, bool allow_batches, RecFmt fmt) {
+    const ShareFormat sf{fmt};
+    if ((!fq1 && (n1 || fq2)) || (!fq2 && n2)) { err = std::string(sf.entry()) + ": a null file with a size, or a second file without a first"; return SHK_E_PARAM; }
+    if (world == 0 || rank >= world) { err = std::string(sf.entry()) + ": rank beyond world"; return SHK_E_PARAM; }
     const Knobs kn;
     const uint8_t *const fq[2] = {fq1, fq2}; const size_t fn[2] = {n1, fq2 ? n2 : 0};
     const int nf = fq2 ? 2 : (fq1 ? 1 : 0);
@@ -907,13 +938,13 @@ int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n
         F.e = trimmed_len(F.t, F.l);
         uint64_t c0 = slice_cut(F.e, rank, world), c1 = slice_cut(F.e, rank + 1, world);
         if (F.walked) bgzf_slice_cuts(F.chain, rank, world, c0, c1);
-        fastq_slice_bounds(F.t, F.e, rank, world, c0, c1, F.s0, F.s1);
+        sf.bounds(F.t, F.e, rank, world, c0, c1, F.s0, F.s1);
         F.host_text = true;
         return SHK_OK;
     };
     auto too_large = [&](uint64_t bases_or_half_bytes) -> bool {
         if (bases_or_half_bytes <= kn.batch_bases) return false;
-        err = "shard_preprocess_fastq: this rank's share exceeds one batch (SHK_BATCH_BASES = " + std::to_string(kn.batch_bases) +
+        err = std::string(sf.entry()) + ": this rank's share exceeds one batch (SHK_BATCH_BASES = " + std::to_string(kn.batch_bases) +
               " packed bases); several batches per rank are not supported: use more ranks or split the input";
         return true;
     };
@@ -921,6 +952,10 @@ int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n
     auto in_batches = [&](uint64_t text_ub) -> int {
         err.clear();
         gpu_packed_free(out.gp); out.gp = GpuPacked();
+        for (GpuPacked &g : out.held_gp) gpu_packed_free(g);
+        for (void *p : out.held_up) device_free(p);
+        out.held_gp.clear(); out.held_up.clear(); out.batches.clear();
+        out.n_seg = out.n_bases = out.n_reads = out.n_input_bases = 0;
         out.in_batches = true; out.text_ub = text_ub;
         return SHK_OK;
     };
@@ -933,7 +968,7 @@ int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n
             else if (f[i].gz) { const uint8_t *t = fq[i] + fn[i] - 4; text += (t[0] | ((uint64_t)t[1] << 8) | ((uint64_t)t[2] << 16) | ((uint64_t)t[3] << 24)) / world; }
             else { if (int rc = host_slice(i)) return rc; text += f[i].s1 - f[i].s0; }
         }
-        if (text / 2 > kn.batch_bases) return in_batches(text);
+        if (sf.bases_ub(text) > kn.batch_bases) return in_batches(text);
     }
     auto finish = [&](bool host_parsed) -> int {
         for (int i = 0; i < nf; i++) {
@@ -943,6 +978,83 @@ int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n
         }
         return SHK_OK;
     };
+    if (sf.fasta()) {
+        // ---- FASTA: file by file — its slice as a span of text in HBM and the device packer, or the host packer on the host's slice
+        // (SHK_HOST_PARSER=1, a host-resident slice below SHK_FASTA_DEVICE_MIN, what the device packer declines)
+        uint64_t text_bytes = 0;
+        for (int i = 0; i < nf; i++) {
+            File &F = f[i];
+            DevSpan span;
+            bool on_host = kn.host_parser;
+            if (!on_host && F.gz && kn.gunzip_device) {
+                int rc = 1;
+                if (F.walked) {
+                    const char *why = ""; uint64_t up = 0;
+                    rc = gpu_bgzf_slice(fq[i], F.chain, rank, world, device, stream, span, up, why, err, fmt);
+                    out.uploaded_bytes += up;
+                    if (!rc) F.route = BgzfSlice;
+                } else {
+                    Text text;
+                    rc = gpu_inflate_member(fq[i], fn[i], device, stream, text, err);
+                    if (!rc) {
+                        out.uploaded_bytes += fn[i];
+                        if ((rc = gpu_text_slice(text, rank, world, stream, span, err, fmt)) == 0) F.route = MemberWhole;
+                    }
+                }
+                if (rc < 0) return code_of(Rc::DeviceNoParam, rc);
+            }
+            Packed gp;
+            if (F.route == None) {
+                if (int rc = host_slice(i)) return rc;
+                F.route = F.gz ? Host : TextSlice;
+                on_host = on_host || F.s1 - F.s0 < kn.fasta_device_min;
+                text_bytes += F.s1 - F.s0;
+            } else text_bytes += span.len;
+            // (a byte is a base: the share goes in batches when its text exceeds one)
+            if (too_large(text_bytes)) return allow_batches ? in_batches(text_bytes) : SHK_E_PARAM;
+            if (!on_host) {
+                Text text;
+                if (F.route == BgzfSlice || F.route == MemberWhole) {
+                    if (int rc = gpu_join_spans(&span, 1, stream, text, err)) return code_of(Rc::DeviceNoParam, rc);
+                    span.blk.put();
+                } else {
+                    if (int rc = gpu_upload_text(F.t + F.s0, (size_t)(F.s1 - F.s0), device, text, err)) return code_of(Rc::DeviceNoParam, rc);
+                    out.uploaded_bytes += text.e;
+                }
+                const int rc = text.e ? sf.device_pack(text, k, min_qual, stream, gp, err) : 0;
+                if (rc < 0) return code_of(Rc::Device, rc);
+                if (rc) { gp.reset(); on_host = true; }    // declined: the host packer owns the message
+            }
+            FastqShare::Batch b{nullptr, nullptr, 0, 0, 0};
+            if (!on_host) {
+                b = FastqShare::Batch{gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases, gp.n_reads};
+                out.n_input_bases += gp.n_input_bases;
+                out.held_gp.push_back(gp);
+                static_cast<GpuPacked &>(gp) = GpuPacked();      // (the blocks are the share's now)
+            } else {
+                F.route = Host;
+                if (int rc = host_slice(i)) return rc;
+                PackedReads pr;
+                if (int rc = sf.host_pack(F.t + F.s0, (size_t)((F.s1 == F.e ? F.l : F.s1) - F.s0), k, min_qual, pr, err)) return code_of(Rc::Parser, rc);
+                out.n_input_bases += pr.n_input_bases;
+                b.n_reads = pr.n_reads;
+                if (pr.n_seg()) {
+                    pr.finish();
+                    void *db = nullptr, *ds = nullptr;
+                    int rc = device_upload(pr.bases.data(), pr.bases.size() * 4, &db, err);
+                    if (!rc) rc = device_upload(pr.seg_off.data(), pr.seg_off.size() * 4, &ds, err);
+                    out.held_up.push_back(db); out.held_up.push_back(ds);
+                    if (rc) return SHK_E_OOM;
+                    out.uploaded_bytes += (pr.bases.size() + pr.seg_off.size()) * 4;
+                    b.d_bases = (const uint32_t *)db; b.d_seg_off = (const uint32_t *)ds; b.n_seg = pr.n_seg(); b.n_bases = pr.n_bases;
+                }
+            }
+            out.n_seg += b.n_seg; out.n_bases += b.n_bases; out.n_reads += b.n_reads;
+            out.batches.push_back(b);
+        }
+        if (out.batches.empty()) out.batches.push_back(FastqShare::Batch{nullptr, nullptr, 0, 0, 0});
+        return finish(false);
+    }
     // ---- the device: every file's slice as a span of text in HBM, joined, parsed
     bool host_parser = kn.host_parser;
     if (!host_parser) {
@@ -1024,13 +1136,14 @@ int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n
 
 // ---- the same share, beyond one batch: batch by batch into pass 1 of the shard layer (preprocess.h) --------------------------
 int read_fastq_share_batches(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual, uint32_t rank,
-                             uint32_t world, int device, void *stream, ShardBatchSink &sink, FastqShare &out, std::string &err) {
-    if ((!fq1 && (n1 || fq2)) || (!fq2 && n2)) { err = "shard_preprocess_fastq: a null file with a size, or a second file without a first"; return SHK_E_PARAM; }
-    if (world == 0 || rank >= world) { err = "shard_preprocess_fastq: rank beyond world"; return SHK_E_PARAM; }
+                             uint32_t world, int device, void *stream, ShardBatchSink &sink, FastqShare &out, std::string &err, RecFmt fmt) {
+    const ShareFormat sf{fmt};
+    if ((!fq1 && (n1 || fq2)) || (!fq2 && n2)) { err = std::string(sf.entry()) + ": a null file with a size, or a second file without a first"; return SHK_E_PARAM; }
+    if (world == 0 || rank >= world) { err = std::string(sf.entry()) + ": rank beyond world"; return SHK_E_PARAM; }
     const Knobs kn;
     const uint8_t *const fq[2] = {fq1, fq2}; const size_t fn[2] = {n1, fq2 ? n2 : 0};
     const int nf = fq2 ? 2 : (fq1 ? 1 : 0);
-    const uint64_t piece_bytes = 2 * kn.batch_bases;      // text per piece: its bases fit one batch
+    const uint64_t piece_bytes = sf.piece_bytes(kn);
     enum Route { None, BgzfSlice, MemberWhole, TextSlice, Host };
     static const char *const route_name[] = {"", "bgzf_slice", "member_whole", "text_slice", "host"};
     struct File {
@@ -1046,7 +1159,7 @@ int read_fastq_share_batches(const uint8_t *fq1, size_t n1, const uint8_t *fq2, 
         F.e = trimmed_len(F.t, F.l);
         uint64_t c0 = slice_cut(F.e, rank, world), c1 = slice_cut(F.e, rank + 1, world);
         if (F.walked) bgzf_slice_cuts(F.chain, rank, world, c0, c1);
-        fastq_slice_bounds(F.t, F.e, rank, world, c0, c1, F.s0, F.s1);
+        sf.bounds(F.t, F.e, rank, world, c0, c1, F.s0, F.s1);
         F.host_text = true;
         return SHK_OK;
     };
@@ -1072,7 +1185,7 @@ int read_fastq_share_batches(const uint8_t *fq1, size_t n1, const uint8_t *fq2, 
     // a piece of regular text on the device -> parser -> one batch.  DECLINED: not regular 4-line FASTQ (nothing was counted)
     auto device_piece = [&](const GpuText &text, uint64_t file_done) -> int {
         Packed gp;
-        const int rc = gpu_pack_fastq(nullptr, 0, nullptr, 0, k, min_qual, 0, stream, gp, err, 0, &text);
+        const int rc = sf.device_pack(text, k, min_qual, stream, gp, err);
         if (rc < 0) return code_of(Rc::Device, rc);
         if (rc) return DECLINED;
         out.n_windows++;
@@ -1081,10 +1194,11 @@ int read_fastq_share_batches(const uint8_t *fq1, size_t n1, const uint8_t *fq2, 
     };
     // the host parser from `from` to the end of the slice (its messages count the slice's records: file_reads came before),
     // a batch every SHK_BATCH_BASES bases
-    auto host_from = [&](int i, uint64_t from, uint64_t file_reads) -> int {
+    // (FASTA: one piece alone, [from, upto))
+    auto host_from = [&](int i, uint64_t from, uint64_t file_reads, uint64_t upto = UINT64_MAX) -> int {
         File &F = f[i];
         // (a slice that reaches the end of the text takes the blank lines behind it along: read_fastq_share says why)
-        const uint64_t end = F.s1 == F.e ? F.l : F.s1;
+        const uint64_t end = upto < F.s1 ? upto : (F.s1 == F.e ? F.l : F.s1);
         if (from >= end) return SHK_OK;
         PackedReads pr;
         int flush_rc = SHK_OK;
@@ -1106,11 +1220,26 @@ int read_fastq_share_batches(const uint8_t *fq1, size_t n1, const uint8_t *fq2, 
             p.reset_stream();
             return flush_rc ? -7 : 0;
         };
-        const int rc = pack_fastq(F.t + from, (size_t)(end - from), k, min_qual, pr, err, 0, nullptr, 0, kn.batch_bases,
-                                  [&](PackedReads &p) { return flush(p, from - F.s0); }, file_reads);
+        const int rc = sf.host_pack(F.t + from, (size_t)(end - from), k, min_qual, pr, err, kn.batch_bases,
+                                    [&](PackedReads &p) { return flush(p, from - F.s0); }, file_reads);
         if (rc == -7) return flush_rc;
         if (rc) return code_of(Rc::Parser, rc);
-        return flush(pr, F.s1 - F.s0) ? flush_rc : SHK_OK;
+        return flush(pr, std::min(end, F.s1) - F.s0) ? flush_rc : SHK_OK;
+    };
+    // A span in pieces of at most piece_bytes, each a batch.  span_at: where the span begins in the file's text; file_base: where
+    // the slice does (progress).  SHK_OK; DECLINED with `stopped` = the span offset at which the host goes on; an error code.
+    auto span_pieces = [&](const DevSpan &span, uint64_t span_at, uint64_t file_base, uint64_t &stopped) -> int {
+        for (uint64_t from = 0; from < span.len;) {
+            Text piece; uint64_t next = 0;
+            const int rc = gpu_span_piece(span, from, piece_bytes, stream, piece, next, err, fmt);
+            if (rc < 0) return code_of(Rc::DeviceNoParam, rc);
+            if (rc && sf.fasta()) { err = sf.one_record_too_long(next - from, kn); return SHK_E_PARAM; }
+            const int prc = rc ? DECLINED : device_piece(piece, span_at + next - file_base);
+            if (prc == DECLINED) { stopped = from; return DECLINED; }
+            if (prc) return prc;
+            from = next;
+        }
+        return SHK_OK;
     };
     for (int i = 0; i < nf; i++) {
         File &F = f[i];
@@ -1123,7 +1252,7 @@ int read_fastq_share_batches(const uint8_t *fq1, size_t n1, const uint8_t *fq2, 
             if (F.walked) {
                 BgzfShareWindows sw;
                 const char *why = "";
-                int rc = sw.open(fq[i], F.chain, rank, world, kn.window.bytes, device, stream, why, err);
+                int rc = sw.open(fq[i], F.chain, rank, world, kn.window.bytes, device, stream, why, err, fmt);
                 if (rc < 0) return code_of(Rc::DeviceNoParam, rc);
                 while (!rc) {
                     GpuText piece; uint64_t at = 0; bool done = false;
@@ -1132,8 +1261,17 @@ int read_fastq_share_batches(const uint8_t *fq1, size_t n1, const uint8_t *fq2, 
                     if (rc) { resume = sw.consumed(); break; }              // this window is the host reader's, and what follows it
                     route = BgzfSlice;
                     if (done) { through = true; break; }
-                    const int prc = device_piece(piece, at + piece.e - sw.run_begin());
-                    if (prc == DECLINED) { resume = at; host_parser = true; break; }
+                    int prc;
+                    if (sf.fasta() && piece.e > piece_bytes) {      // a window (and its carry) of more than a batch: in pieces
+                        DevSpan view; uint64_t stopped = 0;
+                        view.blk = PoolBlock(piece.d, piece.e + 32); view.len = piece.e; view.unterminated = piece.unterminated;
+                        prc = span_pieces(view, at, sw.run_begin(), stopped);
+                        (void)view.blk.take();                      // (the text stays the windows')
+                        if (prc == DECLINED) { resume = at + stopped; host_parser = true; break; }
+                    } else {
+                        prc = device_piece(piece, at + piece.e - sw.run_begin());
+                        if (prc == DECLINED) { resume = at; host_parser = true; break; }
+                    }
                     if (prc) return prc;
                 }
                 out.uploaded_bytes += sw.uploaded();
@@ -1144,18 +1282,13 @@ int read_fastq_share_batches(const uint8_t *fq1, size_t n1, const uint8_t *fq2, 
                 if (!rc) {
                     out.uploaded_bytes += fn[i];
                     DevSpan span;
-                    if ((rc = gpu_text_slice(text, rank, world, stream, span, err)) < 0) return code_of(Rc::DeviceNoParam, rc);
+                    if ((rc = gpu_text_slice(text, rank, world, stream, span, err, fmt)) < 0) return code_of(Rc::DeviceNoParam, rc);
                     route = MemberWhole;
                     through = true;
-                    for (uint64_t from = 0; from < span.len;) {
-                        Text piece; uint64_t next = 0;
-                        rc = gpu_span_piece(span, from, piece_bytes, stream, piece, next, err);
-                        if (rc < 0) return code_of(Rc::DeviceNoParam, rc);
-                        const int prc = rc ? DECLINED : device_piece(piece, next);
-                        if (prc == DECLINED) { resume = span.off + from; host_parser = true; through = false; break; }
-                        if (prc) return prc;
-                        from = next;
-                    }
+                    uint64_t stopped = 0;
+                    const int prc = span_pieces(span, span.off, span.off, stopped);
+                    if (prc == DECLINED) { resume = span.off + stopped; host_parser = true; through = false; }
+                    else if (prc) return prc;
                 }
             }
         }
@@ -1164,22 +1297,38 @@ int read_fastq_share_batches(const uint8_t *fq1, size_t n1, const uint8_t *fq2, 
             if (int rc = host_slice(i)) return rc;
             route = F.gz ? Host : TextSlice;
             uint64_t from = std::max(F.s0, resume);
-            while (!host_parser && from < F.s1) {
+            // FASTA: the host packer takes pieces too (a record is never split, by either packer), and small slices (SHK_FASTA_DEVICE_MIN)
+            const bool host_pieces = sf.fasta() && (host_parser || F.s1 - F.s0 < kn.fasta_device_min);
+            while ((!host_parser || host_pieces) && from < F.s1) {
                 uint64_t end = F.s1;
                 if (F.s1 - from > piece_bytes) {
-                    const uint64_t at = last_record_start(F.t + from, (size_t)piece_bytes);
+                    const uint64_t at = sf.last_start(F.t + from, (size_t)piece_bytes);
+                    if (sf.fasta() && (at == UINT64_MAX || at == 0)) {
+                        const uint64_t nx = fasta_first_record_start(F.t, (size_t)F.s1, (size_t)from + 1);
+                        err = sf.one_record_too_long((nx == UINT64_MAX ? F.s1 : nx) - from, kn);
+                        return SHK_E_PARAM;
+                    }
                     if (at == UINT64_MAX || at == 0) { host_parser = true; break; }      // (no record starts inside the piece)
                     end = from + at;
+                }
+                if (host_pieces) {
+                    route = Host;
+                    if (int rc = host_from(i, from, reads - reads0, end)) return rc;
+                    from = end;
+                    continue;
                 }
                 Text text;
                 if (int rc = gpu_upload_text(F.t + from, (size_t)(end - from), device, text, err)) return code_of(Rc::DeviceNoParam, rc);
                 out.uploaded_bytes += text.e;
                 const int prc = device_piece(text, end - F.s0);
-                if (prc == DECLINED) { host_parser = true; break; }
-                if (prc) return prc;
+                if (prc == DECLINED && sf.fasta()) {              // the host packer on this piece: it owns the message
+                    route = Host;
+                    if (int rc = host_from(i, from, reads - reads0, end)) return rc;
+                } else if (prc == DECLINED) { host_parser = true; break; }
+                else if (prc) return prc;
                 from = end;
             }
-            if (host_parser) {
+            if (host_parser && !sf.fasta()) {
                 route = Host;
                 if (int rc = host_from(i, from, reads - reads0)) return rc;
             }

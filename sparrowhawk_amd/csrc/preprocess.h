@@ -3,6 +3,7 @@
 #pragma once
 #include "handle.h"
 #include "fastq_gpu.h"
+#include "share_windows.h"
 
 int preprocess_impl(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2);
 // shk_preprocess_fasta: whole FASTA files, plain or gzip (SPEC S1a), by the device packer (fasta_gpu.h) or the host packer
@@ -28,6 +29,9 @@ uint32_t emit_threshold_of(const shk_handle *h);
 //   ISIZE sums of the rank's run or the slice bounds of plain text tell, and read_fastq_share_batches then hands the share to
 //   pass 1 batch by batch: a BGZF run in windows of at most SHK_GUNZIP_DEVICE_WINDOW of text, everything else in pieces of about
 //   2 * SHK_BATCH_BASES bytes cut at record starts; the files of a pair one after the other.
+// The same two readers serve shk_shard_preprocess_fasta (fmt = RecFmt::Fasta; SPEC S1a, the slice rule): the bounds are header
+// lines, the packers are gpu_pack_fasta / pack_fasta, a byte of text is a base (pieces of at most SHK_BATCH_BASES bytes), a single
+// record beyond one batch is SHK_E_PARAM, and the files of a pair are packed separately (FastqShare::batches).
 struct FastqShare {
     shk::GpuPacked gp;                                    // parsed on the device
     void *up_bases = nullptr, *up_seg_off = nullptr;      // parsed on the host, uploaded
@@ -39,6 +43,11 @@ struct FastqShare {
     bool in_batches = false;                              // the share exceeds one batch: nothing is held, read_fastq_share_batches reads it
     uint64_t text_ub = 0;                                 // in_batches: bytes of text of the share, or an upper bound (text_ub / 2 bounds its k-mer instances)
     uint64_t n_batches = 0, n_windows = 0;                // batches handed to pass 1; windows and pieces of text they were parsed from
+    // FASTA: the files of a pair are packed separately (the packers' rule on the lines in front of the first header holds per
+    // file), so a share that fits one batch is held as one batch per file — d_bases / d_seg_off stay null, the counters are sums
+    struct Batch { const uint32_t *d_bases, *d_seg_off; uint64_t n_seg, n_bases, n_reads; };
+    std::vector<Batch> batches;
+    std::vector<shk::GpuPacked> held_gp; std::vector<void *> held_up;      // what the batches lie in
     FastqShare() = default;
     FastqShare(const FastqShare &) = delete;
     FastqShare &operator=(const FastqShare &) = delete;
@@ -46,8 +55,11 @@ struct FastqShare {
 };
 // SHK_OK, or the SHK_E_* code with its message in err; an oversized share (beyond one batch) is SHK_E_PARAM unless
 // allow_batches (then SHK_OK with out.in_batches)
+// fmt: the record format — the slice bounds, the packers (FASTA: gpu_pack_fasta from SHK_FASTA_DEVICE_MIN bytes of host-resident
+// slice on, pack_fasta below it; text born on the device is packed there), the cut of pieces and the bases per byte of text
 int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual, uint32_t rank,
-                     uint32_t world, int device, void *stream, FastqShare &out, std::string &err, bool allow_batches = false);
+                     uint32_t world, int device, void *stream, FastqShare &out, std::string &err, bool allow_batches = false,
+                     shk::RecFmt fmt = shk::RecFmt::Fastq);
 
 // where the batches of a share go: pass 1 of the shard layer (api.cpp: shard_preprocess_impl)
 struct ShardBatchSink {
@@ -61,4 +73,5 @@ struct ShardBatchSink {
 // The share of any size, batch by batch into `sink`; out: the counters (nothing is held).  SHK_OK; the SHK_E_* code of a reading
 // error with its message in err; or the code sink.batch returned, with err empty.
 int read_fastq_share_batches(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual, uint32_t rank,
-                             uint32_t world, int device, void *stream, ShardBatchSink &sink, FastqShare &out, std::string &err);
+                             uint32_t world, int device, void *stream, ShardBatchSink &sink, FastqShare &out, std::string &err,
+                             shk::RecFmt fmt = shk::RecFmt::Fastq);

@@ -11,6 +11,9 @@
 
 namespace shk {
 
+// the record format by which a slice, a window or a piece is cut: 4-line FASTQ, or FASTA (fastq.h states both rules)
+enum class RecFmt { Fastq, Fasta };
+
 // the nominal cut c_r of a text of e bytes among `world` ranks
 inline uint64_t slice_cut(uint64_t e, uint32_t r, uint32_t world) { return (uint64_t)((unsigned __int128)e * r / world); }
 

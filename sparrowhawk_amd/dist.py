@@ -211,6 +211,16 @@ def sharded_preprocess_fastq(helper: AssemblyHelper, comm: LibComm, file1, file2
                                                        1 if split else 0))
 
 
+def sharded_preprocess_fasta(helper: AssemblyHelper, comm: LibComm, file1, file2=None, split=True, n_partitions=0):
+    """Collective over `comm`: the sharded preprocess straight from FASTA files (plain, .gz or BGZF), as
+    sharded_preprocess_fastq: split=True, slice `rank` of `world` of the same file(s), cut at header lines (a record is
+    never split); split=False, this rank's own files (file1=None: none).  One C call (shk_shard_preprocess_fasta)."""
+    b1, b2 = _as_bytes(file1), _as_bytes(file2)
+    helper._check(helper._L.shk_shard_preprocess_fasta(helper._h, comm._c, b1, len(b1) if b1 is not None else 0,
+                                                       b2, len(b2) if b2 is not None else 0, int(n_partitions or 0),
+                                                       1 if split else 0))
+
+
 def lib_plan_exchange(part_records_all, rank):
     """The exchange plan as the library computes it (shk_plan_exchange) — same dict as plan_exchange()."""
     L = _lib.load()
