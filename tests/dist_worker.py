@@ -37,6 +37,18 @@ def set_dedupe(cfg, rank):
         os.environ["SHK_SHARD_DEDUPE"] = str(v)
 
 
+def set_env(env):
+    """A case's "env": {NAME: value | None}: the variables set (None: removed), the same on every rank.  Returns what they
+    were, in the same form: handed back here, it restores them."""
+    was = {name: os.environ.get(name) for name in env}
+    for name, v in env.items():
+        if v is None:
+            os.environ.pop(name, None)
+        else:
+            os.environ[name] = str(v)
+    return was
+
+
 def main():
     mode, out_path = sys.argv[1], sys.argv[2]
     import torch
@@ -108,7 +120,8 @@ def main():
     elif mode == "rccl_many":
         # several inputs through shk_shard_preprocess + the collective shk_assemble in ONE launch (process start-up is
         # most of a small case's time): cfg["cases"] = [{fastq, k, min_count, min_qual, do_fit, no_bubble_collapse,
-        # no_dead_end_removal, P}]; every rank writes the list of its results
+        # no_dead_end_removal, P, verbose, timings, env}]; every rank writes the list of its results.  env: set_env, around the
+        # case's handle (made, run and freed under it)
         from sparrowhawk_amd import AssemblyHelper, pack_fastq, ShkError
         from sparrowhawk_amd.dist import LibComm, sharded_preprocess_rccl
         dev = torch.device("cuda", rank % max(1, torch.cuda.device_count()))
@@ -130,6 +143,7 @@ def main():
             d_bases = torch.from_numpy(bases.view(np.int32)).to(dev)
             d_seg = torch.from_numpy(seg.view(np.int32)).to(dev)
             torch.cuda.synchronize()
+            env_was = set_env(cs.get("env") or {})       # (before the handle is made: it reads SHK_STAGE_TIMERS / SHK_KEEP_STAGES then)
             h = AssemblyHelper.new(k, bool(cs.get("verbose", False)), cs["min_count"], cs["min_qual"], 0, False, bool(cs.get("do_fit", False)),
                                    bool(cs.get("no_bubble_collapse", False)), bool(cs.get("no_dead_end_removal", False)))
             set_dedupe(cs, rank)
@@ -143,6 +157,7 @@ def main():
                 res = {"error": str(e)}
             results.append(res)
             h.free()
+            set_env(env_was)
         with open(f"{out_path}.{rank}", "w") as f:
             json.dump(results, f)
         comm.free()

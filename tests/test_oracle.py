@@ -375,3 +375,58 @@ def test_small_graph_campaign_reaches_every_class():
     assert none_removed >= 20 and some_removed >= 20, got
     assert self_links >= 1 and other_links >= 1, got
     assert min(per_variant.values()) >= 12, per_variant
+
+
+def test_sharded_small_graph_campaign_reaches_every_class():
+    """test_gpu_shard_graph_small.py sends the same 160 cases and the 24 wide-key ones through the sharded assembly on 1 to 4
+    ranks, each with a variant in rotation, and ties its path markers to the oracle's contig and k-mer counts.  This says on
+    the CPU, for exactly that assignment, what the runs reach — so that a change to the generator, the seed, the offsets or
+    the rotation cannot hollow the GPU test out unnoticed, and a renamed knob cannot turn a variant into the default."""
+    import test_gpu_shard_graph_small as sg
+    names = [name for name, _, _ in sg.ALL]
+    assert len(set(names)) == len(names) and names[0] == "default"
+    envs = [tuple(sorted(env.items())) + tuple(sorted(kw.items())) for _, env, kw in sg.ALL]
+    assert len(set(envs)) == len(envs), "two variants are the same run"
+    # every knob is one the library reads
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sparrowhawk_amd", "csrc")
+    text = "".join(open(os.path.join(csrc, fn), errors="replace").read() for fn in sorted(os.listdir(csrc)) if fn.endswith((".h", ".hip", ".cpp", ".hpp")))
+    for knob in sg.KNOBS + list(sg.INSPECTION):
+        assert f'"{knob}"' in text, f"{knob} is not read anywhere in sparrowhawk_amd/csrc/"
+    # one rank: the runs per variant, and what every test of the GPU file is certain to tally
+    one_rank = {name: 0 for name in names}
+    tests = {}
+    for c in range(SMALL_GRAPH_CASES):
+        for name, env, kw in sg.one_rank_variants(c):
+            one_rank[name] += 1
+            tests.setdefault(("one rank", c // sg.CASES_PER_BLOCK), set()).update(sg.reachable(env, sg.facts_of("small", c), 1, **kw))
+    for c in range(WIDE_BLOCKS * WIDE_PER_BLOCK):
+        for name, env, kw in sg.wide_variants(c):
+            one_rank[name] += 1
+            tests.setdefault(("one rank, wide keys", c // WIDE_PER_BLOCK), set()).update(sg.reachable(env, sg.facts_of("wide", c), 1, **kw))
+    assert min(one_rank.values()) >= 12, one_rank
+    # several ranks
+    got = dict(rings=0, other_links=0, some_removed=0, none_removed=0, above_256=0)
+    ports = set()
+    for world in sg.WORLDS:
+        picks = sg.world_picks(world)
+        assert 40 <= len(picks) <= 48 and sum(kind == "wide" for _, kind, _, _ in picks) == 4, (world, len(picks))
+        per_variant = {name: 0 for name in names}
+        retry = 0
+        for what, kind, c, (name, env, kw) in picks:
+            f = sg.facts_of(kind, c)
+            per_variant[name] += 1
+            tests.setdefault(("ranks", world), set()).update(sg.reachable(env, f, world, **kw))
+            got["rings"] += f.self_links >= 1; got["other_links"] += f.other_links >= 1
+            got["some_removed"] += f.removed > 0; got["none_removed"] += f.removed == 0; got["above_256"] += f.ncontigs > 256
+            retry += name == "seg_cap1" and f.ncontigs > world
+        assert min(per_variant.values()) >= 2, (world, per_variant)
+        assert retry >= 1, f"{world} ranks: no seg_cap1 case with more contigs than ranks"
+        ports.add(sg.PORT0 + world)
+    assert min(got.values()) >= 1, got
+    assert len(tests) == SMALL_GRAPH_CASES // sg.CASES_PER_BLOCK + WIDE_BLOCKS + len(sg.WORLDS)
+    for test, keys in sorted(tests.items()):
+        assert keys >= set(sg.REQUIRED), f"{test}: never reaches {sorted(set(sg.REQUIRED) - keys)}"
+    # the launches' ports: above 29850 and clear of every other launch of the suite (test_dist.py, test_gpu_configs.py,
+    # test_gpu_shard_writer.py: up to 29833; test_dist.py again: 29892, 29893; the sharded readers: 29932 ... 29954)
+    assert all(29850 < p < 29890 for p in ports), ports
+    print("sharded small-graph campaign:", got, "one-rank runs", one_rank)
