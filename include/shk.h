@@ -124,6 +124,28 @@ int shk_assemble(shk_handle *h);
  * JSON {"outfasta":str,"ncontigs":int,"outdot":str,"outgfa":str,"outgfav2":str}  :7-13 */
 const char *shk_get_assembly(shk_handle *h);
 
+/* ---- the outputs as BGZF (bgzip) files, compressed on the device (SPEC S11a; csrc/bgzf_write_gpu.hip).  No counterpart in
+ * the reference's assembly path; its newer bridge has a compress_output switch for its results. */
+#define SHK_OUT_FASTA 0
+#define SHK_OUT_DOT   1
+#define SHK_OUT_GFA1  2
+#define SHK_OUT_GFA2  3
+/* After shk_assemble: output `which` as a BGZF file whose inflated bytes are exactly the JSON field of shk_get_assembly()
+ * ("outfasta", "outdot", "outgfa", "outgfav2") with its escapes undone.  Compressed on the device: one wave per block of
+ * 65 280 bytes of text, literal-only dynamic-Huffman blocks (a stored block where that is not smaller), bgzip's end marker
+ * behind the last; the bytes are deterministic.  *data is owned by the handle (valid until the next call on it or
+ * shk_free).  SHK_E_STATE before shk_assemble, SHK_E_PARAM for another `which`.  An assembly with no contig gives the file
+ * of the (possibly header-only) field.  Local, not collective: on a sharded assembly every rank may call it and gets the
+ * same bytes.  Each file is made once per handle, at the first call that asks for it.
+ * Timings: bgzf_out_files_x1 (files made), bgzf_out_from_device_x1 (of those, made from the device writer's JSON in HBM, no
+ * upload), bgzf_out_text_MB, bgzf_out_file_MB, bgzf_out_kernels (where stage timers are on), bgzf_out_d2h_host_clock. */
+int shk_get_assembly_bgzf(shk_handle *h, int which, const uint8_t **data, size_t *n);
+/* Before shk_assemble (optional): the outputs that will be asked for, bit `which` each.  Where the JSON is written on the
+ * device (csrc/writer_gpu.h / writer_text_gpu.h) the requested fields are then unescaped and compressed from HBM inside
+ * shk_assemble, before that buffer is let go, and shk_get_assembly_bgzf returns them without any upload.  Mask 0 (the
+ * default): shk_assemble does what it always did.  SHK_E_PARAM for a mask beyond 15, SHK_E_STATE after shk_assemble. */
+int shk_request_assembly_bgzf(shk_handle *h, uint32_t mask);
+
 /* ---- shard layer: one process per GPU (DESIGN.md "Multi-GPU").  It replaces the crate's rayon
  * read-parallel driver (north_star; not in the reference tree).  The
  * k-mer space is split by minimiser-hash partition: partition p belongs to rank p % world.
@@ -399,6 +421,17 @@ int shk_host_gunzip(const uint8_t *gz, size_t n, uint8_t **out, size_t *out_n, u
  * Where SHK_GUNZIP_DEVICE_WINDOW is set, or the text of a BGZF file reaches 4 GiB, the file goes through the windows of
  * shk_preprocess (cut at record starts, the rest carried into the next window) and all its bytes come back. */
 int shk_device_gunzip(const uint8_t *gz, size_t n, uint8_t **out, size_t *out_n, const char **why, double *ms_total);
+/* ---- the BGZF block encoder alone (SPEC S11a; csrc/deflate_write.h: one header compiled for the kernels and for the host) */
+/* host-only: code lengths for 257 counts (out[257], each 0..15, complete); SHK_E_PARAM when no count is > 0 or their sum
+ * reaches 2^32.  A lone used symbol gets length 1. */
+int shk_host_deflate_lengths(const uint32_t counts[257], uint8_t out[257]);
+/* host-only: text as a BGZF file by the shared encoder (malloc'd, shk_host_free) */
+int shk_host_bgzf_compress(const uint8_t *text, size_t n, uint8_t **out, size_t *out_n);
+/* the same on the current HIP device (needs a GPU): byte for byte the host twin's file.  *ms_kernels optional. */
+int shk_device_bgzf_compress(const uint8_t *text, size_t n, uint8_t **out, size_t *out_n, double *ms_kernels);
+/* tests: the same on JSON string content, whose escapes (\n \t \" \\) the device undoes first (k_json_unesc_*: chunks of 2048
+ * bytes, 8 consecutive bytes a thread); SHK_E_INTERNAL for any other byte behind a backslash, or a backslash at the end. */
+int shk_device_bgzf_compress_escaped(const uint8_t *escaped, size_t n, uint8_t **out, size_t *out_n);
 /* SPEC S9 (tips, bubbles) and S10 (chains of simple links, the circular cut) on UNITIG records instead of k-mers — what the
  * sharded assembly runs on every rank's host once the k-mer-level contraction is done on the GPUs (csrc/unitig_graph.h:
  * one record per strand of a unitig; first / last: [n_recs][W] words of its first / last k-mer as spelled; min_*: the

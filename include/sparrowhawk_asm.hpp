@@ -64,6 +64,15 @@ public:
         if (!s) throw std::runtime_error(shk_last_error(h_));
         return s;
     }
+    // the outputs as BGZF files, compressed on the device (shk.h: SHK_OUT_FASTA .. SHK_OUT_GFA2; SPEC S11a).  request: before
+    // assemble(), the files that will be asked for (bit `which` each); get: the file, whose inflated bytes are the field of
+    // get_assembly() with its escapes undone
+    void request_assembly_bgzf(uint32_t mask) { check(shk_request_assembly_bgzf(h_, mask)); }
+    std::vector<uint8_t> get_assembly_bgzf(int which) {
+        const uint8_t *data = nullptr; size_t n = 0;
+        check(shk_get_assembly_bgzf(h_, which, &data, &n));
+        return std::vector<uint8_t>(data, data + n);
+    }
     void on_state(shk_progress_cb cb, void *user) { shk_set_progress_cb(h_, cb, user); }
     shk_handle *raw() { return h_; }
 

@@ -36,6 +36,12 @@ SIGNATURES = {
     "shk_get_preprocessing_info": (_cp, [_vp]),
     "shk_assemble": (_int, [_vp]),
     "shk_get_assembly": (_cp, [_vp]),
+    "shk_get_assembly_bgzf": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(_sz)]),
+    "shk_request_assembly_bgzf": (_int, [_vp, _u32]),
+    "shk_host_deflate_lengths": (_int, [_vp, _vp]),
+    "shk_host_bgzf_compress": (_int, [_cp, _sz, C.POINTER(_vp), C.POINTER(_sz)]),
+    "shk_device_bgzf_compress": (_int, [_cp, _sz, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(C.c_double)]),
+    "shk_device_bgzf_compress_escaped": (_int, [_cp, _sz, C.POINTER(_vp), C.POINTER(_sz)]),
     "shk_shard_partition": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _u32, _vp]),
     "shk_shard_record_bytes": (_u32, [_vp]),
     "shk_shard_pack": (_int, [_vp, _vp, _vp, _u32]),

@@ -15,6 +15,8 @@
 #include <thread>
 #include <vector>
 
+#include "bgzf_write_gpu.h"
+#include "deflate_write.h"
 #include "end_keys.h"
 #include "fasta_gpu.h"
 #include "fastq_gpu.h"
@@ -274,6 +276,91 @@ const char *shk_get_assembly(shk_handle *h) {
     if (h->st != St::Assembled) { h->err = "get_assembly before assemble"; return nullptr; }
     if (h->asm_json_dev) return h->asm_json_dev;
     return h->asm_json.empty() ? "" : (const char *)h->asm_json.data();
+}
+
+// ---- the outputs as BGZF files (SPEC S11a; csrc/bgzf_write_gpu.h) --------------------------------------------------------
+// The JSON-escaped content of field `key` inside the get_assembly() JSON: from behind `"key":"` to in front of the closing
+// quote, the first '"' with an even run of backslashes in front of it.  (The pattern itself cannot stand inside a field: a
+// quote of the content is escaped.)
+static bool json_string_field(const char *json, size_t len, const char *key, const char *&p, size_t &n) {
+    const std::string pat = std::string("\"") + key + "\":\"";
+    const char *at = (const char *)memmem(json, len, pat.data(), pat.size());
+    if (!at) return false;
+    const char *b = at + pat.size(), *end = json + len;
+    for (const char *q = b; q < end;) {
+        q = (const char *)memchr(q, '"', (size_t)(end - q));
+        if (!q) return false;
+        size_t run = 0;
+        while (q - run > b && q[-1 - (ptrdiff_t)run] == '\\') run++;
+        if ((run & 1u) == 0) { p = b; n = (size_t)(q - b); return true; }
+        q++;
+    }
+    return false;
+}
+static int bgzf_code(int rc) { return rc == -6 ? SHK_E_INTERNAL : code_of(Rc::Device, rc); }
+
+int shk_request_assembly_bgzf(shk_handle *h, uint32_t mask) {
+    if (!h) return SHK_E_PARAM;
+    if (h->st == St::Assembled || h->st == St::Failed) return fail(h, SHK_E_STATE, "request_assembly_bgzf: call it before assemble");
+    if (mask > 15u) return fail(h, SHK_E_PARAM, "request_assembly_bgzf: the mask has bits 0 .. 3 (SHK_OUT_FASTA .. SHK_OUT_GFA2)");
+    h->pipe->bgzf_request(mask);
+    return SHK_OK;
+}
+
+int shk_get_assembly_bgzf(shk_handle *h, int which, const uint8_t **data, size_t *n) {
+    return guarded(h, Poison::Never, [&]() -> int {
+        if (h->st != St::Assembled) return fail(h, SHK_E_STATE, "get_assembly_bgzf before assemble");
+        if (which < SHK_OUT_FASTA || which > SHK_OUT_GFA2 || !data || !n) return fail(h, SHK_E_PARAM, "get_assembly_bgzf: which is SHK_OUT_FASTA, SHK_OUT_DOT, SHK_OUT_GFA1 or SHK_OUT_GFA2");
+        if (h->pipe->bgzf_file(which, data, n)) return SHK_OK;
+        static const char *const keys[4] = {"outfasta", "outdot", "outgfa", "outgfav2"};
+        const char *json = shk_get_assembly(h);
+        const size_t len = h->asm_json_dev ? strlen(json) : (h->asm_json.empty() ? 0 : h->asm_json.size() - 1);
+        const char *p = nullptr; size_t pn = 0;
+        if (!json_string_field(json, len, keys[which], p, pn)) return fail(h, SHK_E_INTERNAL, std::string("get_assembly_bgzf: no field ") + keys[which] + " in the assembly JSON");
+        std::string err;
+        if (int rc = h->pipe->bgzf_output(which, p, pn, err)) return fail(h, bgzf_code(rc), err);
+        if (!h->pipe->bgzf_file(which, data, n)) return fail(h, SHK_E_INTERNAL, "get_assembly_bgzf: the file was not kept");
+        return SHK_OK;
+    });
+}
+
+// the block encoder alone, on the host (csrc/deflate_write.h) and on the current device (csrc/bgzf_write_gpu.hip)
+int shk_host_deflate_lengths(const uint32_t counts[257], uint8_t out[257]) {
+    if (!counts || !out) return SHK_E_PARAM;
+    uint64_t sum = 0;
+    for (int i = 0; i < DW_LIT; i++) sum += counts[i];
+    if (sum == 0 || sum > 0xFFFFFFFFull) return SHK_E_PARAM;
+    DwScratch s;
+    dw_rank(counts, DW_LIT, s.order, 0, 1);
+    (void)dw_lengths(counts, DW_LIT, 15, s, out);
+    return SHK_OK;
+}
+int shk_host_bgzf_compress(const uint8_t *text, size_t n, uint8_t **out, size_t *out_n) {
+    if ((!text && n) || !out || !out_n) return SHK_E_PARAM;
+    *out = (uint8_t *)malloc(dw_host_file_bound(n));
+    if (!*out) return SHK_E_OOM;
+    *out_n = dw_host_file(text, n, *out);
+    return SHK_OK;
+}
+static int device_bgzf_compress(const uint8_t *text, size_t n, bool escaped, uint8_t **out, size_t *out_n, double *ms_kernels) {
+    try {
+        if ((!text && n) || !out || !out_n) return SHK_E_PARAM;
+        *out = nullptr; *out_n = 0;
+        std::vector<uint8_t> file; BgzfWriteStats S; std::string err;
+        if (int rc = gpu_bgzf_write_host(text, n, escaped, ms_kernels != nullptr, file, S, err)) return bgzf_code(rc);
+        *out = (uint8_t *)malloc(file.size());
+        if (!*out) return SHK_E_OOM;
+        memcpy(*out, file.data(), file.size());
+        *out_n = file.size();
+        if (ms_kernels) *ms_kernels = S.kernels_ms;
+        return SHK_OK;
+    } catch (...) { return SHK_E_OOM; }
+}
+int shk_device_bgzf_compress(const uint8_t *text, size_t n, uint8_t **out, size_t *out_n, double *ms_kernels) {
+    return device_bgzf_compress(text, n, false, out, out_n, ms_kernels);
+}
+int shk_device_bgzf_compress_escaped(const uint8_t *escaped, size_t n, uint8_t **out, size_t *out_n) {
+    return device_bgzf_compress(escaped, n, true, out, out_n, nullptr);
 }
 
 // ---- packer ------------------------------------------------------------------------------

@@ -129,6 +129,13 @@ public:
     // owned by the pipeline; 1: declined, *why says why (no contig, 2^31 contigs, a contig of 2^32 bases, no device memory)
     virtual int text_assembly_json(const char *seqs, const uint64_t *offsets, const uint64_t *kc, uint64_t n_contigs,
                                    const char **json, size_t *json_len, const char **why, std::string &err) = 0;
+    // The outputs as BGZF files (bgzf_write_gpu.h; which: 0 FASTA, 1 DOT, 2 GFA1, 3 GFA2).  bgzf_request: the files the device
+    // writers make from their JSON in HBM before they let it go (bit `which` each; 0: none, the writers run as they always did).
+    // bgzf_file: the file made earlier, by a writer or by bgzf_output; false: there is none.  bgzf_output: makes it from the
+    // field's JSON-escaped bytes in host memory (uploaded, unescaped, compressed, downloaded).
+    virtual void bgzf_request(uint32_t mask) = 0;
+    virtual bool bgzf_file(int which, const uint8_t **data, size_t *n) const = 0;
+    virtual int bgzf_output(int which, const char *escaped, size_t n, std::string &err) = 0;
     virtual StageTimes &times() = 0;                 // (waits for the events of timers that were stopped without waiting)
     // a host-clock figure added without that wait: for callers with work still to launch behind what the stream holds
     virtual void add_time(const char *name, double ms) = 0;

@@ -27,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "bgzf_write_gpu.h"
 #include "ctl_words.h"
 #include "device_mem.h"
 #include "end_keys.h"
@@ -351,6 +352,36 @@ public:
         else (void)hipStreamSynchronize(stream_);
     }
     void *stream() override { return (void *)stream_; }
+    // ---- the outputs as BGZF files (bgzf_write_gpu.h) ----------------------------------------------------------------
+    void bgzf_request(uint32_t mask) override { bgzf_mask_ = mask & 15u; }
+    bool bgzf_file(int which, const uint8_t **data, size_t *n) const override {
+        if (which < 0 || which > 3 || !bgzf_n_[which]) return false;
+        *data = (const uint8_t *)bgzf_pin_[which].p; *n = bgzf_n_[which];
+        return true;
+    }
+    int wait_stream(std::string &err) { WAIT_STREAM(); return 0; }
+    // src: the field's escaped bytes, in HBM (a device writer's JSON) or in host memory
+    int bgzf_make(int which, const uint8_t *src, size_t n, bool on_device, std::string &err) {
+        const std::function<int(std::string &)> wait = [this](std::string &e) { return wait_stream(e); };
+        BgzfWriteStats S;
+        bgzf_n_[which] = 0;
+        size_t bytes = 0;
+        const int rc = on_device ? gpu_bgzf_write_pinned(src, n, true, stream_, stage_timers_, &wait, bgzf_pin_[which], bytes, S, err)
+                                 : gpu_bgzf_write_host_pinned(src, n, true, stream_, stage_timers_, &wait, bgzf_pin_[which], bytes, S, err);
+        if (rc) return rc;
+        bgzf_n_[which] = bytes;
+        times_.add("bgzf_out_files_x1", 1.0);
+        if (on_device) times_.add("bgzf_out_from_device_x1", 1.0);
+        times_.add("bgzf_out_text_MB", (double)S.text_bytes / 1e6);
+        times_.add("bgzf_out_file_MB", (double)S.file_bytes / 1e6);
+        if (stage_timers_) times_.add("bgzf_out_kernels", S.kernels_ms);
+        times_.add("bgzf_out_d2h_host_clock", S.d2h_ms);
+        return 0;
+    }
+    int bgzf_output(int which, const char *escaped, size_t n, std::string &err) override {
+        if (which < 0 || which > 3) return -1;
+        return bgzf_make(which, (const uint8_t *)escaped, n, false, err);
+    }
     int device() const override { return stream_dev_; }
     uint64_t total_instances() const override { return total_instances_; }
     uint64_t n_distinct() const override { return n_distinct_; }
@@ -2079,6 +2110,15 @@ public:
         times_.add("device_writer_json_MB", (double)total / 1e6);
         times_.add("device_writer_links_x1e-3", nl * 1e-3);
         *json = hjson_.p; if (json_len) *json_len = (size_t)total;
+        if (bgzf_mask_) {
+            // the requested outputs as BGZF files, from the fields' bytes where they lie in HBM: behind the opening quote of
+            // the field to in front of its closing one, the literals of DOT and GFA included
+            const u64 dot_at = lit_at[1] + lit[1].size() - strlen("digraph sparrowhawk {\\n");
+            const u64 from[4] = {base[0], dot_at, lit_at[3] + lit[3].size() - strlen("H\\tVN:Z:1.0\\n"), lit_at[5] + lit[5].size() - strlen("H\\tVN:Z:2.0\\n")};
+            const u64 to[4] = {lit_at[1], lit_at[3] + strlen("}\\n"), lit_at[5], lit_at[7]};
+            for (int which = 0; which < 4; which++)
+                if (bgzf_mask_ >> which & 1u) if (int rc = bgzf_make(which, (const uint8_t *)d_js.p + from[which], (size_t)(to[which] - from[which]), true, err)) return rc;
+        }
         return 0;
     }
 
@@ -2788,6 +2828,9 @@ private:
     DevBuf<char> d_out_keep_; DevBuf<unsigned long long> ends_src_;
     std::vector<unsigned long long> ends_src_host_;
     PinnedBuf hjson_;                 // the JSON of a fragmented assembly, written on the device (device_write_json)
+    PinnedBuf bgzf_pin_[4];           // the outputs as BGZF files (bgzf_make), bgzf_n_ bytes each (0: not made)
+    size_t bgzf_n_[4] = {0, 0, 0, 0};
+    uint32_t bgzf_mask_ = 0;          // the files the device writers make from their JSON in HBM (bgzf_request)
     DevBuf<uint32_t> nb_;
     bool graph_ready_ = false;
     uint64_t tips_removed_ = 0, bubbles_removed_ = 0; int rounds_ = 0;

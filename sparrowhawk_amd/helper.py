@@ -23,6 +23,10 @@ ERR_NAMES = {-1: "SHK_E_PARAM", -2: "SHK_E_STATE", -3: "SHK_E_PARSE", -4: "SHK_E
              -5: "SHK_E_DEVICE", -6: "SHK_E_INTERNAL"}
 
 
+OUT_FASTA, OUT_DOT, OUT_GFA1, OUT_GFA2 = 0, 1, 2, 3      # SHK_OUT_*: `which` of get_assembly_bgzf
+OUT_FIELDS = ("outfasta", "outdot", "outgfa", "outgfav2")    # the get_assembly() field each of them holds
+
+
 class ShkError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{ERR_NAMES.get(code, code)}: {msg}")
@@ -102,6 +106,19 @@ class AssemblyHelper:
         if s is None:
             raise ShkError(-2, self._L.shk_last_error(self._h).decode())
         return s.decode()
+
+    # ---- the outputs as BGZF files, compressed on the device (include/shk.h; SPEC S11a) ------
+    def request_assembly_bgzf(self, mask):
+        """before assemble(): the outputs that will be asked for (bit OUT_FASTA .. OUT_GFA2 each); where the JSON is written
+        on the device they are then compressed from HBM inside assemble()"""
+        self._check(self._L.shk_request_assembly_bgzf(self._h, int(mask)))
+
+    def get_assembly_bgzf(self, which):
+        """output `which` (OUT_FASTA, OUT_DOT, OUT_GFA1, OUT_GFA2) as a BGZF file: gzip.decompress() of it is the field of
+        get_assembly() with its escapes undone"""
+        data, n = C.c_void_p(), C.c_size_t()
+        self._check(self._L.shk_get_assembly_bgzf(self._h, int(which), C.byref(data), C.byref(n)))
+        return C.string_at(data.value, n.value)
 
     # ---- streaming / device-resident forms (include/shk.h) ---------------------------------
     def push_reads(self, chunk):
