@@ -808,7 +808,7 @@ static int shard_preprocess_batches_impl(shk_handle *h, shk_comm *cm, uint32_t n
     return shard_preprocess_impl(h, cm, r, n_partitions);
 }
 
-// shk_shard_preprocess from FASTQ files.  A share that fits one batch is read into ONE packed batch in HBM (preprocess.cpp:
+// shk_shard_preprocess from FASTQ files.  A share that fits one batch is read into ONE packed batch in HBM (share_reader.cpp:
 // read_fastq_share — split: slice `rank` of `world` of the same files on every rank; else the rank's own files, whole), the
 // ranks agree that all of them have their reads, and the batch goes through shard_preprocess_impl as it is.  A larger share is
 // only looked at in front of that agreement (read_fastq_share says in_batches before it uploads anything, where it can) and is
@@ -851,8 +851,8 @@ static int shard_preprocess_fastq_impl(shk_handle *h, shk_comm *cm, const uint8_
         t.add((tag + "windows_x1").c_str(), (double)windows);
         t.add((tag + "read_host_clock").c_str(), now_ms() - t0);
     };
-    if (!sh.in_batches && fasta) {
-        // the files of a pair were packed separately: one batch per file (ShardReads takes any number)
+    if (!sh.in_batches) {
+        // the share is held: FASTQ — the one pooled batch; FASTA — the files of a pair were packed separately, one batch per file
         book(sh, sh.batches.size(), sh.batches.size());
         ShardReads r;
         for (const FastqShare::Batch &b : sh.batches) r.inst_ub += b.n_bases > b.n_seg * (uint64_t)(h->k - 1) ? b.n_bases - b.n_seg * (uint64_t)(h->k - 1) : 0;
@@ -862,15 +862,11 @@ static int shard_preprocess_fastq_impl(shk_handle *h, shk_comm *cm, const uint8_
             for (size_t i = 0; i < sh.batches.size(); i++) {
                 const FastqShare::Batch &b = sh.batches[i];
                 reads += b.n_reads;
-                if (int rc = sink.batch(b.n_seg ? b.d_bases : nullptr, b.n_seg ? b.d_seg_off : nullptr, b.n_seg, b.n_bases, reads, i + 1, sh.batches.size())) return rc;
+                if (int rc = sink.batch(b.n_seg ? b.d_bases() : nullptr, b.n_seg ? b.d_seg_off() : nullptr, b.n_seg, b.n_bases, reads, i + 1, sh.batches.size())) return rc;
             }
             return (int)SHK_OK;
         };
         return shard_preprocess_impl(h, cm, r, n_partitions);
-    }
-    if (!sh.in_batches) {
-        book(sh, 1, 1);
-        return shard_preprocess_impl(h, cm, one_batch(h, sh.n_seg ? sh.d_bases : nullptr, sh.n_seg ? sh.d_seg_off : nullptr, sh.n_seg, sh.n_bases, sh.n_reads), n_partitions);
     }
     // several batches: reading and pass 1 take turns (shard_fastq_read_host_clock then holds both)
     ShardReads r;
@@ -1030,10 +1026,11 @@ int64_t shk_plan_fastq_slices(const uint32_t *isize, uint64_t n_blocks, uint32_t
         return (int64_t)world;
     } catch (...) { return SHK_E_OOM; }
 }
-// the routes of shk_shard_preprocess_fastq with split = 1, without a communicator: the packed batch of slice `rank` of
-// `world` comes back to the host (shk_packed_free)
-int shk_device_pack_fastq_slice(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual,
-                                uint32_t rank, uint32_t world, shk_packed *out, uint64_t *uploaded_bytes, const char **route) {
+// the routes of shk_shard_preprocess_fastq / _fasta with split = 1, without a communicator: the packed batch of slice `rank` of
+// `world` comes back to the host (shk_packed_free).  FASTA: the files of a pair are packed separately, their batches come
+// back as one (file 1's segments, then file 2's).
+static int device_pack_slice(RecFmt fmt, const uint8_t *f1, size_t n1, const uint8_t *f2, size_t n2, uint32_t k, uint32_t min_qual,
+                             uint32_t rank, uint32_t world, shk_packed *out, uint64_t *uploaded_bytes, const char **route) {
     static thread_local std::string msg, route_s;
     try {
         if (!out) return SHK_E_PARAM;
@@ -1041,15 +1038,29 @@ int shk_device_pack_fastq_slice(const uint8_t *fq1, size_t n1, const uint8_t *fq
         if (route) *route = "";
         if ((k & 1u) == 0 || k < SHK_K_MIN || k > SHK_K_MAX) { msg = "k must be odd and within [15, 255]"; if (route) *route = msg.c_str(); return SHK_E_PARAM; }
         FastqShare sh;
-        const int rc = read_fastq_share(fq1, n1, fq2, n2, k, min_qual, rank, world, current_device(), nullptr, sh, msg);
+        const int rc = read_fastq_share(f1, n1, f2, n2, k, min_qual, rank, world, current_device(), nullptr, sh, msg, false, fmt);
         if (uploaded_bytes) *uploaded_bytes = sh.uploaded_bytes;
         if (rc) { if (route) *route = msg.c_str(); return rc; }      // (on failure *route carries the message)
         const size_t nw = (size_t)(sh.n_bases >> 4) + 2;
         out->bases = (uint32_t *)calloc(nw, 4);
         out->seg_off = (uint32_t *)calloc((size_t)sh.n_seg + 1, 4);
         if (!out->bases || !out->seg_off) { shk_packed_free(out); return SHK_E_OOM; }
-        if (sh.n_seg) {
-            if (device_download(out->bases, sh.d_bases, nw * 4, msg) || device_download(out->seg_off, sh.d_seg_off, ((size_t)sh.n_seg + 1) * 4, msg)) {
+        uint64_t base_at = 0, seg_at = 0;
+        for (const FastqShare::Batch &b : sh.batches) {
+            if (!b.n_seg) continue;
+            int bad;
+            if (sh.batches.size() == 1) bad = device_download(out->bases, b.d_bases(), nw * 4, msg) || device_download(out->seg_off, b.d_seg_off(), ((size_t)b.n_seg + 1) * 4, msg);
+            else {
+                std::vector<uint32_t> bases((size_t)(b.n_bases >> 4) + 2), seg((size_t)b.n_seg + 1);
+                bad = device_download(bases.data(), b.d_bases(), bases.size() * 4, msg) || device_download(seg.data(), b.d_seg_off(), seg.size() * 4, msg);
+                for (uint64_t i = 0; !bad && i < b.n_bases; i++) {   // (a test entry: base by base behind what file 1 gave)
+                    const uint32_t code = (bases[(size_t)(i >> 4)] >> (2 * (i & 15))) & 3u;
+                    out->bases[(size_t)((base_at + i) >> 4)] |= code << (2 * ((base_at + i) & 15));
+                }
+                for (uint64_t j = 1; !bad && j <= b.n_seg; j++) out->seg_off[(size_t)(seg_at + j)] = (uint32_t)(base_at + seg[(size_t)j]);
+                base_at += b.n_bases; seg_at += b.n_seg;
+            }
+            if (bad) {
                 shk_packed_free(out);
                 if (route) *route = msg.c_str();
                 return SHK_E_DEVICE;
@@ -1061,44 +1072,13 @@ int shk_device_pack_fastq_slice(const uint8_t *fq1, size_t n1, const uint8_t *fq
         return SHK_OK;
     } catch (...) { return SHK_E_OOM; }
 }
-// its FASTA twin: the files of a pair are packed separately, their batches come back as one (file 1's segments, then file 2's)
+int shk_device_pack_fastq_slice(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual,
+                                uint32_t rank, uint32_t world, shk_packed *out, uint64_t *uploaded_bytes, const char **route) {
+    return device_pack_slice(RecFmt::Fastq, fq1, n1, fq2, n2, k, min_qual, rank, world, out, uploaded_bytes, route);
+}
 int shk_device_pack_fasta_slice(const uint8_t *fa1, size_t n1, const uint8_t *fa2, size_t n2, uint32_t k, uint32_t rank, uint32_t world,
                                 shk_packed *out, uint64_t *uploaded_bytes, const char **route) {
-    static thread_local std::string msg, route_s;
-    try {
-        if (!out) return SHK_E_PARAM;
-        *out = shk_packed();
-        if (route) *route = "";
-        if ((k & 1u) == 0 || k < SHK_K_MIN || k > SHK_K_MAX) { msg = "k must be odd and within [15, 255]"; if (route) *route = msg.c_str(); return SHK_E_PARAM; }
-        FastqShare sh;
-        const int rc = read_fastq_share(fa1, n1, fa2, n2, k, 0, rank, world, current_device(), nullptr, sh, msg, false, RecFmt::Fasta);
-        if (uploaded_bytes) *uploaded_bytes = sh.uploaded_bytes;
-        if (rc) { if (route) *route = msg.c_str(); return rc; }      // (on failure *route carries the message)
-        const size_t nw = (size_t)(sh.n_bases >> 4) + 2;
-        out->bases = (uint32_t *)calloc(nw, 4);
-        out->seg_off = (uint32_t *)calloc((size_t)sh.n_seg + 1, 4);
-        if (!out->bases || !out->seg_off) { shk_packed_free(out); return SHK_E_OOM; }
-        uint64_t base_at = 0, seg_at = 0;
-        for (const FastqShare::Batch &b : sh.batches) {
-            if (!b.n_seg) continue;
-            std::vector<uint32_t> bases((size_t)(b.n_bases >> 4) + 2), seg((size_t)b.n_seg + 1);
-            if (device_download(bases.data(), b.d_bases, bases.size() * 4, msg) || device_download(seg.data(), b.d_seg_off, seg.size() * 4, msg)) {
-                shk_packed_free(out);
-                if (route) *route = msg.c_str();
-                return SHK_E_DEVICE;
-            }
-            for (uint64_t i = 0; i < b.n_bases; i++) {           // (a test entry: base by base behind what file 1 gave)
-                const uint32_t code = (bases[(size_t)(i >> 4)] >> (2 * (i & 15))) & 3u;
-                out->bases[(size_t)((base_at + i) >> 4)] |= code << (2 * ((base_at + i) & 15));
-            }
-            for (uint64_t j = 1; j <= b.n_seg; j++) out->seg_off[(size_t)(seg_at + j)] = (uint32_t)(base_at + seg[(size_t)j]);
-            base_at += b.n_bases; seg_at += b.n_seg;
-        }
-        out->n_seg = sh.n_seg; out->n_bases = sh.n_bases; out->n_reads = sh.n_reads; out->n_input_bases = sh.n_input_bases;
-        route_s = sh.route;
-        if (route) *route = route_s.c_str();
-        return SHK_OK;
-    } catch (...) { return SHK_E_OOM; }
+    return device_pack_slice(RecFmt::Fasta, fa1, n1, fa2, n2, k, 0, rank, world, out, uploaded_bytes, route);
 }
 uint32_t shk_choose_partitions(uint64_t total_instances_ub, uint32_t world, uint32_t key_words) {
     return choose_partitions(total_instances_ub, world ? world : 1, key_words <= 1 ? 100000 : 40000);

@@ -155,6 +155,76 @@ bool bgzf_block(const uint8_t *b, size_t n, size_t &bsize) {
     return false;
 }
 
+// ---- a BGZF chain as the host walks it, and its windows (fastq.h) ------------------------------------------------------------
+int bgzf_walk(const uint8_t *gz, size_t n, BgzfChain &out, const char *&why) {
+    out = BgzfChain();
+    const char *mv = getenv("SHK_GUNZIP_DEVICE_MIN");
+    const size_t min_bytes = (mv && *mv) ? (size_t)strtoull(mv, nullptr, 10) : ((size_t)4 << 20);
+    if (n < min_bytes) { why = "small file"; return 1; }
+    for (size_t p = 0; p < n;) {
+        size_t bs = 0;
+        if (!bgzf_block(gz + p, n - p, bs)) { why = "BGZF block chain broken"; return 1; }
+        if (gz[p + 3] != 4) { why = "a BGZF block with more than the extra field"; return 1; }      // (FNAME, FCOMMENT, FHCRC: bgzip writes none)
+        const size_t hdr = 12 + (gz[p + 10] | ((size_t)gz[p + 11] << 8));
+        const uint8_t *t = gz + p + bs - 8;
+        const uint32_t crc = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+        const uint32_t isize = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+        if (isize > 65536) { why = "a BGZF block of more than 64 KiB"; return 1; }
+        if (!isize) {
+            // an empty block (the end-of-file marker, also in mid-file) gets no wave: a few bytes for zlib
+            uint8_t sink[8];
+            z_stream zs; memset(&zs, 0, sizeof zs);
+            if (inflateInit2(&zs, -15) != Z_OK) { why = "zlib init failed"; return 1; }
+            zs.next_in = (Bytef *)(gz + p + hdr); zs.avail_in = (uInt)(bs - hdr - 8);
+            zs.next_out = sink; zs.avail_out = sizeof sink;
+            const int rc = inflate(&zs, Z_FINISH);
+            const bool ok = rc == Z_STREAM_END && zs.avail_out == sizeof sink && zs.avail_in == 0;
+            inflateEnd(&zs);
+            if (!ok || crc != 0) { why = "a damaged empty BGZF block"; return 1; }
+        } else out.nonempty++;
+        out.blocks.push_back(BgzfChain::Block{(uint64_t)p, (uint32_t)bs, (uint32_t)hdr, isize, crc});
+        out.text += isize; p += bs;
+    }
+    return 0;
+}
+
+int bgzf_cut_windows(BgzfChain &c, uint64_t budget) {
+    std::vector<uint32_t> isize(c.blocks.size());
+    for (size_t i = 0; i < c.blocks.size(); i++) isize[i] = c.blocks[i].isize;
+    std::vector<uint64_t> first;
+    c.windows.clear();
+    if (plan_bgzf_windows(isize.data(), isize.size(), budget, first)) return -1;
+    uint64_t before = 0;
+    for (size_t w = 0; w < first.size(); w++) {
+        BgzfChain::Window win{(size_t)first[w], w + 1 < first.size() ? (size_t)first[w + 1] : c.blocks.size(), 0, 0, 0, before, 0};
+        win.in_off = c.blocks[win.b0].in_off;
+        win.in_end = c.blocks[win.b1 - 1].in_off + c.blocks[win.b1 - 1].bsize;
+        for (size_t b = win.b0; b < win.b1; b++) { win.text += c.blocks[b].isize; win.nonempty += c.blocks[b].isize != 0; }
+        before += win.text;
+        c.windows.push_back(win);
+    }
+    return 0;
+}
+
+BgzfWindowKnob bgzf_window_knob(uint64_t max_bytes) {
+    const char *v = getenv("SHK_GUNZIP_DEVICE_WINDOW");
+    const bool set = v && *v;
+    return BgzfWindowKnob{set, std::max<uint64_t>(std::min<uint64_t>({set ? strtoull(v, nullptr, 10) : 1ull << 30, max_bytes, 3ull << 30}), 65536)};
+}
+
+// bytes of a FASTQ text without its trailing blank lines (the host parser skips them)
+size_t trimmed_len(const uint8_t *t, size_t n) {
+    size_t e = n;
+    for (;;) {
+        if (e >= 2 && t[e - 1] == '\n' && t[e - 2] == '\n') { e -= 1; continue; }
+        if (e >= 3 && t[e - 1] == '\n' && t[e - 2] == '\r' && t[e - 3] == '\n') { e -= 2; continue; }
+        break;
+    }
+    if (e == 1 && t[0] == '\n') e = 0;
+    if (e == 2 && t[0] == '\r' && t[1] == '\n') e = 0;
+    return e;
+}
+
 uint64_t last_record_start(const uint8_t *t, size_t n) {
     // line starts from the back; s1 / s2: the starts of the next line and of the line after next (n: not inside t)
     size_t s1 = n, s2 = n;

@@ -50,6 +50,27 @@ int pack_fasta(const uint8_t *buf, size_t n, uint32_t k, PackedReads &out, std::
 // b[0..n) starts with a whole BGZF block (SAM spec 4.1: a gzip member with a 'BC' extra subfield that holds its size - 1):
 // bsize = that size.  The one rule by which both the host reader and the device inflater (inflate_gpu.hip) walk a chain.
 bool bgzf_block(const uint8_t *b, size_t n, size_t &bsize);
+// A BGZF file as the host sees it before a byte crosses PCIe: every block's place, its ISIZE and CRC (they stand in its
+// trailer), and — once cut — the windows of consecutive blocks whose text fits a budget (inflate_gpu.h: BgzfWindows).
+struct BgzfChain {
+    struct Block { uint64_t in_off; uint32_t bsize, hdr, isize, crc; };      // in_off: of the block's header in the file
+    struct Window { size_t b0, b1; uint64_t in_off, in_end, text, text_before; uint32_t nonempty; };
+    std::vector<Block> blocks;
+    std::vector<Window> windows;
+    uint64_t text = 0, nonempty = 0;      // bytes of text / non-empty blocks of the whole file
+};
+// Walks gz[0..n) as gpu_inflate_member walks a BGZF file (bgzf_block, FLG == 4, ISIZE <= 65536, empty blocks checked by zlib).
+// 0: out.blocks, out.text, out.nonempty are set; 1: not a complete chain of such blocks, or smaller than SHK_GUNZIP_DEVICE_MIN
+// (*why).
+int bgzf_walk(const uint8_t *gz, size_t n, BgzfChain &out, const char *&why);
+// out.windows from out.blocks; -1: a block exceeds the budget
+int bgzf_cut_windows(BgzfChain &c, uint64_t budget);
+// SHK_GUNZIP_DEVICE_WINDOW, bytes of text per window: 1 GiB by default, at most max_bytes (a window and its carry fit one
+// batch) and 3 GiB (32-bit offsets), at least one block of 64 KiB
+struct BgzfWindowKnob { bool set; uint64_t bytes; };
+BgzfWindowKnob bgzf_window_knob(uint64_t max_bytes);
+// bytes of a FASTQ text without its trailing blank lines: what gpu_upload_text (fastq_gpu.h) uploads of t[0..n)
+size_t trimmed_len(const uint8_t *t, size_t n);
 // (the windows of a BGZF chain and the ranks' runs of its blocks — plan_bgzf_windows, plan_fastq_slices, plan_share_windows —
 // and slice_cut: share_windows.h, which a host compiler takes alone)
 // Where the last FASTQ record of t[0..n) starts that is known to be one: a line that begins with '@' and whose line after

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string>
 #include <vector>
+#include "fastq.h"      // trimmed_len: the end-of-text rule gpu_upload_text goes by (host code)
 
 namespace shk {
 
@@ -26,8 +27,6 @@ struct GpuText {
     bool unterminated = false;        // the last line lacks its newline
     double h2d_ms = 0;
 };
-// bytes of a FASTQ text without its trailing blank lines: what gpu_upload_text uploads of t[0..n)
-size_t trimmed_len(const uint8_t *t, size_t n);
 // blocking; uses a stream of its own on `device` (callable from any thread)
 int gpu_upload_text(const uint8_t *t, size_t n, int device, GpuText &out, std::string &err);
 void gpu_text_free(GpuText &t);

@@ -399,19 +399,6 @@ __global__ __launch_bounds__(256) void k_nl_total(const uint8_t *__restrict__ te
 }
 
 
-// bytes of a FASTQ text without its trailing blank lines (the host parser skips them)
-size_t trimmed_len(const uint8_t *t, size_t n) {
-    size_t e = n;
-    for (;;) {
-        if (e >= 2 && t[e - 1] == '\n' && t[e - 2] == '\n') { e -= 1; continue; }
-        if (e >= 3 && t[e - 1] == '\n' && t[e - 2] == '\r' && t[e - 3] == '\n') { e -= 2; continue; }
-        break;
-    }
-    if (e == 1 && t[0] == '\n') e = 0;
-    if (e == 2 && t[0] == '\r' && t[1] == '\n') e = 0;
-    return e;
-}
-
 int gpu_pack_fastq(const uint8_t *t1, size_t n1, const uint8_t *t2, size_t n2, uint32_t k, uint32_t min_qual,
                    uint64_t every, void *stream_v, GpuPacked &out, std::string &err, uint64_t read_base,
                    const GpuText *uploaded) {

@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 #include "device_mem.h"
+#include "fastq.h"
 #include "fastq_gpu.h"
 #include "share_windows.h"
 
@@ -36,33 +37,15 @@ struct GpuInflateStats {
 //  <0  -4 out of device memory (a plain member), -5 HIP error.
 // raw: every byte of the member stays as it is (out.e = the member's size; the tests compare with zlib) — otherwise the text
 // is made ready for the parser (trailing blank lines cut, see above).
-struct BgzfChain;
-// walked: the file's chain as bgzf_walk (below) has walked it already, or null
+// walked: the file's chain as bgzf_walk (fastq.h) has walked it already, or null
 int gpu_inflate_member(const uint8_t *gz, size_t n, int device, void *stream, GpuText &out, std::string &err,
                        GpuInflateStats *stats = nullptr, bool raw = false, const BgzfChain *walked = nullptr);
 
 // ---- a BGZF file of any size, window by window ------------------------------------------------------------------------
 // The chain is walked on the host before a byte crosses PCIe (every block's ISIZE stands in its trailer), cut into windows
-// of consecutive blocks whose text fits a budget (fastq.h: plan_bgzf_windows, the budget: bgzf_window_knob), and each window
-// is uploaded, inflated with window-relative descriptors, and cut at its last record start on the device (BgzfWindows::step).
-struct BgzfChain {
-    struct Block { uint64_t in_off; uint32_t bsize, hdr, isize, crc; };      // in_off: of the block's header in the file
-    struct Window { size_t b0, b1; uint64_t in_off, in_end, text, text_before; uint32_t nonempty; };
-    std::vector<Block> blocks;
-    std::vector<Window> windows;
-    uint64_t text = 0, nonempty = 0;      // bytes of text / non-empty blocks of the whole file
-};
-// Walks gz[0..n) as gpu_inflate_member walks a BGZF file (bgzf_block, FLG == 4, ISIZE <= 65536, empty blocks checked by zlib).
-// 0: out.blocks, out.text, out.nonempty are set; 1: not a complete chain of such blocks, or smaller than SHK_GUNZIP_DEVICE_MIN
-// (*why).  Host only.
-int bgzf_walk(const uint8_t *gz, size_t n, BgzfChain &out, const char *&why);
-// out.windows from out.blocks; -1: a block exceeds the budget
-int bgzf_cut_windows(BgzfChain &c, uint64_t budget);
-
-// SHK_GUNZIP_DEVICE_WINDOW, bytes of text per window: 1 GiB by default, at most max_bytes (a window and its carry fit one
-// batch) and 3 GiB (32-bit offsets), at least one block of 64 KiB
-struct BgzfWindowKnob { bool set; uint64_t bytes; };
-BgzfWindowKnob bgzf_window_knob(uint64_t max_bytes);
+// of consecutive blocks whose text fits a budget (fastq.h: BgzfChain, bgzf_walk, bgzf_cut_windows, the budget: bgzf_window_knob
+// — host code, declared there), and each window is uploaded, inflated with window-relative descriptors, and cut at its last
+// record start on the device (BgzfWindows::step).
 
 // The device side of one file's windows: two input buffers (window w + 1 is uploaded, from a helper thread, while window w
 // is worked on) and two text buffers (window w's text starts with the carry: the partial record left over from window w - 1).
@@ -161,7 +144,7 @@ int gpu_first_record_start(const uint8_t *t, size_t n, uint64_t from, int device
 // last: `from` is not used)
 int gpu_fasta_record_start(const uint8_t *t, size_t n, bool last, uint64_t from, int device, uint64_t &at, std::string &err);
 
-// ---- one rank's slice of a file, for the sharded FASTQ and FASTA entry points (preprocess.cpp: read_fastq_share) ---------
+// ---- one rank's slice of a file, for the sharded FASTQ and FASTA entry points (share_reader.cpp: read_fastq_share) ---------
 // The slice rule is stated in fastq.h (first_record_start, fastq_slice_bounds, plan_fastq_slices; FASTA: fasta_first_record_start,
 // fasta_slice_bounds); here it is applied to text that is born on the device.  fmt: the record format the cuts go by (FASTQ where
 // nothing is said: k_first_record_start / k_last_record_start; FASTA: k_fasta_header_search).  A span is a run of text inside a

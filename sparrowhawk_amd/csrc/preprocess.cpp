@@ -18,13 +18,8 @@
 //   6 route_host                 SHK_HOST_PARSER=1, or every route above declined.  Never declines.
 //   7 push_reads_impl            the streaming entry point: the device parser for a chunk of >= SHK_STREAM_DEVICE_MIN bytes
 //                                that is regular 4-line FASTQ, else the host parser
-//   8 read_fastq_share           the sharded entry point from files (shk_shard_preprocess_fastq): one rank's slice of every file
-//                                as ONE packed batch — per file a BGZF slice, a whole member or a text slice on the device, the
-//                                host reader and the host parser for what the device declines (preprocess.h)
-//   9 read_fastq_share_batches   the same slices where they exceed one batch: window by window (a BGZF run) or piece by piece
-//                                into pass 1 of the shard layer, one batch each
-//     (8 and 9 take a record format, ShareFormat below: with RecFmt::Fasta they are shk_shard_preprocess_fasta — slices, windows
-//      and pieces cut at header lines, the FASTA packers, a byte of text a base, the files of a pair packed separately)
+//   8 read_fastq_share           } the sharded entry points from files (shk_shard_preprocess_fastq / _fasta): one rank's slice of every
+//   9 read_fastq_share_batches   } file as one packed batch, or batch by batch — share_reader.cpp (share_reader.h says how)
 // The device parser (fastq_gpu.hip) takes regular 4-line FASTQ only; irregular framing and every malformed record go to
 // the host parser (fastq.cpp), which owns the error messages.
 #include "preprocess.h"
@@ -40,6 +35,7 @@
 #include "fastq_gpu.h"
 #include "inflate_gpu.h"
 #include "inflate_mt.h"
+#include "read_parts.h"
 
 namespace shk { bool spectrum_fit(const uint64_t *histo500, uint32_t *out); }   // fit.cpp
 
@@ -51,37 +47,6 @@ uint32_t emit_threshold_of(const shk_handle *h) {
 }
 
 namespace {
-
-const size_t FASTA_DEVICE_MIN_DEFAULT = (size_t)1 << 20;
-const int DECLINED = 1;                 // what a route returns when the next one is to be tried (SHK_E_* are <= 0)
-
-// the environment's switches, read once per call (the tests change them between handles of one process)
-struct Knobs {
-    static bool is(const char *v, char c) { return v && *v == c; }
-    static uint64_t num(const char *v, uint64_t dflt) { return (v && *v) ? strtoull(v, nullptr, 10) : dflt; }
-    const bool host_parser = is(getenv("SHK_HOST_PARSER"), '1'), gunzip_device = !is(getenv("SHK_GUNZIP_DEVICE"), '0');
-    const size_t pipeline_min = num(getenv("SHK_FASTQ_PIPELINE_MIN"), 64ull << 20), stream_device_min = num(getenv("SHK_STREAM_DEVICE_MIN"), 8ull << 20);
-    const size_t pieces = (size_t)std::max<long long>(1, (long long)num(getenv("SHK_FASTQ_PIECES"), 4));
-    // FASTA texts below this many bytes go to the host packer (shk_preprocess_fasta; the default: DESIGN.md §5, profiles/fasta)
-    const size_t fasta_device_min = num(getenv("SHK_FASTA_DEVICE_MIN"), FASTA_DEVICE_MIN_DEFAULT);
-    // bases per batch of the host-parsed paths (a batch is limited to 2^32 packed bases by its 32-bit offsets)
-    const uint64_t batch_bases = std::min<uint64_t>(std::max<uint64_t>(num(getenv("SHK_BATCH_BASES"), 1ull << 31), 1024), 3ull << 30);
-    // text per window of route 2 (bytes; default 1 GiB — unmeasured so far): a window and its carry fit one batch.  Set: a BGZF
-    // file beyond it takes route 2 even where it fits one batch.
-    const BgzfWindowKnob window = bgzf_window_knob(2 * batch_bases);
-};
-
-// a device block of the parser that goes back to the pool when its owner goes out of scope (every error and
-// "declined" exit), or at reset() where the success path lets go of it earlier
-template <typename T, void (*Free)(T &)> struct Owned : T {
-    Owned() = default;
-    Owned(Owned &&o) noexcept : T(std::move(static_cast<T &>(o))) { static_cast<T &>(o) = T(); }
-    Owned &operator=(Owned &&o) noexcept { if (this != &o) { reset(); T::operator=(std::move(o)); static_cast<T &>(o) = T(); } return *this; }
-    ~Owned() { reset(); }
-    void reset() { Free(*this); }
-};
-using Text = Owned<GpuText, gpu_text_free>;
-using Packed = Owned<GpuPacked, gpu_packed_free>;
 
 // where a text lies in the whole input: the percentage of a `loop:<n>:<pct>` string (the streaming entry point posts none)
 struct Span { uint64_t base = 0, total = 0; bool pct = true; };
@@ -158,16 +123,13 @@ int run_counting(shk_handle *h, const uint32_t *d_bases, const uint32_t *d_seg_o
 // hand the packed stream on as one batch (upload + pass 1) and empty it; read counters are kept
 int flush_host_batch(shk_handle *h, PackedReads &pr) {
     if (pr.n_seg() == 0) { pr.reset_stream(); return SHK_OK; }
-    pr.finish();
     std::string err;
-    void *d_bases = nullptr, *d_off = nullptr;
+    UploadedReads up;
+    pr.finish();                                          // (in front of the clock, which times the upload alone)
     const double t0 = now_ms();
-    int rc = device_upload(pr.bases.data(), pr.bases.size() * 4, &d_bases, err);
-    if (!rc) rc = device_upload(pr.seg_off.data(), pr.seg_off.size() * 4, &d_off, err);
-    if (rc) { device_free(d_bases); device_free(d_off); return fail(h, SHK_E_OOM, err); }
+    if (upload_packed(pr, up, err)) return fail(h, SHK_E_OOM, err);
     h->pipe->times().add("h2d_upload_host_clock", now_ms() - t0);
-    rc = count_one_batch(h, (const uint32_t *)d_bases, (const uint32_t *)d_off, pr.n_seg(), pr.n_bases);
-    device_free(d_bases); device_free(d_off);
+    const int rc = count_one_batch(h, (const uint32_t *)up.bases, (const uint32_t *)up.seg_off, pr.n_seg(), pr.n_bases);
     pr.reset_stream();
     return rc;
 }
@@ -249,7 +211,7 @@ struct Input {
 };
 
 // Before routes 1 and 2, and before anything is uploaded: 0 some file lacks the gzip magic (neither route), 2 every file is
-// a complete BGZF chain (inflate_gpu.h: bgzf_walk; the chains stay in `in`) whose text — the sum of the blocks' ISIZE
+// a complete BGZF chain (fastq.h: bgzf_walk; the chains stay in `in`) whose text — the sum of the blocks' ISIZE
 // fields — is more than route 1 takes and can be cut into windows, 1 otherwise.
 int plan_device_gunzip(const Knobs &kn, Input &in) {
     const uint8_t *gz[2] = {in.fq1, in.fq2}; const size_t gn[2] = {in.n1, in.fq2 ? in.n2 : 0};
@@ -856,486 +818,4 @@ int preprocess_packed_host_impl(shk_handle *h, const uint32_t *bases, const uint
     h->pipe->times().add("h2d_packed_reads_MB", (double)(want_b + want_s) / 1e6);
     h->pipe->times().add("preprocess_from_host_total_host_clock", now_ms() - t0);
     return rc;
-}
-
-// ---- one rank's share of FASTQ files as one packed batch (preprocess.h) --------------------------------------------------
-FastqShare::~FastqShare() {
-    gpu_packed_free(gp);
-    device_free(up_bases); device_free(up_seg_off);
-    for (shk::GpuPacked &g : held_gp) gpu_packed_free(g);
-    for (void *p : held_up) device_free(p);
-}
-
-namespace {
-// the nominal cuts c_rank and c_(rank + 1) of a walked BGZF chain: the text offsets at which the rank's run and the next begin
-void bgzf_slice_cuts(const BgzfChain &chain, uint32_t rank, uint32_t world, uint64_t &c0, uint64_t &c1) {
-    std::vector<uint32_t> isize(chain.blocks.size());
-    for (size_t i = 0; i < isize.size(); i++) isize[i] = chain.blocks[i].isize;
-    std::vector<uint64_t> first;
-    plan_fastq_slices(isize.data(), isize.size(), world, first);
-    uint64_t off = 0;
-    c0 = c1 = chain.text;
-    for (size_t b = 0; b <= isize.size(); b++) {
-        if (b == first[rank]) c0 = off;
-        if (b == first[rank + 1]) { c1 = off; break; }
-        if (b < isize.size()) off += isize[b];
-    }
-}
-
-// What the record format decides for the two readers below: the name in the messages, the slice bounds, the packers, where
-// host pieces are cut, and how many bases a byte of text can hold (FASTQ: half of the text is bases; FASTA: a byte is a base).
-struct ShareFormat {
-    RecFmt fmt;
-    bool fasta() const { return fmt == RecFmt::Fasta; }
-    const char *entry() const { return fasta() ? "shard_preprocess_fasta" : "shard_preprocess_fastq"; }
-    uint64_t bases_ub(uint64_t text_bytes) const { return fasta() ? text_bytes : text_bytes / 2; }
-    uint64_t piece_bytes(const Knobs &kn) const { return fasta() ? kn.batch_bases : 2 * kn.batch_bases; }      // text per piece: its bases fit one batch
-    void bounds(const uint8_t *t, size_t e, uint32_t rank, uint32_t world, uint64_t c0, uint64_t c1, uint64_t &s0, uint64_t &s1) const {
-        if (fasta()) fasta_slice_bounds(t, e, rank, world, c0, c1, s0, s1); else fastq_slice_bounds(t, e, rank, world, c0, c1, s0, s1);
-    }
-    uint64_t last_start(const uint8_t *t, size_t n) const { return fasta() ? fasta_last_record_start(t, n) : last_record_start(t, n); }
-    // a text on the device -> one packed batch (0; 1 declined: the host packer owns the messages; < 0)
-    int device_pack(const GpuText &text, uint32_t k, uint32_t min_qual, void *stream, GpuPacked &gp, std::string &err) const {
-        return fasta() ? gpu_pack_fasta(nullptr, 0, nullptr, 0, k, 0, stream, gp, err, 0, &text) : gpu_pack_fastq(nullptr, 0, nullptr, 0, k, min_qual, 0, stream, gp, err, 0, &text);
-    }
-    int host_pack(const uint8_t *t, size_t n, uint32_t k, uint32_t min_qual, PackedReads &pr, std::string &err, uint64_t flush_bases = 0,
-                  const FlushFn &flush = nullptr, uint64_t rec_base = 0) const {
-        return fasta() ? pack_fasta(t, n, k, pr, err, 0, nullptr, 0, flush_bases, flush, rec_base) : pack_fastq(t, n, k, min_qual, pr, err, 0, nullptr, 0, flush_bases, flush, rec_base);
-    }
-    std::string one_record_too_long(uint64_t bytes, const Knobs &kn) const {
-        return std::string(entry()) + ": a single FASTA record of " + std::to_string(bytes) + " bytes exceeds one batch (SHK_BATCH_BASES = " +
-               std::to_string(kn.batch_bases) + "): a record is never split";
-    }
-};
-}  // namespace
-
-int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual, uint32_t rank,
-                     uint32_t world, int device, void *stream, FastqShare &out, std::string &err, bool allow_batches, RecFmt fmt) {
-    const ShareFormat sf{fmt};
-    if ((!fq1 && (n1 || fq2)) || (!fq2 && n2)) { err = std::string(sf.entry()) + ": a null file with a size, or a second file without a first"; return SHK_E_PARAM; }
-    if (world == 0 || rank >= world) { err = std::string(sf.entry()) + ": rank beyond world"; return SHK_E_PARAM; }
-    const Knobs kn;
-    const uint8_t *const fq[2] = {fq1, fq2}; const size_t fn[2] = {n1, fq2 ? n2 : 0};
-    const int nf = fq2 ? 2 : (fq1 ? 1 : 0);
-    enum Route { None, BgzfSlice, MemberWhole, TextSlice, Host };
-    static const char *const route_name[] = {"", "bgzf_slice", "member_whole", "text_slice", "host"};
-    struct File {
-        BgzfChain chain; bool walked = false, gz = false;      // walked: a complete BGZF chain — its cuts lie at block starts, on every route
-        ByteVec st; const uint8_t *t = nullptr; size_t l = 0, e = 0; bool host_text = false;
-        uint64_t s0 = 0, s1 = 0;                                // the slice inside the host text
-        Route route = None;
-    } f[2];
-    for (int i = 0; i < nf; i++) {
-        f[i].gz = fn[i] >= 18 && fq[i][0] == 0x1F && fq[i][1] == 0x8B;
-        size_t bs = 0; const char *why = "";
-        f[i].walked = f[i].gz && bgzf_block(fq[i], fn[i], bs) && bgzf_walk(fq[i], fn[i], f[i].chain, why) == 0;
-    }
-    // the host's text of file i (read once) and the slice in it
-    auto host_slice = [&](int i) -> int {
-        File &F = f[i];
-        if (F.host_text) return SHK_OK;
-        if (int ri = maybe_inflate(fq[i], fn[i], F.st, F.t, F.l, err)) return code_of(Rc::Inflater, ri);
-        F.e = trimmed_len(F.t, F.l);
-        uint64_t c0 = slice_cut(F.e, rank, world), c1 = slice_cut(F.e, rank + 1, world);
-        if (F.walked) bgzf_slice_cuts(F.chain, rank, world, c0, c1);
-        sf.bounds(F.t, F.e, rank, world, c0, c1, F.s0, F.s1);
-        F.host_text = true;
-        return SHK_OK;
-    };
-    auto too_large = [&](uint64_t bases_or_half_bytes) -> bool {
-        if (bases_or_half_bytes <= kn.batch_bases) return false;
-        err = std::string(sf.entry()) + ": this rank's share exceeds one batch (SHK_BATCH_BASES = " + std::to_string(kn.batch_bases) +
-              " packed bases); several batches per rank are not supported: use more ranks or split the input";
-        return true;
-    };
-    // beyond one batch, for the caller that takes batches: nothing is held, read_fastq_share_batches reads the share (again)
-    auto in_batches = [&](uint64_t text_ub) -> int {
-        err.clear();
-        gpu_packed_free(out.gp); out.gp = GpuPacked();
-        for (GpuPacked &g : out.held_gp) gpu_packed_free(g);
-        for (void *p : out.held_up) device_free(p);
-        out.held_gp.clear(); out.held_up.clear(); out.batches.clear();
-        out.n_seg = out.n_bases = out.n_reads = out.n_input_bases = 0;
-        out.in_batches = true; out.text_ub = text_ub;
-        return SHK_OK;
-    };
-    if (allow_batches) {
-        // decided before anything is uploaded, where the host can tell: the ISIZE sums of the rank's run, the slice bounds of plain
-        // text, a plain member's ISIZE field over the ranks (a guess: what it misses is found after the inflation, below)
-        uint64_t text = 0;
-        for (int i = 0; i < nf; i++) {
-            if (f[i].walked) { uint64_t c0 = 0, c1 = 0; bgzf_slice_cuts(f[i].chain, rank, world, c0, c1); text += c1 - c0; }
-            else if (f[i].gz) { const uint8_t *t = fq[i] + fn[i] - 4; text += (t[0] | ((uint64_t)t[1] << 8) | ((uint64_t)t[2] << 16) | ((uint64_t)t[3] << 24)) / world; }
-            else { if (int rc = host_slice(i)) return rc; text += f[i].s1 - f[i].s0; }
-        }
-        if (sf.bases_ub(text) > kn.batch_bases) return in_batches(text);
-    }
-    auto finish = [&](bool host_parsed) -> int {
-        for (int i = 0; i < nf; i++) {
-            const Route r = host_parsed ? Host : f[i].route;
-            out.n_bgzf_slice += r == BgzfSlice; out.n_member_whole += r == MemberWhole; out.n_text_slice += r == TextSlice; out.n_host += r == Host;
-            if (out.route.find(route_name[r]) == std::string::npos) out.route += (out.route.empty() ? "" : "+") + std::string(route_name[r]);
-        }
-        return SHK_OK;
-    };
-    if (sf.fasta()) {
-        // ---- FASTA: file by file — its slice as a span of text in HBM and the device packer, or the host packer on the host's slice
-        // (SHK_HOST_PARSER=1, a host-resident slice below SHK_FASTA_DEVICE_MIN, what the device packer declines)
-        uint64_t text_bytes = 0;
-        for (int i = 0; i < nf; i++) {
-            File &F = f[i];
-            DevSpan span;
-            bool on_host = kn.host_parser;
-            if (!on_host && F.gz && kn.gunzip_device) {
-                int rc = 1;
-                if (F.walked) {
-                    const char *why = ""; uint64_t up = 0;
-                    rc = gpu_bgzf_slice(fq[i], F.chain, rank, world, device, stream, span, up, why, err, fmt);
-                    out.uploaded_bytes += up;
-                    if (!rc) F.route = BgzfSlice;
-                } else {
-                    Text text;
-                    rc = gpu_inflate_member(fq[i], fn[i], device, stream, text, err);
-                    if (!rc) {
-                        out.uploaded_bytes += fn[i];
-                        if ((rc = gpu_text_slice(text, rank, world, stream, span, err, fmt)) == 0) F.route = MemberWhole;
-                    }
-                }
-                if (rc < 0) return code_of(Rc::DeviceNoParam, rc);
-            }
-            Packed gp;
-            if (F.route == None) {
-                if (int rc = host_slice(i)) return rc;
-                F.route = F.gz ? Host : TextSlice;
-                on_host = on_host || F.s1 - F.s0 < kn.fasta_device_min;
-                text_bytes += F.s1 - F.s0;
-            } else text_bytes += span.len;
-            // (a byte is a base: the share goes in batches when its text exceeds one)
-            if (too_large(text_bytes)) return allow_batches ? in_batches(text_bytes) : SHK_E_PARAM;
-            if (!on_host) {
-                Text text;
-                if (F.route == BgzfSlice || F.route == MemberWhole) {
-                    if (int rc = gpu_join_spans(&span, 1, stream, text, err)) return code_of(Rc::DeviceNoParam, rc);
-                    span.blk.put();
-                } else {
-                    if (int rc = gpu_upload_text(F.t + F.s0, (size_t)(F.s1 - F.s0), device, text, err)) return code_of(Rc::DeviceNoParam, rc);
-                    out.uploaded_bytes += text.e;
-                }
-                const int rc = text.e ? sf.device_pack(text, k, min_qual, stream, gp, err) : 0;
-                if (rc < 0) return code_of(Rc::Device, rc);
-                if (rc) { gp.reset(); on_host = true; }    // declined: the host packer owns the message
-            }
-            FastqShare::Batch b{nullptr, nullptr, 0, 0, 0};
-            if (!on_host) {
-                b = FastqShare::Batch{gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases, gp.n_reads};
-                out.n_input_bases += gp.n_input_bases;
-                out.held_gp.push_back(gp);
-                static_cast<GpuPacked &>(gp) = GpuPacked();      // (the blocks are the share's now)
-            } else {
-                F.route = Host;
-                if (int rc = host_slice(i)) return rc;
-                PackedReads pr;
-                if (int rc = sf.host_pack(F.t + F.s0, (size_t)((F.s1 == F.e ? F.l : F.s1) - F.s0), k, min_qual, pr, err)) return code_of(Rc::Parser, rc);
-                out.n_input_bases += pr.n_input_bases;
-                b.n_reads = pr.n_reads;
-                if (pr.n_seg()) {
-                    pr.finish();
-                    void *db = nullptr, *ds = nullptr;
-                    int rc = device_upload(pr.bases.data(), pr.bases.size() * 4, &db, err);
-                    if (!rc) rc = device_upload(pr.seg_off.data(), pr.seg_off.size() * 4, &ds, err);
-                    out.held_up.push_back(db); out.held_up.push_back(ds);
-                    if (rc) return SHK_E_OOM;
-                    out.uploaded_bytes += (pr.bases.size() + pr.seg_off.size()) * 4;
-                    b.d_bases = (const uint32_t *)db; b.d_seg_off = (const uint32_t *)ds; b.n_seg = pr.n_seg(); b.n_bases = pr.n_bases;
-                }
-            }
-            out.n_seg += b.n_seg; out.n_bases += b.n_bases; out.n_reads += b.n_reads;
-            out.batches.push_back(b);
-        }
-        if (out.batches.empty()) out.batches.push_back(FastqShare::Batch{nullptr, nullptr, 0, 0, 0});
-        return finish(false);
-    }
-    // ---- the device: every file's slice as a span of text in HBM, joined, parsed
-    bool host_parser = kn.host_parser;
-    if (!host_parser) {
-        DevSpan spans[2];
-        for (int i = 0; i < nf; i++) {
-            File &F = f[i];
-            if (F.gz && kn.gunzip_device) {
-                int rc = 1;
-                if (F.walked) {
-                    const char *why = ""; uint64_t up = 0;
-                    rc = gpu_bgzf_slice(fq[i], F.chain, rank, world, device, stream, spans[i], up, why, err);
-                    out.uploaded_bytes += up;
-                    if (!rc) F.route = BgzfSlice;
-                } else {
-                    Text text;
-                    rc = gpu_inflate_member(fq[i], fn[i], device, stream, text, err);
-                    if (!rc) {
-                        out.uploaded_bytes += fn[i];
-                        if ((rc = gpu_text_slice(text, rank, world, stream, spans[i], err)) == 0) F.route = MemberWhole;
-                    }
-                }
-                if (rc < 0) return code_of(Rc::DeviceNoParam, rc);
-            }
-            if (F.route != None) continue;
-            // plain text, or what the device inflater declined: cut on the host, the slice alone is uploaded
-            if (int rc = host_slice(i)) return rc;
-            Text text;
-            if (int rc = gpu_upload_text(F.t + F.s0, (size_t)(F.s1 - F.s0), device, text, err)) return code_of(Rc::DeviceNoParam, rc);
-            out.uploaded_bytes += text.e;
-            spans[i].len = text.e; spans[i].unterminated = text.unterminated;
-            spans[i].blk = PoolBlock(text.d, text.pool_bytes);
-            static_cast<GpuText &>(text) = GpuText();      // (the block is the span's now)
-            F.route = F.gz ? Host : TextSlice;
-        }
-        uint64_t bytes = 0;
-        for (int i = 0; i < nf; i++) bytes += spans[i].len;
-        if (too_large(bytes / 2)) return allow_batches ? in_batches(bytes) : SHK_E_PARAM;
-        Text joined;
-        if (int rc = gpu_join_spans(spans, nf, stream, joined, err)) return code_of(Rc::DeviceNoParam, rc);
-        for (int i = 0; i < nf; i++) spans[i].blk.put();
-        const int rc = gpu_pack_fastq(nullptr, 0, nullptr, 0, k, min_qual, 0, stream, out.gp, err, 0, &joined);
-        if (rc < 0) { gpu_packed_free(out.gp); out.gp = GpuPacked(); return code_of(Rc::Device, rc); }
-        if (rc == 0) {
-            if (too_large(out.gp.n_bases)) return allow_batches ? in_batches(bytes) : SHK_E_PARAM;
-            out.d_bases = out.gp.d_bases; out.d_seg_off = out.gp.d_seg_off;
-            out.n_seg = out.gp.n_seg; out.n_bases = out.gp.n_bases; out.n_reads = out.gp.n_reads; out.n_input_bases = out.gp.n_input_bases;
-            return finish(false);
-        }
-        gpu_packed_free(out.gp); out.gp = GpuPacked();
-        host_parser = true;                               // not regular 4-line FASTQ: the host parser owns the messages
-    }
-    // ---- the host parser on the same slices
-    PackedReads pr;
-    for (int i = 0; i < nf; i++) {
-        if (int rc = host_slice(i)) return rc;
-        // A slice that reaches the end of the text takes the blank lines behind it along: trimmed_len cannot tell a blank line
-        // from the line end that closes the empty quality line of a last record without bases, and the parser skips the others.
-        const uint64_t end = f[i].s1 == f[i].e ? f[i].l : f[i].s1;
-        if (int rc = pack_fastq(f[i].t + f[i].s0, (size_t)(end - f[i].s0), k, min_qual, pr, err)) return code_of(Rc::Parser, rc);
-    }
-    if (too_large(pr.n_bases)) {
-        if (!allow_batches) return SHK_E_PARAM;
-        uint64_t text = 0;
-        for (int i = 0; i < nf; i++) text += f[i].s1 - f[i].s0;
-        return in_batches(text);
-    }
-    out.n_reads = pr.n_reads; out.n_input_bases = pr.n_input_bases;
-    if (pr.n_seg()) {
-        pr.finish();
-        int rc = device_upload(pr.bases.data(), pr.bases.size() * 4, &out.up_bases, err);
-        if (!rc) rc = device_upload(pr.seg_off.data(), pr.seg_off.size() * 4, &out.up_seg_off, err);
-        if (rc) return SHK_E_OOM;
-        out.uploaded_bytes += (pr.bases.size() + pr.seg_off.size()) * 4;
-        out.d_bases = (const uint32_t *)out.up_bases; out.d_seg_off = (const uint32_t *)out.up_seg_off;
-        out.n_seg = pr.n_seg(); out.n_bases = pr.n_bases;
-    }
-    return finish(true);
-}
-
-// ---- the same share, beyond one batch: batch by batch into pass 1 of the shard layer (preprocess.h) --------------------------
-int read_fastq_share_batches(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual, uint32_t rank,
-                             uint32_t world, int device, void *stream, ShardBatchSink &sink, FastqShare &out, std::string &err, RecFmt fmt) {
-    const ShareFormat sf{fmt};
-    if ((!fq1 && (n1 || fq2)) || (!fq2 && n2)) { err = std::string(sf.entry()) + ": a null file with a size, or a second file without a first"; return SHK_E_PARAM; }
-    if (world == 0 || rank >= world) { err = std::string(sf.entry()) + ": rank beyond world"; return SHK_E_PARAM; }
-    const Knobs kn;
-    const uint8_t *const fq[2] = {fq1, fq2}; const size_t fn[2] = {n1, fq2 ? n2 : 0};
-    const int nf = fq2 ? 2 : (fq1 ? 1 : 0);
-    const uint64_t piece_bytes = sf.piece_bytes(kn);
-    enum Route { None, BgzfSlice, MemberWhole, TextSlice, Host };
-    static const char *const route_name[] = {"", "bgzf_slice", "member_whole", "text_slice", "host"};
-    struct File {
-        BgzfChain chain; bool walked = false, gz = false;
-        ByteVec st; const uint8_t *t = nullptr; size_t l = 0, e = 0; bool host_text = false;
-        uint64_t s0 = 0, s1 = 0;                           // the slice inside the host text
-        uint64_t est = 0;                                  // bytes of text of the slice, as far as known beforehand (progress)
-    } f[2];
-    auto host_slice = [&](int i) -> int {                  // the host's text of file i (read once) and the slice in it
-        File &F = f[i];
-        if (F.host_text) return SHK_OK;
-        if (int ri = maybe_inflate(fq[i], fn[i], F.st, F.t, F.l, err)) return code_of(Rc::Inflater, ri);
-        F.e = trimmed_len(F.t, F.l);
-        uint64_t c0 = slice_cut(F.e, rank, world), c1 = slice_cut(F.e, rank + 1, world);
-        if (F.walked) bgzf_slice_cuts(F.chain, rank, world, c0, c1);
-        sf.bounds(F.t, F.e, rank, world, c0, c1, F.s0, F.s1);
-        F.host_text = true;
-        return SHK_OK;
-    };
-    uint64_t total = 0;
-    for (int i = 0; i < nf; i++) {
-        File &F = f[i];
-        F.gz = fn[i] >= 18 && fq[i][0] == 0x1F && fq[i][1] == 0x8B;
-        size_t bs = 0; const char *why = "";
-        F.walked = F.gz && bgzf_block(fq[i], fn[i], bs) && bgzf_walk(fq[i], fn[i], F.chain, why) == 0;
-        if (F.walked) { uint64_t c0 = 0, c1 = 0; bgzf_slice_cuts(F.chain, rank, world, c0, c1); F.est = c1 - c0; }
-        else if (F.gz) { const uint8_t *t = fq[i] + fn[i] - 4; F.est = (t[0] | ((uint64_t)t[1] << 8) | ((uint64_t)t[2] << 16) | ((uint64_t)t[3] << 24)) / world; }
-        else { if (int rc = host_slice(i)) return rc; F.est = F.s1 - F.s0; }
-        total += F.est;
-    }
-    uint64_t reads = 0, before = 0;                        // the rank's reads so far; the text of the files that are done
-    int at_file = 0;
-    auto hand = [&](const uint32_t *d_bases, const uint32_t *d_seg_off, uint64_t n_seg, uint64_t n_bases, uint64_t file_done) -> int {
-        out.n_batches++; out.n_seg += n_seg; out.n_bases += n_bases;
-        const int rc = sink.batch(n_seg ? d_bases : nullptr, n_seg ? d_seg_off : nullptr, n_seg, n_bases, reads, before + std::min(file_done, f[at_file].est), total);
-        if (rc) err.clear();
-        return rc;
-    };
-    // a piece of regular text on the device -> parser -> one batch.  DECLINED: not regular 4-line FASTQ (nothing was counted)
-    auto device_piece = [&](const GpuText &text, uint64_t file_done) -> int {
-        Packed gp;
-        const int rc = sf.device_pack(text, k, min_qual, stream, gp, err);
-        if (rc < 0) return code_of(Rc::Device, rc);
-        if (rc) return DECLINED;
-        out.n_windows++;
-        reads += gp.n_reads; out.n_reads += gp.n_reads; out.n_input_bases += gp.n_input_bases;
-        return hand(gp.d_bases, gp.d_seg_off, gp.n_seg, gp.n_bases, file_done);
-    };
-    // the host parser from `from` to the end of the slice (its messages count the slice's records: file_reads came before),
-    // a batch every SHK_BATCH_BASES bases
-    // (FASTA: one piece alone, [from, upto))
-    auto host_from = [&](int i, uint64_t from, uint64_t file_reads, uint64_t upto = UINT64_MAX) -> int {
-        File &F = f[i];
-        // (a slice that reaches the end of the text takes the blank lines behind it along: read_fastq_share says why)
-        const uint64_t end = upto < F.s1 ? upto : (F.s1 == F.e ? F.l : F.s1);
-        if (from >= end) return SHK_OK;
-        PackedReads pr;
-        int flush_rc = SHK_OK;
-        uint64_t counted = 0, counted_in = 0;              // reads and input bases of pr that are in the totals already
-        auto flush = [&](PackedReads &p, uint64_t file_done) -> int {
-            if (p.n_seg() == 0 && p.n_reads == counted) return 0;      // (nothing new)
-            reads += p.n_reads - counted; out.n_reads += p.n_reads - counted; counted = p.n_reads;
-            out.n_input_bases += p.n_input_bases - counted_in; counted_in = p.n_input_bases;
-            void *d_bases = nullptr, *d_off = nullptr;
-            if (p.n_seg()) {
-                p.finish();
-                int rc = device_upload(p.bases.data(), p.bases.size() * 4, &d_bases, err);
-                if (!rc) rc = device_upload(p.seg_off.data(), p.seg_off.size() * 4, &d_off, err);
-                if (rc) { device_free(d_bases); device_free(d_off); flush_rc = SHK_E_OOM; return -7; }
-                out.uploaded_bytes += (p.bases.size() + p.seg_off.size()) * 4;
-            }
-            flush_rc = hand((const uint32_t *)d_bases, (const uint32_t *)d_off, p.n_seg(), p.n_bases, file_done);
-            device_free(d_bases); device_free(d_off);
-            p.reset_stream();
-            return flush_rc ? -7 : 0;
-        };
-        const int rc = sf.host_pack(F.t + from, (size_t)(end - from), k, min_qual, pr, err, kn.batch_bases,
-                                    [&](PackedReads &p) { return flush(p, from - F.s0); }, file_reads);
-        if (rc == -7) return flush_rc;
-        if (rc) return code_of(Rc::Parser, rc);
-        return flush(pr, std::min(end, F.s1) - F.s0) ? flush_rc : SHK_OK;
-    };
-    // A span in pieces of at most piece_bytes, each a batch.  span_at: where the span begins in the file's text; file_base: where
-    // the slice does (progress).  SHK_OK; DECLINED with `stopped` = the span offset at which the host goes on; an error code.
-    auto span_pieces = [&](const DevSpan &span, uint64_t span_at, uint64_t file_base, uint64_t &stopped) -> int {
-        for (uint64_t from = 0; from < span.len;) {
-            Text piece; uint64_t next = 0;
-            const int rc = gpu_span_piece(span, from, piece_bytes, stream, piece, next, err, fmt);
-            if (rc < 0) return code_of(Rc::DeviceNoParam, rc);
-            if (rc && sf.fasta()) { err = sf.one_record_too_long(next - from, kn); return SHK_E_PARAM; }
-            const int prc = rc ? DECLINED : device_piece(piece, span_at + next - file_base);
-            if (prc == DECLINED) { stopped = from; return DECLINED; }
-            if (prc) return prc;
-            from = next;
-        }
-        return SHK_OK;
-    };
-    for (int i = 0; i < nf; i++) {
-        File &F = f[i];
-        at_file = i;
-        Route route = None;
-        uint64_t resume = 0;                               // the file's text in front of this offset has been handed over
-        bool host_parser = kn.host_parser, through = false;
-        const uint64_t reads0 = reads;
-        if (!kn.host_parser && F.gz && kn.gunzip_device) {
-            if (F.walked) {
-                BgzfShareWindows sw;
-                const char *why = "";
-                int rc = sw.open(fq[i], F.chain, rank, world, kn.window.bytes, device, stream, why, err, fmt);
-                if (rc < 0) return code_of(Rc::DeviceNoParam, rc);
-                while (!rc) {
-                    GpuText piece; uint64_t at = 0; bool done = false;
-                    rc = sw.next(piece, at, done, why, err);
-                    if (rc < 0) return code_of(Rc::DeviceNoParam, rc);
-                    if (rc) { resume = sw.consumed(); break; }              // this window is the host reader's, and what follows it
-                    route = BgzfSlice;
-                    if (done) { through = true; break; }
-                    int prc;
-                    if (sf.fasta() && piece.e > piece_bytes) {      // a window (and its carry) of more than a batch: in pieces
-                        DevSpan view; uint64_t stopped = 0;
-                        view.blk = PoolBlock(piece.d, piece.e + 32); view.len = piece.e; view.unterminated = piece.unterminated;
-                        prc = span_pieces(view, at, sw.run_begin(), stopped);
-                        (void)view.blk.take();                      // (the text stays the windows')
-                        if (prc == DECLINED) { resume = at + stopped; host_parser = true; break; }
-                    } else {
-                        prc = device_piece(piece, at + piece.e - sw.run_begin());
-                        if (prc == DECLINED) { resume = at; host_parser = true; break; }
-                    }
-                    if (prc) return prc;
-                }
-                out.uploaded_bytes += sw.uploaded();
-            } else {
-                Text text;
-                int rc = gpu_inflate_member(fq[i], fn[i], device, stream, text, err);
-                if (rc < 0) return code_of(Rc::DeviceNoParam, rc);
-                if (!rc) {
-                    out.uploaded_bytes += fn[i];
-                    DevSpan span;
-                    if ((rc = gpu_text_slice(text, rank, world, stream, span, err, fmt)) < 0) return code_of(Rc::DeviceNoParam, rc);
-                    route = MemberWhole;
-                    through = true;
-                    uint64_t stopped = 0;
-                    const int prc = span_pieces(span, span.off, span.off, stopped);
-                    if (prc == DECLINED) { resume = span.off + stopped; host_parser = true; through = false; }
-                    else if (prc) return prc;
-                }
-            }
-        }
-        if (!through) {
-            // plain text, what the device declined, SHK_HOST_PARSER=1: the host's text, cut on the host
-            if (int rc = host_slice(i)) return rc;
-            route = F.gz ? Host : TextSlice;
-            uint64_t from = std::max(F.s0, resume);
-            // FASTA: the host packer takes pieces too (a record is never split, by either packer), and small slices (SHK_FASTA_DEVICE_MIN)
-            const bool host_pieces = sf.fasta() && (host_parser || F.s1 - F.s0 < kn.fasta_device_min);
-            while ((!host_parser || host_pieces) && from < F.s1) {
-                uint64_t end = F.s1;
-                if (F.s1 - from > piece_bytes) {
-                    const uint64_t at = sf.last_start(F.t + from, (size_t)piece_bytes);
-                    if (sf.fasta() && (at == UINT64_MAX || at == 0)) {
-                        const uint64_t nx = fasta_first_record_start(F.t, (size_t)F.s1, (size_t)from + 1);
-                        err = sf.one_record_too_long((nx == UINT64_MAX ? F.s1 : nx) - from, kn);
-                        return SHK_E_PARAM;
-                    }
-                    if (at == UINT64_MAX || at == 0) { host_parser = true; break; }      // (no record starts inside the piece)
-                    end = from + at;
-                }
-                if (host_pieces) {
-                    route = Host;
-                    if (int rc = host_from(i, from, reads - reads0, end)) return rc;
-                    from = end;
-                    continue;
-                }
-                Text text;
-                if (int rc = gpu_upload_text(F.t + from, (size_t)(end - from), device, text, err)) return code_of(Rc::DeviceNoParam, rc);
-                out.uploaded_bytes += text.e;
-                const int prc = device_piece(text, end - F.s0);
-                if (prc == DECLINED && sf.fasta()) {              // the host packer on this piece: it owns the message
-                    route = Host;
-                    if (int rc = host_from(i, from, reads - reads0, end)) return rc;
-                } else if (prc == DECLINED) { host_parser = true; break; }
-                else if (prc) return prc;
-                from = end;
-            }
-            if (host_parser && !sf.fasta()) {
-                route = Host;
-                if (int rc = host_from(i, from, reads - reads0)) return rc;
-            }
-        }
-        before += F.est;
-        out.n_bgzf_slice += route == BgzfSlice; out.n_member_whole += route == MemberWhole; out.n_text_slice += route == TextSlice; out.n_host += route == Host;
-        if (out.route.find(route_name[route]) == std::string::npos) out.route += (out.route.empty() ? "" : "+") + std::string(route_name[route]);
-    }
-    return SHK_OK;
 }

@@ -3,6 +3,7 @@
 #pragma once
 #include "handle.h"
 #include "fastq_gpu.h"
+#include "share_reader.h"      // routes 8 and 9: one rank's share of FASTQ / FASTA files
 #include "share_windows.h"
 
 int preprocess_impl(shk_handle *h, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2);
@@ -16,62 +17,3 @@ int preprocess_packed_host_impl(shk_handle *h, const uint32_t *bases, const uint
                                 uint64_t n_bases, uint64_t n_reads);
 // the count below which pass 2 emits no row (the shard layer's pass 2 uses the same)
 uint32_t emit_threshold_of(const shk_handle *h);
-
-// ---- one rank's share of FASTQ files as packed batches in HBM: what shk_shard_preprocess_fastq hands to the shard layer and
-// (one batch alone) shk_device_pack_fastq_slice copies back (preprocess.cpp).  Slice `rank` of `world` of every file (fastq.h:
-// the slice rule; world 1: the whole file).  Routes, per file: a BGZF chain — the blocks of the rank's run alone are uploaded
-// and inflated (inflate_gpu.h: gpu_bgzf_slice, BgzfShareWindows); a plain gzip member — inflated whole on the device, then cut
-// (a deflate stream cannot be entered in the middle); plain text — cut on the host, the slice alone is uploaded.  Whatever
-// the device declines is read on the host, whole, and cut there by the same rule; text that is not regular 4-line FASTQ goes
-// through the host parser, which owns the messages (record numbers count from the slice's start).
-//   A share that fits ONE batch (SHK_BATCH_BASES): read_fastq_share — both files of a pair pooled into the one batch.
-//   A larger one (the sharded entry point alone): read_fastq_share says so (in_batches) before it uploads anything, where the
-//   ISIZE sums of the rank's run or the slice bounds of plain text tell, and read_fastq_share_batches then hands the share to
-//   pass 1 batch by batch: a BGZF run in windows of at most SHK_GUNZIP_DEVICE_WINDOW of text, everything else in pieces of about
-//   2 * SHK_BATCH_BASES bytes cut at record starts; the files of a pair one after the other.
-// The same two readers serve shk_shard_preprocess_fasta (fmt = RecFmt::Fasta; SPEC S1a, the slice rule): the bounds are header
-// lines, the packers are gpu_pack_fasta / pack_fasta, a byte of text is a base (pieces of at most SHK_BATCH_BASES bytes), a single
-// record beyond one batch is SHK_E_PARAM, and the files of a pair are packed separately (FastqShare::batches).
-struct FastqShare {
-    shk::GpuPacked gp;                                    // parsed on the device
-    void *up_bases = nullptr, *up_seg_off = nullptr;      // parsed on the host, uploaded
-    const uint32_t *d_bases = nullptr, *d_seg_off = nullptr;
-    uint64_t n_seg = 0, n_bases = 0, n_reads = 0, n_input_bases = 0;      // (in batches: summed over them)
-    uint64_t uploaded_bytes = 0;                          // compressed or text (or host-packed) bytes that crossed PCIe
-    uint32_t n_bgzf_slice = 0, n_member_whole = 0, n_text_slice = 0, n_host = 0;      // files by route; n_host: read or parsed on the host
-    std::string route;                                    // the routes' names, '+' between two that differ
-    bool in_batches = false;                              // the share exceeds one batch: nothing is held, read_fastq_share_batches reads it
-    uint64_t text_ub = 0;                                 // in_batches: bytes of text of the share, or an upper bound (text_ub / 2 bounds its k-mer instances)
-    uint64_t n_batches = 0, n_windows = 0;                // batches handed to pass 1; windows and pieces of text they were parsed from
-    // FASTA: the files of a pair are packed separately (the packers' rule on the lines in front of the first header holds per
-    // file), so a share that fits one batch is held as one batch per file — d_bases / d_seg_off stay null, the counters are sums
-    struct Batch { const uint32_t *d_bases, *d_seg_off; uint64_t n_seg, n_bases, n_reads; };
-    std::vector<Batch> batches;
-    std::vector<shk::GpuPacked> held_gp; std::vector<void *> held_up;      // what the batches lie in
-    FastqShare() = default;
-    FastqShare(const FastqShare &) = delete;
-    FastqShare &operator=(const FastqShare &) = delete;
-    ~FastqShare();
-};
-// SHK_OK, or the SHK_E_* code with its message in err; an oversized share (beyond one batch) is SHK_E_PARAM unless
-// allow_batches (then SHK_OK with out.in_batches)
-// fmt: the record format — the slice bounds, the packers (FASTA: gpu_pack_fasta from SHK_FASTA_DEVICE_MIN bytes of host-resident
-// slice on, pack_fasta below it; text born on the device is packed there), the cut of pieces and the bases per byte of text
-int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual, uint32_t rank,
-                     uint32_t world, int device, void *stream, FastqShare &out, std::string &err, bool allow_batches = false,
-                     shk::RecFmt fmt = shk::RecFmt::Fastq);
-
-// where the batches of a share go: pass 1 of the shard layer (api.cpp: shard_preprocess_impl)
-struct ShardBatchSink {
-    virtual ~ShardBatchSink() = default;
-    // One batch (< 2^32 bases; n_seg == 0: reads without a segment) -> pass 1; the batch's memory is the caller's again on return.
-    // reads: this rank's reads so far, the batch's included; text_done of text_total: how much of the share's text is consumed
-    // (the percentage of the progress string).  SHK_OK, or the code of an error that is set in the handle.
-    virtual int batch(const uint32_t *d_bases, const uint32_t *d_seg_off, uint64_t n_seg, uint64_t n_bases, uint64_t reads,
-                      uint64_t text_done, uint64_t text_total) = 0;
-};
-// The share of any size, batch by batch into `sink`; out: the counters (nothing is held).  SHK_OK; the SHK_E_* code of a reading
-// error with its message in err; or the code sink.batch returned, with err empty.
-int read_fastq_share_batches(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, uint32_t k, uint32_t min_qual, uint32_t rank,
-                             uint32_t world, int device, void *stream, ShardBatchSink &sink, FastqShare &out, std::string &err,
-                             shk::RecFmt fmt = shk::RecFmt::Fastq);
