@@ -469,6 +469,23 @@ char *shk_device_unitig_chains(uint32_t k, uint64_t n_recs, const uint64_t *firs
  * for one preprocess+assemble); this returns the cache to the driver.  SHK_NO_POOL=1 disables it. */
 void shk_release_cached_memory(void);
 
+/* ---- test support: the block cache's fill-on-hand-out mode.  A block of the cache is never cleared: a buffer starts with what
+ * its previous user left, and — a request is rounded up to 4 KiB (to 256 MiB above 256 MiB) and a cached block of up to
+ * bytes + bytes/2 + 1 MiB may be handed out instead — ends in a tail nobody wrote.  With the mode on, every block is filled
+ * with `word`, the whole rounded block, fresh or reused, before it is handed out, and so are the two device allocations that
+ * do not come from the cache (the uploads of the host-buffer entry points, a communicator's stage buffer): the contents a
+ * buffer starts with become an input a test chooses, and no result may depend on it.  Off by default, where it costs one
+ * atomic load per hand-out.  The fill runs on the null stream and waits for the whole device, so the mode serialises the
+ * handles of a process: it shows a dependence on stale memory, not a race.  SHK_POOL_FILL=<hex word> in the environment,
+ * read once where SHK_NO_POOL is read, turns it on from the start (rank workers, tools).
+ *   shk_debug_pool_fill          sets the mode for the process; returns the previous `on`
+ *   shk_debug_pool_filled_bytes  the bytes filled so far in this process
+ *   shk_debug_pool_probe         takes a block for `bytes`, downloads its first and last 32-bit word, gives it back (needs a
+ *                                GPU); *block_bytes: the size of the block that was handed out.  SHK_OK, SHK_E_OOM, SHK_E_DEVICE */
+int shk_debug_pool_fill(int on, uint32_t word);
+uint64_t shk_debug_pool_filled_bytes(void);
+int shk_debug_pool_probe(size_t bytes, uint32_t *first_word, uint32_t *last_word, size_t *block_bytes);
+
 /* Measurement helper (bench.py): best rate in GB/s of `iters` pure streaming reads of a
  * `bytes` device buffer on the current HIP device — the achievable HBM read peak of this box, reported
  * beside the nominal 8 TB/s.  No counterpart in the reference. */

@@ -104,6 +104,9 @@ SIGNATURES = {
     "shk_host_unitig_chains": (_vp, [_u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "shk_device_unitig_chains": (_vp, [_u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "shk_release_cached_memory": (None, []),
+    "shk_debug_pool_fill": (_int, [_int, _u32]),
+    "shk_debug_pool_filled_bytes": (_u64, []),
+    "shk_debug_pool_probe": (_int, [_sz, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_sz)]),
     "shk_measure_stream_read": (_int, [_sz, _int, C.POINTER(C.c_double)]),
     "shk_version": (_cp, []),
 }

@@ -71,6 +71,20 @@ static std::set<ShardComm *> &live_comms() { static auto *s = new std::set<Shard
 static bool comm_is_live(ShardComm *c) { std::lock_guard<std::mutex> lk(g_live_mu); return live_comms().count(c) != 0; }
 
 void shk_release_cached_memory(void) { device_pool_trim(); big_trim(); }
+// ---- test support: the pool's fill-on-hand-out mode (block_cache.h)
+int shk_debug_pool_fill(int on, uint32_t word) { return device_pool_fill(on != 0, word); }
+uint64_t shk_debug_pool_filled_bytes(void) { return device_pool_filled_bytes(); }
+int shk_debug_pool_probe(size_t bytes, uint32_t *first_word, uint32_t *last_word, size_t *block_bytes) {
+    PoolBlock b;
+    if (!b.get(bytes)) return SHK_E_OOM;
+    std::string err;
+    uint32_t first = 0, last = 0;
+    if (device_download(&first, b.p, 4, err) || device_download(&last, b.as<char>() + b.bytes - 4, 4, err)) return SHK_E_DEVICE;
+    if (first_word) *first_word = first;
+    if (last_word) *last_word = last;
+    if (block_bytes) *block_bytes = b.bytes;
+    return SHK_OK;
+}
 int shk_measure_stream_read(size_t bytes, int iters, double *gbs) {
     std::string err;
     const int rc = stream_read_gbs(bytes, iters, gbs, err);

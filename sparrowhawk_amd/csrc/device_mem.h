@@ -37,6 +37,12 @@ int device_download(void *host, const void *dptr, size_t bytes, std::string &err
 void *device_pool_alloc(size_t &bytes, int *hip_error = nullptr);
 void device_pool_release(void *p, size_t bytes);
 void device_pool_trim();
+// test mode of the pool (block_cache.h; shk_debug_pool_fill): on, every block is filled with `word`, all of it, when it is
+// handed out.  device_pool_fill returns the previous `on`.  device_fill_outside_pool: for the two device allocations that do
+// not come from the pool (device_upload, the communicator's stage buffer) — filled by the same rule, nothing when off.
+int device_pool_fill(bool on, uint32_t word);
+uint64_t device_pool_filled_bytes();
+void device_fill_outside_pool(void *p, size_t bytes);
 
 // peak device memory per handle (Assembler.ts:69-71,137 reports peak wasm memory with every assembly): an accounting context
 // is made per handle, carried by the thread that serves it (mem_acct_set returns the previous one), and every block the pool

@@ -37,14 +37,33 @@ int device_count() {
     return n;
 }
 
-static BlockCache &dev_pool() {               // never destroyed (HIP teardown order); SHK_NO_POOL=1 is read once
+// The fill of the pool's test mode (block_cache.h).  The null stream, then a wait for the WHOLE device: the library owns
+// hipStreamNonBlocking streams (fastq_gpu.hip, inflate_gpu.hip, the copy stream), which the null stream does not order itself
+// against, and the pool does not know which stream will use the block.  So this mode serialises the handles of a process: it
+// shows a result that depends on stale memory, it does not show races.  (A tail of bytes % 4 exists only outside the pool.)
+static void hip_fill(void *p, size_t bytes, uint32_t word) {
+    if (bytes / 4) (void)hipMemsetD32Async((hipDeviceptr_t)p, (int)word, bytes / 4, nullptr);
+    for (size_t i = bytes & ~(size_t)3; i < bytes; i++) (void)hipMemsetD8Async((hipDeviceptr_t)((char *)p + i), (unsigned char)(word >> (8 * (i & 3))), 1, nullptr);
+    (void)hipDeviceSynchronize();
+}
+static BlockCache &dev_pool() {               // never destroyed (HIP teardown order); SHK_NO_POOL=1 and SHK_POOL_FILL are read once
     static BlockCache *p = [] {
         const char *v = getenv("SHK_NO_POOL");
-        const BlockBackend hip{current_device, [](void **q, size_t bytes) { return (int)hipMalloc(q, bytes); }, [](void *q) { (void)hipFree(q); }};
-        return new BlockCache(hip, !(v && *v == '1'));
+        const BlockBackend hip{current_device, [](void **q, size_t bytes) { return (int)hipMalloc(q, bytes); }, [](void *q) { (void)hipFree(q); }, hip_fill};
+        BlockCache *c = new BlockCache(hip, !(v && *v == '1'));
+        const char *f = getenv("SHK_POOL_FILL");          // <hex word>: the test mode is on from the start (rank workers, tools)
+        if (f && *f) {
+            char *end = nullptr;
+            const unsigned long long w = strtoull(f, &end, 16);
+            if (end != f && !*end && w <= 0xFFFFFFFFull) c->set_fill(true, (uint32_t)w);
+        }
+        return c;
     }();
     return *p;
 }
+int device_pool_fill(bool on, uint32_t word) { return dev_pool().set_fill(on, word); }
+uint64_t device_pool_filled_bytes() { return dev_pool().filled_bytes.load(); }
+void device_fill_outside_pool(void *p, size_t bytes) { dev_pool().fill_outside(p, bytes); }
 void device_pool_trim() { dev_pool().trim(); }
 void *device_pool_alloc(size_t &bytes, int *hip_error) {
     int e = 0;
@@ -98,6 +117,7 @@ std::mutex &upload_token(int dev) { static std::mutex m[16]; return m[(unsigned)
 int device_upload(const void *host, size_t bytes, void **dptr, std::string &err) {
     *dptr = nullptr;
     HIPCHK(hipMalloc(dptr, bytes ? bytes : 4));
+    device_fill_outside_pool(*dptr, bytes ? bytes : 4);
     if (bytes) {
         hipError_t e = hipMemcpy(*dptr, host, bytes, hipMemcpyHostToDevice);
         if (e != hipSuccess) { (void)hipFree(*dptr); *dptr = nullptr; err = hipGetErrorString(e); return -5; }

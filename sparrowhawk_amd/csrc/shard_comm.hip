@@ -149,6 +149,7 @@ ShardComm *comm_create(const uint8_t id[SHARD_UNIQUE_ID_BYTES], int rank, int wo
         err = "out of device memory (communicator staging)";
         (void)R.CommDestroy(c->comm); delete c; return nullptr;
     }
+    device_fill_outside_pool(c->stage, c->stage_bytes);      // (not a block of the pool: the pool's test mode covers it all the same)
     return c;
 }
 

@@ -1,8 +1,10 @@
 // The bookkeeping of the device block pool (csrc/block_cache.h) and its two owners (csrc/device_mem.h: PoolBlock, PoolScope)
-// on a backend of malloc / free with counters and a settable "current device": no GPU, no HIP.  Built with
+// on a backend of malloc / free with counters and a settable "current device", and the fill-on-hand-out test mode of the
+// pool on a backend whose fill writes (or only notes) what it is asked for: no GPU, no HIP.  Built with
 // -fsanitize=address,undefined by tests/test_device_pool_host.py; prints "ok" and returns 0, or names the line that failed.
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <set>
 #include <string>
 
@@ -161,6 +163,113 @@ static void test_trim() {
     c.trim(); CHECK(g_frees == f0 + 5);                   // every cached block exactly once
 }
 
+// ---- the fill-on-hand-out mode: a backend whose blocks are written by malloc's owner (0xA5 everywhere, so a byte the fill
+// missed shows) and whose fill is counted
+static long g_fills = 0; static uint64_t g_fill_bytes = 0;
+static int dirty_alloc(void **p, size_t bytes) { const int e = fake_alloc(p, bytes); if (!e) memset(*p, 0xA5, bytes); return e; }
+static void fake_fill(void *p, size_t bytes, uint32_t word) {
+    g_fills++; g_fill_bytes += bytes;
+    for (size_t i = 0; i < bytes; i++) ((unsigned char *)p)[i] = (unsigned char)(word >> (8 * (i & 3)));
+}
+static const BlockBackend DIRTY{fake_cur_dev, dirty_alloc, fake_free, fake_fill};
+// a backend that never touches the memory: the fill notes what it was asked for
+static void *g_noted_p = nullptr; static size_t g_noted_bytes = 0; static uint32_t g_noted_word = 0;
+static void note_fill(void *p, size_t bytes, uint32_t word) { g_fills++; g_fill_bytes += bytes; g_noted_p = p; g_noted_bytes = bytes; g_noted_word = word; }
+static const BlockBackend UNTOUCHED{fake_cur_dev, fake_alloc, fake_free, note_fill};
+
+static bool all_words(const void *p, size_t bytes, uint32_t word) {
+    for (size_t i = 0; i < bytes; i++) if (((const unsigned char *)p)[i] != (unsigned char)(word >> (8 * (i & 3)))) return false;
+    return true;
+}
+
+static void test_fill() {
+    const uint32_t W = 0x01020304u;                       // (four different bytes: a byte-wise fill in the wrong order shows)
+    BlockCache c(DIRTY, true);
+    size_t b = 0;
+    const long f0 = g_fills; const uint64_t fb0 = g_fill_bytes;
+    // off: the backend's fill is never called, nothing is counted
+    void *p = get(c, 5000, &b); CHECK(b == 8192 && all_words(p, b, 0xA5A5A5A5u) && g_fills == f0 && c.filled_bytes == 0);
+    c.put(p, b);
+    void *q = get(c, 4097, &b); CHECK(q == p && g_fills == f0 && c.filled_bytes == 0);
+    c.put(q, b);
+    c.fill_outside(q, 16); CHECK(g_fills == f0 && all_words(q, 16, 0xA5A5A5A5u));
+    c.trim();
+    // on: the setter returns the previous state
+    CHECK(c.set_fill(true, W) == 0 && c.set_fill(true, W) == 1);
+    uint64_t handed = 0;
+    // a fresh block, all of the rounded size
+    const long a0 = g_allocs;
+    p = get(c, 5000, &b); CHECK(g_allocs == a0 + 1 && b == 8192 && all_words(p, b, W)); handed += b;
+    // a reused block of the same size, dirtied by its user meanwhile
+    memset(p, 0x5A, b); c.put(p, b);
+    q = get(c, 8192, &b); CHECK(q == p && g_allocs == a0 + 1 && b == 8192 && all_words(q, b, W)); handed += b;
+    c.put(q, b);
+    // a reused larger block: its tail beyond the bytes asked for is filled too
+    void *big = get(c, 3 << 20, &b); CHECK(b == (3u << 20)); handed += b;
+    memset(big, 0x5A, b); c.put(big, b);
+    q = get(c, (2 << 20) + 1, &b); CHECK(q == big && b == (3u << 20) && all_words(q, b, W)); handed += b;
+    c.put(q, b);
+    // another word takes effect at the next hand-out
+    CHECK(c.set_fill(true, 0xFFFFFFFFu) == 1);
+    q = get(c, 100, &b); CHECK(b == 8192 && all_words(q, b, 0xFFFFFFFFu)); handed += b;
+    c.put(q, b);
+    CHECK(c.set_fill(true, W) == 1);
+    // the retry after trim(): the first allocation is refused, the cache dropped, the second block filled
+    const long fr0 = g_frees;
+    g_refuse = 1;
+    p = get(c, 64 << 10, &b); CHECK(p && b == (64u << 10) && g_frees > fr0 && c.free_blocks.empty() && all_words(p, b, W)); handed += b;
+    c.put(p, b);
+    // a refusal that stays one fills nothing
+    const long f1 = g_fills;
+    g_refuse = 2;
+    size_t want = 1 << 20; int e = 0;
+    CHECK(!c.get(want, e) && e != 0 && g_fills == f1);
+    // memory from outside the cache, by the same rule: the bytes given, no rounding
+    unsigned char outside[24]; memset(outside, 0xA5, sizeof outside);
+    c.fill_outside(outside, 10); CHECK(all_words(outside, 10, W) && all_words(outside + 12, 12, 0xA5A5A5A5u) && outside[10] == 0xA5 && outside[11] == 0xA5);
+    c.fill_outside(nullptr, 8); c.fill_outside(outside, 0);
+    CHECK(c.filled_bytes == handed + 10 && g_fill_bytes - fb0 == handed + 10);
+    // off again: the previous state comes back, and nothing more is filled or counted
+    CHECK(c.set_fill(false, 0) == 1 && c.set_fill(false, 0) == 0);
+    const long f2 = g_fills;
+    p = get(c, 64 << 10, &b); memset(p, 0x5A, b); c.put(p, b);
+    q = get(c, 64 << 10, &b); CHECK(q == p && all_words(q, b, 0x5A5A5A5Au) && g_fills == f2 && c.filled_bytes == handed + 10);
+    c.put(q, b);
+    c.trim();
+    CHECK(g_live.empty());
+    // a disabled cache (SHK_NO_POOL) fills its fresh blocks all the same
+    {
+        BlockCache d(DIRTY, false);
+        d.set_fill(true, W);
+        p = get(d, 1, &b); CHECK(b == 4096 && all_words(p, b, W) && d.filled_bytes == 4096);
+        d.put(p, b);
+    }
+    // a backend without a fill: the mode is accepted and does nothing
+    {
+        BlockCache n(FAKE, true);
+        n.set_fill(true, W);
+        p = get(n, 1, &b); CHECK(p && n.filled_bytes == 0);
+        n.put(p, b); n.trim();
+    }
+    CHECK(g_live.empty());
+}
+
+// above 256 MiB the rounded size is what is filled (memory never touched: address space only)
+static void test_fill_large() {
+    BlockCache c(UNTOUCHED, true);
+    c.set_fill(true, 7);
+    size_t b = 0;
+    void *p = get(c, ((size_t)256 << 20) + 1, &b);
+    CHECK(b == (size_t)512 << 20 && g_noted_p == p && g_noted_bytes == b && g_noted_word == 7 && c.filled_bytes == b);
+    c.put(p, b);
+    g_noted_p = nullptr;
+    void *q = get(c, (size_t)400 << 20, &b);              // the cached 512 MiB block again: filled whole again
+    CHECK(q == p && b == (size_t)512 << 20 && g_noted_p == p && g_noted_bytes == b && c.filled_bytes == 2 * b);
+    c.put(q, b);
+    c.trim();
+    CHECK(g_live.empty());
+}
+
 // ---- the owners, over a pool of this backend
 static BlockCache g_pool(FAKE, true);
 static long g_releases = 0, g_syncs = 0;
@@ -235,6 +344,8 @@ int main() {
     test_refusals();
     test_disabled();
     test_trim();
+    test_fill();
+    test_fill_large();
     test_pool_block();
     test_pool_scope();
     CHECK(g_live.empty() && g_allocs == g_frees);         // the counters balance

@@ -120,9 +120,11 @@ def main():
     elif mode == "rccl_many":
         # several inputs through shk_shard_preprocess + the collective shk_assemble in ONE launch (process start-up is
         # most of a small case's time): cfg["cases"] = [{fastq, k, min_count, min_qual, do_fit, no_bubble_collapse,
-        # no_dead_end_removal, P, verbose, timings, env}]; every rank writes the list of its results.  env: set_env, around the
-        # case's handle (made, run and freed under it)
-        from sparrowhawk_amd import AssemblyHelper, pack_fastq, ShkError
+        # no_dead_end_removal, P, verbose, timings, env, pool_fill}]; every rank writes the list of its results.  env: set_env,
+        # around the case's handle (made, run and freed under it).  pool_fill: a hex word — the pool's fill-on-hand-out mode
+        # (shk_debug_pool_fill) is switched on with it before the handle is made and put back after the handle is freed; the
+        # result then says how many bytes were filled meanwhile ("pool_filled_bytes")
+        from sparrowhawk_amd import AssemblyHelper, pack_fastq, ShkError, _lib
         from sparrowhawk_amd.dist import LibComm, sharded_preprocess_rccl
         dev = torch.device("cuda", rank % max(1, torch.cuda.device_count()))
         torch.cuda.set_device(dev)
@@ -144,6 +146,10 @@ def main():
             d_seg = torch.from_numpy(seg.view(np.int32)).to(dev)
             torch.cuda.synchronize()
             env_was = set_env(cs.get("env") or {})       # (before the handle is made: it reads SHK_STAGE_TIMERS / SHK_KEEP_STAGES then)
+            fill = cs.get("pool_fill")
+            if fill is not None:
+                L = _lib.load()
+                fill_was, filled0 = L.shk_debug_pool_fill(1, int(fill, 16)), L.shk_debug_pool_filled_bytes()
             h = AssemblyHelper.new(k, bool(cs.get("verbose", False)), cs["min_count"], cs["min_qual"], 0, False, bool(cs.get("do_fit", False)),
                                    bool(cs.get("no_bubble_collapse", False)), bool(cs.get("no_dead_end_removal", False)))
             set_dedupe(cs, rank)
@@ -157,6 +163,9 @@ def main():
                 res = {"error": str(e)}
             results.append(res)
             h.free()
+            if fill is not None:
+                res["pool_filled_bytes"] = L.shk_debug_pool_filled_bytes() - filled0
+                L.shk_debug_pool_fill(fill_was, int(fill, 16))
             set_env(env_was)
         with open(f"{out_path}.{rank}", "w") as f:
             json.dump(results, f)
