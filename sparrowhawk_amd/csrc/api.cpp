@@ -23,6 +23,7 @@
 #include "inflate_gpu.h"
 #include "inflate_mt.h"
 #include "preprocess.h"
+#include "shard_preprocess.h"
 #include "unitig_graph.h"
 #include "unitig_graph_gpu.h"
 
@@ -132,80 +133,7 @@ void shk_free(shk_handle *h) {
 const char *shk_last_error(shk_handle *h) { return h ? h->err.c_str() : "null handle"; }
 void shk_set_progress_cb(shk_handle *h, shk_progress_cb cb, void *user) { if (h) { h->cb = cb; h->cb_user = user; } }
 
-// ---- shard layer: the single-GPU preprocess cut at its two exchange points ----------------------
-
-static int shard_partition_impl(shk_handle *h, const void *d_bases, const void *d_seg_off, uint64_t n_seg, uint64_t n_bases,
-                        uint64_t n_reads, uint32_t n_partitions, uint64_t *part_records) {
-    if (!h || !part_records) return SHK_E_PARAM;
-    if (h->st != St::Fresh) return fail(h, SHK_E_STATE, "shard_partition: handle already used");
-    h->post_start();
-    h->n_reads = n_reads;
-    std::vector<uint64_t> pr;
-    std::string err;
-    int rc = h->pipe->shard_partition((const uint32_t *)d_bases, (const uint32_t *)d_seg_off, n_seg, n_bases, n_partitions, pr, err);
-    if (rc) return fail_rc(h, Rc::Device, rc, err);
-    memcpy(part_records, pr.data(), (size_t)n_partitions * 8);
-    h->post_mode(("loop:" + std::to_string(n_reads) + ":100").c_str());
-    h->post_loop_edge("loop:end");
-    h->st = St::Sharding;
-    return SHK_OK;
-}
-
 uint32_t shk_shard_record_bytes(shk_handle *h) { return h && h->pipe ? h->pipe->rec_words() * 8u : 0u; }
-
-static int shard_pack_impl(shk_handle *h, void *d_send, const uint64_t *base_records, uint32_t n_partitions) {
-    if (!h || !base_records) return SHK_E_PARAM;
-    if (h->st != St::Sharding) return fail(h, SHK_E_STATE, "shard_pack: call shard_partition first");
-    std::string err;
-    int rc = h->pipe->shard_pack(d_send, base_records, n_partitions, err);
-    return rc ? fail_rc(h, Rc::Device, rc, err) : SHK_OK;
-}
-
-static int shard_count_impl(shk_handle *h, const void *d_recv, const uint64_t *run_off, const uint32_t *run_cnt,
-                    uint32_t n_owned, uint32_t n_sources, uint64_t *histo500_local, uint64_t *n_instances_local,
-                    const void *d_recv_w = nullptr /* weights of the records (deduplicated by their sources) */) {
-    if (!h || !histo500_local) return SHK_E_PARAM;
-    if (h->st != St::Sharding) return fail(h, SHK_E_STATE, "shard_count: call shard_partition first");
-    std::string err;
-    if (!h->do_bloom && h->chunk_size == 0) h->post("preprocess:bulk:sorting");
-    int rc = h->pipe->shard_count(d_recv, d_recv_w, run_off, run_cnt, n_owned, n_sources, emit_threshold_of(h), histo500_local, err);
-    if (rc) return fail_rc(h, Rc::Device, rc, err);
-    if (n_instances_local) *n_instances_local = h->pipe->total_instances();
-    return SHK_OK;
-}
-
-static int shard_rows_impl(shk_handle *h, const uint64_t *histo500_global, const void **d_keys, const void **d_cnt,
-                   uint64_t *n_rows, uint32_t *used_min_count) {
-    if (!h || !histo500_global || !d_keys || !d_cnt || !n_rows) return SHK_E_PARAM;
-    if (h->st != St::Sharding) return fail(h, SHK_E_STATE, "shard_rows: call shard_count first");
-    memcpy(h->histo, histo500_global, sizeof h->histo);
-    h->used_min_count = h->min_count; h->fit_ok = false;
-    if (h->do_fit) {
-        h->post_mode("fitting");
-        uint32_t v = 0;
-        if (spectrum_fit(h->histo, &v)) { h->used_min_count = v; h->fit_ok = true; }
-    }
-    h->post_mode("filtering");
-    std::string err;
-    int rc = h->pipe->shard_rows(h->used_min_count, d_keys, d_cnt, n_rows, err);
-    if (rc) return fail_rc(h, Rc::DeviceNoParam, rc, err);
-    if (used_min_count) *used_min_count = h->used_min_count;
-    return SHK_OK;
-}
-
-static int shard_set_solid_impl(shk_handle *h, const void *const *d_keys, const void *d_cnt, uint64_t n_rows,
-                        uint64_t n_instances_global) {
-    if (!h) return SHK_E_PARAM;
-    if (h->st != St::Sharding) return fail(h, SHK_E_STATE, "shard_set_solid: call shard_rows first");
-    std::string err;
-    int rc = h->pipe->shard_set_solid(d_keys, d_cnt, n_rows, h->histo, n_instances_global, err);
-    if (rc) return fail_rc(h, Rc::Device, rc, err);
-    h->post("preprocess:saving");
-    h->pre_json = preprocessing_json(h->pipe->n_solid(), h->histo, h->used_min_count);
-    h->st = St::Preprocessed;
-    h->post("preprocess:end");
-    return SHK_OK;
-}
 
 const char *shk_get_preprocessing_info(shk_handle *h) {
     if (!h) return nullptr;
@@ -503,401 +431,7 @@ uint64_t shk_peak_device_bytes(shk_handle *h) { return h ? mem_acct_peak(h->mem)
 void shk_host_mem_counter(const int64_t *deltas, size_t n, uint64_t *peak, uint64_t *current) { mem_acct_replay(deltas, n, peak, current); }
 
 // ---- collectives inside the library (shard_comm.hip: RCCL) ---------------------------------------------
-struct shk_comm { ShardComm *c = nullptr; };
 static thread_local std::string g_comm_err;
-
-// This rank's reads as shard_preprocess_impl takes them: a step that hands over any number of batches (none, one, several: the
-// ranks need not agree), each of which goes through pass 1 at once and is the step's again afterwards.
-//   inst_ub   the k-mer instances of all the batches — n_bases - n_seg * (k - 1) summed — where the rank knows them before it
-//             starts (packed reads), else an upper bound (files read window by window: text bytes / 2).  What the rank adds to
-//             the instance all-reduce from which P is chosen (n_partitions == 0): pass 1 of the FIRST batch needs P.
-//   feed      calls sink.batch once per batch; SHK_OK, or the code of an error that is set in the handle (a failure in a later
-//             batch travels with the size exchange, as every failure of pass 1 does)
-//   n_reads   where feed does not count them itself (it then leaves h->n_reads to the sink's last batch)
-struct ShardReads {
-    uint64_t inst_ub = 0, n_reads = 0;
-    std::function<int(ShardBatchSink &)> feed;
-};
-
-static int shard_preprocess_impl(shk_handle *h, shk_comm *cm, const ShardReads &reads, uint32_t n_partitions) {
-    if (!cm || !cm->c) return fail(h, SHK_E_PARAM, "shard_preprocess: null communicator");
-    if (h->st != St::Fresh) return fail(h, SHK_E_STATE, "shard_preprocess: handle already used");
-    if (comm_device(cm->c) != h->pipe->device()) return fail(h, SHK_E_PARAM, "shard_preprocess: communicator and handle live on different devices");
-    ShardComm *c = cm->c;
-    const uint32_t world = (uint32_t)comm_world(c), rank = (uint32_t)comm_rank(c);
-    const uint32_t W = (2 * h->k + 63) / 64;
-    void *st = h->pipe->stream();
-    std::string err;
-    const double t0 = now_ms();
-    // SHK_STAGE_LOG=1: after every step the stream is drained and the step's name goes to stderr (which step a fault belongs to)
-    const bool stage_log = getenv("SHK_STAGE_LOG") != nullptr;
-    auto stage = [&](const char *what) {
-        if (!stage_log) return;
-        std::string e2; const int r2 = device_stream_sync(st, e2);
-        fprintf(stderr, "[shard_preprocess rank %u] %s done%s\n", rank, what, r2 ? " (stream error)" : ""); fflush(stderr);
-    };
-    // A failure on ONE rank (device memory, a slice that overflows, a partition beyond 2^32 records: all depend on that
-    // rank's share of the reads) must not leave the others blocked in the next collective: every local step's result
-    // travels with the next small collective — as an extra element of one that exists anyway, or as a one-word
-    // all-reduce in front of the two big exchanges — and all ranks leave together.  A collective that fails itself
-    // marks the communicator broken (shk_comm_free then aborts it: peers fail fast).
-    auto peer_failed = [&](const char *stage) {
-        return fail(h, SHK_E_DEVICE, std::string("shard_preprocess: another rank failed during ") + stage + " (this rank's state is intact up to there; free the handle)");
-    };
-    // SHK_FAULT_INJECT=<step> (read — shk_shard_preprocess_fastq alone — | pass1 | pack | count | rows | keep | alloc) makes that local step of THIS process fail: the tests
-    // set it on one rank to see every rank leave with an error instead of hanging.  It never changes a result.
-    const char *inject = getenv("SHK_FAULT_INJECT");
-    auto injected = [&](const char *step) -> int {
-        return (inject && !strcmp(inject, step)) ? fail(h, SHK_E_INTERNAL, std::string("injected fault (SHK_FAULT_INJECT=") + step + ")") : SHK_OK;
-    };
-    auto agree = [&](int local_rc, const char *stage) -> int {
-        uint64_t f = local_rc ? 1u : 0u;
-        std::string e2;
-        if (int rc = comm_allreduce_host_u64(c, &f, 1, st, e2)) { if (local_rc) return local_rc; err = e2; return fail_rc(h, Rc::Device, rc, err); }
-        if (local_rc) return local_rc;
-        return f ? peer_failed(stage) : SHK_OK;
-    };
-    // ---- the partition count must be the same everywhere: from the global instance count
-    if (n_partitions == 0) {
-        uint64_t inst = reads.inst_ub;
-        if (int rc = comm_allreduce_host_u64(c, &inst, 1, st, err)) return fail_rc(h, Rc::Device, rc, err);
-        n_partitions = choose_partitions(inst, world, W == 1 ? 100000 : 40000);
-    }
-    if (n_partitions < world) return fail(h, SHK_E_PARAM, "shard_preprocess: fewer partitions than ranks");
-    const uint32_t P = n_partitions;
-    // ---- pass 1 on this rank's reads, then the records are deduplicated HERE, before they cross the fabric (at 100x a
-    // super-k-mer record recurs ~50 times; count_part.h: k_dedupe_partitions): distinct records + u32 weights travel.
-    // SHK_SHARD_DEDUPE: 0 = never, 1 = always, default = when the distinct records of all ranks are at most half of the raw
-    // ones (error-rich reads do not deduplicate, and their partitions need the k-mer-level repartition, which counts
-    // unweighted records).  Bloom mode counts raw records too.  The decision is taken from the gathered rows: same everywhere.
-    std::vector<uint64_t> part(2 * (size_t)P + 2, 0);      // [0,P) records to send, [P,2P) raw records, [2P] = this rank failed, [2P+1] = 0 raw / 1 auto / 2 always
-    // pass 1 batch by batch: every batch into the same P partitions (Pipeline::shard_add_batch), one progress string each
-    struct Sink : ShardBatchSink {
-        shk_handle *h; uint64_t n_batches = 0, inst = 0, last_pct = 0;
-        explicit Sink(shk_handle *hh) : h(hh) {}
-        int batch(const uint32_t *d_bases, const uint32_t *d_seg_off, uint64_t n_seg, uint64_t n_bases, uint64_t n_reads, uint64_t text_done,
-                  uint64_t text_total) override {
-            std::string e2;
-            if (int rc = h->pipe->shard_add_batch(d_bases, d_seg_off, n_seg, n_bases, e2)) return fail_rc(h, Rc::Device, rc, e2);
-            n_batches++;
-            inst += n_bases > n_seg * (uint64_t)(h->k - 1) ? n_bases - n_seg * (uint64_t)(h->k - 1) : 0;
-            h->n_reads = n_reads;
-            last_pct = text_total ? std::min<uint64_t>(100, std::max<uint64_t>(last_pct, (uint64_t)((unsigned __int128)100 * text_done / text_total))) : 100;
-            h->post_mode(("loop:" + std::to_string(n_reads) + ":" + std::to_string(last_pct)).c_str());
-            return SHK_OK;
-        }
-    } sink(h);
-    int rc_p1 = SHK_OK;
-    h->post_start();
-    h->n_reads = reads.n_reads;
-    { std::string e2; if (int r2 = h->pipe->shard_begin(P, e2)) rc_p1 = fail_rc(h, Rc::Device, r2, e2); }
-    if (!rc_p1) rc_p1 = reads.feed(sink);
-    if (!rc_p1) {
-        std::vector<uint64_t> pr; std::string e2;
-        if (int r2 = h->pipe->shard_totals(pr, e2)) rc_p1 = fail_rc(h, Rc::Device, r2, e2);
-        else memcpy(part.data(), pr.data(), (size_t)P * 8);
-    }
-    if (!rc_p1) {
-        if (sink.n_batches == 0 || sink.last_pct != 100) h->post_mode(("loop:" + std::to_string(h->n_reads) + ":100").c_str());
-        h->post_loop_edge("loop:end");
-        h->st = St::Sharding;
-    }
-    if (!rc_p1) rc_p1 = injected("pass1");
-    if (!rc_p1) {
-        memcpy(&part[P], &part[0], (size_t)P * 8);
-        const char *dd = getenv("SHK_SHARD_DEDUPE");
-        const uint64_t mode = (dd && *dd == '0') || h->do_bloom ? 0u : ((dd && *dd == '1') ? 2u : 1u);
-        if (mode) {
-            std::vector<uint64_t> pr(part.begin(), part.begin() + P);
-            std::string e2;
-            if (int r2 = h->pipe->shard_dedupe(pr, e2)) rc_p1 = fail_rc(h, Rc::DeviceNoParam, r2, e2);
-            else memcpy(&part[0], pr.data(), (size_t)P * 8);
-        }
-        part[2 * (size_t)P + 1] = mode;
-    }
-    part[2 * (size_t)P] = rc_p1 ? 1u : 0u;
-    stage("pass 1 + dedupe");
-    // ---- the size exchange: every rank learns what every rank holds per partition
-    const size_t ROW = 2 * (size_t)P + 2;
-    std::vector<uint64_t> all_raw((size_t)world * ROW), all((size_t)world * P), raw_counts((size_t)world * P);
-    if (int rc = comm_allgather_host_u64(c, part.data(), ROW, all_raw.data(), st, err)) { if (rc_p1) return rc_p1; return fail_rc(h, Rc::Device, rc, err); }
-    if (rc_p1) return rc_p1;
-    bool weighted = true, forced = false;
-    uint64_t sum_dd = 0, sum_raw = 0;
-    for (uint32_t r = 0; r < world; r++) {
-        const uint64_t *row = &all_raw[(size_t)r * ROW];
-        if (row[2 * (size_t)P]) return peer_failed("pass 1");
-        if (row[2 * (size_t)P + 1] == 0) weighted = false;
-        if (row[2 * (size_t)P + 1] == 2) forced = true;
-        for (uint32_t p = 0; p < P; p++) { sum_dd += row[p]; sum_raw += row[P + p]; }
-        memcpy(&raw_counts[(size_t)r * P], row + P, (size_t)P * 8);
-    }
-    if (weighted && !forced && sum_dd * 2 > sum_raw) weighted = false;
-    for (uint32_t r = 0; r < world; r++) memcpy(&all[(size_t)r * P], &all_raw[(size_t)r * ROW + (weighted ? 0 : P)], (size_t)P * 8);
-    if (!weighted) h->pipe->shard_drop_dedup();
-    h->pipe->times().add("shard_records_deduplicated_x1", weighted ? 1.0 : 0.0);
-    ExchangePlan plan;
-    const uint64_t rec_bytes = (uint64_t)h->pipe->rec_words() * 8u;
-    uint64_t n_send = 0, n_recv = 0;
-    // ---- pack (destination-major) and exchange
-    // (on every way out — errors included — the stream is drained, through the watchdog, before the blocks go back)
-    PoolScope sc([c, st] { std::string e; (void)comm_stream_wait(c, st, e); });
-    uint8_t *send = nullptr, *recv = nullptr, *send_w = nullptr, *recv_w = nullptr, *gk[8] = {}, *gc = nullptr;
-    {
-        int rc_pack = SHK_OK;
-        if (int rc = plan_exchange(all.data(), world, P, rank, plan, err)) rc_pack = fail_rc(h, Rc::Device, rc, err);
-        if (!rc_pack && weighted) {
-            // (a partition's record index — and a record's multiplicity — are 32 bits wide in pass 2: the limit is on the RAW records)
-            for (uint32_t p = rank; p < P && !rc_pack; p += world) {
-                uint64_t t = 0;
-                for (uint32_t r = 0; r < world; r++) t += raw_counts[(size_t)r * P + p];
-                if (t > 0xFFFFFFF0ull) rc_pack = fail(h, SHK_E_PARAM, "a partition holds more than 2^32 records");
-            }
-        }
-        if (!rc_pack) {
-            for (uint32_t r = 0; r < world; r++) { n_send += plan.send_counts[r]; n_recv += plan.recv_counts[r]; }
-            std::string e2;
-            send = sc.get<uint8_t>((size_t)(n_send * rec_bytes + 64), e2);
-            recv = sc.get<uint8_t>((size_t)(n_recv * rec_bytes + 64), e2);
-            if (weighted) {
-                send_w = sc.get<uint8_t>((size_t)(n_send * 4 + 64), e2);
-                recv_w = sc.get<uint8_t>((size_t)(n_recv * 4 + 64), e2);
-            }
-            if (!send || !recv || (weighted && (!send_w || !recv_w))) rc_pack = fail(h, SHK_E_OOM, "shard_preprocess: device memory for the record exchange");
-        }
-        if (!rc_pack && weighted) {
-            std::string e2;
-            if (int r2 = h->pipe->shard_pack_dedup(send, send_w, plan.base.data(), P, e2)) rc_pack = fail_rc(h, Rc::Device, r2, e2);
-        } else if (!rc_pack) rc_pack = shard_pack_impl(h, send, plan.base.data(), P);
-        if (!rc_pack) rc_pack = injected("pack");
-        stage("pack");
-        if (int rc = agree(rc_pack, "the packing of the records")) return rc;
-    }
-    {
-        std::vector<uint64_t> so(world), sb(world), ro(world), rb(world);
-        uint64_t a = 0, b = 0;
-        for (uint32_t r = 0; r < world; r++) {
-            so[r] = a; sb[r] = plan.send_counts[r] * rec_bytes; a += sb[r];
-            ro[r] = b; rb[r] = plan.recv_counts[r] * rec_bytes; b += rb[r];
-        }
-        const double tx = now_ms();
-        if (int rc = comm_alltoallv(c, send, so.data(), sb.data(), recv, ro.data(), rb.data(), st, err)) return fail_rc(h, Rc::Device, rc, err);
-        if (weighted) {
-            // the weights: same element offsets as the records, 4 bytes each
-            for (uint32_t r = 0; r < world; r++) { so[r] = so[r] / rec_bytes * 4; sb[r] = plan.send_counts[r] * 4; ro[r] = ro[r] / rec_bytes * 4; rb[r] = plan.recv_counts[r] * 4; }
-            if (int rc = comm_alltoallv(c, send_w, so.data(), sb.data(), recv_w, ro.data(), rb.data(), st, err, 4)) return fail_rc(h, Rc::Device, rc, err);
-        }
-        if (int rc = comm_stream_wait(c, st, err)) { comm_mark_broken(c); return fail_rc(h, Rc::Device, rc, err); }
-        h->pipe->times().add("shard_exchange_host_clock", now_ms() - tx);
-        h->pipe->times().add("shard_exchange_sent_MB", (double)(n_send * (rec_bytes + (weighted ? 4 : 0))) / 1e6);
-    }
-    stage("exchange");
-    sc.release(send_w); send_w = nullptr;          // (the stream is idle: the wait above)
-    sc.release(send); send = nullptr;
-    // ---- pass 2 over the owned partitions, then the global histogram ([501] = ranks that failed)
-    // ([500] k-mer instances counted, [501] ranks that failed, [502] k-mer instances this rank's READS hold: after the
-    // all-reduce [500] must equal [502] — a record exchange that lost or duplicated data cannot pass unnoticed)
-    uint64_t red[SHK_HISTO_BINS + 3] = {0};
-    const uint64_t inst_in_reads = sink.inst;             // (summed over this rank's batches)
-    int rc_cnt = shard_count_impl(h, recv, plan.run_off.data(), plan.run_cnt.data(), (uint32_t)plan.owned.size(), world, red,
-                                  &red[SHK_HISTO_BINS], weighted ? recv_w : nullptr);
-    stage("pass 2");
-    if (!rc_cnt) rc_cnt = injected("count");
-    if (rc_cnt) memset(red, 0, sizeof red);
-    red[SHK_HISTO_BINS + 1] = rc_cnt ? 1u : 0u;
-    red[SHK_HISTO_BINS + 2] = inst_in_reads;
-    if (int rc = comm_allreduce_host_u64(c, red, SHK_HISTO_BINS + 3, st, err)) { if (rc_cnt) return rc_cnt; return fail_rc(h, Rc::Device, rc, err); }
-    if (rc_cnt) return rc_cnt;
-    if (red[SHK_HISTO_BINS + 1]) return peer_failed("pass 2");
-    if (red[SHK_HISTO_BINS] != red[SHK_HISTO_BINS + 2])
-        return fail(h, SHK_E_INTERNAL, "shard_preprocess: the ranks counted " + std::to_string(red[SHK_HISTO_BINS]) + " k-mer instances, their reads hold " +
-                                       std::to_string(red[SHK_HISTO_BINS + 2]) + ": the record exchange lost or duplicated data");
-    // ---- fit / filter (identical on every rank), local solid rows
-    const void *keys[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; const void *cnt = nullptr;
-    uint64_t n_local = 0; uint32_t used = 0;
-    int rc_rows = shard_rows_impl(h, red, keys, &cnt, &n_local, &used);
-    stage("filter");
-    if (stage_log && !rc_rows && n_local && n_local < (1u << 24)) {          // (debug aid: are the rank's solid k-mers distinct?)
-        std::vector<std::vector<uint64_t>> kw(W, std::vector<uint64_t>(n_local));
-        bool ok = true;
-        for (uint32_t j = 0; j < W && ok; j++) { void *dp = const_cast<void *>(keys[j]); std::string e3; ok = device_download(kw[j].data(), dp, n_local * 8, e3) == 0; }
-        if (ok) {
-            std::vector<uint32_t> idx(n_local);
-            for (uint32_t i = 0; i < n_local; i++) idx[i] = i;
-            std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { for (int j = (int)W - 1; j >= 0; j--) if (kw[j][a] != kw[j][b]) return kw[j][a] < kw[j][b]; return false; });
-            uint64_t dup = 0;
-            for (uint32_t i = 1; i < n_local; i++) {
-                bool eq = true; for (uint32_t j = 0; j < W; j++) eq = eq && kw[j][idx[i]] == kw[j][idx[i - 1]];
-                if (eq && dup < 4) fprintf(stderr, "[shard_preprocess rank %u]   duplicate k-mer %016llx at rows %u and %u\n", rank, (unsigned long long)kw[0][idx[i]], idx[i - 1], idx[i]);
-                dup += eq;
-            }
-            fprintf(stderr, "[shard_preprocess rank %u] %llu local solid k-mers, %llu duplicates\n", rank, (unsigned long long)n_local, (unsigned long long)dup); fflush(stderr);
-        }
-    }
-    if (!rc_rows) rc_rows = injected("rows");
-    // ---- all-gather of the solid rows
-    std::vector<uint64_t> counts2((size_t)world * 2), counts(world);
-    const uint64_t mine2[2] = {rc_rows ? 0u : n_local, rc_rows ? 1u : 0u};
-    if (int rc = comm_allgather_host_u64(c, mine2, 2, counts2.data(), st, err)) { if (rc_rows) return rc_rows; return fail_rc(h, Rc::Device, rc, err); }
-    if (rc_rows) return rc_rows;
-    for (uint32_t r = 0; r < world; r++) { if (counts2[2 * r + 1]) return peer_failed("the filter"); counts[r] = counts2[2 * r]; }
-    // ---- the graph stays sharded (default): every rank keeps its own rows and shk_assemble() runs collectively over this
-    // communicator (csrc/shard_graph.h).  SHK_SHARD_GRAPH=0: round 2's path — gather the solid set, assemble on every rank.
-    {
-        const char *sg = getenv("SHK_SHARD_GRAPH");
-        if (!(sg && *sg == '0')) {
-            int rc_keep = SHK_OK;
-            { std::string e2; const int r2 = h->pipe->shard_keep_local(world, rank, P, counts.data(), red, red[SHK_HISTO_BINS], e2);
-              if (r2) rc_keep = fail(h, r2 == -1 ? SHK_E_PARAM : SHK_E_DEVICE, e2); }
-            if (!rc_keep) rc_keep = injected("keep");
-            if (int rc = agree(rc_keep, "the hand-over to the sharded assembly")) return rc;
-            h->shard_comm = c;
-            h->post("preprocess:saving");
-            h->pre_json = preprocessing_json(h->pipe->n_solid_global(), h->histo, h->used_min_count);
-            h->st = St::Preprocessed;
-            h->post("preprocess:end");
-            h->pipe->times().add("shard_preprocess_host_clock", now_ms() - t0);
-            return SHK_OK;
-        }
-    }
-    uint64_t n_total = 0;
-    std::vector<uint64_t> off8(world), len8(world), off4(world), len4(world);
-    for (uint32_t r = 0; r < world; r++) { off8[r] = n_total * 8; len8[r] = counts[r] * 8; off4[r] = n_total * 4; len4[r] = counts[r] * 4; n_total += counts[r]; }
-    {
-        int rc_alloc = SHK_OK;
-        for (uint32_t j = 0; j < W && !rc_alloc; j++) {
-            std::string e2;
-            gk[j] = sc.get<uint8_t>((size_t)(n_total * 8 + 64), e2);
-            if (!gk[j]) rc_alloc = fail(h, SHK_E_OOM, "shard_preprocess: device memory for the solid set");
-        }
-        if (!rc_alloc) {
-            std::string e2;
-            gc = sc.get<uint8_t>((size_t)(n_total * 4 + 64), e2);
-            if (!gc) rc_alloc = fail(h, SHK_E_OOM, "shard_preprocess: device memory for the solid set");
-        }
-        if (!rc_alloc) rc_alloc = injected("alloc");
-        if (int rc = agree(rc_alloc, "the allocation of the solid set")) return rc;
-    }
-    for (uint32_t j = 0; j < W; j++)
-        if (int rc = comm_allgatherv(c, keys[j], gk[j], off8.data(), len8.data(), st, err)) return fail_rc(h, Rc::Device, rc, err);
-    if (int rc = comm_allgatherv(c, cnt, gc, off4.data(), len4.data(), st, err)) return fail_rc(h, Rc::Device, rc, err);
-    if (int rc = comm_stream_wait(c, st, err)) { comm_mark_broken(c); return fail_rc(h, Rc::Device, rc, err); }
-    const void *kp[8] = {gk[0], gk[1], gk[2], gk[3], gk[4], gk[5], gk[6], gk[7]};
-    if (int rc = shard_set_solid_impl(h, kp, gc, n_total, red[SHK_HISTO_BINS])) return rc;
-    h->pipe->times().add("shard_preprocess_host_clock", now_ms() - t0);
-    return SHK_OK;
-}
-
-// one batch that lies in HBM already
-static ShardReads one_batch(shk_handle *h, const void *d_bases, const void *d_seg_off, uint64_t n_seg, uint64_t n_bases, uint64_t n_reads) {
-    ShardReads r;
-    r.inst_ub = n_bases > n_seg * (uint64_t)(h->k - 1) ? n_bases - n_seg * (uint64_t)(h->k - 1) : 0;
-    r.n_reads = n_reads;
-    r.feed = [=](ShardBatchSink &sink) { return sink.batch((const uint32_t *)d_bases, (const uint32_t *)d_seg_off, n_seg, n_bases, n_reads, 1, 1); };
-    return r;
-}
-
-// several (shk_shard_preprocess_batches): the reads posted with a batch are n_reads in proportion to the bases so far
-static int shard_preprocess_batches_impl(shk_handle *h, shk_comm *cm, uint32_t n_batches, const void *const *d_bases, const void *const *d_seg_off,
-                                         const uint64_t *n_seg, const uint64_t *n_bases, uint64_t n_reads, uint32_t n_partitions) {
-    if (n_batches && (!d_bases || !d_seg_off || !n_seg || !n_bases)) return fail(h, SHK_E_PARAM, "shard_preprocess_batches: null batch arrays");
-    if (n_batches == 1) return shard_preprocess_impl(h, cm, one_batch(h, d_bases[0], d_seg_off[0], n_seg[0], n_bases[0], n_reads), n_partitions);
-    ShardReads r;
-    uint64_t total_bases = 0;
-    for (uint32_t b = 0; b < n_batches; b++) {
-        if (n_seg[b] && (!d_bases[b] || !d_seg_off[b])) return fail(h, SHK_E_PARAM, "shard_preprocess_batches: a batch with segments and no memory");
-        r.inst_ub += n_bases[b] > n_seg[b] * (uint64_t)(h->k - 1) ? n_bases[b] - n_seg[b] * (uint64_t)(h->k - 1) : 0;
-        total_bases += n_bases[b];
-    }
-    r.n_reads = n_reads;
-    r.feed = [=](ShardBatchSink &sink) {
-        uint64_t bases = 0;
-        for (uint32_t b = 0; b < n_batches; b++) {
-            bases += n_bases[b];
-            const uint64_t so_far = b + 1 == n_batches || !total_bases ? n_reads : (uint64_t)((unsigned __int128)n_reads * bases / total_bases);
-            if (int rc = sink.batch((const uint32_t *)d_bases[b], (const uint32_t *)d_seg_off[b], n_seg[b], n_bases[b], so_far, b + 1, n_batches)) return rc;
-        }
-        return (int)SHK_OK;
-    };
-    return shard_preprocess_impl(h, cm, r, n_partitions);
-}
-
-// shk_shard_preprocess from FASTQ files.  A share that fits one batch is read into ONE packed batch in HBM (share_reader.cpp:
-// read_fastq_share — split: slice `rank` of `world` of the same files on every rank; else the rank's own files, whole), the
-// ranks agree that all of them have their reads, and the batch goes through shard_preprocess_impl as it is.  A larger share is
-// only looked at in front of that agreement (read_fastq_share says in_batches before it uploads anything, where it can) and is
-// read inside pass 1, window by window (read_fastq_share_batches): its failures travel with the size exchange.
-static int shard_preprocess_fastq_impl(shk_handle *h, shk_comm *cm, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2,
-                                       uint32_t n_partitions, int split, RecFmt fmt = RecFmt::Fastq) {
-    // (FASTA, shk_shard_preprocess_fasta: the same steps — the readers take the format; its names in the messages and the timings)
-    const bool fasta = fmt == RecFmt::Fasta;
-    const std::string entry = fasta ? "shard_preprocess_fasta" : "shard_preprocess_fastq", tag = fasta ? "shard_fasta_" : "shard_fastq_";
-    if (!cm || !cm->c) return fail(h, SHK_E_PARAM, entry + ": null communicator");
-    if (h->st != St::Fresh) return fail(h, SHK_E_STATE, entry + ": handle already used");
-    if (comm_device(cm->c) != h->pipe->device()) return fail(h, SHK_E_PARAM, entry + ": communicator and handle live on different devices");
-    ShardComm *c = cm->c;
-    void *st = h->pipe->stream();
-    const double t0 = now_ms();
-    FastqShare sh;
-    // (declared after the share: its blocks go back to the pool with the stream idle, on every way out)
-    struct DrainOnExit { void *st; ~DrainOnExit() { std::string e; (void)device_stream_sync(st, e); } } drain{st};
-    // A rank whose reading fails (a parse error, a damaged stream, memory) enters the first collective all the same, with
-    // "I failed": it returns its own code and message, every other rank "another rank failed during reading".
-    std::string err;
-    const uint32_t s_rank = split ? (uint32_t)comm_rank(c) : 0u, s_world = split ? (uint32_t)comm_world(c) : 1u;
-    int rc_read = read_fastq_share(fq1, n1, fq2, n2, h->k, h->min_qual, s_rank, s_world, h->pipe->device(), st, sh, err, true, fmt);
-    if (rc_read) rc_read = fail(h, rc_read, err);
-    const char *inject = getenv("SHK_FAULT_INJECT");      // (step `read`: see shard_preprocess_impl)
-    if (!rc_read && inject && !strcmp(inject, "read")) rc_read = fail(h, SHK_E_INTERNAL, "injected fault (SHK_FAULT_INJECT=read)");
-    uint64_t failed = rc_read ? 1u : 0u;
-    std::string e2;
-    if (int rc = comm_allreduce_host_u64(c, &failed, 1, st, e2)) return rc_read ? rc_read : fail_rc(h, Rc::Device, rc, e2);
-    if (rc_read) return rc_read;
-    if (failed) return fail(h, SHK_E_DEVICE, entry + ": another rank failed during reading (this rank's handle is untouched; free it)");
-    auto book = [h, t0, tag](const FastqShare &s, uint64_t batches, uint64_t windows) {
-        auto &t = h->pipe->times();
-        if (s.n_bgzf_slice) t.add((tag + "bgzf_slice_x1").c_str(), (double)s.n_bgzf_slice);
-        if (s.n_member_whole) t.add((tag + "member_whole_x1").c_str(), (double)s.n_member_whole);
-        if (s.n_text_slice) t.add((tag + "text_slice_x1").c_str(), (double)s.n_text_slice);
-        if (s.n_host) t.add((tag + "host_x1").c_str(), (double)s.n_host);
-        t.add((tag + "uploaded_bytes").c_str(), (double)s.uploaded_bytes);
-        t.add((tag + "batches_x1").c_str(), (double)batches);
-        t.add((tag + "windows_x1").c_str(), (double)windows);
-        t.add((tag + "read_host_clock").c_str(), now_ms() - t0);
-    };
-    if (!sh.in_batches) {
-        // the share is held: FASTQ — the one pooled batch; FASTA — the files of a pair were packed separately, one batch per file
-        book(sh, sh.batches.size(), sh.batches.size());
-        ShardReads r;
-        for (const FastqShare::Batch &b : sh.batches) r.inst_ub += b.n_bases > b.n_seg * (uint64_t)(h->k - 1) ? b.n_bases - b.n_seg * (uint64_t)(h->k - 1) : 0;
-        r.n_reads = sh.n_reads;
-        r.feed = [&sh](ShardBatchSink &sink) -> int {
-            uint64_t reads = 0;
-            for (size_t i = 0; i < sh.batches.size(); i++) {
-                const FastqShare::Batch &b = sh.batches[i];
-                reads += b.n_reads;
-                if (int rc = sink.batch(b.n_seg ? b.d_bases() : nullptr, b.n_seg ? b.d_seg_off() : nullptr, b.n_seg, b.n_bases, reads, i + 1, sh.batches.size())) return rc;
-            }
-            return (int)SHK_OK;
-        };
-        return shard_preprocess_impl(h, cm, r, n_partitions);
-    }
-    // several batches: reading and pass 1 take turns (shard_fastq_read_host_clock then holds both)
-    ShardReads r;
-    r.inst_ub = fasta ? sh.text_ub : sh.text_ub / 2;
-    const uint64_t uploaded_before = sh.uploaded_bytes;
-    r.feed = [&](ShardBatchSink &sink) -> int {
-        FastqShare got;
-        std::string e3;
-        int rc = read_fastq_share_batches(fq1, n1, fq2, n2, h->k, h->min_qual, s_rank, s_world, h->pipe->device(), st, sink, got, e3, fmt);
-        if (rc && !e3.empty()) rc = fail(h, rc, e3);
-        got.uploaded_bytes += uploaded_before;
-        book(got, got.n_batches, got.n_windows);
-        if (!rc) h->n_reads = got.n_reads;
-        return rc;
-    };
-    return shard_preprocess_impl(h, cm, r, n_partitions);
-}
 
 int shk_comm_unique_id(uint8_t id[SHK_UNIQUE_ID_BYTES]) {
     try { return comm_unique_id(id, g_comm_err) == 0 ? SHK_OK : SHK_E_DEVICE; }
@@ -925,38 +459,22 @@ void shk_comm_free(shk_comm *c) {
     comm_destroy(c->c);
     delete c;
 }
+// (the collective calls abort a communicator whose collective failed on this rank alone before they return: shard_preprocess.cpp)
 int shk_shard_preprocess(shk_handle *h, shk_comm *c, const void *d_bases, const void *d_seg_off, uint64_t n_seg,
                          uint64_t n_bases, uint64_t n_reads, uint32_t n_partitions) {
-    return guarded(h, Poison::AfterFirstBatch, [&] {
-        const int rc = shard_preprocess_impl(h, c, one_batch(h, d_bases, d_seg_off, n_seg, n_bases, n_reads), n_partitions);
-        // a collective that failed on this rank alone: abort now, so that the peers' waits end (shard_comm.h: comm_stream_wait)
-        if (rc != SHK_OK && c && c->c && comm_broken(c->c)) comm_abort_now(c->c);
-        return rc;
-    });
+    return guarded(h, Poison::AfterFirstBatch, [&] { return shard_preprocess_one_impl(h, c, d_bases, d_seg_off, n_seg, n_bases, n_reads, n_partitions); });
 }
 int shk_shard_preprocess_batches(shk_handle *h, shk_comm *c, uint32_t n_batches, const void *const *d_bases, const void *const *d_seg_off,
                                  const uint64_t *n_seg, const uint64_t *n_bases, uint64_t n_reads, uint32_t n_partitions) {
-    return guarded(h, Poison::AfterFirstBatch, [&] {
-        const int rc = shard_preprocess_batches_impl(h, c, n_batches, d_bases, d_seg_off, n_seg, n_bases, n_reads, n_partitions);
-        if (rc != SHK_OK && c && c->c && comm_broken(c->c)) comm_abort_now(c->c);
-        return rc;
-    });
+    return guarded(h, Poison::AfterFirstBatch, [&] { return shard_preprocess_batches_impl(h, c, n_batches, d_bases, d_seg_off, n_seg, n_bases, n_reads, n_partitions); });
 }
 int shk_shard_preprocess_fastq(shk_handle *h, shk_comm *c, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2,
                                uint32_t n_partitions, int split) {
-    return guarded(h, Poison::AfterFirstBatch, [&] {
-        const int rc = shard_preprocess_fastq_impl(h, c, fq1, n1, fq2, n2, n_partitions, split);
-        if (rc != SHK_OK && c && c->c && comm_broken(c->c)) comm_abort_now(c->c);
-        return rc;
-    });
+    return guarded(h, Poison::AfterFirstBatch, [&] { return shard_preprocess_fastq_impl(h, c, fq1, n1, fq2, n2, n_partitions, split, RecFmt::Fastq); });
 }
 int shk_shard_preprocess_fasta(shk_handle *h, shk_comm *c, const uint8_t *fa1, size_t n1, const uint8_t *fa2, size_t n2,
                                uint32_t n_partitions, int split) {
-    return guarded(h, Poison::AfterFirstBatch, [&] {
-        const int rc = shard_preprocess_fastq_impl(h, c, fa1, n1, fa2, n2, n_partitions, split, RecFmt::Fasta);
-        if (rc != SHK_OK && c && c->c && comm_broken(c->c)) comm_abort_now(c->c);
-        return rc;
-    });
+    return guarded(h, Poison::AfterFirstBatch, [&] { return shard_preprocess_fastq_impl(h, c, fa1, n1, fa2, n2, n_partitions, split, RecFmt::Fasta); });
 }
 int shk_plan_exchange(const uint64_t *part_records_all, uint32_t world, uint32_t n_partitions, uint32_t rank,
                       uint64_t *base, uint64_t *send_counts, uint64_t *recv_counts, uint64_t *run_off, uint32_t *run_cnt) {

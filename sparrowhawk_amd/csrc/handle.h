@@ -1,4 +1,4 @@
-// handle.h — what api.cpp and preprocess.cpp share: the handle behind the C ABI (include/shk.h), its call-order
+// handle.h — what api.cpp, preprocess.cpp and shard_preprocess.cpp share: the handle behind the C ABI (include/shk.h), its call-order
 // state, the guards an entry point runs under and the mapping of the library's internal return codes.
 #pragma once
 #include "../../include/shk.h"

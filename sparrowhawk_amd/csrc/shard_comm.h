@@ -57,19 +57,7 @@ int comm_allreduce_host_u64(ShardComm *c, uint64_t *host_inout, size_t n, void *
 int comm_allgather_host_u64(ShardComm *c, const uint64_t *host_in, size_t n, uint64_t *host_out /* [world][n] */, void *stream,
                             std::string &err);
 
-// ---- pure host logic of the record exchange (tested on CPU against sparrowhawk_amd/dist.py: plan_exchange) ----
-// part_records_all: [world][P] records rank s holds for partition p; partition p belongs to rank p % world.
-struct ExchangePlan {
-    std::vector<uint32_t> owned;          // partitions this rank counts, ascending
-    std::vector<uint64_t> base;           // [P] record offset of partition p in the send buffer (destination-major)
-    std::vector<uint64_t> send_counts;    // [world] records sent to each destination
-    std::vector<uint64_t> recv_counts;    // [world] records received from each source
-    std::vector<uint64_t> run_off;        // [n_owned][world] record offset of source s's run of owned partition j in the receive buffer
-    std::vector<uint32_t> run_cnt;        // [n_owned][world]
-};
-int plan_exchange(const uint64_t *part_records_all, uint32_t world, uint32_t P, uint32_t rank, ExchangePlan &out,
-                  std::string &err);
-// power of two in [64, 16384], >= world, ~per_part k-mer instances per partition
-uint32_t choose_partitions(uint64_t total_instances_ub, uint32_t world, uint64_t per_part);
-
 }  // namespace shk
+
+// the pure host logic of the record exchange (ExchangePlan, plan_exchange, choose_partitions): its own header, no HIP
+#include "exchange_plan.h"

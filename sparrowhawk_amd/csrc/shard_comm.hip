@@ -355,43 +355,4 @@ int comm_allgather_host_u64(ShardComm *c, const uint64_t *host_in, size_t n, uin
     return comm_stream_wait(c, stream, err);
 }
 
-// ---- host-side plan -------------------------------------------------------------------------------
-uint32_t choose_partitions(uint64_t total_instances_ub, uint32_t world, uint64_t per_part) {
-    uint32_t P = 64;
-    while (P < 16384u && (uint64_t)P * per_part < total_instances_ub) P <<= 1;
-    while (P < world) P <<= 1;
-    return P;
-}
-
-int plan_exchange(const uint64_t *pr, uint32_t world, uint32_t P, uint32_t rank, ExchangePlan &out, std::string &err) {
-    if (!pr || world < 1 || rank >= world || P < world) { err = "plan_exchange: bad arguments"; return -1; }
-    const uint64_t *mine = pr + (uint64_t)rank * P;
-    out.base.assign(P, 0); out.send_counts.assign(world, 0); out.recv_counts.assign(world, 0);
-    uint64_t off = 0;
-    for (uint32_t d = 0; d < world; d++)                       // destination-major, partitions ascending
-        for (uint32_t p = d; p < P; p += world) { out.base[p] = off; off += mine[p]; out.send_counts[d] += mine[p]; }
-    out.owned.clear();
-    for (uint32_t p = rank; p < P; p += world) out.owned.push_back(p);
-    const uint32_t n_owned = (uint32_t)out.owned.size();
-    std::vector<uint64_t> recv_base(world, 0);
-    for (uint32_t s = 0; s < world; s++) {
-        uint64_t t = 0;
-        for (uint32_t j = 0; j < n_owned; j++) t += pr[(uint64_t)s * P + out.owned[j]];
-        out.recv_counts[s] = t;
-    }
-    for (uint32_t s = 1; s < world; s++) recv_base[s] = recv_base[s - 1] + out.recv_counts[s - 1];
-    out.run_off.assign((uint64_t)n_owned * world, 0); out.run_cnt.assign((uint64_t)n_owned * world, 0);
-    for (uint32_t s = 0; s < world; s++) {
-        uint64_t within = 0;                                   // source s sends its partitions for this rank in ascending order
-        for (uint32_t j = 0; j < n_owned; j++) {
-            const uint64_t c = pr[(uint64_t)s * P + out.owned[j]];
-            if (c > 0xFFFFFFFFull) { err = "plan_exchange: more than 2^32 records of one partition on one rank"; return -1; }
-            out.run_off[(uint64_t)j * world + s] = recv_base[s] + within;
-            out.run_cnt[(uint64_t)j * world + s] = (uint32_t)c;
-            within += c;
-        }
-    }
-    return 0;
-}
-
 }  // namespace shk

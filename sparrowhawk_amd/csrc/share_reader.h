@@ -52,7 +52,7 @@ int read_fastq_share(const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n
                      uint32_t world, int device, void *stream, FastqShare &out, std::string &err, bool allow_batches = false,
                      shk::RecFmt fmt = shk::RecFmt::Fastq);
 
-// where the batches of a share go: pass 1 of the shard layer (api.cpp: shard_preprocess_impl)
+// where the batches of a share go: pass 1 of the shard layer (shard_preprocess.cpp: sp_pass1, the Sink)
 struct ShardBatchSink {
     virtual ~ShardBatchSink() = default;
     // One batch (< 2^32 bases; n_seg == 0: reads without a segment) -> pass 1; the batch's memory is the caller's again on return.
